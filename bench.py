@@ -7,11 +7,16 @@ slot on reset() and its mj_step; --auto-reset same_step re-spawns inside the ter
 MuJoCo's default Newton solver with its default iteration cap / tolerance (100 / 1e-8); --solver pgs selects PGS.  One "step" = one ``env.step(action)`` over the whole batch, exactly what the reference's ``step``
 does for one env: mj_step + observation/termination assembly.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Every rank owns an independent shard of 4096 envs (weak scaling, no data-path collective; the process group only
 provides the start/stop barrier and the max-over-ranks time).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the
+benchmark measures: the CPU baseline, the steady-state window, the secondary workloads and BASELINE configs, and the
+roofline block (HIP events around every EVENT_STRIDE-th timed launch, figures of the committed profiling passes).
+--dump-outputs DIR writes what the last timed step returned (rank 0's shard) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -371,6 +376,54 @@ def _self_collision(args):
     return 'capsule' if args.self_collision == 'capsule' else None
 
 
+def result_line(args, env, hm, shard, world, dt, n):
+    """The headline fields of the JSON line (rank 0): throughput of the K timed steps and the workload they ran."""
+    from gym_quadruped_amd.sharding import aggregate_throughput
+    return {
+        'metric': 'env-steps/sec (batched)', 'value': aggregate_throughput([dt] * world, args.steps, n), 'unit': 'env-steps/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup, 'device_warmup_steps': DEVICE_WARMUP_STEPS, 'ms_per_step': dt / args.steps * 1e3,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
+        'data': 'synthetic',
+        'config': {'workload': f'{args.robot} {args.scene}, {n} envs/GPU, random-action rollout (50*N(0,1) torques), '
+                               f'{"ALL_OBS" if args.obs == "all" else "_DEFAULT_OBS"} ({env._obs_dim} scalars), '
+                               f'auto-reset on termination ({env.auto_reset_mode}), sim_dt 0.002, {args.solver} solver <=100 it tol 1e-8, robot self-collision {"off" if _self_collision(args) is False or args.solver == "pgs" else ("on (mesh pairs: capsule proxies)" if _self_collision(args) == "capsule" else "on (mesh pairs: GJK / EPA on the hulls, as mjc_Convex)")}'
+                               + (', IMU plug-in' if args.imu else '') + ((', 5x5 HeightMap following the base (rays cast by the step kernel)' if hm.follow_base else ', 5x5 HeightMap every step') if args.heightmap else ''),
+                   'envs_per_gpu': n, 'total_envs': shard.global_envs, 'parallelism': f'env-shards x{world} (no collectives)'},
+    }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, env, last, hm):
+    """What a caller of the timed path holds after its last step: env.step's (obs, reward, terminated, truncated, info), the
+    fp64 state (env.qpos / env.qvel) and, with --heightmap, the map - one DIR/<name>.npy each ('obs_feet_pos@base' for the
+    observable 'feet_pos:base'), float32 (float64 where the library keeps fp64).  Past DUMP_MAX_BYTES a fixed, seeded sample of
+    env rows is written, its indices in env_index.npy."""
+    obs, reward, terminated, truncated, info = last
+    arrays = {f'obs_{k.replace(":", "@")}': v for k, v in obs.items()}
+    arrays.update(reward=reward, terminated=terminated, truncated=truncated, qpos=env.qpos, qvel=env.qvel)
+    arrays.update({f'info_{k}': v for k, v in info.items() if torch.is_tensor(v)})
+    if hm is not None:
+        arrays['heightmap'] = hm.data
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype in (np.float64, np.int64) else np.float32) for k, v in arrays.items()}
+    n = env.num_envs
+    # the sample below picks env rows: every array must be one row per env
+    odd = {k: v.shape for k, v in arrays.items() if v.ndim == 0 or v.shape[0] != n}
+    if odd:
+        raise ValueError(f'--dump-outputs: arrays without a leading dimension of {n} envs: {odd}')
+    row_bytes = sum(v.nbytes for v in arrays.values()) / n
+    if row_bytes * n > DUMP_MAX_BYTES:
+        budget = DUMP_MAX_BYTES - 256 * (len(arrays) + 1)   # room for the .npy headers (128 bytes each)
+        keep = np.sort(np.random.default_rng(0).choice(n, int(budget // (row_bytes + 8)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays['env_index'] = keep.astype(np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(out_dir / f'{k}.npy', v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -392,10 +445,13 @@ def main():
                          "'capsule' = capsule proxies in their place (approximation), 'off' = no robot-robot contacts")
     ap.add_argument('--imu', action='store_true', help='BASELINE config 5: IMU plug-in (6 observables; robots that expose accelerometer + gyro sensors)')
     ap.add_argument('--heightmap', action='store_true', help='BASELINE config 5: a 5x5 HeightMap @ 0.1 m updated every step')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: CPU baseline, steady-state window, '
+                                                        'secondary workloads and BASELINE configs, roofline figures')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy (float32 / float64)')
     ap.add_argument('--dist-backend', default='nccl', help=argparse.SUPPRESS)   # test hook: 'gloo' together with GQ_BENCH_SHARE_DEVICE=1 runs the
     args = ap.parse_args()                                                       # N-rank protocol with every rank on GPU 0 (one-GPU boxes)
 
-    from gym_quadruped_amd.sharding import aggregate_throughput, shard_plan
+    from gym_quadruped_amd.sharding import shard_plan
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -409,7 +465,7 @@ def main():
     # N > 1: rank 0 still times the 1-core leg (the other ranks wait for it at the rendezvous; nothing of it is inside the
     # timed region), so that a scaling line carries its CPU baseline too; the all-cores leg stays with the N = 1 line
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline() if world == 1 else cpu_baseline(seconds_budget=10.0, all_cores=False)
     dist = None
     # GQ_BENCH_FORCE_DIST=1 (tests/test_gpu_boundary.py): a ONE-rank torchrun launch also goes through the process-group path - the RCCL
@@ -484,18 +540,18 @@ def main():
         env.step(pool[i % 64])
     # timed region: exactly K steps bracketed by barrier + synchronize
     # HIP events around the kernel launch of every EVENT_STRIDE-th step (on the launch stream): an event pair per launch
-    # puts two extra packets between consecutive kernels and costs ~5 % of the step time it is there to measure
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if i % EVENT_STRIDE == 0 else None
+    # puts two extra packets between consecutive kernels and costs ~5 % of the step time it is there to measure; a plain run
+    # (no roofline block) records none
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.full and i % EVENT_STRIDE == 0 else None
           for i in range(args.steps)]
     env._profile_events = None
     barrier()
     t0 = time.perf_counter()
-    nterm = 0
     for i in range(args.steps):
         env._profile_events = ev[i]  # HIP events around the step-kernel launch on the launch stream
-        o_i = env.step(pool[i % 64])[0]
+        last = env.step(pool[i % 64])
         if hm is not None:
-            update_hm(o_i)
+            update_hm(last[0])
     env._profile_events = None
     barrier()
     dt = time.perf_counter() - t0
@@ -503,6 +559,16 @@ def main():
         t = torch.tensor([dt], device=device if args.dist_backend == 'nccl' else 'cpu', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # before anything else steps the env: the observation tensors are views that the next step overwrites
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), env, last, hm)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line(args, env, hm, shard, world, dt, n)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     kernel_ms = float(np.mean([p[0].elapsed_time(p[1]) for p in ev if p is not None]))
     # steady state: a short timed window (the driver's 20 steps) sits at the start of a fresh rollout, before most robots have
     # fallen for the first time; the same env simply keeps stepping for STEADY_STEPS more steps and that rate is reported next
@@ -531,32 +597,21 @@ def main():
         if args.solver == 'newton' and args.obs == 'all' and n == ENVS_PER_GPU:
             secondary.update(config_lines(QuadrupedEnv, n, device, pool))
     if rank == 0:
-        total_envs = shard.global_envs
-        value = aggregate_throughput([dt] * world, args.steps, n)   # dt is already the max over ranks
+        out = result_line(args, env, hm, shard, world, dt, n)
+        value = out['value']
         bytes_step = algorithmic_bytes_per_env_step(env._obs_dim)
         achieved = n * bytes_step / (kernel_ms * 1e-3) / 1e9
         # the committed counter passes were taken on the headline workload: replayed for that workload only
         headline = (args.robot == 'mini_cheetah' and args.scene == 'flat' and args.solver == 'newton' and args.obs == 'all' and n == ENVS_PER_GPU
                     and _self_collision(args) is None and not args.imu and not args.heightmap and args.auto_reset == 'next_step' and not args.no_auto_reset)
         traffic = pmc_traffic() if headline else (None, {'note': 'HBM counters are committed for the headline workload only (profiles/rNN_hbm_counters.md)'})
-        out = {
-            'metric': 'env-steps/sec (batched)', 'value': value, 'unit': 'env-steps/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup, 'device_warmup_steps': DEVICE_WARMUP_STEPS, 'ms_per_step': dt / args.steps * 1e3,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-            'data': 'synthetic',
-            'config': {'workload': f'{args.robot} {args.scene}, {n} envs/GPU, random-action rollout (50*N(0,1) torques), '
-                                   f'{"ALL_OBS" if args.obs == "all" else "_DEFAULT_OBS"} ({env._obs_dim} scalars), '
-                                   f'auto-reset on termination ({env.auto_reset_mode}), sim_dt 0.002, {args.solver} solver <=100 it tol 1e-8, robot self-collision {"off" if _self_collision(args) is False or args.solver == "pgs" else ("on (mesh pairs: capsule proxies)" if _self_collision(args) == "capsule" else "on (mesh pairs: GJK / EPA on the hulls, as mjc_Convex)")}'
-                                   + (', IMU plug-in' if args.imu else '') + ((', 5x5 HeightMap following the base (rays cast by the step kernel)' if hm.follow_base else ', 5x5 HeightMap every step') if args.heightmap else ''),
-                       'envs_per_gpu': n, 'total_envs': total_envs, 'parallelism': f'env-shards x{world} (no collectives)',
-                       'state_finite': finite},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic[0], 'traffic_source': traffic[1], 'kernel': 'gq::step_kernel',
-                         'kernel_ms': kernel_ms, 'bytes_per_env_step': bytes_step,
-                         'valu_issue': valu_issue(kernel_ms) if headline else None,
-                         'tail': launch_tail() if headline else None,
-                         'note': 'algorithmic bytes / HIP-event kernel time; the step is latency/VALU bound, not HBM bound'},
-        }
+        out['config']['state_finite'] = finite
+        out['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                           'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic[0], 'traffic_source': traffic[1], 'kernel': 'gq::step_kernel',
+                           'kernel_ms': kernel_ms, 'bytes_per_env_step': bytes_step,
+                           'valu_issue': valu_issue(kernel_ms) if headline else None,
+                           'tail': launch_tail() if headline else None,
+                           'note': 'algorithmic bytes / HIP-event kernel time; the step is latency/VALU bound, not HBM bound'}
         if steady is not None:
             secondary = dict(secondary or {}, steady_state=steady)
         elif args.steps >= STEADY_STEPS:

@@ -251,9 +251,33 @@ def test_bench_process_group_path_initialises_rccl_on_one_rank():
     root = Path(__file__).resolve().parents[1]
     env = dict(os.environ, GQ_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', '29541',
-                        str(root / 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-secondary'],
+                        str(root / 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--full', '--no-cpu-baseline', '--no-secondary'],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [x for x in r.stdout.splitlines() if x.startswith('{')][-1]
     d = json.loads(line)
     assert d['n_gpus'] == 1 and d['steps'] == 20 and d['scaling'] == 'weak' and d['value'] > 1e7 and d['config']['state_finite']
+
+
+def test_bench_plain_run_dumps_the_same_outputs_with_and_without_the_process_group(tmp_path):
+    """A plain bench line (no --full) run twice with --dump-outputs: once on its own, once through the one-rank process-group path
+    (its early return: barrier + destroy_process_group).  Same arguments -> the same inputs, and the step kernel (pair exchange
+    included) is deterministic, so the two dumps are equal bit for bit."""
+    import json, os, subprocess, sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    bench = [str(root / 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5']
+    runs = {'solo': ([sys.executable] + bench, dict(os.environ)),
+            'pg': ([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
+                    '--master-port', '29543'] + bench, dict(os.environ, GQ_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0'))}
+    for name, (cmd, env) in runs.items():
+        r = subprocess.run(cmd + ['--dump-outputs', str(tmp_path / name)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([x for x in r.stdout.splitlines() if x.startswith('{')][-1])
+        assert d['steps'] == 20 and d['ms_per_step'] > 0 and d['value'] > 1e7 and 'roofline' not in d and 'cpu_baseline' not in d
+    files = sorted(p.name for p in (tmp_path / 'solo').iterdir())
+    assert files == sorted(p.name for p in (tmp_path / 'pg').iterdir()) and 'qpos.npy' in files and 'obs_feet_pos@base.npy' in files
+    for f in files:
+        a, b = np.load(tmp_path / 'solo' / f), np.load(tmp_path / 'pg' / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 4096 and np.isfinite(a).all(), f
+        np.testing.assert_array_equal(a, b, err_msg=f)
