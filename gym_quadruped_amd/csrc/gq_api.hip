@@ -55,6 +55,8 @@ static int scene_variant(const GqModel* m) {
   for (int g = 0; g < m->host.nlg; g++) { const int t = m->host.lg[g].ptype; if (t == 2 || t == 3 || t == 6) return 2; }
   return 1;
 }
+/* the self-collision stage runs for a model with self-collision pairs */
+static int has_self(const GqModel* m) { return m->host.nsp > 0; }
 struct GqBatch {
   GqModel* model;
   GqDevBatch host;
@@ -68,7 +70,6 @@ struct GqBatch {
   int xq_slots; bool xq_on;
   float* sepc;          /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
   int stop_stage;       /* profiling aid: GQ_STOP_STAGE at batch creation */
-  int force_self;       /* profiling aid: GQ_FORCE_SELF=1 runs the self-collision kernel variant even for a model without pairs */
   /* argument block of step_kernel: device copy, host shadow of what the device holds, pinned staging ring for the
    * (rare) stream-ordered re-upload */
   gq::FusedArgs* dev_args;
@@ -210,9 +211,8 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
    * reads no environment variable (tests/test_host_and_abi.py checks its objects for getenv) */
 #ifdef GQ_DEV_KNOBS
   { const char* s = getenv("GQ_STOP_STAGE"); b->stop_stage = s ? atoi(s) : 0; }
-  { const char* s = getenv("GQ_FORCE_SELF"); b->force_self = (s && atoi(s)) ? 1 : 0; }
 #else
-  b->stop_stage = 0; b->force_self = 0;
+  b->stop_stage = 0;
 #endif
   HIP_TRY_OR_DESTROY(hipMalloc(&b->dev_args, sizeof(gq::FusedArgs)), gq_batch_destroy(b));
   HIP_TRY_OR_DESTROY(hipHostMalloc(&b->staging, sizeof(gq::FusedArgs) * GQ_ARG_SLOTS, hipHostMallocDefault), gq_batch_destroy(b));
@@ -405,6 +405,11 @@ static void fill_reset_args(gq::ResetArgs* a, GqBatch* b, const uint8_t* mask, c
   a->cfg.cmd_reset = b->host.rs_cmd_reset;
 }
 
+/* one launch of the step kernel over n_envs envs from c->env0: the variant follows the batch's model (solver, cone, scene) */
+static void launch_step_kernel(const GqBatch* b, const gq::StepCall* c, int n_envs, hipStream_t stream) {
+  const GqModel* m = b->model;
+  gq_launch_step(b->dev_args, c, n_envs, m->host.solver, m->host.cone, scene_variant(m), has_self(m), stream);
+}
 static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const uint8_t* mask, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
                        int32_t* episode, uint8_t* lift_failed, void* hip_stream, const char* who) {
   if (!b || !st.qpos || !st.qvel || !st.qacc || !st.qacc_warmstart || !st.time || !out.obs || !out.reward ||
@@ -421,7 +426,7 @@ static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const
   gq::StepCall c{};
   c.ctrl = ctrl; c.mask = mask; c.debug = b->host.debug_envs > 0 ? b->debug : nullptr; c.env0 = env0;
   c.auto_reset = auto_reset ? (auto_reset->autoreset_next_step ? 2 : 1) : 0; c.first_pass = 0; c.stop_stage = b->stop_stage;
-  gq_launch_step(b->dev_args, &c, count, b->model->host.solver, b->model->host.cone, scene_variant(b->model), (b->model->host.nsp > 0 || b->force_self), (hipStream_t)hip_stream);
+  launch_step_kernel(b, &c, count, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -451,8 +456,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
     gq::StepCall c{};
     c.ctrl = ctrl_seq; c.n_steps = n_steps; c.ctrl_stride = b->host.n_envs * 12; c.obs_seq = obs_seq;
     c.auto_reset = auto_reset ? 2 : 0; c.stop_stage = b->stop_stage;
-    gq_launch_step(b->dev_args, &c, b->host.n_envs, b->model->host.solver, b->model->host.cone, scene_variant(b->model),
-                   (b->model->host.nsp > 0 || b->force_self), (hipStream_t)hip_stream);
+    launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return GQ_OK;
   }
@@ -485,8 +489,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
     for (int s = 0; s < shards && herr == hipSuccess; s++) {
       const int e0 = (int)((long long)s * N / shards), e1 = (int)((long long)(s + 1) * N / shards);
       c.env0 = e0;
-      gq_launch_step(b->dev_args, &c, e1 - e0, b->model->host.solver, b->model->host.cone, scene_variant(b->model),
-                     (b->model->host.nsp > 0 || b->force_self), b->shard_stream[s]);
+      launch_step_kernel(b, &c, e1 - e0, b->shard_stream[s]);
       RO_TRY(hipGetLastError());
       if (obs_seq) RO_TRY(hipMemcpyAsync(obs_seq + ((size_t)k * N + e0) * od, out.obs + (size_t)e0 * od, (size_t)(e1 - e0) * od * sizeof(float), hipMemcpyDeviceToDevice, b->shard_stream[s]));
     }
@@ -501,7 +504,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
   return GQ_OK;
 }
 
-/* mailboxes, queues and the policy stream of a batch; the XCD census of the device (one probe launch) */
+/* mailboxes, queues and the policy stream of a batch; which XCDs the device exposes (one probe launch) */
 static int mailbox_setup_impl(GqBatch* b);
 static int mailbox_setup(GqBatch* b) {
   if (b->mb.ready) return GQ_OK;
@@ -529,7 +532,7 @@ static int mailbox_setup_impl(GqBatch* b) {
   h.nq = nq; h.qcap = qcap; h.n_envs = N;
   HIP_TRY(hipMalloc(&h.act, sizeof(float) * 12 * (size_t)N));
   HIP_TRY(hipMalloc(&h.steps_done, sizeof(int32_t) * (size_t)N));
-  HIP_TRY(hipMalloc(&h.issued, sizeof(int32_t) * 2 * (size_t)N)); /* + N words of the XCD census experiment */
+  HIP_TRY(hipMalloc(&h.issued, sizeof(int32_t) * (size_t)N));
   HIP_TRY(hipMalloc(&h.q_items, sizeof(int32_t) * (size_t)nq * qcap));
   HIP_TRY(hipMalloc(&h.q_ctr, sizeof(int32_t) * (size_t)nq * 3 * GQ_MB_QSTRIDE));
   HIP_TRY(hipMalloc(&h.status, sizeof(int32_t) * 8));
@@ -546,17 +549,6 @@ static int mailbox_setup_impl(GqBatch* b) {
   b->mb.ready = true;
   return GQ_OK;
 }
-
-#ifdef GQ_MB_DEBUG
-/* experiment hook of -DGQ_MB_DEBUG builds (tools/closed_loop_debug.py; not part of the ABI): copy the XCD census words of the last closed rollout to the host */
-int gq_mailbox_census(GqBatch* b, int32_t* out_host) {
-  if (!b || !b->mb.ready) return GQ_EINVAL;
-  DeviceGuard guard(b->model->device);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out_host, b->mb.host.issued + b->host.n_envs, sizeof(int32_t) * (size_t)b->host.n_envs, hipMemcpyDeviceToHost));
-  return GQ_OK;
-}
-#endif
 
 int gq_mailbox_get(GqBatch* b, GqMailboxView* out) {
   if (!b || !out) { SET_ERR("gq_mailbox_get: null argument"); return GQ_EINVAL; }
@@ -618,7 +610,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
     gq::StepCall ci{};
     ci.n_steps = n_steps; ci.obs_seq = obs_seq; ci.act_seq = act_seq; ci.policy = b->mb.policy_dev;
     ci.auto_reset = auto_reset ? 2 : 0; ci.stop_stage = 0;
-    gq_launch_step(b->dev_args, &ci, N, b->model->host.solver, b->model->host.cone, scene_variant(b->model), (b->model->host.nsp > 0 || b->force_self), stream);
+    launch_step_kernel(b, &ci, N, stream);
     HIP_TRY(hipGetLastError());
     return GQ_OK;
   }
@@ -628,17 +620,9 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
                                                       * one env (workgroups are dealt round-robin over the XCDs; the surplus finds its queue empty and leaves) */
   h.n_steps = n_steps; h.obs_seq = obs_seq; h.act_seq = act_seq;
   h.timeout_ticks = (int64_t)((timeout_s > 0.0 ? timeout_s : 5.0) * 1e8);
-  h.flags = 0;
-#ifdef GQ_MB_DEBUG
-#ifdef GQ_DEV_KNOBS
-  { const char* fl = getenv("GQ_MB_FLAGS"); h.flags = fl ? atoi(fl) : 0; } /* fence / census experiments (tools/closed_loop_debug.py), development builds only */
-#else
-  h.flags = 0;
-#endif
-#endif
   /* fresh rollout state, ordered on the caller's stream */
   HIP_TRY(hipMemsetAsync(h.steps_done, 0, sizeof(int32_t) * (size_t)N, stream));
-  HIP_TRY(hipMemsetAsync(h.issued, 0, sizeof(int32_t) * 2 * (size_t)N, stream));
+  HIP_TRY(hipMemsetAsync(h.issued, 0, sizeof(int32_t) * (size_t)N, stream));
   HIP_TRY(hipMemsetAsync(h.q_items, 0, sizeof(int32_t) * (size_t)h.nq * h.qcap, stream));
   HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * (size_t)h.nq * 3 * GQ_MB_QSTRIDE, stream));
   HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
@@ -647,7 +631,6 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   HIP_TRY(hipMemcpyAsync(b->mb.dev, b->mb.staging, sizeof h, hipMemcpyHostToDevice, stream));
   gq::StepCall c{};
   c.auto_reset = auto_reset ? 2 : 0;
-  const int boxes = scene_variant(b->model), self = (b->model->host.nsp > 0 || b->force_self);
   if (pd) {
     /* the policy must be RESIDENT before the step wavefronts take every slot of the device: launch it first, on its own stream,
      * and wait until each of its workgroups has reported in */
@@ -671,7 +654,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
       }
     }
   }
-  if (!gq_launch_mailbox_step(b->dev_args, &c, b->mb.dev, step_waves, b->model->host.solver, b->model->host.cone, boxes, self, stream)) {
+  if (!gq_launch_mailbox_step(b->dev_args, &c, b->mb.dev, step_waves, b->model->host.solver, b->model->host.cone, scene_variant(b->model), has_self(b->model), stream)) {
     SET_ERR("gq_rollout_closed: no mailbox variant of the step kernel for this model in this build"); return GQ_EINVAL;
   }
   HIP_TRY(hipGetLastError());
@@ -714,7 +697,7 @@ int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const floa
   if (rc != GQ_OK) return rc;
   gq::StepCall c{};
   c.mask = mask; c.first_pass = 1; c.debug = b->host.debug_envs > 0 ? b->debug : nullptr;
-  gq_launch_step(b->dev_args, &c, b->host.n_envs, b->model->host.solver, b->model->host.cone, scene_variant(b->model), (b->model->host.nsp > 0 || b->force_self), (hipStream_t)hip_stream);
+  launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -773,8 +756,7 @@ int gq_forward(GqBatch* b, int stage, const float* ctrl, GqState st, GqObsOut ou
   if (rc != GQ_OK) return rc;
   gq::StepCall c{};
   c.ctrl = ctrl; c.debug = b->debug; c.forward = stage == 1 ? 1 : 2;
-  gq_launch_step(b->dev_args, &c, b->host.n_envs, b->model->host.solver, b->model->host.cone, scene_variant(b->model),
-                 (b->model->host.nsp > 0 || b->force_self), (hipStream_t)hip_stream);
+  launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

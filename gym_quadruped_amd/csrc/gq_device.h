@@ -24,18 +24,13 @@ namespace gq {
 
 /* The lane index is deliberately opaque to the optimiser (empty asm volatile): per-lane address arithmetic then stays
  * next to its use instead of being hoisted to the kernel prologue and kept live (or spilled) across the whole step. */
-#ifndef GQ_WPB
-#define GQ_WPB 1 /* wavefronts (= envs) per workgroup */
-#endif
 __device__ __forceinline__ int lane_id() {
-  int l = GQ_WPB == 1 ? (int)threadIdx.x : (int)(threadIdx.x & (GQ_WAVE - 1));
+  int l = (int)threadIdx.x;
   asm volatile("" : "+v"(l));
   return l;
 }
 /* index of this wavefront's env within the launch */
-__device__ __forceinline__ int wave_index() {
-  return GQ_WPB == 1 ? (int)blockIdx.x : (int)blockIdx.x * GQ_WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-}
+__device__ __forceinline__ int wave_index() { return (int)blockIdx.x; }
 
 /* LDS hand-off between lanes of the single wavefront of this workgroup.  With a 64-thread workgroup the
  * s_barrier degenerates (LLVM drops it for single-wave groups) and what remains is the lgkmcnt wait + the

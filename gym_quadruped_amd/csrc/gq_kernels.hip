@@ -62,14 +62,11 @@ __device__ __forceinline__ void pd_inline(const GQ_MODEL PolicyPdDev& P, const S
  * its two-pass waves.  Next-step mode: the env waits (pending flag) and spends its next launch on reset_wave + the
  * reset's mj_step instead of a user step - every wave runs exactly one mj_step per launch. */
 template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST = false>
-__global__ void __launch_bounds__(GQ_WAVE * GQ_WPB, 4) step_kernel(const FusedArgs* __restrict__ A, const StepCall c) {
+__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __restrict__ A, const StepCall c) {
   const long long t_entry = (GQ_TICKSET && MODE == 1) ? cycles() : 0; /* sub-stage builds (gq_step_kernel.h GQ_TICKSET) count from here */
-  const int widx = wave_index();
-  if (GQ_WPB > 1 && widx >= c.count) return;
-  const int env = widx + c.env0;
+  const int env = wave_index() + c.env0;
   if (c.mask && !gptr(c.mask)[env]) return; /* wave-uniform */
-  __shared__ WaveMem Ws[GQ_WPB];
-  WaveMem& W = Ws[GQ_WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+  __shared__ WaveMem W;
 #if GQ_TICKSET
   if (lane_id() == 0) W.tk_T = nullptr;
 #endif
@@ -111,7 +108,7 @@ __global__ void __launch_bounds__(GQ_WAVE * GQ_WPB, 4) step_kernel(const FusedAr
  * each pops tickets of ITS XCD's ready queue until every env-step of the rollout has been claimed.  Production Newton variants only. */
 template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM>
 __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
-  __shared__ WaveMem W; /* one wavefront per workgroup (the GQ_WPB > 1 experiment builds never launch this kernel) */
+  __shared__ WaveMem W;
 #if GQ_TICKSET
   if (lane_id() == 0) W.tk_T = nullptr;
 #endif
@@ -147,7 +144,6 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArg
     }
     const int env = (item & 0xffffff) - 1;
     adopt_fence();
-    if (MB.flags & 2) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     /* the env's step index is only needed to place the row in obs_seq: otherwise that round trip is not taken */
     const int k = MB.obs_seq ? __builtin_amdgcn_readfirstlane(ld_pub(MB.steps_done + env)) : 0;
     StepCall ck = c0;
@@ -156,7 +152,6 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArg
     ck.obs_seq = MB.obs_seq ? MB.obs_seq + (size_t)k * N * mptr(A->s.batch)->obs_dim : nullptr;
     const StepCall& c = ck;
     int pass = 0;
-    if ((MB.flags & 32) && lane_id() == 0) add_pub(MB.issued + N + env, 1 << (4 * xcc_id())); /* experiment: which XCDs ever stepped this env (nibble counters, <= 15 steps) */
     WaveCtx C;
     int hint = load_rows<SOLVER, true>(A->s, c, W, env, true, C);
     bool respawn = c.auto_reset == 2 && C.pend; /* wave-uniform */
@@ -169,7 +164,6 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArg
     }
     step_wave<SOLVER, 0, CONE, BOXES, SELF, PRIM, true>(A->s, c, W, pass, hint, C);
     publish_fence(); /* state rows are in this XCD's L2, the observation row has been written through */
-    if (MB.flags & 4) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     if (lane_id() == 0) add_pub(MB.steps_done + env, 1);
     wave_barrier();
     played++;
@@ -218,7 +212,6 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
       if (k >= K) continue;
       all_done = false;
       if (ld_pub(MB.steps_done + e) < k) continue; /* the observation after step k - 1 is not out yet */
-      if (MB.flags & 8) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       /* (the observation words are read AFTER the count has been seen: loads of one batch may be served in any order) */
       const float* row = obs + (size_t)e * od;
       float qj[12], qd[12];
@@ -233,7 +226,6 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
         if (MB.act_seq) MB.act_seq[((size_t)k * N + e) * 12 + j] = a;
       }
       publish_fence();
-      if (MB.flags & 1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       st_pub(items + (s & qmask), (((s >> qshift) & 0x7f) << 24) | (e + 1)); /* the item (lap of its ticket | env + 1) - after the action is in place */
       MB.issued[e] = k + 1;
       progress = true;
@@ -253,12 +245,9 @@ __global__ void xcc_probe_kernel(int32_t* mask) {
 
 #endif /* GQ_IN_MISC */
 template <bool BOXES>
-__global__ void __launch_bounds__(GQ_WAVE * GQ_WPB) reset_kernel(ResetArgs a, const int n_envs) {
-  const int widx = wave_index();
-  if (GQ_WPB > 1 && widx >= n_envs) return;
-  if (a.mask && !gptr(a.mask)[widx]) return;
-  __shared__ WaveMem Ws[GQ_WPB];
-  WaveMem& W = Ws[GQ_WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+__global__ void __launch_bounds__(GQ_WAVE) reset_kernel(ResetArgs a) {
+  if (a.mask && !gptr(a.mask)[wave_index()]) return;
+  __shared__ WaveMem W;
 #if GQ_TICKSET
   if (lane_id() == 0) W.tk_T = nullptr;
 #endif
@@ -436,15 +425,14 @@ static bool launch_variant(const gq::FusedArgs* dev_args, const gq::StepCall* c,
 #endif
   {
     gq::StepCall call = *c;
-    call.count = n_envs;
     if constexpr (M == 0) {
       if (c->n_steps > 1 || c->policy) { /* persistent rollout (also a one-step one with the policy inline: only this variant evaluates it): production kernel only */
-        hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P, true>), dim3((n_envs + GQ_WPB - 1) / GQ_WPB), dim3(GQ_WAVE * GQ_WPB), 0, stream, dev_args, call);
+        hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P, true>), dim3(n_envs), dim3(GQ_WAVE), 0, stream, dev_args, call);
         return true;
       }
     }
     call.n_steps = 1;
-    hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P>), dim3((n_envs + GQ_WPB - 1) / GQ_WPB), dim3(GQ_WAVE * GQ_WPB), 0, stream, dev_args, call);
+    hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P>), dim3(n_envs), dim3(GQ_WAVE), 0, stream, dev_args, call);
     return true;
   }
 }
@@ -506,9 +494,7 @@ static bool launch_mailbox_variant(const gq::FusedArgs* dev_args, const gq::Step
   else { hipLaunchKernelGGL((gq::mailbox_step_kernel<1, C, B, SF, P>), dim3(waves), dim3(GQ_WAVE), 0, stream, dev_args, *c, mb); return true; }
 }
 static bool dispatch_mailbox(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int cone, int boxes, int self, hipStream_t stream) {
-#if GQ_WPB != 1
-  return false;
-#elif defined(GQ_DEV_ONLY)
+#if defined(GQ_DEV_ONLY)
   if (!(!boxes && self && cone == (GQ_DEV_ONLY != 0))) return false;
   return launch_mailbox_variant<(GQ_DEV_ONLY != 0), false, true, true>(dev_args, c, mb, waves, stream);
 #else
@@ -549,7 +535,7 @@ extern "C" void gq_launch_ray(const GQ_GLOBAL GqDevModel* model, const double* o
   hipLaunchKernelGGL(gq::ray_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, model, origin, dir, total, dist, geom);
 }
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, int boxes, hipStream_t stream) {
-  if (boxes) hipLaunchKernelGGL(gq::reset_kernel<true>, dim3((n_envs + GQ_WPB - 1) / GQ_WPB), dim3(GQ_WAVE * GQ_WPB), 0, stream, *a, n_envs);
-  else hipLaunchKernelGGL(gq::reset_kernel<false>, dim3((n_envs + GQ_WPB - 1) / GQ_WPB), dim3(GQ_WAVE * GQ_WPB), 0, stream, *a, n_envs);
+  if (boxes) hipLaunchKernelGGL(gq::reset_kernel<true>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
+  else hipLaunchKernelGGL(gq::reset_kernel<false>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
 }
 #endif /* GQ_IN_MISC */

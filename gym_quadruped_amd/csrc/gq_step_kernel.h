@@ -83,7 +83,6 @@ struct StepCall {
   int32_t n_steps;      /* 0 / 1: a single step */
   int32_t ctrl_stride;  /* floats between the control rows of consecutive steps */
   float* obs_seq;
-  int32_t count;        /* envs of this launch: wavefronts past env0 + count (the last workgroup of a multi-wave launch) return at once */
   /* closed loop INSIDE the persistent rollout (gq_rollout_closed, inline mode): the wavefront derives the action of its env's next
    * step from the observation row it has just written (PolicyPdDev below, device memory); controls are then not read from ctrl */
   const struct PolicyPdDev* policy;
@@ -114,8 +113,6 @@ struct MailboxDev {
   int32_t n_envs, n_steps, qcap, nq;
   int32_t xcc_queue[16];  /* HW_REG_XCC_ID -> queue */
   int64_t timeout_ticks;  /* deadline of every wait, 100 MHz ticks */
-  int32_t flags;          /* experiment switches (env GQ_MB_FLAGS): 1 policy: device-scope release fence before the item store; 2 step: device-scope
-                           * acquire fence after the item; 4 step: release fence before the count; 8 policy: acquire fence after the count */
 };
 /* built-in policy: joint-space PD towards a posture, torque_j = kp_j (q_des_j - q_j) - kd_j qd_j (rounded after every operation,
  * like the elementwise torch expression); col_*: columns of the joint angles / velocities in the observation row */

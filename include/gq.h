@@ -434,8 +434,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
  * wavefront that writes env e's action must run on the XCD of queue e % n_queues (GqMailboxView.xcc_queue maps HW_REG_XCC_ID to
  * queues) - action row, observation row and counters of an env then meet in ONE L2, like the env's state rows, and device-scope
  * (sc1) accesses + a wait for the stores are all the ordering needed.  A producer on another XCD should be paired with device-scope
- * fences (a -DGQ_MB_DEBUG build of the library reads them from the environment - GQ_MB_FLAGS: 1 release on the policy side, 2 acquire on
- * the stepping side; measured cost of the latter 14 % - the product build compiles the switches to 0).
+ * fences: a release on the policy side, an acquire on the stepping side (measured cost of the latter 14 %).
  * mode GQ_CLOSED_INLINE: the built-in policy is evaluated by the wavefront that steps the env, right where the observation row is
  * written (the persistent kernel of gq_rollout(shards = 0) with the action derived instead of read): the turn-around of an action
  * is zero instead of two trips through device memory, which matters when there are no more envs than wavefront slots - every env

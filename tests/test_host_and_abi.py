@@ -371,7 +371,7 @@ def test_plane_support_tables_never_hide_the_support_vertex(robot):
 
 
 def test_product_library_reads_no_environment_variable():
-    """The profiling knobs (GQ_STOP_STAGE, GQ_FORCE_SELF, GQ_SELF_CUT, GQ_MB_FLAGS) belong to development builds (tools/dev_build.sh,
+    """The profiling knobs (GQ_STOP_STAGE, GQ_SELF_CUT) belong to development builds (tools/dev_build.sh,
     -DGQ_DEV_KNOBS): the product sources call getenv only under that macro or under the emulator's trace macro, and the built library has no
     undefined reference to getenv."""
     import re

@@ -12,6 +12,11 @@ ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / 'gym_quadruped_amd' / 'csrc'
 
 
+def product_flags():
+    """the Makefile's device flags (include paths relative to CSRC)"""
+    return subprocess.run(['make', '-s', '-C', str(CSRC), 'print-flags'], check=True, capture_output=True, text=True).stdout.split()
+
+
 def function_ranges(path):
     """[(first_line, name)] of the __device__ functions / stage markers of a header."""
     out = []
@@ -30,9 +35,8 @@ def main(solver='1'):
     ranges = {p.name: function_ranges(p) for p in CSRC.glob('*.h')}
     with tempfile.TemporaryDirectory() as td:
         out = Path(td) / 'k.s'
-        subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', f'-I{ROOT}/include', f'-I{CSRC}',
-                        '-fno-hip-fp32-correctly-rounded-divide-sqrt', '-fno-slp-vectorize', '-mllvm', '-amdgpu-sched-strategy=iterative-maxocc', '-mllvm', '-disable-machine-licm', '-gline-tables-only', '-S', '--cuda-device-only', '-o', str(out), str(CSRC / 'gq_kernels.hip')],
-                       check=True, capture_output=True)
+        subprocess.run(['/opt/rocm/bin/hipcc', *product_flags(), '-gline-tables-only', '-S', '--cuda-device-only', '-o', str(out), 'gq_kernels.hip'],
+                       check=True, capture_output=True, cwd=CSRC)
         files, cur, infn = {}, (0, 0), False
         cnt = collections.defaultdict(collections.Counter)
         for line in out.read_text().splitlines():

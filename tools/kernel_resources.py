@@ -10,9 +10,11 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / 'gym_quadruped_amd' / 'csrc'
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', f'-I{ROOT}/include', f'-I{CSRC}', '-Wno-unused-value', '-fno-hip-fp32-correctly-rounded-divide-sqrt',
-         '-fno-slp-vectorize', '-mllvm', '-amdgpu-sched-strategy=iterative-maxocc', '-mllvm', '-disable-machine-licm', '-gline-tables-only',
-         '-Rpass-analysis=kernel-resource-usage', '-S', '--cuda-device-only']
+
+
+def product_flags():
+    """the Makefile's device flags (include paths relative to CSRC)"""
+    return subprocess.run(['make', '-s', '-C', str(CSRC), 'print-flags'], check=True, capture_output=True, text=True).stdout.split()
 
 
 def short(name):
@@ -24,10 +26,11 @@ def short(name):
 
 def main(argv):
     out_md = Path(argv[0]) if argv and not argv[0].startswith('--') else None
-    keep = Path(argv[argv.index('--keep-asm') + 1]) if '--keep-asm' in argv else None
+    keep = Path(argv[argv.index('--keep-asm') + 1]).resolve() if '--keep-asm' in argv else None
     with tempfile.TemporaryDirectory() as td:
         asm = keep or Path(td) / 'k.s'
-        r = subprocess.run(['/opt/rocm/bin/hipcc', *FLAGS, '-o', str(asm), str(CSRC / 'gq_kernels.hip')], capture_output=True, text=True)
+        r = subprocess.run(['/opt/rocm/bin/hipcc', *product_flags(), '-gline-tables-only', '-Rpass-analysis=kernel-resource-usage', '-S', '--cuda-device-only',
+                            '-o', str(asm), 'gq_kernels.hip'], capture_output=True, text=True, cwd=CSRC)
         if r.returncode:
             sys.exit(r.stderr[-3000:])
         rows, cur = collections.OrderedDict(), None

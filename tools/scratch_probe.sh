@@ -3,8 +3,7 @@
 # (boxes 1: world-box variants for hull-only robots, 2: with the exact primitive pairs - aliengo, go2, b2)
 CONE=${1:-0}; BOXES=${2:-2}; shift; shift
 cd "$(dirname "$0")/../gym_quadruped_amd/csrc"
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -I. -I../../include -Wno-unused-value -fno-hip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize \
-  -mllvm -amdgpu-sched-strategy=iterative-maxocc -mllvm -disable-machine-licm -DGQ_DEV_ONLY=$CONE -DGQ_DEV_BOXES=$BOXES -gline-tables-only \
+hipcc $(make -s print-flags) -DGQ_DEV_ONLY=$CONE -DGQ_DEV_BOXES=$BOXES -gline-tables-only \
   -Rpass-analysis=kernel-resource-usage -S --cuda-device-only "$@" -o /tmp/dev_probe.s gq_kernels.hip 2> /tmp/dev_probe.err || { tail -20 /tmp/dev_probe.err; exit 1; }
 python3 - <<'PY'
 import re, collections

@@ -12,12 +12,16 @@ ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / 'gym_quadruped_amd' / 'csrc'
 
 
+def product_flags():
+    """the Makefile's device flags (include paths relative to CSRC)"""
+    return subprocess.run(['make', '-s', '-C', str(CSRC), 'print-flags'], check=True, capture_output=True, text=True).stdout.split()
+
+
 def main(solver='1', SELF='0'):
     with tempfile.TemporaryDirectory() as td:
         out = Path(td) / 'k.s'
-        subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', f'-I{ROOT}/include', f'-I{CSRC}',
-                        '-fno-hip-fp32-correctly-rounded-divide-sqrt', '-fno-slp-vectorize', '-mllvm', '-amdgpu-sched-strategy=iterative-maxocc', '-mllvm', '-disable-machine-licm', '-gline-tables-only', '-S', '--cuda-device-only', '-o', str(out), str(CSRC / 'gq_kernels.hip')],
-                       check=True, capture_output=True)
+        subprocess.run(['/opt/rocm/bin/hipcc', *product_flags(), '-gline-tables-only', '-S', '--cuda-device-only', '-o', str(out), 'gq_kernels.hip'],
+                       check=True, capture_output=True, cwd=CSRC)
         files, cur, infn, cnt = {}, (0, 0), False, collections.Counter()
         for line in out.read_text().splitlines():
             m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', line)

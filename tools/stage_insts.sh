@@ -1,5 +1,5 @@
 #!/bin/bash
-# (the GQ_STOP_STAGE / GQ_SELF_CUT / GQ_FORCE_SELF knobs used below exist in DEVELOPMENT builds only - tools/dev_build.sh, -DGQ_DEV_KNOBS, selected with
+# (the GQ_STOP_STAGE knob used below exists in DEVELOPMENT builds only - tools/dev_build.sh, -DGQ_DEV_KNOBS, selected with
 # GQ_LIBGQ_PATH; the product library reads no environment variable)
 # Dynamic instruction counts per stage (runs on the GPU box): the step kernel is cut short after stage marker k
 # (GQ_STOP_STAGE) and SQ_INSTS_VALU / SALU / LDS + SQ_WAVE_CYCLES are collected per cut; differences between
