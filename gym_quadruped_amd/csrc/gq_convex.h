@@ -513,17 +513,32 @@ GQ_CVX_FN bool cvx_pair_wave(LdsF shp, LdsF poly, const GQ_MODEL float* vx, cons
     }
     const int gfv = shfl_idx(fv, take ? eg : lane); /* the face behind the rim edge: its vertices (it is not in the patch: its lane keeps them) */
     /* the fan's own neighbours: the new face whose rim edge starts where this one's ends, and the one whose edge ends where this one's
-     * starts - first match in rim order = lane order of the taking lanes (v_readlane per rim edge: the loop over the LDS list it replaces
-     * was a dependent LDS read per edge) */
-    int n1 = lane, n2 = lane;
+     * starts - first match in rim order = the lowest of the taking lanes.  Lane-parallel, through two byte tables keyed by vertex in the
+     * words of the rim list (read above, dead until the next iteration): S[v] = the lowest taking lane whose edge starts at v, E[v] = ...
+     * ends at v.  Every lane writes its slots at once; where several write one byte (a rim that passes a vertex twice) one of them is
+     * left, and the lower lanes write again until the lowest holds every slot - a simple rim needs no second round.  (Replaces a
+     * wave-uniform loop of two v_readlane per rim edge, up to 24.) */
+    int n1, n2;
     {
-      bool s1 = false, s2 = false;
-      for (uint64_t tm = ballot(take); tm;) { /* wave-uniform */
-        const int src = ffs64(tm); tm &= tm - 1;
-        const int ka = bcast(ea, src), kb = bcast(eb, src);
-        if (!s1 && ka == eb) { n1 = src; s1 = true; }
-        if (!s2 && kb == ea) { n2 = src; s2 = true; }
+      GQ_LDS uint8_t* const S = (GQ_LDS uint8_t*)RIM;
+      GQ_LDS uint8_t* const E = S + GQ_CVX_MAXV;
+      static_assert(2 * GQ_CVX_MAXV <= 4 * GQ_CVX_MAXRIM && GQ_CVX_MAXV % 4 == 0, "fan tables in the rim list");
+      wave_barrier();
+      if (lane < GQ_CVX_MAXV / 2) RIM[lane] = 0x40404040; /* every byte GQ_WAVE: no lane */
+      wave_barrier();
+      if (take) { S[ea] = (uint8_t)lane; E[eb] = (uint8_t)lane; }
+      for (;;) { /* wave-uniform */
+        wave_barrier();
+        const int sa = S[ea], ee = E[eb];
+        n1 = S[eb]; n2 = E[ea];
+        const bool w1 = take && sa > lane, w2 = take && ee > lane;
+        if (!ballot(w1 || w2)) break;
+        wave_barrier();
+        if (w1) S[ea] = (uint8_t)lane;
+        if (w2) E[eb] = (uint8_t)lane;
       }
+      if (n1 >= GQ_WAVE) n1 = lane;
+      if (n2 >= GQ_WAVE) n2 = lane;
     }
     wave_barrier();
     if (take) {
