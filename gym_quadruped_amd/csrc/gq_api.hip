@@ -19,8 +19,8 @@
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
 
-extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, int boxes, int self, hipStream_t stream);
-extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, int boxes, hipStream_t stream);
+extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
+extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
@@ -28,7 +28,7 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
-extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, int boxes, int self, hipStream_t stream);
+extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
 #define GQ_ARG_SLOTS 8
 static thread_local char g_err[512] = "";
@@ -46,17 +46,18 @@ struct GqModel {
   float *vx, *vy, *vz;
   float* hf;            /* device elevations of the scene's height field (NULL: none) */
   int nvert;
+  gq::Scene scene;      /* the step-kernel variants the model runs (model_scene) */
 };
-/* kernel variant by scene: 0 flat, 1 world boxes / height field, 2 the same for a robot with sphere / capsule / box link
- * geoms (exact pair routines compiled in; gq_step_body.h PRIM) */
-static int scene_variant(const GqModel* m) {
-  if (!(m->host.nbox > 0 || m->host.hf_nrow > 0)) return 0;
-  /* lg[] is indexed by link geom (item[] is in contact order: feet and link geoms interleaved by geom id) */
-  for (int g = 0; g < m->host.nlg; g++) { const int t = m->host.lg[g].ptype; if (t == 2 || t == 3 || t == 6) return 2; }
-  return 1;
+/* world boxes / height field: the world scenes, split by whether the robot has sphere / capsule / box link geoms (exact pair routines
+ * compiled in; gq_step_body.h PRIM); flat: the self-collision stage runs for a model with self-collision pairs */
+static gq::Scene model_scene(const GqDevModel& h) {
+  if (h.nbox > 0 || h.hf_nrow > 0) {
+    /* lg[] is indexed by link geom (item[] is in contact order: feet and link geoms interleaved by geom id) */
+    for (int g = 0; g < h.nlg; g++) { const int t = h.lg[g].ptype; if (t == 2 || t == 3 || t == 6) return gq::SCENE_WORLD_PRIM; }
+    return gq::SCENE_WORLD_HULL;
+  }
+  return h.nsp > 0 ? gq::SCENE_FLAT_SELF : gq::SCENE_FLAT;
 }
-/* the self-collision stage runs for a model with self-collision pairs */
-static int has_self(const GqModel* m) { return m->host.nsp > 0; }
 struct GqBatch {
   GqModel* model;
   GqDevBatch host;
@@ -145,7 +146,7 @@ int gq_model_create(const GqModelDesc* desc, int device, GqModel** out) {
   if (!m) return GQ_ENOMEM;
   std::vector<float> vx, vy, vz;
   if (gq_build_dev_model(desc, &m->host, &vx, &vy, &vz, g_err, sizeof g_err)) { delete m; return GQ_EINVAL; }
-  m->device = device; m->nvert = (int)vx.size();
+  m->device = device; m->nvert = (int)vx.size(); m->scene = model_scene(m->host);
   DeviceGuard guard(device);
   if (m->host.hf_nrow > 0) {
     std::vector<float> hf;
@@ -275,7 +276,7 @@ int gq_batch_set_heightmap(GqBatch* b, int rows, int cols, float dist_x, float d
   if (!b) { SET_ERR("gq_batch_set_heightmap: null batch"); return GQ_EINVAL; }
   if (!out) { b->heightmap = nullptr; b->host.hm_rows = b->host.hm_cols = 0; b->batch_dirty = true; return GQ_OK; }
   if (rows <= 0 || cols <= 0 || rows > 4096 || cols > 4096 || rows * cols > 4096 || !(dist_x > 0.0f) || !(dist_y > 0.0f)) { SET_ERR("gq_batch_set_heightmap: bad grid (%d x %d cells of %g x %g m)", rows, cols, (double)dist_x, (double)dist_y); return GQ_EINVAL; }
-  if (scene_variant(b->model) == 0) { SET_ERR("gq_batch_set_heightmap: the scene has no world boxes / height field - every ray ends on the floor plane; use gq_heightmap"); return GQ_EINVAL; }
+  if (!gq::scene_boxes(b->model->scene)) { SET_ERR("gq_batch_set_heightmap: the scene has no world boxes / height field - every ray ends on the floor plane; use gq_heightmap"); return GQ_EINVAL; }
   b->heightmap = out;
   b->host.hm_rows = rows; b->host.hm_cols = cols; b->host.hm_dx = dist_x; b->host.hm_dy = dist_y;
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
@@ -408,7 +409,7 @@ static void fill_reset_args(gq::ResetArgs* a, GqBatch* b, const uint8_t* mask, c
 /* one launch of the step kernel over n_envs envs from c->env0: the variant follows the batch's model (solver, cone, scene) */
 static void launch_step_kernel(const GqBatch* b, const gq::StepCall* c, int n_envs, hipStream_t stream) {
   const GqModel* m = b->model;
-  gq_launch_step(b->dev_args, c, n_envs, m->host.solver, m->host.cone, scene_variant(m), has_self(m), stream);
+  gq_launch_step(b->dev_args, c, n_envs, m->host.solver, m->host.cone, m->scene, stream);
 }
 static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const uint8_t* mask, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
                        int32_t* episode, uint8_t* lift_failed, void* hip_stream, const char* who) {
@@ -654,7 +655,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
       }
     }
   }
-  if (!gq_launch_mailbox_step(b->dev_args, &c, b->mb.dev, step_waves, b->model->host.solver, b->model->host.cone, scene_variant(b->model), has_self(b->model), stream)) {
+  if (!gq_launch_mailbox_step(b->dev_args, &c, b->mb.dev, step_waves, b->model->host.solver, b->model->host.cone, b->model->scene, stream)) {
     SET_ERR("gq_rollout_closed: no mailbox variant of the step kernel for this model in this build"); return GQ_EINVAL;
   }
   HIP_TRY(hipGetLastError());
@@ -690,7 +691,7 @@ int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const floa
   r.clear_terminated = out.terminated; r.clear_truncated = out.truncated; r.clear_invalid = out.invalid_contact;
   r.lift_pending = b->lift_pending;
   { const int rcb = flush_batch(b, (hipStream_t)hip_stream); if (rcb != GQ_OK) return rcb; }
-  gq_launch_reset(&r, b->host.n_envs, scene_variant(b->model), (hipStream_t)hip_stream);
+  gq_launch_reset(&r, b->host.n_envs, b->model->scene, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   /* the reset's own mj_step with zero control (quadruped_env.py:334, :397); friction committed after it (:403-404) */
   const int rc = ensure_args(b, st, out, episode, lift_failed, nullptr, (hipStream_t)hip_stream);

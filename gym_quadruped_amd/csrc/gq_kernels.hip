@@ -6,20 +6,18 @@
  */
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include <gq_device.h>
 #include "gq_step_body.h"
 
-/* Parallel build (csrc/Makefile): this file is compiled once per PART, each translation unit instantiating one group of step-kernel
- * variants (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one unit took 7.5 minutes, the parts build side by side in
- * about one).  GQ_PART undefined: everything in one unit (tools/dev_build.sh development builds).  Part GQ_PART_MISC holds the
- * non-template kernels, the launch entry points and the dispatch over the parts. */
+/* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
+ * unit took 7.5 minutes, the parts build side by side in about one).  part_of() at the end of the file assigns every kernel variant to its
+ * part; part 0 holds the non-template kernels, the launch entry points and the dispatch over the parts.  GQ_PART undefined: everything in
+ * one unit (make dev, tools/kernel_resources.py, isa_report.py). */
 #ifndef GQ_PART
 #define GQ_PART (-1)
 #endif
-#define GQ_PART_MISC 18
-#define GQ_IN_MISC (GQ_PART < 0 || GQ_PART == GQ_PART_MISC)
-constexpr int gq_step_part(int S, int M, bool C, bool B) { return ((S == 0 ? 0 : (C ? 2 : 1)) * 3 + M) * 2 + (B ? 1 : 0); } /* 0 .. 17 */
-constexpr int gq_mailbox_part(bool C, bool B) { return 19 + (C ? 2 : 0) + (B ? 1 : 0); }                                   /* 19 .. 22 */
+#define GQ_IN_MISC (GQ_PART <= 0)
 
 namespace gq {
 
@@ -399,86 +397,126 @@ __global__ void ray_kernel(const GQ_GLOBAL GqDevModel* model, const double* orig
 }
 
 #endif /* GQ_IN_MISC */
-}  // namespace gq
 
-#if GQ_IN_MISC
-extern "C" void gq_launch_heightmap(const GQ_GLOBAL GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
-                                    float dist_x, float dist_y, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(gq::heightmap_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, center, center_stride, yaw, yaw_stride, n_envs, rows, cols, dist_x, dist_y, out);
+/* ---- the kernel variants, the part that builds each, and the run-time dispatch to them.  A variant is a Key: solver (0 PGS, 1 Newton),
+ * mode (0 production; 1 debug record + stage timers; 2 stage cut, gq_debug_stop_stage - its early returns cost the production kernel ~8 %
+ * when merely compiled in), cone (1 elliptic, Newton only: gq_model_create rejects it with PGS), scene, and mailbox (1: the closed-loop
+ * rollout's mailbox_step_kernel, production Newton only; 0: step_kernel, whose production mode also has its PERSIST twin). */
+struct Key { int solver, mode, cone, scene, mailbox; };
+constexpr bool key_exists(Key k) { return !(k.solver == 0 && k.cone) && !(k.mailbox && (k.solver == 0 || k.mode != 0)); }
+/* part 0: the non-template kernels and the launch entry points; 1-18: step variants by solver and cone x mode x flat or world scene;
+ * 19-22: mailbox variants by cone x flat or world scene.  Each part is one translation unit (-DGQ_PART=k); the Makefile's NPARTS is checked. */
+constexpr int part_of(Key k) {
+  const int world = scene_boxes(Scene(k.scene));
+  return k.mailbox ? 19 + 2 * k.cone + world : 1 + ((k.solver + k.cone) * 3 + k.mode) * 2 + world;
 }
-
-#endif /* GQ_IN_MISC */
-/* Development builds (tools/dev_build.sh: -DGQ_DEV_ONLY=<0|1>, cone = 0 pyramidal / 1 elliptic) instantiate only the flat-scene
- * self-collision Newton variants (production + instrumented) - a 15 s build for A/B timing of kernel experiments through
- * GQ_LIBGQ_PATH; any other launch aborts.  The product library is built without the macro and carries every variant. */
+constexpr int kParts = part_of({1, 0, 1, SCENE_WORLD_PRIM, 1}) + 1;
+#ifdef GQ_NPARTS
+static_assert(GQ_NPARTS == kParts, "csrc/Makefile NPARTS does not match part_of()");
+#endif
+/* Development builds (make dev, tools/dev_build.sh: -DGQ_DEV_ONLY=<cone>, one unit, a 15 s build for A/B timing of kernel experiments
+ * through GQ_LIBGQ_PATH) carry the Newton step variants of one cone and one scene - flat + self-collision, -DGQ_DEV_BOXES=1 world hull,
+ * =2 world prim - without the stage cut unless -DGQ_DEV_CUTS=1, and the flat self-collision mailbox variant; any other step launch aborts. */
+#ifdef GQ_DEV_ONLY
 #ifndef GQ_DEV_BOXES
-#define GQ_DEV_BOXES 0 /* -DGQ_DEV_BOXES=1: the development build carries the world-box / height-field variants instead of the flat ones */
+#define GQ_DEV_BOXES 0
 #endif
 #ifndef GQ_DEV_CUTS
-#define GQ_DEV_CUTS 0 /* -DGQ_DEV_CUTS=1: the development build also carries the stage-cut variant (tools/stage_cuts.py) */
+#define GQ_DEV_CUTS 0
 #endif
-template <int S, int M, bool C, bool B, bool SF, bool P = true>
-static bool launch_variant(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, hipStream_t stream) {
-  if constexpr (GQ_PART >= 0 && gq_step_part(S, M, C, B) != GQ_PART) return false; else
-#ifdef GQ_DEV_ONLY
-  if constexpr (!(S == 1 && (M != 2 || GQ_DEV_CUTS) && B == (GQ_DEV_BOXES != 0) && (!B || P == (GQ_DEV_BOXES == 2)) && SF && C == (GQ_DEV_ONLY != 0))) { fprintf(stderr, "libgq development build: kernel variant solver=%d mode=%d cone=%d boxes=%d self=%d not compiled in\n", S, M, int(C), int(B), int(SF)); abort(); } else
+constexpr Scene kDevScene = GQ_DEV_BOXES == 2 ? SCENE_WORLD_PRIM : GQ_DEV_BOXES ? SCENE_WORLD_HULL : SCENE_FLAT_SELF;
+constexpr bool in_build(Key k) {
+  return k.solver == 1 && k.cone == (GQ_DEV_ONLY != 0) && (k.mode != 2 || GQ_DEV_CUTS) && k.scene == (k.mailbox ? SCENE_FLAT_SELF : kDevScene);
+}
+#else
+constexpr bool in_build(Key) { return true; }
 #endif
-  {
-    gq::StepCall call = *c;
+/* does the unit of part `part` (-1: the single-unit build) instantiate variant k? */
+constexpr bool compiled_in(Key k, int part) { return key_exists(k) && in_build(k) && (part < 0 || part_of(k) == part); }
+
+struct Launch { Key key; const FusedArgs* args; const StepCall* c; const MailboxDev* mb; int grid /* workgroups */; hipStream_t stream; };
+template <int S, int M, int CONE, int SC, int MB>
+static void launch_variant(const Launch& L) {
+  constexpr bool C = CONE, B = scene_boxes(Scene(SC)), SF = scene_self(Scene(SC)), P = scene_prim(Scene(SC));
+  StepCall call = *L.c;
+  if constexpr (MB) {
+    hipLaunchKernelGGL((mailbox_step_kernel<S, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call, L.mb);
+  } else {
     if constexpr (M == 0) {
-      if (c->n_steps > 1 || c->policy) { /* persistent rollout (also a one-step one with the policy inline: only this variant evaluates it): production kernel only */
-        hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P, true>), dim3(n_envs), dim3(GQ_WAVE), 0, stream, dev_args, call);
-        return true;
+      if (call.n_steps > 1 || call.policy) { /* persistent rollout (also a one-step one with the policy inline: only this variant evaluates it): production kernel only */
+        hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+        return;
       }
     }
     call.n_steps = 1;
-    hipLaunchKernelGGL((gq::step_kernel<S, M, C, B, SF, P>), dim3(n_envs), dim3(GQ_WAVE), 0, stream, dev_args, call);
-    return true;
+    hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
   }
 }
-
-/* the run-time choice among the variants of THIS translation unit; false: the variant lives in another part */
-static bool dispatch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, int boxes, int self, hipStream_t stream) {
-  /* 0: production; 1: debug record + stage timers; 2: stage cut (GQ_STOP_STAGE / gq_debug_stop_stage) - the early returns
-   * of the cut cost the production kernel ~8 % when merely compiled in, hence a variant of their own.
-   * Scene variants: flat (no world geoms beyond the floor), flat + robot self-collision, world boxes / height field (always
-   * with the self-collision stage compiled in; a model without pairs skips it at run time). */
-  const int mode = c->debug != nullptr ? 1 : (c->stop_stage != 0 ? 2 : 0);
-#define GQ_LAUNCH(S, M, C) (boxes == 2 ? launch_variant<S, M, C, true, true, true>(dev_args, c, n_envs, stream) \
-                            : boxes ? launch_variant<S, M, C, true, true, false>(dev_args, c, n_envs, stream) \
-                            : self ? launch_variant<S, M, C, false, true>(dev_args, c, n_envs, stream) \
-                            : launch_variant<S, M, C, false, false>(dev_args, c, n_envs, stream))
-#define GQ_LAUNCH_MODE(S, C) (mode == 1 ? GQ_LAUNCH(S, 1, C) : mode == 2 ? GQ_LAUNCH(S, 2, C) : GQ_LAUNCH(S, 0, C))
-  if (solver == 1 && cone) return GQ_LAUNCH_MODE(1, true);
-  if (solver == 1) return GQ_LAUNCH_MODE(1, false);
-  return GQ_LAUNCH_MODE(0, false); /* PGS: pyramidal cones only (gq_model_create rejects elliptic cones with solver 0) */
-#undef GQ_LAUNCH_MODE
-#undef GQ_LAUNCH
+/* f(std::integral_constant<int, v>{}) for the run-time v in [0, N): turns one field of a key into a template argument */
+template <int N, class F>
+static bool with_const(int v, F&& f) {
+  static_assert(N <= 4, "with_const: add cases");
+  switch (v) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: if constexpr (N > 1) return f(std::integral_constant<int, 1>{}); break;
+    case 2: if constexpr (N > 2) return f(std::integral_constant<int, 2>{}); break;
+    case 3: if constexpr (N > 3) return f(std::integral_constant<int, 3>{}); break;
+  }
+  return false;
 }
-#define GQ_CAT2(a, b) a##b
-#define GQ_CAT(a, b) GQ_CAT2(a, b)
-#if GQ_PART >= 0 && GQ_PART < GQ_PART_MISC
-extern "C" bool GQ_CAT(gq_launch_step_p, GQ_PART)(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, int boxes, int self, hipStream_t stream) {
-  return dispatch_step(dev_args, c, n_envs, solver, cone, boxes, self, stream);
+/* launches L's variant if the unit of part PART instantiates it; false otherwise */
+template <int PART>
+static bool dispatch(const Launch& L) {
+  const Key& k = L.key;
+  return with_const<2>(k.solver, [&](auto S) { return with_const<3>(k.mode, [&](auto M) { return with_const<2>(k.cone, [&](auto C) {
+         return with_const<SCENE_COUNT>(k.scene, [&](auto SC) { return with_const<2>(k.mailbox, [&](auto MB) {
+    if constexpr (!compiled_in({S, M, C, SC, MB}, PART)) return false;
+    else { launch_variant<S, M, C, SC, MB>(L); return true; }
+  }); }); }); }); });
 }
+/* the entry point of part PART > 0, instantiated in that part's unit only */
+template <int PART> bool launch_part(const Launch& L);
+#if GQ_PART > 0
+template <int PART> bool launch_part(const Launch& L) { return dispatch<PART>(L); }
+template bool launch_part<GQ_PART>(const Launch&);
 #endif
 #if GQ_IN_MISC
-#if GQ_PART >= 0
-#define GQ_P(k) extern "C" bool gq_launch_step_p##k(const gq::FusedArgs*, const gq::StepCall*, int, int, int, int, int, hipStream_t);
-GQ_P(0) GQ_P(1) GQ_P(2) GQ_P(3) GQ_P(4) GQ_P(5) GQ_P(6) GQ_P(7) GQ_P(8) GQ_P(9) GQ_P(10) GQ_P(11) GQ_P(12) GQ_P(13) GQ_P(14) GQ_P(15) GQ_P(16) GQ_P(17)
-#undef GQ_P
-#endif
-extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, int boxes, int self, hipStream_t stream) {
-#if GQ_PART >= 0
-  static bool (*const part[18])(const gq::FusedArgs*, const gq::StepCall*, int, int, int, int, int, hipStream_t) = {
-    gq_launch_step_p0, gq_launch_step_p1, gq_launch_step_p2, gq_launch_step_p3, gq_launch_step_p4, gq_launch_step_p5, gq_launch_step_p6, gq_launch_step_p7, gq_launch_step_p8,
-    gq_launch_step_p9, gq_launch_step_p10, gq_launch_step_p11, gq_launch_step_p12, gq_launch_step_p13, gq_launch_step_p14, gq_launch_step_p15, gq_launch_step_p16, gq_launch_step_p17};
-  const int mode = c->debug != nullptr ? 1 : (c->stop_stage != 0 ? 2 : 0);
-  const int k = gq_step_part(solver == 1 ? 1 : 0, mode, solver == 1 && cone, boxes != 0);
-  if (!part[k](dev_args, c, n_envs, solver, cone, boxes, self, stream)) { fprintf(stderr, "libgq: step-kernel part %d does not hold solver=%d mode=%d cone=%d boxes=%d self=%d\n", k, solver, mode, cone, boxes, self); abort(); }
+template <int... I>
+static bool launch_in_part(const Launch& L, std::integer_sequence<int, I...>) {
+  static constexpr bool (*entry[])(const Launch&) = {&launch_part<I + 1>...};
+  return entry[part_of(L.key) - 1](L);
+}
+static bool launch_key(const Launch& L) {
+#if GQ_PART < 0
+  return dispatch<-1>(L);
 #else
-  dispatch_step(dev_args, c, n_envs, solver, cone, boxes, self, stream);
+  return launch_in_part(L, std::make_integer_sequence<int, kParts - 1>{});
 #endif
+}
+#endif /* GQ_IN_MISC */
+}  // namespace gq
+
+#if GQ_IN_MISC
+extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream) {
+  const int newton = solver == 1; /* PGS: pyramidal cones only */
+  const gq::Key k{newton, c->debug != nullptr ? 1 : (c->stop_stage != 0 ? 2 : 0), newton && cone, scene, 0};
+  if (!gq::launch_key({k, dev_args, c, nullptr, n_envs, stream})) {
+    fprintf(stderr, "libgq: step-kernel variant solver=%d mode=%d cone=%d scene=%d is not compiled into this build\n", k.solver, k.mode, k.cone, k.scene);
+    abort();
+  }
+}
+/* returns 0 if the scene / solver combination has no mailbox variant compiled in */
+extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream) {
+  const int newton = solver == 1;
+  return gq::launch_key({{newton, 0, newton && cone, scene, 1}, dev_args, c, mb, waves, stream}) ? 1 : 0;
+}
+extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream) {
+  if (gq::scene_boxes(scene)) hipLaunchKernelGGL(gq::reset_kernel<true>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
+  else hipLaunchKernelGGL(gq::reset_kernel<false>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
+}
+extern "C" void gq_launch_heightmap(const GQ_GLOBAL GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
+                                    float dist_x, float dist_y, float* out, hipStream_t stream) {
+  hipLaunchKernelGGL(gq::heightmap_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, center, center_stride, yaw, yaw_stride, n_envs, rows, cols, dist_x, dist_y, out);
 }
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
   hipLaunchKernelGGL(gq::xcc_probe_kernel, dim3(4096), dim3(GQ_WAVE), 0, stream, mask);
@@ -486,56 +524,10 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
-#endif /* GQ_IN_MISC */
-/* mailbox variants of this translation unit (parts 19 .. 22: pyramidal / elliptic x flat / world geoms) */
-template <bool C, bool B, bool SF, bool P>
-static bool launch_mailbox_variant(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, hipStream_t stream) {
-  if constexpr (GQ_PART >= 0 && gq_mailbox_part(C, B) != GQ_PART) return false;
-  else { hipLaunchKernelGGL((gq::mailbox_step_kernel<1, C, B, SF, P>), dim3(waves), dim3(GQ_WAVE), 0, stream, dev_args, *c, mb); return true; }
-}
-static bool dispatch_mailbox(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int cone, int boxes, int self, hipStream_t stream) {
-#if defined(GQ_DEV_ONLY)
-  if (!(!boxes && self && cone == (GQ_DEV_ONLY != 0))) return false;
-  return launch_mailbox_variant<(GQ_DEV_ONLY != 0), false, true, true>(dev_args, c, mb, waves, stream);
-#else
-#define GQ_MB_SCENE(C) (boxes == 2 ? launch_mailbox_variant<C, true, true, true>(dev_args, c, mb, waves, stream) \
-                        : boxes ? launch_mailbox_variant<C, true, true, false>(dev_args, c, mb, waves, stream) \
-                        : self ? launch_mailbox_variant<C, false, true, true>(dev_args, c, mb, waves, stream) \
-                        : launch_mailbox_variant<C, false, false, true>(dev_args, c, mb, waves, stream))
-  return cone ? GQ_MB_SCENE(true) : GQ_MB_SCENE(false);
-#undef GQ_MB_SCENE
-#endif
-}
-#if GQ_PART > GQ_PART_MISC
-extern "C" bool GQ_CAT(gq_launch_mailbox_p, GQ_PART)(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int cone, int boxes, int self, hipStream_t stream) {
-  return dispatch_mailbox(dev_args, c, mb, waves, cone, boxes, self, stream);
-}
-#endif
-#if GQ_IN_MISC
-#if GQ_PART >= 0
-#define GQ_P(k) extern "C" bool gq_launch_mailbox_p##k(const gq::FusedArgs*, const gq::StepCall*, const gq::MailboxDev*, int, int, int, int, hipStream_t);
-GQ_P(19) GQ_P(20) GQ_P(21) GQ_P(22)
-#undef GQ_P
-#endif
-/* returns 0 if the scene / solver combination has no mailbox variant compiled in */
-extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, int boxes, int self, hipStream_t stream) {
-  if (solver != 1) return 0;
-#if GQ_PART >= 0
-  static bool (*const part[4])(const gq::FusedArgs*, const gq::StepCall*, const gq::MailboxDev*, int, int, int, int, hipStream_t) = {
-    gq_launch_mailbox_p19, gq_launch_mailbox_p20, gq_launch_mailbox_p21, gq_launch_mailbox_p22};
-  return part[gq_mailbox_part(cone != 0, boxes != 0) - 19](dev_args, c, mb, waves, cone, boxes, self, stream) ? 1 : 0;
-#else
-  return dispatch_mailbox(dev_args, c, mb, waves, cone, boxes, self, stream) ? 1 : 0;
-#endif
-}
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream) {
   hipLaunchKernelGGL(gq::jac_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, qpos, body, point, jacp, jacr);
 }
 extern "C" void gq_launch_ray(const GQ_GLOBAL GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream) {
   hipLaunchKernelGGL(gq::ray_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, model, origin, dir, total, dist, geom);
-}
-extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, int boxes, hipStream_t stream) {
-  if (boxes) hipLaunchKernelGGL(gq::reset_kernel<true>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
-  else hipLaunchKernelGGL(gq::reset_kernel<false>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);
 }
 #endif /* GQ_IN_MISC */

@@ -35,102 +35,6 @@ __device__ __forceinline__ float mul_m_row(const WaveMem& W, const float* v, int
   return s;
 }
 
-/* L'DL of one tree-sparse system given in the Mc/Mb layout -> F (lanes 0-3 legs, lane 0 base block) */
-__device__ inline void factor_tree_one(WaveMem& W, const float (*Sc)[9], const float (*Sb)[6], float* F) {
-  const int lane = lane_id();
-  float(*acc)[21] = W.acc2;
-  if (lane < 4) {
-    const int hh = 6 + 3 * lane, t = hh + 1, c = hh + 2;
-    float rc[9], rt[8], rh[7], bb[21];
-#pragma unroll
-    for (int j = 0; j < 6; j++) { rc[j] = Sc[c - 6][j]; rt[j] = Sc[t - 6][j]; rh[j] = Sc[hh - 6][j]; }
-    rc[6] = Sc[c - 6][6]; rc[7] = Sc[c - 6][7]; rc[8] = Sc[c - 6][8];
-    rt[6] = Sc[t - 6][6]; rt[7] = Sc[t - 6][7];
-    rh[6] = Sc[hh - 6][6];
-#pragma unroll
-    for (int q = 0; q < 21; q++) bb[q] = 0.0f;
-    const float ic = fast_rcp(rc[8]);
-    {
-      float tmp = rc[7] * ic;
-#pragma unroll
-      for (int j = 0; j <= 7; j++) rt[j] -= rc[j] * tmp;
-      rc[7] = tmp;
-      tmp = rc[6] * ic;
-#pragma unroll
-      for (int j = 0; j <= 6; j++) rh[j] -= rc[j] * tmp;
-      rc[6] = tmp;
-#pragma unroll
-      for (int i = 5; i >= 0; i--) {
-        tmp = rc[i] * ic;
-#pragma unroll
-        for (int j = 0; j <= i; j++) bb[i * (i + 1) / 2 + j] -= rc[j] * tmp;
-        rc[i] = tmp;
-      }
-    }
-    const float it = fast_rcp(rt[7]);
-    {
-      float tmp = rt[6] * it;
-#pragma unroll
-      for (int j = 0; j <= 6; j++) rh[j] -= rt[j] * tmp;
-      rt[6] = tmp;
-#pragma unroll
-      for (int i = 5; i >= 0; i--) {
-        tmp = rt[i] * it;
-#pragma unroll
-        for (int j = 0; j <= i; j++) bb[i * (i + 1) / 2 + j] -= rt[j] * tmp;
-        rt[i] = tmp;
-      }
-    }
-    const float ih = fast_rcp(rh[6]);
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-      const float tmp = rh[i] * ih;
-#pragma unroll
-      for (int j = 0; j <= i; j++) bb[i * (i + 1) / 2 + j] -= rh[j] * tmp;
-      rh[i] = tmp;
-    }
-#pragma unroll
-    for (int j = 0; j < 6; j++) { F[GQ_F_LC(c - 6, j)] = rc[j]; F[GQ_F_LC(t - 6, j)] = rt[j]; F[GQ_F_LC(hh - 6, j)] = rh[j]; }
-    F[GQ_F_LC(c - 6, 6)] = rc[6]; F[GQ_F_LC(c - 6, 7)] = rc[7]; F[GQ_F_LC(t - 6, 6)] = rt[6];
-    F[GQ_F_DINV(c)] = ic; F[GQ_F_DINV(t)] = it; F[GQ_F_DINV(hh)] = ih;
-#pragma unroll
-    for (int q = 0; q < 21; q++) acc[lane][q] = bb[q];
-  }
-  wave_barrier();
-  { /* 6x6 base block, row-parallel: lane i < 6 owns row i (lower part); pivots k = 5..0, row k is broadcast with
-     * v_readlane and the rows above it are updated at once */
-    float row[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      float v = 0.0f;
-      if (lane < 6 && j <= lane) {
-        const int q = lane * (lane + 1) / 2 + j;
-        v = Sb[lane][j] + acc[0][q] + acc[1][q] + acc[2][q] + acc[3][q];
-      }
-      row[j] = v;
-    }
-#pragma unroll
-    for (int k = 5; k >= 0; k--) {
-      float rk[6];
-#pragma unroll
-      for (int j = 0; j <= k; j++) rk[j] = bcast(row[j], k);
-      const float inv = fast_rcp(rk[k]);
-      float rki = 0.0f;
-#pragma unroll
-      for (int j = 0; j < k; j++) rki = (lane == j) ? rk[j] : rki;
-      const float tmp = rki * inv;
-#pragma unroll
-      for (int j = 0; j < k; j++) row[j] -= (lane < k && j <= lane) ? rk[j] * tmp : 0.0f;
-      if (lane == k) {
-        F[GQ_F_DINV(k)] = inv;
-#pragma unroll
-        for (int j = 0; j < k; j++) F[GQ_F_LB(k, j)] = rk[j] * inv;
-      }
-    }
-  }
-  wave_barrier();
-}
-
 /* out <- S^-1 g for a tree-sparse symmetric positive definite S (Mc/Mb layout) + h_d * damping on the diagonal: Gaussian
  * elimination and back-substitution fused, entirely in the registers of lanes 0-3.  Lane L eliminates calf, thigh and hip
  * of leg L from the augmented system (S | g); the four Schur contributions to the 6x6 base block and its right-hand side
@@ -524,56 +428,6 @@ __device__ inline void solve_tree_fused2(const float (*Sc)[9], const float (*Sb)
     if (lane == 0) {
 #pragma unroll
       for (int j = 0; j < 6; j++) { out[j] = xb[j]; out2[j] = yb[j]; }
-    }
-  }
-  wave_barrier();
-}
-
-/* single right-hand side solve, leg-parallel: out <- (L'DL)^-1 g ; g, out: LDS [18] (may alias) */
-__device__ inline void solve_tree_one(WaveMem& W, const float* F, const float* g, float* out) {
-  const int lane = lane_id();
-  float(*acc)[21] = W.acc2;
-  float xc = 0.0f, xt = 0.0f, xh = 0.0f;
-  const int hh = 6 + 3 * (lane & 3), t = hh + 1, c = hh + 2;
-  if (lane < 4) { /* backward substitution inside the leg, contributions to the base collected per leg */
-    xc = g[c];
-    xt = g[t] - F[GQ_F_LC(c - 6, 7)] * xc;
-    xh = g[hh] - F[GQ_F_LC(c - 6, 6)] * xc - F[GQ_F_LC(t - 6, 6)] * xt;
-#pragma unroll
-    for (int j = 0; j < 6; j++) acc[lane][j] = F[GQ_F_LC(c - 6, j)] * xc + F[GQ_F_LC(t - 6, j)] * xt + F[GQ_F_LC(hh - 6, j)] * xh;
-  }
-  wave_barrier();
-  if (lane == 0) {
-    float xb[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) xb[j] = g[j] - (acc[0][j] + acc[1][j] + acc[2][j] + acc[3][j]);
-#pragma unroll
-    for (int k = 5; k >= 1; k--)
-#pragma unroll
-      for (int j = 0; j < k; j++) xb[j] -= F[GQ_F_LB(k, j)] * xb[k];
-#pragma unroll
-    for (int k = 0; k < 6; k++) xb[k] *= F[GQ_F_DINV(k)];
-#pragma unroll
-    for (int k = 1; k < 6; k++)
-#pragma unroll
-      for (int j = 0; j < k; j++) xb[k] -= F[GQ_F_LB(k, j)] * xb[j];
-#pragma unroll
-    for (int k = 0; k < 6; k++) acc[4][k] = xb[k];
-  }
-  wave_barrier();
-  if (lane < 4) {
-    float xb[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) xb[j] = acc[4][j];
-    xh *= F[GQ_F_DINV(hh)]; xt *= F[GQ_F_DINV(t)]; xc *= F[GQ_F_DINV(c)];
-#pragma unroll
-    for (int j = 0; j < 6; j++) { xh -= F[GQ_F_LC(hh - 6, j)] * xb[j]; xt -= F[GQ_F_LC(t - 6, j)] * xb[j]; xc -= F[GQ_F_LC(c - 6, j)] * xb[j]; }
-    xt -= F[GQ_F_LC(t - 6, 6)] * xh;
-    xc -= F[GQ_F_LC(c - 6, 6)] * xh + F[GQ_F_LC(c - 6, 7)] * xt;
-    out[hh] = xh; out[t] = xt; out[c] = xc;
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 6; j++) out[j] = xb[j];
     }
   }
   wave_barrier();

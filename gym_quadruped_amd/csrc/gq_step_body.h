@@ -500,8 +500,8 @@ __device__ __forceinline__ int load_rows(const StepArgs& a, const StepCall& call
  * (zero control, friction committed afterwards, termination flags of pass 0 are kept).  pass 2: the reset's own step of
  * a next-step auto-reset (as pass 1, flags cleared).  Returns `terminated`. */
 /* SOLVER 0: PGS (mj_solPGS), 1: Newton (mj_solNewton, MuJoCo's default).  MODE 0: production; 2: production + the
- * GQ_STOP_STAGE cut; 1 (DBG): the variant with the debug record, the
- * stage timers and the GQ_STOP_STAGE cut compiled in - the production variant carries none of it (no timer
+ * GQ_STOP_STAGE cut (the early returns of GQ_TICK); 1 (DBG): the variant with the debug record and the
+ * stage timers compiled in - the production variant carries none of it (no timer
  * accumulators or row data kept live for the record: they cost registers inside the solver loop).
  * CONE: elliptic friction cones (Newton only): contacts take dim rows [n, t1, t2, torsion, roll1, roll2].
  * BOXES: the scene has static world boxes (gq_boxes.h; Newton only): contacts carry their own normal.

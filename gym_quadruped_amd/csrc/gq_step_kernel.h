@@ -68,6 +68,15 @@ struct StepArgs {
 #define GQ_XQ_ITEM 64
 #define GQ_XQ_MARGIN 40
 #define GQ_XQ_RES 48 /* hit, dist, normal (3), point (3) */
+/* The scene a model's step-kernel variants are built for (gq_api.hip model_scene; the launch entry points of gq_kernels.hip take it):
+ * flat (no world geoms beyond the floor), flat + robot self-collision, world boxes / height field for a robot of hulls only, and the
+ * same for a robot with sphere / capsule / box link geoms.  The world scenes always carry the self-collision stage (a model without
+ * pairs skips it at run time).  scene_boxes / scene_self / scene_prim give the BOXES / SELF / PRIM template arguments of the kernels;
+ * the flat scenes keep PRIM = true, the default their kernel names were first instantiated with. */
+enum Scene : int { SCENE_FLAT, SCENE_FLAT_SELF, SCENE_WORLD_HULL, SCENE_WORLD_PRIM, SCENE_COUNT };
+constexpr bool scene_boxes(Scene s) { return s == SCENE_WORLD_HULL || s == SCENE_WORLD_PRIM; }
+constexpr bool scene_self(Scene s) { return s != SCENE_FLAT; }
+constexpr bool scene_prim(Scene s) { return s != SCENE_WORLD_HULL; }
 struct StepCall {
   const float* ctrl;    /* [N][nu] or NULL (zero control) */
   const uint8_t* mask;  /* [N] or NULL */
@@ -326,8 +335,7 @@ __device__ __forceinline__ float philox_normal(uint32_t c0, uint32_t c1, uint32_
                                                          * instructions of Payne-Hanek range reduction into every kernel variant) */
 }
 
-/* dof tree of the fixed topology: parent of dof d */
-__device__ __forceinline__ int dof_parent(int d) { return d < 6 ? d - 1 : ((d - 6) % 3 == 0 ? 5 : d - 1); }
+/* dof tree of the fixed topology: body of dof d */
 __device__ __forceinline__ int dof_body(int d) { return d < 6 ? 0 : d - 5; }
 
 /* solimp impedance (mj_makeImpedance::getimpedance) */

@@ -80,7 +80,7 @@ extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_
       int pass = call.first_pass;
       gq::WaveCtx C;
       const bool boxes = M.nbox > 0 || M.hf_nrow > 0, self = M.nsp > 0;
-      bool prims = false; /* as gq_api.hip scene_variant: the PRIM variants serve robots with sphere / capsule / box link geoms */
+      bool prims = false; /* as gq_api.hip model_scene: the PRIM variants serve robots with sphere / capsule / box link geoms */
       for (int g = 0; g < M.nlg; g++) prims = prims || M.lg[g].ptype == 2 || M.lg[g].ptype == 3 || M.lg[g].ptype == 6;
       int hint = M.solver == 1 ? gq::load_rows<1>(f.s, call, W, e, pass == 0, C) : gq::load_rows<0>(f.s, call, W, e, pass == 0, C);
       bool respawn = call.auto_reset == 2 && C.pend;
