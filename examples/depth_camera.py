@@ -1,0 +1,44 @@
+"""The reference's camera example (examples/aliengo_with_camera.py), batched: depth and segmentation images of every env from the
+``robotcam`` camera on aliengo's trunk, saved as .npy instead of shown with cv2.
+
+    python examples/depth_camera.py [scene] [num_envs] [steps]"""
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from gym_quadruped_amd.quadruped_env import QuadrupedEnv  # noqa: E402
+from gym_quadruped_amd.sensors import Camera  # noqa: E402
+
+robot_name = 'aliengo'
+scene_name = sys.argv[1] if len(sys.argv) > 1 else 'stairs'   # "flat", "stairs", "perlin", "random_boxes", ...
+num_envs = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+steps = int(sys.argv[3]) if len(sys.argv) > 3 else 100
+
+env = QuadrupedEnv(
+    robot=robot_name,
+    scene=scene_name,
+    ref_base_lin_vel=0.5,
+    base_vel_command_type='forward',
+    state_obs_names=tuple(QuadrupedEnv.ALL_OBS),
+    num_envs=num_envs,
+)
+obs = env.reset()
+
+cam = Camera(
+    width=640,
+    height=480,
+    fps=30,
+    mj_model=env.robot_model,
+    mj_data=env.sim_data,
+    cam_name='robotcam',  # camera must be inserted on the .xml file of the robot in order to work
+    save_dir='data_',
+)
+
+for _ in range(steps):
+    sim_time = float(env.simulation_time[0])            # every env advances in lock step
+    action = env.action_space.sample() * 0
+    state, reward, is_terminated, is_truncated, info = env.step(action=action)
+    if sim_time - cam.last_sim_time >= cam.interval:    # camera at its own fps
+        cam.shoot(autosave=True)                        # depth [N, H, W] and seg [N, H, W] as .npy
+        cam.last_sim_time = float(env.simulation_time[0])
+env.close()

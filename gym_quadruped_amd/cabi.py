@@ -12,7 +12,7 @@ import numpy as np
 from .mjcf import ModelDesc
 
 GQ_NLEG = 4
-GQ_ABI_VERSION = 630   # include/gq.h
+GQ_ABI_VERSION = 640   # include/gq.h
 # optional extra output rows of the step kernel (include/gq.h gq_batch_set_outputs)
 GQ_DYN = dict(MC=0, MB=108, BIAS=144, XPOS=162, XMAT=201, FOOT=318, STRIDE=336)
 GQ_CON_MAX, GQ_CON_REC = 12, 24
@@ -395,6 +395,29 @@ def hull_graphs(md: ModelDesc):
     out = (adr, num, np.asarray(adj if adj else [0], dtype=np.int32))
     _GRAPH_CACHE[key] = out
     return out
+
+
+def hull_planes(md: ModelDesc, tol=1e-9):
+    """Face planes of the mesh clouds' convex hulls, for gq_camera's Cyrus-Beck test: scipy's ``ConvexHull(...).equations`` with the
+    coplanar triangles of one facet merged, each plane's offset then set to the largest n.v over the cloud (so every vertex lies inside and
+    the plane touches the hull).  Geom frame.  Returns (planes [P][4] f64 (n, d) with n.x <= d inside, plane_adr [ncloud + 1] int32
+    prefix offsets by cloud; clouds no mesh geom uses have none)."""
+    from scipy.spatial import ConvexHull
+    mesh_clouds = {int(md.geom_cloudid[g]) for g in range(md.ngeom) if int(md.geom_cloudid[g]) >= 0 and int(md.geom_type[g]) == GEOM_MESH}
+    planes, adr = [], [0]
+    for cl in range(len(md.cloud_vertnum)):
+        if cl in mesh_clouds:
+            a, n = int(md.cloud_vertadr[cl]), int(md.cloud_vertnum[cl])
+            V = np.asarray(md.vert_pos[a:a + n], dtype=np.float64)
+            kept = []
+            for eq in ConvexHull(V).equations:
+                nrm = eq[:3] / np.linalg.norm(eq[:3])
+                if not any(np.dot(nrm, k) > 1.0 - 1e-10 for k in kept):
+                    kept.append(nrm)
+            for nrm in kept:
+                planes.append(np.concatenate([nrm, [float(np.max(V @ nrm))]]))
+        adr.append(len(planes))
+    return np.asarray(planes if planes else np.zeros((0, 4)), dtype=np.float64).reshape(-1, 4), np.asarray(adr, dtype=np.int32)
 
 
 class MarshalledModel:

@@ -18,10 +18,12 @@
 #include <gq_device.h>
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
+#include "gq_camera.h"
 
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
+extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
                                     float dist_x, float dist_y, float* out, hipStream_t stream);
@@ -47,6 +49,8 @@ struct GqModel {
   float* hf;            /* device elevations of the scene's height field (NULL: none) */
   int nvert;
   gq::Scene scene;      /* the step-kernel variants the model runs (model_scene) */
+  int ngeom, ncloud;
+  int32_t lg_cloud[GQ_MAXLG]; /* GqModelDesc cloud of lg[i] (gq_camera's face-plane table is indexed by cloud) */
 };
 /* world boxes / height field: the world scenes, split by whether the robot has sphere / capsule / box link geoms (exact pair routines
  * compiled in; gq_step_body.h PRIM); flat: the self-collision stage runs for a model with self-collision pairs */
@@ -70,6 +74,8 @@ struct GqBatch {
   int32_t* xq;          /* device: convex pair exchange (gq_exchange.h) - models with convex self pairs only, else NULL */
   int xq_slots; bool xq_on;
   float* sepc;          /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
+  float* cam_rec;       /* device: gq_camera's pose-pass records [N][GQ_CAM_REC] (lazily allocated) */
+  double* cam_pos;      /* device: ... and camera origins [N][3] */
   int stop_stage;       /* profiling aid: GQ_STOP_STAGE at batch creation */
   /* argument block of step_kernel: device copy, host shadow of what the device holds, pinned staging ring for the
    * (rare) stream-ordered re-upload */
@@ -147,6 +153,8 @@ int gq_model_create(const GqModelDesc* desc, int device, GqModel** out) {
   std::vector<float> vx, vy, vz;
   if (gq_build_dev_model(desc, &m->host, &vx, &vy, &vz, g_err, sizeof g_err)) { delete m; return GQ_EINVAL; }
   m->device = device; m->nvert = (int)vx.size(); m->scene = model_scene(m->host);
+  m->ngeom = desc->ngeom; m->ncloud = desc->ncloud;
+  for (int i = 0; i < m->host.nlg; i++) m->lg_cloud[i] = desc->geom_cloudid[m->host.item_geomid[4 + i]];
   DeviceGuard guard(device);
   if (m->host.hf_nrow > 0) {
     std::vector<float> hf;
@@ -243,6 +251,7 @@ int gq_batch_destroy(GqBatch* b) {
   if (!b) return GQ_OK;
   DeviceGuard guard(b->model->device);
   hipFree(b->dev); hipFree(b->friction_next); hipFree(b->pending); hipFree(b->lift_pending); hipFree(b->load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
+  hipFree(b->cam_rec); hipFree(b->cam_pos);
   if (b->staging) hipHostFree(b->staging);
   if (b->batch_staging) hipHostFree(b->batch_staging);
   mailbox_free(b);
@@ -742,6 +751,46 @@ int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float
   if (!b || !origin || !dir || !dist || n_rays <= 0) { SET_ERR("gq_ray: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   gq_launch_ray(b->model->dev, origin, dir, b->host.n_envs * n_rays, dist, geom, (hipStream_t)hip_stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
+              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream) {
+  if (!b || !qpos || !pos || !quat || !depth) { SET_ERR("gq_camera: null argument"); return GQ_EINVAL; }
+  if (qpos_stride < 19) { SET_ERR("gq_camera: qpos_stride %d < 19", qpos_stride); return GQ_EINVAL; }
+  if (body < 0 || body > GQ_NB) { SET_ERR("gq_camera: body id %d out of range (0 = world .. %d)", body, GQ_NB); return GQ_EINVAL; }
+  if (width <= 0 || height <= 0 || (size_t)width * height > (1u << 24)) { SET_ERR("gq_camera: bad image size %d x %d", width, height); return GQ_EINVAL; }
+  if (!(fovy_deg > 0.0f && fovy_deg < 180.0f)) { SET_ERR("gq_camera: fovy %g is not in (0, 180) degrees", (double)fovy_deg); return GQ_EINVAL; }
+  if (!(znear > 0.0f && zfar > znear)) { SET_ERR("gq_camera: need 0 < znear < zfar (got %g, %g)", (double)znear, (double)zfar); return GQ_EINVAL; }
+  if (flags & ~3) { SET_ERR("gq_camera: unknown flags 0x%x", flags); return GQ_EINVAL; }
+  const double qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
+  if (!(qn > 0.0)) { SET_ERR("gq_camera: zero quaternion"); return GQ_EINVAL; }
+  GqModel* m = b->model;
+  gq::CamCall c{};
+  for (int i = 0; i < m->host.nlg; i++) {
+    if (m->host.lg[i].ptype != 0) continue;
+    if (!hull_planes || !hull_plane_adr) { SET_ERR("gq_camera: the model has hull geoms and no face planes were passed"); return GQ_EINVAL; }
+    const int cl = m->lg_cloud[i];
+    if (cl < 0 || cl >= m->ncloud) { SET_ERR("gq_camera: link geom %d has no cloud", i); return GQ_EINVAL; }
+    c.plane_adr[i] = hull_plane_adr[cl]; c.plane_num[i] = hull_plane_adr[cl + 1] - hull_plane_adr[cl];
+    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("gq_camera: cloud %d has %d face planes (a hull has at least 4)", cl, c.plane_num[i]); return GQ_EINVAL; }
+  }
+  DeviceGuard guard(m->device);
+  const int n = b->host.n_envs;
+  if (!b->cam_rec) {
+    HIP_TRY(hipMalloc(&b->cam_rec, sizeof(float) * GQ_CAM_REC * (size_t)n));
+    HIP_TRY(hipMalloc(&b->cam_pos, sizeof(double) * 3 * (size_t)n));
+  }
+  const double th = std::tan(0.5 * (double)fovy_deg * 3.14159265358979323846 / 180.0);
+  c.qpos = qpos; c.qpos_stride = qpos_stride; c.body = body;
+  for (int k = 0; k < 3; k++) c.pos[k] = pos[k];
+  for (int k = 0; k < 4; k++) c.quat[k] = (float)(quat[k] / qn);
+  c.width = width; c.height = height; c.flags = flags; c.ngeom = m->ngeom;
+  c.tan_x = (float)(th * width / height); c.tan_y = (float)th; c.znear = znear; c.zfar = zfar;
+  c.planes = hull_planes; c.rec = b->cam_rec; c.cpos = b->cam_pos; c.xpos_out = cam_xpos; c.xmat_out = cam_xmat; c.depth = depth; c.seg = seg;
+  gq_launch_camera(m->dev, &c, n, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

@@ -1,0 +1,351 @@
+/*
+ * gq_camera.h - the depth / segmentation camera (include/gq.h gq_camera; the reference renders it with mujoco.Renderer,
+ * sensors/rgbd_camera.py) as a ray caster, in two launches (gq_kernels.hip camera_pose_kernel, camera_pixel_kernel):
+ *  - pose pass, one wavefront per env: the kinematics of the caller's qpos, the camera frame (body pose o camera offset), and, lane = robot
+ *    geom, every geom's frame relative to the camera (fp32) into the batch's scratch record.  The camera origin in the world is fp64.
+ *  - pixel pass, one wavefront per 8 x 8 tile of one env: lane = candidate culls the robot geoms and the world boxes against the tile's
+ *    view cone (two ballots, as heightmap_rays does for boxes), then lane = pixel walks the survivors wave-uniformly.
+ * Also the static-geom ray tests that gq_ray's ray_kernel and the pixel pass share (slab, height-field cell walk).
+ * Semantics: pixel (r, c) looks along ((2 (c + .5) / W - 1) tan(fovy / 2) W / H, (1 - 2 (r + .5) / H) tan(fovy / 2), -1) in
+ * the camera frame, so a hit's ray parameter is its planar depth; the nearest hit in [znear, zfar] wins, none gives zfar.  Convex geoms are
+ * seen only from outside (front faces): a ray that starts inside one, or enters it before znear, does not see it.
+ */
+#pragma once
+#include "gq_step_body.h"
+
+namespace gq {
+
+#define GQ_CAM_TILE 8                          /* a wavefront renders one GQ_CAM_TILE x GQ_CAM_TILE tile */
+#define GQ_CAM_NROB (4 + GQ_MAXLG)             /* robot geoms: the four foot spheres, then lg[] */
+#define GQ_CAM_REC (12 + 12 * GQ_CAM_NROB)     /* scratch floats per env: camera rotation (9, world), pad (3), per robot geom R (9) t (3) */
+
+/* one gq_camera call, by value in both launches */
+struct CamCall {
+  const double* qpos; int qpos_stride;
+  int body;                                    /* ModelDesc body of the camera, 0 = world */
+  double pos[3]; float quat[4];                /* camera frame in the body frame (quat normalised) */
+  int width, height, flags, ngeom;             /* flags: bit 0 robot, bit 1 static scene; ngeom: segmentation id of the floor */
+  float tan_x, tan_y, znear, zfar;             /* tan(fovy / 2) W / H, tan(fovy / 2) */
+  const float* planes;                         /* [P][4] face planes n.x <= d of the hull geoms, geom frame */
+  int32_t plane_adr[GQ_MAXLG], plane_num[GQ_MAXLG]; /* per lg[]: first plane and count (0: not a hull) */
+  float* rec;                                  /* [N][GQ_CAM_REC] batch scratch: pose pass -> pixel pass */
+  double* cpos;                                /* [N][3] batch scratch: camera origin, world, fp64 */
+  double* xpos_out; float* xmat_out;           /* optional copies for the caller */
+  float* depth; int32_t* seg;                  /* [N][H][W] */
+};
+
+/* ---- static-geom ray tests (T = double: gq_ray; the pixel pass uses float for boxes, origin relative to the camera) */
+template <class T> __device__ __forceinline__ T ray_far();   /* "no bound yet" */
+template <> __device__ __forceinline__ double ray_far<double>() { return 1e300; }
+template <> __device__ __forceinline__ float ray_far<float>() { return 1e30f; }
+template <class T>
+__device__ inline bool ray_triangle(const T* o, const T* d, const T* a, const T* b, const T* c, T& t) {
+  const T e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  const T pv[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+  const T det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
+  if (fabs(det) < T(1e-14)) return false;
+  const T inv = T(1) / det, tv[3] = {o[0] - a[0], o[1] - a[1], o[2] - a[2]};
+  const T u = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) * inv;
+  if (u < T(-1e-9) || u > T(1) + T(1e-9)) return false;
+  const T qv[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+  const T v = (d[0] * qv[0] + d[1] * qv[1] + d[2] * qv[2]) * inv;
+  if (v < T(-1e-9) || u + v > T(1) + T(1e-9)) return false;
+  t = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * inv;
+  return t >= T(0);
+}
+/* slab test of the ray o + t d against the box |x_k| <= s_k (box frame); tin / tout come in as the caller's bounds */
+template <class T>
+__device__ inline bool ray_slab(const T* ol, const T* dl, const T* s, T& tin, T& tout) {
+  bool hit = true;
+  for (int k = 0; k < 3 && hit; k++) {
+    if (fabs(dl[k]) < T(1e-14)) { hit = fabs(ol[k]) <= s[k]; continue; }
+    T t0 = (-s[k] - ol[k]) / dl[k], t1 = (s[k] - ol[k]) / dl[k];
+    if (t0 > t1) { const T tt = t0; t0 = t1; t1 = tt; }
+    if (t0 > tin) tin = t0;
+    if (t1 < tout) tout = t1;
+    hit = tin <= tout;
+  }
+  return hit;
+}
+/* a world box: r = origin - box centre, d: direction, both in world axes */
+template <class T, class Box>
+__device__ inline bool ray_box(const Box& B, const T* r, const T* d, T& tin, T& tout) {
+  T ol[3], dl[3], s[3];
+  for (int k = 0; k < 3; k++) {
+    ol[k] = (T)B.mat[k] * r[0] + (T)B.mat[3 + k] * r[1] + (T)B.mat[6 + k] * r[2];
+    dl[k] = (T)B.mat[k] * d[0] + (T)B.mat[3 + k] * d[1] + (T)B.mat[6 + k] * d[2];
+    s[k] = (T)B.size[k];
+  }
+  return ray_slab(ol, dl, s, tin, tout);
+}
+/* the height field: ol = origin - hf_pos.  The cells under the ray's ground track are walked from the parameter max(tmin, entry into the
+ * field's bounding box), two triangles each; returns the first hit >= tmin, -1 if none. */
+template <class T, class Mref>
+__device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T tmin) {
+  const T sx = M.hf_sx, sy = M.hf_sy, dx = M.hf_dx, dy = M.hf_dy, zmax = (T)M.hf_zmax;
+  /* parameter interval of the ray inside the field's bounding box [-sx, sx] x [-sy, sy] x [0, zmax] */
+  T t0 = tmin, t1 = ray_far<T>();
+  bool in = true;
+  const T lo[3] = {-sx, -sy, T(0)}, hi[3] = {sx, sy, zmax};
+  for (int k = 0; k < 3 && in; k++) {
+    if (fabs(d[k]) < T(1e-14)) { in = ol[k] >= lo[k] && ol[k] <= hi[k]; continue; }
+    T a = (lo[k] - ol[k]) / d[k], b2 = (hi[k] - ol[k]) / d[k];
+    if (a > b2) { const T tt = a; a = b2; b2 = tt; }
+    if (a > t0) t0 = a;
+    if (b2 < t1) t1 = b2;
+    in = t0 <= t1;
+  }
+  if (!in) return T(-1);
+  const int nc = M.hf_ncol, nr = M.hf_nrow;
+  const float* H = M.hf_data;
+  /* walk the cells along the ground track from t0 to t1 (2-D DDA) */
+  T t = t0;
+  const T px = ol[0] + t * d[0], py = ol[1] + t * d[1];
+  int c = (int)floor((px + sx) / dx), r = (int)floor((py + sy) / dy);
+  c = c < 0 ? 0 : (c > nc - 2 ? nc - 2 : c); r = r < 0 ? 0 : (r > nr - 2 ? nr - 2 : r);
+  const int stc = d[0] > 0 ? 1 : -1, str = d[1] > 0 ? 1 : -1;
+  for (int it = 0; it < nc + nr + 2; it++) {
+    const T x0 = -sx + dx * c, y0 = -sy + dy * r, x1 = x0 + dx, y1 = y0 + dy;
+    const T h00 = H[r * nc + c], h10 = H[r * nc + c + 1], h01 = H[(r + 1) * nc + c], h11 = H[(r + 1) * nc + c + 1];
+    const T A[3] = {x0, y0, h00}, B[3] = {x1, y0, h10}, Cc[3] = {x0, y1, h01}, D[3] = {x1, y1, h11};
+    T th, tb = T(-1);
+    if (ray_triangle(ol, d, A, B, Cc, th) && th >= tmin) tb = th;
+    if (ray_triangle(ol, d, D, Cc, B, th) && th >= tmin && (tb < T(0) || th < tb)) tb = th;
+    if (tb >= T(0)) return tb;
+    /* next cell: the nearer of the two cell borders the track crosses */
+    const T tx = fabs(d[0]) < T(1e-14) ? ray_far<T>() : ((stc > 0 ? x1 : x0) - ol[0]) / d[0];
+    const T ty = fabs(d[1]) < T(1e-14) ? ray_far<T>() : ((str > 0 ? y1 : y0) - ol[1]) / d[1];
+    if (tx < ty) { c += stc; t = tx; } else { r += str; t = ty; }
+    if (t > t1 || c < 0 || r < 0 || c > nc - 2 || r > nr - 2) break;
+  }
+  return T(-1);
+}
+
+/* ---- robot geoms, in the geom frame (o, d: the ray there).  Each returns the entry parameter (front face), or -1 when the ray starts
+ * inside or misses; the caller keeps entries in [znear, best]. */
+__device__ inline float cam_sphere(V3 o, V3 d, float r) {
+  const float a = dot(d, d), b = dot(o, d), c = dot(o, o) - r * r;
+  if (c <= 0.0f) return -1.0f;
+  const float disc = b * b - a * c;
+  return disc < 0.0f ? -1.0f : (-b - sqrtf(disc)) / a;
+}
+__device__ inline float cam_cylinder(V3 o, V3 d, float r, float h) {   /* axis z, radius r, half length h */
+  float tin = -1e30f, tout = 1e30f;
+  if (fabsf(d.z) < 1e-20f) { if (fabsf(o.z) > h) return -1.0f; }
+  else {
+    float t0 = (-h - o.z) / d.z, t1 = (h - o.z) / d.z;
+    if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
+    tin = t0; tout = t1;
+  }
+  const float a = d.x * d.x + d.y * d.y, b = o.x * d.x + o.y * d.y, c = o.x * o.x + o.y * o.y - r * r;
+  if (a < 1e-20f) { if (c > 0.0f) return -1.0f; }
+  else {
+    const float disc = b * b - a * c;
+    if (disc < 0.0f) return -1.0f;
+    const float s = sqrtf(disc);
+    tin = fmaxf(tin, (-b - s) / a); tout = fminf(tout, (-b + s) / a);
+  }
+  return tin <= tout ? tin : -1.0f;
+}
+__device__ inline float cam_capsule(V3 o, V3 d, float r, float h) {
+  const float zc = fminf(fmaxf(o.z, -h), h);
+  if (o.x * o.x + o.y * o.y + (o.z - zc) * (o.z - zc) <= r * r) return -1.0f;   /* inside */
+  float best = 1e30f;
+  const float tc = cam_cylinder(o, d, r, h), t0 = cam_sphere(o - v3(0.0f, 0.0f, h), d, r), t1 = cam_sphere(o + v3(0.0f, 0.0f, h), d, r);
+  if (tc > 0.0f) best = tc;
+  if (t0 > 0.0f && t0 < best) best = t0;
+  if (t1 > 0.0f && t1 < best) best = t1;
+  return best < 1e30f ? best : -1.0f;
+}
+/* Cyrus-Beck against the hull's face planes; the plane loop is wave-uniform (the addresses too: scalar loads) */
+__device__ inline float cam_hull(V3 o, V3 d, const float* P, int n) {
+  float tin = -1e30f, tout = 1e30f;
+  bool miss = false;
+  for (int k = 0; k < n; k++) {
+    const V3 nk = v3(P[4 * k], P[4 * k + 1], P[4 * k + 2]);
+    const float den = dot(nk, d), num = P[4 * k + 3] - dot(nk, o);
+    if (fabsf(den) < 1e-20f) { miss |= num < 0.0f; continue; }
+    const float t = num / den;
+    if (den < 0.0f) tin = fmaxf(tin, t); else tout = fminf(tout, t);
+  }
+  return !miss && tin <= tout ? tin : -1.0f;
+}
+
+/* pose pass: one wavefront per env; W: the wave's LDS */
+template <class Mref>
+__device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall& c, const int env) {
+  const int lane = lane_id();
+#if GQ_TICKSET
+  if (lane == 0) W.tk_T = nullptr;
+#endif
+  if (lane < 19) {
+    const double q = c.qpos[(size_t)env * c.qpos_stride + lane];
+    if (lane < 2) W.bxy[lane] = q;
+    else if (lane == 2) W.basez = (float)q;
+    else if (lane < 7) W.qb[lane - 3] = (float)q;
+    else W.qj[lane - 7] = (float)q;
+  }
+  wave_barrier();
+  stage_kinematics(W, link_fetch(m, lane));
+  /* the camera frame relative to the base x/y, like every kinematic quantity */
+  float Rq[9], Rc[9];
+  q2mat(Rq, Q4{c.quat[0], c.quat[1], c.quat[2], c.quat[3]});
+  V3 pc;
+  if (c.body == 0) {
+    pc = v3((float)(c.pos[0] - W.bxy[0]), (float)(c.pos[1] - W.bxy[1]), (float)c.pos[2]);
+    for (int k = 0; k < 9; k++) Rc[k] = Rq[k];
+  } else {
+    const int kb = c.body - 1;
+    pc = ld3(W.xpos[kb]) + matvec(W.xmat[kb], v3((float)c.pos[0], (float)c.pos[1], (float)c.pos[2]));
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) Rc[3 * i + j] = W.xmat[kb][3 * i] * Rq[j] + W.xmat[kb][3 * i + 1] * Rq[3 + j] + W.xmat[kb][3 * i + 2] * Rq[6 + j];
+  }
+  float* rec = c.rec + (size_t)env * GQ_CAM_REC;
+  if (lane < 9) {
+    rec[lane] = Rc[lane];
+    if (c.xmat_out) c.xmat_out[(size_t)env * 9 + lane] = Rc[lane];
+  } else if (lane < 12) {
+    const int k = lane - 9;
+    const double p = c.body == 0 ? c.pos[k] : (k == 0 ? W.bxy[0] + (double)pc.x : k == 1 ? W.bxy[1] + (double)pc.y : (double)pc.z);
+    c.cpos[(size_t)env * 3 + k] = p;
+    if (c.xpos_out) c.xpos_out[(size_t)env * 3 + k] = p;
+  }
+  /* lane = robot geom: its frame in the camera frame, R = Rc' Rg, t = Rc' (pg - pc) */
+  const int nrob = 4 + m.nlg;
+  if (lane < nrob) {
+    V3 pg;
+    float Rg[9];
+    if (lane < 4) {
+      const FootRec FR = foot_fetch(m, lane);
+      const int b = 3 + 3 * FR.leg;
+      pg = ld3(W.xpos[b]) + matvec(W.xmat[b], ld3(FR.pos));
+      for (int k = 0; k < 9; k++) Rg[k] = (k % 4 == 0) ? 1.0f : 0.0f;
+    } else {
+      const auto& G = m.lg[lane - 4];
+      const int b = G.body;
+      pg = ld3(W.xpos[b]) + matvec(W.xmat[b], ld3(G.pos));
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Rg[3 * i + j] = W.xmat[b][3 * i] * G.mat[j] + W.xmat[b][3 * i + 1] * G.mat[3 + j] + W.xmat[b][3 * i + 2] * G.mat[6 + j];
+    }
+    float* o = rec + 12 + 12 * lane;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) o[3 * i + j] = Rc[i] * Rg[j] + Rc[3 + i] * Rg[3 + j] + Rc[6 + i] * Rg[6 + j];
+    st3(o + 9, matTvec(Rc, pg - pc));
+  }
+}
+
+/* does the sphere (centre ctr, camera frame) meet the cone (unit axis ax, half angle (ca, sa)) within the depth range?  Conservative:
+ * behind the apex the distance to the cone is underestimated. */
+__device__ __forceinline__ bool cam_cone_sphere(V3 ctr, float rad, V3 ax, float ca, float sa, float znear, float zfar) {
+  rad += 1e-3f;   /* slack for fp32 rounding of the frames: culling must never drop a visible geom */
+  if (-ctr.z + rad < znear || -ctr.z - rad > zfar) return false;
+  const float a = dot(ctr, ax);
+  const V3 p = ctr - a * ax;
+  return sqrtf(dot(p, p)) * ca - a * sa <= rad;
+}
+
+/* pixel pass: one wavefront renders tile `tile` of env `env` */
+template <class Mref>
+__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const int tile, const int env) {
+  const int lane = lane_id(), W = c.width, H = c.height;
+  const int tiles_x = (W + GQ_CAM_TILE - 1) / GQ_CAM_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
+  const int row = ty * GQ_CAM_TILE + lane / GQ_CAM_TILE, col = tx * GQ_CAM_TILE + lane % GQ_CAM_TILE;
+  const bool valid = row < H && col < W;
+  const int r = row < H ? row : H - 1, cl = col < W ? col : W - 1;   /* lanes past the image edge mirror a pixel and do not store */
+  const V3 d = v3((2.0f * ((float)cl + 0.5f) / (float)W - 1.0f) * c.tan_x, (1.0f - 2.0f * ((float)r + 0.5f) / (float)H) * c.tan_y, -1.0f);
+  const float* rec = c.rec + (size_t)env * GQ_CAM_REC;
+  float Rc[9];
+  for (int k = 0; k < 9; k++) Rc[k] = rec[k];
+  const double co[3] = {c.cpos[(size_t)env * 3], c.cpos[(size_t)env * 3 + 1], c.cpos[(size_t)env * 3 + 2]};
+  /* the tile's view cone: axis through the tile centre, half angle to the farthest corner ray */
+  const int c0 = tx * GQ_CAM_TILE, c1 = imin(c0 + GQ_CAM_TILE, W), r0 = ty * GQ_CAM_TILE, r1 = imin(r0 + GQ_CAM_TILE, H);
+  const float xl = (2.0f * c0 / W - 1.0f) * c.tan_x, xh = (2.0f * c1 / W - 1.0f) * c.tan_x;
+  const float yh = (1.0f - 2.0f * r0 / H) * c.tan_y, yl = (1.0f - 2.0f * r1 / H) * c.tan_y;
+  V3 ax = v3(0.5f * (xl + xh), 0.5f * (yl + yh), -1.0f);
+  ax = (1.0f / sqrtf(dot(ax, ax))) * ax;
+  float ca = 1.0f;
+  for (int k = 0; k < 4; k++) {
+    const V3 q = v3(k & 1 ? xh : xl, k & 2 ? yh : yl, -1.0f);
+    ca = fminf(ca, dot(q, ax) / sqrtf(dot(q, q)));
+  }
+  const float sa = sqrtf(fmaxf(0.0f, 1.0f - ca * ca));
+  /* cull, lane = candidate */
+  const int nrob = 4 + M.nlg, nbox = M.nbox;
+  uint64_t rob = 0, box[2] = {0, 0};
+  if (c.flags & 1) {
+    bool near = false;
+    if (lane < nrob) {
+      const float* g = rec + 12 + 12 * lane;
+      V3 ctr = ld3(g + 9);
+      float rad;
+      if (lane < 4) rad = M.foot_radius[lane];
+      else {
+        const auto& G = M.lg[lane - 4];
+        ctr = ctr + matvec(g, ld3(G.aabb_c));
+        rad = sqrtf(G.aabb_h[0] * G.aabb_h[0] + G.aabb_h[1] * G.aabb_h[1] + G.aabb_h[2] * G.aabb_h[2]) + G.radius;
+      }
+      near = cam_cone_sphere(ctr, rad, ax, ca, sa, c.znear, c.zfar);
+    }
+    rob = ballot(near);
+  }
+  if (c.flags & 2)
+    for (int half = 0; half < 2 && half * GQ_WAVE < nbox; half++) { /* wave-uniform */
+      const int b = half * GQ_WAVE + lane;
+      bool near = false;
+      if (b < nbox) {
+        const V3 v = v3((float)((double)M.box[b].pos[0] - co[0]), (float)((double)M.box[b].pos[1] - co[1]), (float)((double)M.box[b].pos[2] - co[2]));
+        near = cam_cone_sphere(matTvec(Rc, v), M.box[b].rad, ax, ca, sa, c.znear, c.zfar);
+      }
+      box[half] = ballot(near);
+    }
+  /* cast, lane = pixel */
+  float best = c.zfar;
+  int id = -1;
+  const V3 dw = matvec(Rc, d);   /* the ray in world axes */
+  if (c.flags & 2) {
+    if (dw.z < 0.0f && co[2] >= 0.0) { /* the floor: a one-sided plane, hit from above */
+      const float t = (float)(-co[2] / (double)dw.z);
+      if (t >= c.znear && t <= best) { best = t; id = c.ngeom; }
+    }
+    const float dv[3] = {dw.x, dw.y, dw.z};
+    for (int half = 0; half < 2; half++)
+      for (uint64_t todo = box[half]; todo; todo &= todo - 1) { /* wave-uniform */
+        const int b = half * GQ_WAVE + ffs64(todo);
+        const float rv[3] = {(float)(co[0] - (double)M.box[b].pos[0]), (float)(co[1] - (double)M.box[b].pos[1]), (float)(co[2] - (double)M.box[b].pos[2])};
+        float tin = -1e30f, tout = 1e30f;
+        if (ray_box(M.box[b], rv, dv, tin, tout) && tin >= c.znear && tin <= best) { best = tin; id = c.ngeom + 1 + b; }
+      }
+    if (M.hf_nrow > 0) { /* fp64: the walk runs in the field's own coordinates */
+      const double ol[3] = {co[0] - (double)M.hf_pos[0], co[1] - (double)M.hf_pos[1], co[2] - (double)M.hf_pos[2]}, dd[3] = {dw.x, dw.y, dw.z};
+      const double t = ray_hfield(M, ol, dd, (double)c.znear);
+      if (t >= 0.0 && t <= (double)best) { best = (float)t; id = c.ngeom + 1 + nbox; }
+    }
+  }
+  for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform */
+    const int g = ffs64(todo);
+    const float* gr = rec + 12 + 12 * g;
+    const V3 t = ld3(gr + 9), o = (-1.0f) * matTvec(gr, t), dl = matTvec(gr, d);
+    float th;
+    if (g < 4) th = cam_sphere(o, dl, M.foot_radius[g]);
+    else {
+      const auto& G = M.lg[g - 4];
+      const int pt = G.ptype;
+      if (pt == 2) th = cam_sphere(o, dl, G.psize[0]);
+      else if (pt == 3) th = cam_capsule(o, dl, G.psize[0], G.psize[1]);
+      else if (pt == 5) th = cam_cylinder(o, dl, G.psize[0], G.psize[1]);
+      else if (pt == 6) {
+        const float ov[3] = {o.x, o.y, o.z}, dv[3] = {dl.x, dl.y, dl.z}, s[3] = {G.psize[0], G.psize[1], G.psize[2]};
+        float tin = -1e30f, tout = 1e30f;
+        th = ray_slab(ov, dv, s, tin, tout) ? tin : -1.0f;
+      } else th = cam_hull(o, dl, c.planes + 4 * c.plane_adr[g - 4], c.plane_num[g - 4]);
+    }
+    if (th >= c.znear && th <= best) { best = th; id = M.item_geomid[g]; }
+  }
+  if (valid) {
+    const size_t px = ((size_t)env * H + row) * W + col;
+    c.depth[px] = best;
+    if (c.seg) c.seg[px] = id;
+  }
+}
+
+}  // namespace gq

@@ -52,6 +52,8 @@ _JOINT_DEF = dict(type='hinge', pos='0 0 0', axis='0 0 1', range='0 0', limited=
                   actuatorfrcrange='0 0', actuatorfrclimited='auto')
 _MOTOR_DEF = dict(ctrlrange='0 0', ctrllimited='auto', forcerange='0 0', forcelimited='auto', gear='1 0 0 0 0 0')
 _SITE_DEF = dict(pos='0 0 0', quat='1 0 0 0')
+_CAMERA_DEF = dict(pos='0 0 0', fovy='45', mode='fixed')
+CAMERA_MODES = {'fixed': 0, 'track': 1, 'trackcom': 2, 'targetbody': 3, 'targetbodycom': 4}
 
 
 def _f(s, n=None):
@@ -95,6 +97,39 @@ def quat_z_to_vec(v):
 
 def axis_angle_quat(axis, angle):
     return np.concatenate([[np.cos(angle / 2)], np.sin(angle / 2) * np.asarray(axis)])
+
+
+def mat_to_quat(R):
+    """Unit quaternion (wxyz, w >= 0) of a rotation matrix."""
+    from scipy.spatial.transform import Rotation
+    q = Rotation.from_matrix(np.asarray(R, dtype=np.float64)).as_quat(scalar_first=True)
+    return q if q[0] >= 0 else -q
+
+
+def frame_quat(a, eulerseq='xyz'):
+    """Orientation of a frame element (MuJoCo's alternative orientation specifiers, radians): ``axisangle``, ``xyaxes``,
+    ``zaxis``, ``euler`` (sequence ``<compiler eulerseq>``: lower case rotates about the moving axes, upper case about
+    the fixed ones), else ``quat``.  Returns the normalised quaternion (wxyz)."""
+    if 'axisangle' in a:
+        aa = _f(a['axisangle'], 4)
+        q = axis_angle_quat(aa[:3] / np.linalg.norm(aa[:3]), aa[3])
+    elif 'xyaxes' in a:
+        xy = _f(a['xyaxes'], 6)
+        x = xy[:3] / np.linalg.norm(xy[:3])
+        y = xy[3:] - x * np.dot(x, xy[3:])
+        y /= np.linalg.norm(y)
+        q = mat_to_quat(np.stack([x, y, np.cross(x, y)], 1))
+    elif 'zaxis' in a:
+        q = quat_z_to_vec(_f(a['zaxis'], 3))
+    elif 'euler' in a:
+        e = _f(a['euler'], 3)
+        q = np.array([1.0, 0.0, 0.0, 0.0])
+        for ax, ang in zip(eulerseq, e):
+            r = axis_angle_quat(np.eye(3)['xyz'.index(ax.lower())], ang)
+            q = quat_mul(q, r) if ax.islower() else quat_mul(r, q)
+    else:
+        q = _f(a.get('quat', '1 0 0 0'), 4)
+    return q / np.linalg.norm(q)
 
 
 # ----------------------------------------------------------------------------- defaults
@@ -272,6 +307,13 @@ class ModelDesc:
     # <contact><exclude body1= body2=/> pairs (body ids)
     exclude_body1: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
     exclude_body2: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
+    # cameras (<camera> inside bodies; cam_mode: CAMERA_MODES, 0 = fixed)
+    cam_names: list = dataclasses.field(default_factory=list)
+    cam_bodyid: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
+    cam_pos: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros((0, 3)))
+    cam_quat: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros((0, 4)))
+    cam_fovy: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0))   # degrees
+    cam_mode: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
 
     # ---- (de)serialisation: plain JSON tables
     def to_json(self) -> str:
@@ -287,7 +329,10 @@ class ModelDesc:
 
     @classmethod
     def from_json(cls, text: str) -> 'ModelDesc':
-        d = json.loads(text)
+        return cls.from_dict(json.loads(text))
+
+    @classmethod
+    def from_dict(cls, d: dict) -> 'ModelDesc':
         kw = {}
         for f in dataclasses.fields(cls):
             if f.name not in d:   # field added after the table was written: dataclass default
@@ -341,6 +386,7 @@ class _Compiler:
             raise ValueError('only <compiler angle="radian"> models are supported')
         self.autolimits = comp.get('autolimits', 'true') == 'true'
         self.meshdir = comp.get('meshdir', '')
+        self.eulerseq = comp.get('eulerseq', 'xyz')
         opt = {}
         for o in root.findall('option'):
             opt.update(o.attrib)
@@ -361,7 +407,8 @@ class _Compiler:
         G = dict(names=[], type=[], body=[], pos=[], quat=[], size=[], friction=[], margin=[], gap=[], condim=[],
                  contype=[], conaffinity=[], priority=[], solref=[], solimp=[], solmix=[], group=[], mesh=[])
         S = dict(names=[], body=[], pos=[], quat=[])
-        self.B, self.J, self.D, self.G, self.S = B, J, D, G, S
+        CAM = dict(names=[], body=[], pos=[], quat=[], fovy=[], mode=[])
+        self.B, self.J, self.D, self.G, self.S, self.CAM = B, J, D, G, S, CAM
         self.nq = self.nv = 0
 
         for wb in root.findall('worldbody'):
@@ -441,6 +488,8 @@ class _Compiler:
             key_names=key_names, meaninertia=0.0, total_mass=float(np.sum(B['mass'])),
             exclude_body1=arr([B['names'].index(e.attrib['body1']) for c in root.findall('contact') for e in c.findall('exclude')], np.int32),
             exclude_body2=arr([B['names'].index(e.attrib['body2']) for c in root.findall('contact') for e in c.findall('exclude')], np.int32),
+            cam_names=CAM['names'], cam_bodyid=arr(CAM['body'], np.int32), cam_pos=arr(CAM['pos']).reshape(len(CAM['names']), 3),
+            cam_quat=arr(CAM['quat']).reshape(len(CAM['names']), 4), cam_fovy=arr(CAM['fovy']), cam_mode=arr(CAM['mode'], np.int32),
         )
         set_const(md)
         return md
@@ -497,6 +546,17 @@ class _Compiler:
                 S['body'].append(body_id)
                 S['pos'].append(_f(a['pos'], 3))
                 S['quat'].append(_f(a['quat'], 4))
+            elif ch.tag == 'camera':
+                a = self.defaults.resolve('camera', ch, childclass, _CAMERA_DEF)
+                if a['mode'] not in CAMERA_MODES:
+                    raise ValueError(f'camera {a.get("name", "")!r}: unknown mode {a["mode"]!r}')
+                C = self.CAM
+                C['names'].append(a.get('name', ''))
+                C['body'].append(body_id)
+                C['pos'].append(_f(a['pos'], 3))
+                C['quat'].append(frame_quat(a, self.eulerseq))
+                C['fovy'].append(float(a['fovy']))
+                C['mode'].append(CAMERA_MODES[a['mode']])
         for ch in elem:
             if ch.tag != 'body':
                 continue
@@ -755,9 +815,16 @@ def compile_mjcf(xml_path, mesh_hulls=True) -> ModelDesc:
 _MODEL_DIR = Path(__file__).parent / 'model_data'
 
 
+CAMERA_FIELDS = ('cam_names', 'cam_bodyid', 'cam_pos', 'cam_quat', 'cam_fovy', 'cam_mode')
+CAMERA_TABLE = _MODEL_DIR / 'cameras.json'   # {robot stem: the CAMERA_FIELDS of its table}, robots with cameras only
+
+
 def load_compiled(robot_file_stem: str) -> ModelDesc:
-    """Load a committed, pre-compiled robot table (``model_data/<stem>.json``)."""
+    """Load a committed, pre-compiled robot table (``model_data/<stem>.json``) and its cameras (``model_data/cameras.json``)."""
     p = _MODEL_DIR / f'{robot_file_stem}.json'
     if not p.exists():
         raise FileNotFoundError(f'no compiled model table {p}; run tools/compile_models.py or pass mjcf_path=')
-    return sort_cloud_vertices(ModelDesc.from_json(p.read_text()))
+    d = json.loads(p.read_text())
+    if CAMERA_TABLE.exists():
+        d.update(json.loads(CAMERA_TABLE.read_text()).get(robot_file_stem, {}))
+    return sort_cloud_vertices(ModelDesc.from_dict(d))

@@ -547,6 +547,11 @@ class QuadrupedEnv(AccessorsMixin):
         return self.mjModel
 
     @property
+    def sim_data(self):
+        """What the reference's sensors take as ``mj_data`` (reference :1034 returns the MjData): here the batched env itself."""
+        return self
+
+    @property
     def lift_failed(self):
         """Per-env flag of the reset RuntimeError condition (reference :387-388)."""
         return self._lift_failed.view(torch.bool)

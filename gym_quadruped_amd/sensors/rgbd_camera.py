@@ -1,0 +1,238 @@
+"""Batched depth / segmentation camera - mirror of the reference's ``gym_quadruped/sensors/rgbd_camera.py`` (``Camera`` :12-334).
+
+The reference renders one ``mujoco.Renderer`` image per call.  Here ``gq_camera`` ray casts the images of every env in two kernel
+launches (csrc/gq_camera.h), against the collision geometry the device model holds: the robot's foot spheres and link geoms, the floor,
+the world boxes and the height field.  Visual-only geoms (``contype = conaffinity = 0``, group-2 meshes) have no geometry in this
+package, so silhouettes follow the collision shapes; each env is its own world (other envs' robots are never drawn).  There is no
+rasteriser and no material: ``image`` (RGB) raises.  DESIGN.md §2 pins the pixel rays, the depth rules and the segmentation ids.
+
+The pose is that of the ``qpos`` the images are cast from - the env's current state by default.  MuJoCo's ``update_scene`` after
+``mj_step`` shows the kinematics of the step's START (mjData.xpos is not updated by the integrator): a caller who wants that timing
+passes a ``qpos`` saved before the step to ``render(qpos=...)``.
+"""
+from __future__ import annotations
+
+import os
+from datetime import datetime
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..cabi import hull_planes
+from ..mjcf import CAMERA_MODES
+
+
+class Camera:
+    """``Camera(width, height, fps, mj_model, mj_data, cam_name='', save_dir='data/img/')`` as in the reference, batched over the envs of
+    ``mj_data`` (the ``QuadrupedEnv``; ``env.sim_data``).  Extensions: a camera that is not in the MJCF - ``body`` (name or ModelDesc
+    index, 0 = world), ``pos``, ``quat`` (wxyz, MuJoCo's camera frame: looks along -z, y up) and ``fovy`` (degrees) - and the depth range
+    ``znear`` / ``zfar`` (metres; MuJoCo's defaults scaled by a 1 m extent)."""
+
+    def __init__(self, width, height, fps, mj_model, mj_data, cam_name: str = '', save_dir='data/img/', *, body=None, pos=None, quat=None,
+                 fovy=None, znear: float = 0.01, zfar: float = 50.0):
+        env = mj_data
+        md = env.mjModel
+        self._env, self._md = env, md
+        self._cam_name = cam_name
+        if cam_name:
+            if cam_name not in md.cam_names:
+                raise ValueError(f'no camera {cam_name!r} in model {md.name} (cameras: {md.cam_names})')
+            self._cam_id = md.cam_names.index(cam_name)
+            mode = int(md.cam_mode[self._cam_id])
+            if mode != CAMERA_MODES['fixed']:
+                name = [k for k, v in CAMERA_MODES.items() if v == mode][0]
+                raise ValueError(f'camera {cam_name!r} has mode="{name}": only fixed cameras (mode="fixed") are supported')
+            body_id, cpos, cquat, cfovy = int(md.cam_bodyid[self._cam_id]), md.cam_pos[self._cam_id], md.cam_quat[self._cam_id], float(md.cam_fovy[self._cam_id])
+        elif body is not None:
+            self._cam_id = -1
+            body_id, cpos, cquat, cfovy = (md.body_names.index(body) if isinstance(body, str) else int(body)), (0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0), 45.0
+        else:
+            raise ValueError('Camera needs cam_name= (a <camera> of the MJCF) or body= (extension: a camera given by body, pos, quat, fovy)')
+        self._body = body_id
+        self._pos = np.asarray(cpos if pos is None else pos, dtype=np.float64).reshape(3)
+        self._quat = np.asarray(cquat if quat is None else quat, dtype=np.float64).reshape(4)
+        self._quat = self._quat / np.linalg.norm(self._quat)
+        self._fovy = float(cfovy if fovy is None else fovy)
+        self._znear, self._zfar = float(znear), float(zfar)
+        self._width, self._height = int(width), int(height)
+        self.interval = float(1 / fps)
+        t = env.simulation_time
+        self.last_time = float(t.reshape(-1)[0]) if torch.is_tensor(t) else float(t)
+        self.save_counter = 0
+        timestamp = str(datetime.now()).replace(':', '_').replace(' ', '_')
+        self._save_dir = os.path.join(save_dir + self._cam_name + '/', 'data_' + timestamp)
+        self.K = self.intrinsic_mat
+        # face planes of the hull clouds: built once per camera
+        P, adr = hull_planes(md)
+        self._planes = torch.as_tensor(P, dtype=torch.float32, device=env.device).contiguous() if len(P) else None
+        self._plane_adr = np.ascontiguousarray(adr, dtype=np.int32) if len(P) else None
+        N, H, W, dev = env.num_envs, self._height, self._width, env.device
+        self._depth_plane = torch.zeros(N, H, W, dtype=torch.float32, device=dev)
+        self._seg = torch.full((N, H, W), -1, dtype=torch.int32, device=dev)
+        self._xpos = torch.zeros(N, 3, dtype=torch.float64, device=dev)
+        self._xmat = torch.zeros(N, 9, dtype=torch.float32, device=dev)
+
+    # ------------------------------------------------------------------ the reference's properties
+    @property
+    def height(self) -> int:
+        return self._height
+
+    @property
+    def width(self) -> int:
+        return self._width
+
+    @property
+    def last_sim_time(self) -> float:
+        """The last simulation time, in seconds, from a camera function call (set by the caller, as in the reference)."""
+        return self.last_time
+
+    @last_sim_time.setter
+    def last_sim_time(self, time) -> None:
+        self.last_time = time
+
+    @property
+    def save_dir(self) -> str:
+        return self._save_dir
+
+    @property
+    def name(self) -> str:
+        return self._cam_name
+
+    @property
+    def id(self) -> int:
+        """Index of the camera in ``mj_model.cam_names``; -1 for a camera given by ``body=``."""
+        return self._cam_id
+
+    @property
+    def fov(self) -> float:
+        """Vertical field of view (MuJoCo's ``cam_fovy``), degrees."""
+        return self._fovy
+
+    @property
+    def intrinsic_mat(self) -> np.ndarray:
+        """The reference's pinhole matrix, as written there (rgbd_camera.py :120-147): the vertical fovy sets both focal lengths."""
+        theta = np.deg2rad(self.fov)
+        f_x = (self._width / 2) / np.tan(theta / 2)
+        f_y = (self._height / 2) / np.tan(theta / 2)
+        u_0 = (self._width - 1) / 2.0
+        v_0 = (self._height - 1) / 2.0
+        return np.array([[f_x, 0, u_0], [0, f_y, v_0], [0, 0, 1]])
+
+    @property
+    def frame_config(self) -> torch.Tensor:
+        """Camera -> world ``[N, 4, 4]`` float64 in MuJoCo's camera frame (x right, y up, looking along -z), as of the last render.
+        The reference's version cannot run (``T[:3, :3] = Rotation.from_matrix(...)`` assigns a non-array); this is what it means."""
+        T = torch.zeros(self._env.num_envs, 4, 4, dtype=torch.float64, device=self._env.device)
+        T[:, :3, :3] = self._xmat.reshape(-1, 3, 3).double()
+        T[:, :3, 3] = self._xpos
+        T[:, 3, 3] = 1.0
+        return T
+
+    @property
+    def projection_mat(self) -> torch.Tensor:
+        """World -> pixel ``[N, 3, 4]`` float64: ``K @ [R | t]`` in the OpenCV convention (x right, y down, z forward), as of the last
+        render.  The reference's ``K (3x3) @ T (4x4)`` is a shape error; this is the matrix its name promises.  For a square image a
+        world point projects to the pixel centre (column, row) its ray goes through."""
+        Rmj = self._xmat.reshape(-1, 3, 3).double()
+        flip = torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=torch.float64, device=Rmj.device))
+        Rcv = flip @ Rmj.transpose(1, 2)
+        t = -(Rcv @ self._xpos.unsqueeze(-1))
+        K = torch.as_tensor(self.K, dtype=torch.float64, device=Rmj.device)
+        return K @ torch.cat([Rcv, t], dim=2)
+
+    # ------------------------------------------------------------------ images
+    def render(self, qpos=None):
+        """Cast depth and segmentation of every env from ``qpos`` ([N, 19] float64, default: the env's current state)."""
+        env = self._env
+        q = env.qpos if qpos is None else torch.as_tensor(qpos, dtype=torch.float64, device=env.device).reshape(-1, 19).expand(env.num_envs, 19).contiguous()
+        if q.stride(1) != 1:
+            q = q.contiguous()
+        self._keep = q   # alive until the next call: the launch is asynchronous
+        stream = torch.cuda.current_stream(env.device).cuda_stream
+        pos = (np.ctypeslib.as_ctypes(self._pos))
+        quat = (np.ctypeslib.as_ctypes(self._quat))
+        _lib.check(_lib.lib().gq_camera(env._hbatch, q.data_ptr(), int(q.stride(0)), self._body, pos, quat, self._fovy, self._width, self._height,
+                                        self._znear, self._zfar, 3, None if self._planes is None else self._planes.data_ptr(),
+                                        None if self._plane_adr is None else np.ctypeslib.as_ctypes(self._plane_adr),
+                                        self._depth_plane.data_ptr(), self._seg.data_ptr(), self._xpos.data_ptr(), self._xmat.data_ptr(), stream), 'gq_camera')
+
+    @property
+    def depth_plane(self) -> torch.Tensor:
+        """Planar depth ``[N, H, W]`` (distance along the camera's -z; what the renderer's depth buffer holds), zfar where nothing is hit."""
+        self.render()
+        return self._depth_plane
+
+    def _range(self, depth_plane):
+        # the reference's algebra, verbatim (rgbd_camera.py depth_image): the ROW index pairs with K[0][2] and K[0][0].  For a square
+        # image this is the Euclidean range along each pixel's ray; for other shapes it is the reference's quirk, kept.
+        K = self.K
+        i, j = torch.meshgrid(torch.arange(self.height, device=depth_plane.device), torch.arange(self.width, device=depth_plane.device), indexing='ij')
+        x_camera = (i - K[0][2]) * depth_plane / K[0][0]
+        y_camera = (j - K[1][2]) * depth_plane / K[1][1]
+        return torch.sqrt(depth_plane ** 2 + x_camera ** 2 + y_camera ** 2)
+
+    @property
+    def depth_image(self) -> torch.Tensor:
+        """``[N, H, W]`` float32: the reference's ``depth_image`` of the planar depth."""
+        self.render()
+        self._depth_image = self._range(self._depth_plane)
+        return self._depth_image
+
+    @property
+    def seg_image(self) -> torch.Tensor:
+        """``[N, H, W]`` int32 segmentation ids: a robot geom's ModelDesc geom index, ``ngeom`` the floor, ``ngeom + 1 + b`` world box b,
+        ``ngeom + 1 + nbox`` the height field, -1 no hit.  MuJoCo numbers the whole scene's geoms, so its ids differ from these."""
+        self.render()
+        self._seg_image = self._seg
+        return self._seg
+
+    @property
+    def point_cloud(self) -> torch.Tensor:
+        """``[N, H * W, 3]``: the reference's ``_depth_to_point_cloud(depth_image)``."""
+        self._point_cloud = self._depth_to_point_cloud(self.depth_image)
+        return self._point_cloud
+
+    def _depth_to_point_cloud(self, depth_image: torch.Tensor) -> torch.Tensor:
+        # rgbd_camera.py _depth_to_point_cloud, batched: K^-1 [x, y, 1] * (-depth), x = column, y = row
+        n, height, width = depth_image.shape
+        y, x = torch.meshgrid(torch.arange(height, device=depth_image.device), torch.arange(width, device=depth_image.device), indexing='ij')
+        hom = torch.stack([x.flatten(), y.flatten(), torch.ones_like(x.flatten())]).to(torch.float64)
+        K_inv = torch.as_tensor(np.linalg.inv(self.intrinsic_mat), dtype=torch.float64, device=depth_image.device)
+        pts = (K_inv @ hom).unsqueeze(0) * (-depth_image.reshape(n, 1, -1).double())
+        return pts.transpose(1, 2).to(depth_image.dtype)
+
+    @property
+    def image(self):
+        raise NotImplementedError('Camera.image (RGB) is not available: the camera is a ray caster - there is no rasteriser and the '
+                                  'models carry no materials.  depth_image, depth_plane, seg_image and point_cloud are.')
+
+    def shoot(self, autosave: bool = True, img: bool = False, depth: bool = True, seg: bool = True) -> None:
+        """Cast once and keep depth image, point cloud and segmentation (``img=True`` raises: no RGB)."""
+        if img:
+            self.image
+        self.render()
+        self._depth_image = self._range(self._depth_plane)
+        self._point_cloud = self._depth_to_point_cloud(self._depth_image)
+        self._seg_image = self._seg.clone()
+        if autosave:
+            self.save(depth=depth, seg=seg, fresh=False)
+
+    def save(self, img_name: str = '', img: bool = False, depth: bool = False, seg: bool = False, fresh: bool = True) -> None:
+        """Save depth ``[N, H, W]`` and segmentation ``[N, H, W]`` as ``.npy`` (the reference writes PNGs through cv2, which is not a
+        dependency here).  ``fresh=False``: save what the last ``shoot`` cast instead of casting again."""
+        if img:
+            self.image
+        os.makedirs(os.path.join(self._save_dir, 'images'), exist_ok=True)
+        if fresh:
+            self.render()
+            self._depth_image, self._seg_image = self._range(self._depth_plane), self._seg
+        print(f'saving {"depth image " if depth else ""}{"segmentation image " if seg else ""}to {self.save_dir}')
+        stem = f'{img_name}_' if img_name else ''
+        suffix = '' if img_name else f'_{self.save_counter}'
+        if seg:
+            np.save(os.path.join(self._save_dir, f'{stem}seg{suffix}.npy'), self._seg_image.cpu().numpy())
+        if depth:
+            np.save(os.path.join(self._save_dir, 'images', f'{stem}depth{suffix}.npy'), self._depth_image.cpu().numpy())
+        if not img_name:
+            self.save_counter += 1

@@ -19,6 +19,7 @@
  *   mujoco.mj_ray                  sensors/heightmap.py:90-99     gq_ray (general rays), gq_heightmap (the HeightMap grid)
  *   mujoco.mj_contactForce         quadruped_env.py:852    gq_contact_force (contact rows of gq_batch_set_outputs); summed per foot: obs epilogue
  *   mujoco.mj_fullM                quadruped_env.py:940    dyn rows of gq_batch_set_outputs (production kernel); gq_full_mass (inspection record)
+ *   mujoco.Renderer depth / segmentation  sensors/rgbd_camera.py   gq_camera (ray cast, collision geometry)
  *
  * Conventions
  *  - plain C, no exceptions cross the boundary; every function returns 0 on
@@ -61,8 +62,9 @@ extern "C" {
  * (gq_rollout_closed, gq_mailbox_get), GqObsOut.contacts_dropped; 500 = lap-tagged mailbox queue items, gq_struct_sizes(out[8]),
  * GqModelDesc.plane_* (optional); 510 = gq_batch_set_heightmap (no struct changed); 600 = GqModelDesc.vert_adj* / plane_order (hull
  * graphs: multi-point mesh-plane contacts), the general convex narrow phase (GJK / EPA) behind the same tables; 610 = gq_batch_set_pair_exchange
- * (no struct changed); 620 = GqModelDesc.support_grid (optional); 630 = that grid 16 x 16 cells per face (was 8 x 8). */
-#define GQ_ABI_VERSION 630
+ * (no struct changed); 620 = GqModelDesc.support_grid (optional); 630 = that grid 16 x 16 cells per face (was 8 x 8); 640 = gq_camera
+ * (no struct changed). */
+#define GQ_ABI_VERSION 640
 #ifndef GQ_SUPPORT_GRID
 #define GQ_SUPPORT_GRID 16 /* cells per edge of a cube-map face of GqModelDesc.support_grid */
 #endif
@@ -514,6 +516,26 @@ int gq_jac(GqBatch* b, const double* qpos, int body, const double* point, float*
  * dist: device [N][n_rays] f32 out, -1 where nothing is hit; geom: device [N][n_rays] i32 out or NULL (0 floor,
  * 1 + box index, 1 + nbox for the height field, -1 none).  One thread per ray. */
 int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float* dist, int32_t* geom, void* hip_stream);
+
+/* The depth and segmentation images of mujoco.Renderer (sensors/rgbd_camera.py: Camera.depth_image / seg_image) for every env, ray cast
+ * against the collision geometry the model holds: the robot's geoms (foot spheres and link geoms) and the static scene (floor plane,
+ * world boxes, height field).  Each env is its own world: other envs' robots are never drawn.  Two launches on hip_stream: a pose pass
+ * (the kinematics of `qpos`, one wavefront per env) and a pixel pass (one wavefront per 8 x 8 tile of one env).
+ *   qpos: device [N][qpos_stride] f64 (the pose drawn); body: ModelDesc body index of the camera, 0 = world; pos / quat: host, the camera
+ *   frame in the body frame (MuJoCo's camera frame: looks along -z, y up); fovy_deg: vertical field of view; znear / zfar: depth range;
+ *   flags: bit 0 draws the robot, bit 1 the static scene.
+ *   hull_planes: device [P][4] f32 face planes (n, d), n.x <= d inside, in the geom frame of the hull (mesh) clouds; hull_plane_adr: host
+ *   [ncloud + 1] prefix offsets into it, indexed by GqModelDesc cloud id.  Both may be NULL only for a model without hull geoms (GQ_EINVAL).
+ *   depth: device [N][H][W] f32 planar depth (distance along the camera's -z), zfar where nothing is hit in [znear, zfar];
+ *   seg: device [N][H][W] i32 or NULL: the GqModelDesc geom index of a robot geom, ngeom for the floor, ngeom + 1 + b for world box b,
+ *   ngeom + 1 + nbox for the height field, -1 for no hit; cam_xpos: device [N][3] f64 world or NULL; cam_xmat: device [N][9] f32 (row
+ *   major, columns = camera axes in the world) or NULL.
+ * Pixel (r, c), row 0 at the top, looks along ((2 (c + .5) / W - 1) tan(fovy / 2) W / H, (1 - 2 (r + .5) / H) tan(fovy / 2), -1) in the
+ * camera frame.  Convex geoms are drawn by their front faces only: a ray that starts inside one does not see it, and a hit nearer than
+ * znear is discarded (the ray goes on).  The batch owns a scratch block (allocated by the first call, 2 KB per env). */
+int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
+              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream);
 
 /* mujoco.mj_step1 (quadruped_env.py:376, :384: position + velocity stages) and mujoco.mj_forward (:1321: through the
  * accelerations) for every env WITHOUT advancing the state: stage 1 = mj_step1 (kinematics, inertias, collision,

@@ -1,0 +1,58 @@
+"""Time gq_camera (sensors.Camera.render: the pose pass and the pixel pass) with HIP events for a batch of envs.
+
+    python tools/camera_probe.py [--envs 4096] [--frames 50] [--warmup 5]
+
+Cases: aliengo robotcam 64 x 64 on flat, random_boxes and perlin; mini_cheetah 64 x 64 with a camera under the trunk looking back at
+the legs; aliengo flat 128 x 128.  Prints one JSON line per case: median and spread of the per-frame time (ms)."""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from gym_quadruped_amd.mjcf import mat_to_quat  # noqa: E402
+from gym_quadruped_amd.quadruped_env import QuadrupedEnv  # noqa: E402
+from gym_quadruped_amd.sensors import Camera  # noqa: E402
+
+CASES = [('aliengo', 'flat', 64), ('aliengo', 'random_boxes', 64), ('aliengo', 'perlin', 64), ('mini_cheetah', 'flat', 64), ('aliengo', 'flat', 128)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--envs', type=int, default=4096)
+    ap.add_argument('--frames', type=int, default=50)
+    ap.add_argument('--warmup', type=int, default=5)
+    a = ap.parse_args()
+    for robot, scene, S in CASES:
+        env = QuadrupedEnv(robot, scene=scene, num_envs=a.envs, device='cuda:0', state_obs_names=('qpos',), seed=0)
+        env.reset(seed=0)
+        g = torch.Generator(device='cuda:0').manual_seed(0)
+        for _ in range(30):
+            env.step(torch.randn(a.envs, 12, generator=g, device='cuda:0') * 5.0)
+        if robot == 'aliengo':
+            cam = Camera(S, S, 30, env.robot_model, env.sim_data, cam_name='robotcam')
+        else:
+            q = mat_to_quat(np.stack([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]], 1))
+            cam = Camera(S, S, 30, env.robot_model, env.sim_data, body='base', pos=(0.35, 0.0, -0.12), quat=q, fovy=90.0)
+        for _ in range(a.warmup):
+            cam.render()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.frames):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); cam.render(); e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        hit = float((cam._depth_plane < cam._zfar).float().mean())
+        print(json.dumps(dict(robot=robot, scene=scene, size=S, envs=a.envs, frames=a.frames, median_ms=float(np.median(ms)),
+                              p10_ms=float(np.percentile(ms, 10)), p90_ms=float(np.percentile(ms, 90)), hit_fraction=hit)), flush=True)
+        env.close()
+        del env, cam
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
