@@ -1,9 +1,12 @@
-"""The reference's camera example (examples/aliengo_with_camera.py), batched: depth and segmentation images of every env from the
-``robotcam`` camera on aliengo's trunk, saved as .npy instead of shown with cv2.
+"""The reference's camera example (examples/aliengo_with_camera.py), batched: RGB, depth and segmentation images of every env from the
+``robotcam`` camera on aliengo's trunk, saved as .npy instead of shown with cv2; and a tracking video frame of every env
+(``env.render('rgb_array')``) at the end.
 
     python examples/depth_camera.py [scene] [num_envs] [steps]"""
 import sys
 from pathlib import Path
+
+import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from gym_quadruped_amd.quadruped_env import QuadrupedEnv  # noqa: E402
@@ -32,6 +35,7 @@ cam = Camera(
     mj_data=env.sim_data,
     cam_name='robotcam',  # camera must be inserted on the .xml file of the robot in order to work
     save_dir='data_',
+    rgb=True,             # cam.image: [N, H, W, 3] uint8 (default Appearance: the model's geom colours, a checker floor)
 )
 
 for _ in range(steps):
@@ -39,6 +43,9 @@ for _ in range(steps):
     action = env.action_space.sample() * 0
     state, reward, is_terminated, is_truncated, info = env.step(action=action)
     if sim_time - cam.last_sim_time >= cam.interval:    # camera at its own fps
-        cam.shoot(autosave=True)                        # depth [N, H, W] and seg [N, H, W] as .npy
+        cam.shoot(autosave=True, img=True)              # image [N, H, W, 3], depth [N, H, W] and seg [N, H, W] as .npy
         cam.last_sim_time = float(env.simulation_time[0])
+frame = env.render('rgb_array')                         # [N, 240, 320, 3] uint8 from a camera tracking each base
+Path(cam.save_dir).mkdir(parents=True, exist_ok=True)
+np.save(Path(cam.save_dir) / 'render.npy', frame.cpu().numpy())
 env.close()

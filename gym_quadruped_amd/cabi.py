@@ -12,7 +12,7 @@ import numpy as np
 from .mjcf import ModelDesc
 
 GQ_NLEG = 4
-GQ_ABI_VERSION = 640   # include/gq.h
+GQ_ABI_VERSION = 650   # include/gq.h
 # optional extra output rows of the step kernel (include/gq.h gq_batch_set_outputs)
 GQ_DYN = dict(MC=0, MB=108, BIAS=144, XPOS=162, XMAT=201, FOOT=318, STRIDE=336)
 GQ_CON_MAX, GQ_CON_REC = 12, 24
@@ -77,6 +77,23 @@ class GqResetCfg(C.Structure):
 class GqImuCfg(C.Structure):
     _fields_ = [('site_pos', C.c_double * 3), ('site_quat', C.c_double * 4), ('accel_noise', C.c_float),
                 ('gyro_noise', C.c_float), ('accel_bias_rate', C.c_float), ('gyro_bias_rate', C.c_float), ('seed', C.c_uint64)]
+
+
+GQ_CAM_ROBOT, GQ_CAM_SCENE, GQ_CAM_TRACK = 1, 2, 4   # gq_camera / gq_camera_shaded flags
+GQ_CAM_MAXLIGHT = 7
+
+
+class GqCamLight(C.Structure):
+    _fields_ = [('pos', C.c_float * 3), ('dir', C.c_float * 3), ('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3),
+                ('attenuation', C.c_float * 3), ('cutoff', C.c_float), ('exponent', C.c_float), ('directional', C.c_int32)]
+
+
+class GqCamShade(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('nlight', C.c_int32), ('geom_mat', C.c_void_p), ('box_mat', C.c_float * 7),
+                ('floor_rgb1', C.c_float * 3), ('floor_rgb2', C.c_float * 3), ('floor_square', C.c_float), ('floor_mark_rgb', C.c_float * 3),
+                ('floor_mark_w', C.c_float), ('floor_specular', C.c_float), ('floor_shininess', C.c_float), ('floor_emission', C.c_float),
+                ('bg_top', C.c_float * 3), ('bg_bottom', C.c_float * 3), ('head_ambient', C.c_float * 3), ('head_diffuse', C.c_float * 3),
+                ('head_specular', C.c_float * 3), ('head_active', C.c_int32), ('light', GqCamLight * GQ_CAM_MAXLIGHT)]
 
 
 class GqObsOut(C.Structure):

@@ -24,6 +24,7 @@ extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, int n_envs, hipStream_t stream);
+extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
                                     float dist_x, float dist_y, float* out, hipStream_t stream);
@@ -755,27 +756,30 @@ int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float
   return GQ_OK;
 }
 
-int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
-              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
-              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream) {
-  if (!b || !qpos || !pos || !quat || !depth) { SET_ERR("gq_camera: null argument"); return GQ_EINVAL; }
-  if (qpos_stride < 19) { SET_ERR("gq_camera: qpos_stride %d < 19", qpos_stride); return GQ_EINVAL; }
-  if (body < 0 || body > GQ_NB) { SET_ERR("gq_camera: body id %d out of range (0 = world .. %d)", body, GQ_NB); return GQ_EINVAL; }
-  if (width <= 0 || height <= 0 || (size_t)width * height > (1u << 24)) { SET_ERR("gq_camera: bad image size %d x %d", width, height); return GQ_EINVAL; }
-  if (!(fovy_deg > 0.0f && fovy_deg < 180.0f)) { SET_ERR("gq_camera: fovy %g is not in (0, 180) degrees", (double)fovy_deg); return GQ_EINVAL; }
-  if (!(znear > 0.0f && zfar > znear)) { SET_ERR("gq_camera: need 0 < znear < zfar (got %g, %g)", (double)znear, (double)zfar); return GQ_EINVAL; }
-  if (flags & ~3) { SET_ERR("gq_camera: unknown flags 0x%x", flags); return GQ_EINVAL; }
+/* gq_camera / gq_camera_shaded: the checks and the call record both share (fn: the entry point's name for the error text); allocates the
+ * batch's scratch block on first use */
+static int camera_call(const char* fn, GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg,
+                       int width, int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                       float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, gq::CamCall& c) {
+  if (!b || !qpos || !pos || !quat || !depth) { SET_ERR("%s: null argument", fn); return GQ_EINVAL; }
+  if (qpos_stride < 19) { SET_ERR("%s: qpos_stride %d < 19", fn, qpos_stride); return GQ_EINVAL; }
+  if (body < 0 || body > GQ_NB) { SET_ERR("%s: body id %d out of range (0 = world .. %d)", fn, body, GQ_NB); return GQ_EINVAL; }
+  if (width <= 0 || height <= 0 || (size_t)width * height > (1u << 24)) { SET_ERR("%s: bad image size %d x %d", fn, width, height); return GQ_EINVAL; }
+  if (!(fovy_deg > 0.0f && fovy_deg < 180.0f)) { SET_ERR("%s: fovy %g is not in (0, 180) degrees", fn, (double)fovy_deg); return GQ_EINVAL; }
+  if (!(znear > 0.0f && zfar > znear)) { SET_ERR("%s: need 0 < znear < zfar (got %g, %g)", fn, (double)znear, (double)zfar); return GQ_EINVAL; }
+  if (flags & ~(GQ_CAM_ROBOT | GQ_CAM_SCENE | GQ_CAM_TRACK)) { SET_ERR("%s: unknown flags 0x%x", fn, flags); return GQ_EINVAL; }
+  if ((flags & GQ_CAM_TRACK) && body == 0) { SET_ERR("%s: GQ_CAM_TRACK needs a body camera (body > 0)", fn); return GQ_EINVAL; }
   const double qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
-  if (!(qn > 0.0)) { SET_ERR("gq_camera: zero quaternion"); return GQ_EINVAL; }
+  if (!(qn > 0.0)) { SET_ERR("%s: zero quaternion", fn); return GQ_EINVAL; }
   GqModel* m = b->model;
-  gq::CamCall c{};
+  c = gq::CamCall{};
   for (int i = 0; i < m->host.nlg; i++) {
     if (m->host.lg[i].ptype != 0) continue;
-    if (!hull_planes || !hull_plane_adr) { SET_ERR("gq_camera: the model has hull geoms and no face planes were passed"); return GQ_EINVAL; }
+    if (!hull_planes || !hull_plane_adr) { SET_ERR("%s: the model has hull geoms and no face planes were passed", fn); return GQ_EINVAL; }
     const int cl = m->lg_cloud[i];
-    if (cl < 0 || cl >= m->ncloud) { SET_ERR("gq_camera: link geom %d has no cloud", i); return GQ_EINVAL; }
+    if (cl < 0 || cl >= m->ncloud) { SET_ERR("%s: link geom %d has no cloud", fn, i); return GQ_EINVAL; }
     c.plane_adr[i] = hull_plane_adr[cl]; c.plane_num[i] = hull_plane_adr[cl + 1] - hull_plane_adr[cl];
-    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("gq_camera: cloud %d has %d face planes (a hull has at least 4)", cl, c.plane_num[i]); return GQ_EINVAL; }
+    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("%s: cloud %d has %d face planes (a hull has at least 4)", fn, cl, c.plane_num[i]); return GQ_EINVAL; }
   }
   DeviceGuard guard(m->device);
   const int n = b->host.n_envs;
@@ -790,7 +794,102 @@ int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const d
   c.width = width; c.height = height; c.flags = flags; c.ngeom = m->ngeom;
   c.tan_x = (float)(th * width / height); c.tan_y = (float)th; c.znear = znear; c.zfar = zfar;
   c.planes = hull_planes; c.rec = b->cam_rec; c.cpos = b->cam_pos; c.xpos_out = cam_xpos; c.xmat_out = cam_xmat; c.depth = depth; c.seg = seg;
-  gq_launch_camera(m->dev, &c, n, (hipStream_t)hip_stream);
+  return GQ_OK;
+}
+
+int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
+              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream) {
+  gq::CamCall c;
+  const int rc = camera_call("gq_camera", b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                             depth, seg, cam_xpos, cam_xmat, c);
+  if (rc != GQ_OK) return rc;
+  DeviceGuard guard(b->model->device);
+  gq_launch_camera(b->model->dev, &c, b->host.n_envs, (hipStream_t)hip_stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+/* GqCamShade -> the kernel's CamShade: every field checked (include/gq.h gq_camera_shaded), directions normalised, cutoffs as cosines */
+static bool cam_finite(const float* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+static bool cam_unit_range(const float* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!(v[k] >= 0.0f && v[k] <= 1.0f)) return false;
+  return true;
+}
+static int camera_shade(const GqCamShade* in, gq::CamShade& s) {
+  const char* fn = "gq_camera_shaded";
+  if (!in) { SET_ERR("%s: null shade", fn); return GQ_EINVAL; }
+  if (in->struct_size != (int32_t)sizeof(GqCamShade)) { SET_ERR("%s: GqCamShade.struct_size %d != %d (header mismatch)", fn, in->struct_size, (int)sizeof(GqCamShade)); return GQ_EINVAL; }
+  if (!in->geom_mat) { SET_ERR("%s: null geom_mat", fn); return GQ_EINVAL; }
+  if (in->nlight < 0 || in->nlight > GQ_CAM_MAXLIGHT) { SET_ERR("%s: nlight %d is not in [0, %d]", fn, in->nlight, GQ_CAM_MAXLIGHT); return GQ_EINVAL; }
+  if (in->head_active != 0 && in->head_active != 1) { SET_ERR("%s: head_active %d is not 0 / 1", fn, in->head_active); return GQ_EINVAL; }
+  struct { const char* name; const float* v; int n; } unit[] = {
+      {"box_mat", in->box_mat, 7}, {"floor_rgb1", in->floor_rgb1, 3}, {"floor_rgb2", in->floor_rgb2, 3}, {"floor_mark_rgb", in->floor_mark_rgb, 3},
+      {"floor_specular", &in->floor_specular, 1}, {"floor_shininess", &in->floor_shininess, 1}, {"floor_emission", &in->floor_emission, 1},
+      {"bg_top", in->bg_top, 3}, {"bg_bottom", in->bg_bottom, 3}, {"head_ambient", in->head_ambient, 3}, {"head_diffuse", in->head_diffuse, 3},
+      {"head_specular", in->head_specular, 3}};
+  for (const auto& u : unit)
+    if (!cam_unit_range(u.v, u.n)) { SET_ERR("%s: %s has a value outside [0, 1] (or not finite)", fn, u.name); return GQ_EINVAL; }
+  if (!(std::isfinite(in->floor_square) && in->floor_square > 0.0f)) { SET_ERR("%s: floor_square %g is not > 0", fn, (double)in->floor_square); return GQ_EINVAL; }
+  if (!(std::isfinite(in->floor_mark_w) && in->floor_mark_w >= 0.0f)) { SET_ERR("%s: floor_mark_w %g is not >= 0", fn, (double)in->floor_mark_w); return GQ_EINVAL; }
+  s = gq::CamShade{};
+  s.geom_mat = in->geom_mat;
+  for (int k = 0; k < 7; k++) s.box_mat[k] = in->box_mat[k];
+  for (int k = 0; k < 3; k++) {
+    s.rgb1[k] = in->floor_rgb1[k]; s.rgb2[k] = in->floor_rgb2[k]; s.mark_rgb[k] = in->floor_mark_rgb[k];
+    s.top[k] = in->bg_top[k]; s.bottom[k] = in->bg_bottom[k];
+  }
+  s.square = in->floor_square; s.mark_w = in->floor_mark_w;
+  s.floor_mat[0] = in->floor_specular; s.floor_mat[1] = in->floor_shininess; s.floor_mat[2] = in->floor_emission;
+  if (in->head_active) {
+    gq::CamLight& h = s.light[s.nlight++];
+    for (int k = 0; k < 3; k++) { h.amb[k] = in->head_ambient[k]; h.dif[k] = in->head_diffuse[k]; h.spe[k] = in->head_specular[k]; }
+    h.kind = 0;
+  }
+  for (int l = 0; l < in->nlight; l++) {
+    const GqCamLight& L = in->light[l];
+    if (!cam_finite(L.pos, 3) || !cam_finite(L.dir, 3) || !cam_finite(L.attenuation, 3) || !std::isfinite(L.cutoff) || !std::isfinite(L.exponent)) {
+      SET_ERR("%s: light %d has a value that is not finite", fn, l); return GQ_EINVAL;
+    }
+    if (!cam_unit_range(L.ambient, 3) || !cam_unit_range(L.diffuse, 3) || !cam_unit_range(L.specular, 3)) { SET_ERR("%s: light %d has a colour outside [0, 1]", fn, l); return GQ_EINVAL; }
+    if (L.directional != 0 && L.directional != 1) { SET_ERR("%s: light %d directional %d is not 0 / 1", fn, l, L.directional); return GQ_EINVAL; }
+    if (!(L.cutoff > 0.0f && L.cutoff <= 90.0f)) { SET_ERR("%s: light %d cutoff %g is not in (0, 90] degrees", fn, l, (double)L.cutoff); return GQ_EINVAL; }
+    if (!(L.exponent >= 0.0f)) { SET_ERR("%s: light %d exponent %g < 0", fn, l, (double)L.exponent); return GQ_EINVAL; }
+    if (L.attenuation[0] < 0.0f || L.attenuation[1] < 0.0f || L.attenuation[2] < 0.0f || L.attenuation[0] + L.attenuation[1] + L.attenuation[2] <= 0.0f) {
+      SET_ERR("%s: light %d attenuation must be >= 0 and not all zero", fn, l); return GQ_EINVAL;
+    }
+    const double dn = std::sqrt((double)L.dir[0] * L.dir[0] + (double)L.dir[1] * L.dir[1] + (double)L.dir[2] * L.dir[2]);
+    if (!(dn > 0.0)) { SET_ERR("%s: light %d has a zero direction", fn, l); return GQ_EINVAL; }
+    gq::CamLight& o = s.light[s.nlight++];
+    for (int k = 0; k < 3; k++) {
+      o.pos[k] = L.pos[k]; o.dir[k] = (float)(L.dir[k] / dn); o.att[k] = L.attenuation[k];
+      o.amb[k] = L.ambient[k]; o.dif[k] = L.diffuse[k]; o.spe[k] = L.specular[k];
+    }
+    o.cos_cut = (float)std::cos((double)L.cutoff * 3.14159265358979323846 / 180.0); o.expo = L.exponent;
+    o.kind = L.directional ? 1 : 2;
+  }
+  return GQ_OK;
+}
+
+int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
+                     int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                     float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, void* hip_stream) {
+  gq::CamShade s;
+  int rc = camera_shade(shade, s);
+  if (rc != GQ_OK) return rc;
+  if (!rgba) { SET_ERR("gq_camera_shaded: null rgba"); return GQ_EINVAL; }
+  gq::CamCall c;
+  rc = camera_call("gq_camera_shaded", b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                   depth, seg, cam_xpos, cam_xmat, c);
+  if (rc != GQ_OK) return rc;
+  s.rgba = reinterpret_cast<uint32_t*>(rgba);
+  DeviceGuard guard(b->model->device);
+  gq_launch_camera_shaded(b->model->dev, &c, &s, b->host.n_envs, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

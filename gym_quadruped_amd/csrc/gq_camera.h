@@ -24,7 +24,7 @@ struct CamCall {
   const double* qpos; int qpos_stride;
   int body;                                    /* ModelDesc body of the camera, 0 = world */
   double pos[3]; float quat[4];                /* camera frame in the body frame (quat normalised) */
-  int width, height, flags, ngeom;             /* flags: bit 0 robot, bit 1 static scene; ngeom: segmentation id of the floor */
+  int width, height, flags, ngeom;             /* flags: bit 0 robot, bit 1 static scene, bit 2 track; ngeom: segmentation id of the floor */
   float tan_x, tan_y, znear, zfar;             /* tan(fovy / 2) W / H, tan(fovy / 2) */
   const float* planes;                         /* [P][4] face planes n.x <= d of the hull geoms, geom frame */
   int32_t plane_adr[GQ_MAXLG], plane_num[GQ_MAXLG]; /* per lg[]: first plane and count (0: not a hull) */
@@ -32,6 +32,24 @@ struct CamCall {
   double* cpos;                                /* [N][3] batch scratch: camera origin, world, fp64 */
   double* xpos_out; float* xmat_out;           /* optional copies for the caller */
   float* depth; int32_t* seg;                  /* [N][H][W] */
+};
+
+/* the shaded pixel pass (gq_camera_shaded): GqCamShade as the library resolved it, by value */
+#define GQ_CAM_NLIGHT 8                        /* lights, headlight included */
+struct CamLight {
+  float pos[3], dir[3];                        /* world; dir unit (kind 0: unused) */
+  float amb[3], dif[3], spe[3], att[3];
+  float cos_cut, expo;                         /* spot cone: cos(cutoff), exponent */
+  int kind;                                    /* 0 headlight (L = camera +z), 1 directional, 2 spot */
+};
+struct CamShade {
+  const float* geom_mat;                       /* [ngeom][7] rgba, specular, shininess, emission (device) */
+  uint32_t* rgba;                              /* [N][H][W] RGBA8 */
+  float box_mat[7];                            /* world boxes, same layout */
+  float rgb1[3], rgb2[3], mark_rgb[3], square, mark_w, floor_mat[3];   /* floor / height field checker; floor_mat: spec, shin, emis */
+  float top[3], bottom[3];                     /* background */
+  int nlight;
+  CamLight light[GQ_CAM_NLIGHT];
 };
 
 /* ---- static-geom ray tests (T = double: gq_ray; the pixel pass uses float for boxes, origin relative to the camera) */
@@ -55,13 +73,13 @@ __device__ inline bool ray_triangle(const T* o, const T* d, const T* a, const T*
 }
 /* slab test of the ray o + t d against the box |x_k| <= s_k (box frame); tin / tout come in as the caller's bounds */
 template <class T>
-__device__ inline bool ray_slab(const T* ol, const T* dl, const T* s, T& tin, T& tout) {
+__device__ inline bool ray_slab(const T* ol, const T* dl, const T* s, T& tin, T& tout, int* axis = nullptr) {   /* axis: the slab that sets tin */
   bool hit = true;
   for (int k = 0; k < 3 && hit; k++) {
     if (fabs(dl[k]) < T(1e-14)) { hit = fabs(ol[k]) <= s[k]; continue; }
     T t0 = (-s[k] - ol[k]) / dl[k], t1 = (s[k] - ol[k]) / dl[k];
     if (t0 > t1) { const T tt = t0; t0 = t1; t1 = tt; }
-    if (t0 > tin) tin = t0;
+    if (t0 > tin) { tin = t0; if (axis) *axis = k; }
     if (t1 < tout) tout = t1;
     hit = tin <= tout;
   }
@@ -69,19 +87,20 @@ __device__ inline bool ray_slab(const T* ol, const T* dl, const T* s, T& tin, T&
 }
 /* a world box: r = origin - box centre, d: direction, both in world axes */
 template <class T, class Box>
-__device__ inline bool ray_box(const Box& B, const T* r, const T* d, T& tin, T& tout) {
+__device__ inline bool ray_box(const Box& B, const T* r, const T* d, T& tin, T& tout, int* axis = nullptr) {
   T ol[3], dl[3], s[3];
   for (int k = 0; k < 3; k++) {
     ol[k] = (T)B.mat[k] * r[0] + (T)B.mat[3 + k] * r[1] + (T)B.mat[6 + k] * r[2];
     dl[k] = (T)B.mat[k] * d[0] + (T)B.mat[3 + k] * d[1] + (T)B.mat[6 + k] * d[2];
     s[k] = (T)B.size[k];
   }
-  return ray_slab(ol, dl, s, tin, tout);
+  return ray_slab(ol, dl, s, tin, tout, axis);
 }
 /* the height field: ol = origin - hf_pos.  The cells under the ray's ground track are walked from the parameter max(tmin, entry into the
- * field's bounding box), two triangles each; returns the first hit >= tmin, -1 if none. */
+ * field's bounding box), two triangles each; returns the first hit >= tmin, -1 if none.  tri: the triangle hit, 2 (row ncol + col) + k
+ * (k = 0: corners (c, r), (c + 1, r), (c, r + 1); k = 1: (c + 1, r + 1), (c, r + 1), (c + 1, r)). */
 template <class T, class Mref>
-__device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T tmin) {
+__device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T tmin, int* tri = nullptr) {
   const T sx = M.hf_sx, sy = M.hf_sy, dx = M.hf_dx, dy = M.hf_dy, zmax = (T)M.hf_zmax;
   /* parameter interval of the ray inside the field's bounding box [-sx, sx] x [-sy, sy] x [0, zmax] */
   T t0 = tmin, t1 = ray_far<T>();
@@ -109,9 +128,13 @@ __device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T t
     const T h00 = H[r * nc + c], h10 = H[r * nc + c + 1], h01 = H[(r + 1) * nc + c], h11 = H[(r + 1) * nc + c + 1];
     const T A[3] = {x0, y0, h00}, B[3] = {x1, y0, h10}, Cc[3] = {x0, y1, h01}, D[3] = {x1, y1, h11};
     T th, tb = T(-1);
+    int k = 0;
     if (ray_triangle(ol, d, A, B, Cc, th) && th >= tmin) tb = th;
-    if (ray_triangle(ol, d, D, Cc, B, th) && th >= tmin && (tb < T(0) || th < tb)) tb = th;
-    if (tb >= T(0)) return tb;
+    if (ray_triangle(ol, d, D, Cc, B, th) && th >= tmin && (tb < T(0) || th < tb)) { tb = th; k = 1; }
+    if (tb >= T(0)) {
+      if (tri) *tri = 2 * (r * nc + c) + k;
+      return tb;
+    }
     /* next cell: the nearer of the two cell borders the track crosses */
     const T tx = fabs(d[0]) < T(1e-14) ? ray_far<T>() : ((stc > 0 ? x1 : x0) - ol[0]) / d[0];
     const T ty = fabs(d[1]) < T(1e-14) ? ray_far<T>() : ((str > 0 ? y1 : y0) - ol[1]) / d[1];
@@ -122,15 +145,17 @@ __device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T t
 }
 
 /* ---- robot geoms, in the geom frame (o, d: the ray there).  Each returns the entry parameter (front face), or -1 when the ray starts
- * inside or misses; the caller keeps entries in [znear, best]. */
+ * inside or misses; the caller keeps entries in [znear, best].  part: which surface the entry is on (cam_shade); callers that do not
+ * shade pass a local they never read. */
 __device__ inline float cam_sphere(V3 o, V3 d, float r) {
   const float a = dot(d, d), b = dot(o, d), c = dot(o, o) - r * r;
   if (c <= 0.0f) return -1.0f;
   const float disc = b * b - a * c;
   return disc < 0.0f ? -1.0f : (-b - sqrtf(disc)) / a;
 }
-__device__ inline float cam_cylinder(V3 o, V3 d, float r, float h) {   /* axis z, radius r, half length h */
+__device__ inline float cam_cylinder(V3 o, V3 d, float r, float h, int& part) {   /* axis z, radius r, half length h; part 0 side, 1 cap */
   float tin = -1e30f, tout = 1e30f;
+  part = 1;
   if (fabsf(d.z) < 1e-20f) { if (fabsf(o.z) > h) return -1.0f; }
   else {
     float t0 = (-h - o.z) / d.z, t1 = (h - o.z) / d.z;
@@ -142,31 +167,38 @@ __device__ inline float cam_cylinder(V3 o, V3 d, float r, float h) {   /* axis z
   else {
     const float disc = b * b - a * c;
     if (disc < 0.0f) return -1.0f;
-    const float s = sqrtf(disc);
-    tin = fmaxf(tin, (-b - s) / a); tout = fminf(tout, (-b + s) / a);
+    const float s = sqrtf(disc), ts = (-b - s) / a;
+    if (ts > tin) part = 0;
+    tin = fmaxf(tin, ts); tout = fminf(tout, (-b + s) / a);
   }
   return tin <= tout ? tin : -1.0f;
 }
-__device__ inline float cam_capsule(V3 o, V3 d, float r, float h) {
+__device__ inline float cam_capsule(V3 o, V3 d, float r, float h, int& part) {   /* part 0 cylinder, 1 cap at +h, 2 cap at -h */
   const float zc = fminf(fmaxf(o.z, -h), h);
   if (o.x * o.x + o.y * o.y + (o.z - zc) * (o.z - zc) <= r * r) return -1.0f;   /* inside */
   float best = 1e30f;
-  const float tc = cam_cylinder(o, d, r, h), t0 = cam_sphere(o - v3(0.0f, 0.0f, h), d, r), t1 = cam_sphere(o + v3(0.0f, 0.0f, h), d, r);
+  int pc;
+  const float tc = cam_cylinder(o, d, r, h, pc), t0 = cam_sphere(o - v3(0.0f, 0.0f, h), d, r), t1 = cam_sphere(o + v3(0.0f, 0.0f, h), d, r);
+  part = 0;
   if (tc > 0.0f) best = tc;
-  if (t0 > 0.0f && t0 < best) best = t0;
-  if (t1 > 0.0f && t1 < best) best = t1;
+  if (t0 > 0.0f && t0 < best) { best = t0; part = 1; }
+  if (t1 > 0.0f && t1 < best) { best = t1; part = 2; }
   return best < 1e30f ? best : -1.0f;
 }
 /* Cyrus-Beck against the hull's face planes; the plane loop is wave-uniform (the addresses too: scalar loads) */
-__device__ inline float cam_hull(V3 o, V3 d, const float* P, int n) {
+__device__ inline float cam_hull(V3 o, V3 d, const float* P, int n, int& part) {   /* part: the entry plane */
   float tin = -1e30f, tout = 1e30f;
+  part = 0;
   bool miss = false;
   for (int k = 0; k < n; k++) {
     const V3 nk = v3(P[4 * k], P[4 * k + 1], P[4 * k + 2]);
     const float den = dot(nk, d), num = P[4 * k + 3] - dot(nk, o);
     if (fabsf(den) < 1e-20f) { miss |= num < 0.0f; continue; }
     const float t = num / den;
-    if (den < 0.0f) tin = fmaxf(tin, t); else tout = fminf(tout, t);
+    if (den < 0.0f) {
+      if (t > tin) part = k;
+      tin = fmaxf(tin, t);
+    } else tout = fminf(tout, t);
   }
   return !miss && tin <= tout ? tin : -1.0f;
 }
@@ -193,6 +225,9 @@ __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall
   V3 pc;
   if (c.body == 0) {
     pc = v3((float)(c.pos[0] - W.bxy[0]), (float)(c.pos[1] - W.bxy[1]), (float)c.pos[2]);
+    for (int k = 0; k < 9; k++) Rc[k] = Rq[k];
+  } else if (c.flags & 4) { /* GQ_CAM_TRACK: the body's position, the offset and the orientation in world axes */
+    pc = ld3(W.xpos[c.body - 1]) + v3((float)c.pos[0], (float)c.pos[1], (float)c.pos[2]);
     for (int k = 0; k < 9; k++) Rc[k] = Rq[k];
   } else {
     const int kb = c.body - 1;
@@ -244,9 +279,13 @@ __device__ __forceinline__ bool cam_cone_sphere(V3 ctr, float rad, V3 ax, float 
   return sqrtf(dot(p, p)) * ca - a * sa <= rad;
 }
 
-/* pixel pass: one wavefront renders tile `tile` of env `env` */
 template <class Mref>
-__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const int tile, const int env) {
+__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
+                                     V3 dw, float best, int id, int slot, int part, int nbox);
+
+/* pixel pass: one wavefront renders tile `tile` of env `env`; SHADE: also its RGBA image (sh) */
+template <bool SHADE, class Mref>
+__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const CamShade* sh, const int tile, const int env) {
   const int lane = lane_id(), W = c.width, H = c.height;
   const int tiles_x = (W + GQ_CAM_TILE - 1) / GQ_CAM_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
   const int row = ty * GQ_CAM_TILE + lane / GQ_CAM_TILE, col = tx * GQ_CAM_TILE + lane % GQ_CAM_TILE;
@@ -298,9 +337,10 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const i
       }
       box[half] = ballot(near);
     }
-  /* cast, lane = pixel */
+  /* cast, lane = pixel.  The shaded pass also keeps what the winner is: slot (robot geom g / world box b / height-field triangle) and part
+   * (the surface of the primitive the entry is on); its normal is formed once, after the walk.  The depth-only pass never reads them. */
   float best = c.zfar;
-  int id = -1;
+  int id = -1, slot = 0, part = 0;
   const V3 dw = matvec(Rc, d);   /* the ray in world axes */
   if (c.flags & 2) {
     if (dw.z < 0.0f && co[2] >= 0.0) { /* the floor: a one-sided plane, hit from above */
@@ -313,12 +353,20 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const i
         const int b = half * GQ_WAVE + ffs64(todo);
         const float rv[3] = {(float)(co[0] - (double)M.box[b].pos[0]), (float)(co[1] - (double)M.box[b].pos[1]), (float)(co[2] - (double)M.box[b].pos[2])};
         float tin = -1e30f, tout = 1e30f;
-        if (ray_box(M.box[b], rv, dv, tin, tout) && tin >= c.znear && tin <= best) { best = tin; id = c.ngeom + 1 + b; }
+        int ax_in = 0;
+        if (ray_box(M.box[b], rv, dv, tin, tout, SHADE ? &ax_in : nullptr) && tin >= c.znear && tin <= best) {
+          best = tin; id = c.ngeom + 1 + b;
+          if (SHADE) { slot = b; part = ax_in; }
+        }
       }
     if (M.hf_nrow > 0) { /* fp64: the walk runs in the field's own coordinates */
       const double ol[3] = {co[0] - (double)M.hf_pos[0], co[1] - (double)M.hf_pos[1], co[2] - (double)M.hf_pos[2]}, dd[3] = {dw.x, dw.y, dw.z};
-      const double t = ray_hfield(M, ol, dd, (double)c.znear);
-      if (t >= 0.0 && t <= (double)best) { best = (float)t; id = c.ngeom + 1 + nbox; }
+      int tri = 0;
+      const double t = ray_hfield(M, ol, dd, (double)c.znear, SHADE ? &tri : nullptr);
+      if (t >= 0.0 && t <= (double)best) {
+        best = (float)t; id = c.ngeom + 1 + nbox;
+        if (SHADE) slot = tri;
+      }
     }
   }
   for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform */
@@ -326,26 +374,131 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const i
     const float* gr = rec + 12 + 12 * g;
     const V3 t = ld3(gr + 9), o = (-1.0f) * matTvec(gr, t), dl = matTvec(gr, d);
     float th;
+    int pg = 0;
     if (g < 4) th = cam_sphere(o, dl, M.foot_radius[g]);
     else {
       const auto& G = M.lg[g - 4];
       const int pt = G.ptype;
       if (pt == 2) th = cam_sphere(o, dl, G.psize[0]);
-      else if (pt == 3) th = cam_capsule(o, dl, G.psize[0], G.psize[1]);
-      else if (pt == 5) th = cam_cylinder(o, dl, G.psize[0], G.psize[1]);
+      else if (pt == 3) th = cam_capsule(o, dl, G.psize[0], G.psize[1], pg);
+      else if (pt == 5) th = cam_cylinder(o, dl, G.psize[0], G.psize[1], pg);
       else if (pt == 6) {
         const float ov[3] = {o.x, o.y, o.z}, dv[3] = {dl.x, dl.y, dl.z}, s[3] = {G.psize[0], G.psize[1], G.psize[2]};
         float tin = -1e30f, tout = 1e30f;
-        th = ray_slab(ov, dv, s, tin, tout) ? tin : -1.0f;
-      } else th = cam_hull(o, dl, c.planes + 4 * c.plane_adr[g - 4], c.plane_num[g - 4]);
+        th = ray_slab(ov, dv, s, tin, tout, SHADE ? &pg : nullptr) ? tin : -1.0f;
+      } else {
+        th = cam_hull(o, dl, c.planes + 4 * c.plane_adr[g - 4], c.plane_num[g - 4], pg);
+        pg += c.plane_adr[g - 4];   /* the entry plane, as an index into c.planes */
+      }
     }
-    if (th >= c.znear && th <= best) { best = th; id = M.item_geomid[g]; }
+    if (th >= c.znear && th <= best) {
+      best = th; id = M.item_geomid[g];
+      if (SHADE) { slot = g; part = pg; }
+    }
   }
+  const size_t px = ((size_t)env * H + row) * W + col;
   if (valid) {
-    const size_t px = ((size_t)env * H + row) * W + col;
     c.depth[px] = best;
     if (c.seg) c.seg[px] = id;
   }
+  if constexpr (SHADE) {
+    const uint32_t rgba = cam_shade(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox);
+    if (valid) sh->rgba[px] = rgba;
+  }
+}
+
+/* ---- shading (gq_camera_shaded): the winner's normal, its material and the lights, fp32 in the camera frame */
+__device__ __forceinline__ V3 cam_unit(V3 a) { return (1.0f / sqrtf(dot(a, a))) * a; }
+__device__ __forceinline__ uint32_t cam_byte(float x) { return (uint32_t)floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f) + 0.5f); }
+/* x^e for x in [0, 1], e >= 0 on the transcendental unit (v_log_f32 / v_exp_f32, as fast_pow_ratio; the library powf is hundreds of
+ * instructions of special cases); 0^0 = 1 */
+__device__ __forceinline__ float cam_pow(float x, float e) { return e > 0.0f ? __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)) : 1.0f; }
+
+template <class Mref>
+__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
+                                     V3 dw, float best, int id, int slot, int part, int nbox) {
+  float col[3], mat[3];   /* base colour; specular, shininess, emission */
+  V3 n;                   /* outward normal, camera frame (not yet unit) */
+  if (id < 0) { /* background: the gradient over the world z of the unit ray */
+    const float s = 0.5f * (1.0f + dw.z / sqrtf(dot(dw, dw)));
+    return cam_byte(S.bottom[0] + (S.top[0] - S.bottom[0]) * s) | cam_byte(S.bottom[1] + (S.top[1] - S.bottom[1]) * s) << 8 |
+           cam_byte(S.bottom[2] + (S.top[2] - S.bottom[2]) * s) << 16 | 0xff000000u;
+  }
+  if (id < c.ngeom) { /* robot geom `slot`: its frame in the camera frame, the hit in the geom frame */
+    const float* gr = rec + 12 + 12 * slot;
+    const V3 t = ld3(gr + 9), p = (-1.0f) * matTvec(gr, t) + best * matTvec(gr, d);
+    V3 nl = p;   /* spheres */
+    if (slot >= 4) {
+      const auto& G = M.lg[slot - 4];
+      const int pt = G.ptype;
+      const float h = G.psize[1];
+      if (pt == 3) nl = part == 0 ? v3(p.x, p.y, 0.0f) : p - v3(0.0f, 0.0f, part == 1 ? h : -h);
+      else if (pt == 5) nl = part == 0 ? v3(p.x, p.y, 0.0f) : v3(0.0f, 0.0f, p.z > 0.0f ? 1.0f : -1.0f);
+      else if (pt == 6) {
+        const V3 dl = matTvec(gr, d);
+        const float dk = part == 0 ? dl.x : part == 1 ? dl.y : dl.z, s = dk > 0.0f ? -1.0f : 1.0f;
+        nl = v3(part == 0 ? s : 0.0f, part == 1 ? s : 0.0f, part == 2 ? s : 0.0f);
+      } else if (pt != 2) nl = ld3(c.planes + 4 * part);
+    }
+    n = matvec(gr, nl);
+    const float* gm = S.geom_mat + 7 * id;
+    col[0] = gm[0]; col[1] = gm[1]; col[2] = gm[2]; mat[0] = gm[4]; mat[1] = gm[5]; mat[2] = gm[6];
+  } else {
+    V3 nw = v3(0.0f, 0.0f, 1.0f);   /* the floor */
+    const int b = id - c.ngeom - 1;
+    if (b >= 0 && b < nbox) { /* world box: the entry face of slab `part` */
+      const auto& B = M.box[slot];
+      const V3 ax = v3(B.mat[part], B.mat[3 + part], B.mat[6 + part]);
+      nw = dot(ax, dw) > 0.0f ? (-1.0f) * ax : ax;
+      for (int k = 0; k < 3; k++) col[k] = S.box_mat[k];
+      for (int k = 0; k < 3; k++) mat[k] = S.box_mat[4 + k];
+    } else {
+      if (b == nbox) { /* height-field triangle `slot` */
+        const int nc = M.hf_ncol, cell = slot >> 1, r = cell / nc, cc = cell % nc;
+        const float* Hf = M.hf_data;
+        const float dx = M.hf_dx, dy = M.hf_dy;
+        if (slot & 1) {
+          const float h11 = Hf[(r + 1) * nc + cc + 1];
+          nw = v3((Hf[(r + 1) * nc + cc] - h11) * dy, (Hf[r * nc + cc + 1] - h11) * dx, dx * dy);
+        } else {
+          const float h00 = Hf[r * nc + cc];
+          nw = v3(-(Hf[r * nc + cc + 1] - h00) * dy, -(Hf[(r + 1) * nc + cc] - h00) * dx, dx * dy);
+        }
+      }
+      /* the checker in world x / y: the fp64 origin reduced modulo two squares, then the fp32 ray */
+      const double p2 = 2.0 * (double)S.square;
+      const float ox = (float)(co[0] - p2 * floor(co[0] / p2)), oy = (float)(co[1] - p2 * floor(co[1] / p2));
+      const float fx = (ox + best * dw.x) / S.square, fy = (oy + best * dw.y) / S.square, ix = floorf(fx), iy = floorf(fy);
+      const float ux = fx - ix, uy = fy - iy;
+      const float edge = fminf(fminf(ux, 1.0f - ux), fminf(uy, 1.0f - uy)) * S.square;
+      const float* rgb = edge < S.mark_w ? S.mark_rgb : (((int)ix + (int)iy) & 1) ? S.rgb2 : S.rgb1;
+      for (int k = 0; k < 3; k++) col[k] = rgb[k];
+      for (int k = 0; k < 3; k++) mat[k] = S.floor_mat[k];
+    }
+    n = matTvec(Rc, nw);
+  }
+  n = cam_unit(n);
+  const V3 v = (-1.0f) * cam_unit(d), ph = best * d;   /* towards the camera; the hit, camera frame */
+  float out[3] = {mat[2] * col[0], mat[2] * col[1], mat[2] * col[2]};
+  const float shin = 128.0f * mat[1];
+  for (int l = 0; l < S.nlight; l++) { /* wave-uniform: each light is taken into the camera frame once per wave */
+    const CamLight& Lt = S.light[l];
+    V3 L = v3(0.0f, 0.0f, 1.0f);
+    float w = 1.0f;   /* attenuation x spot */
+    if (Lt.kind == 1) L = (-1.0f) * matTvec(Rc, ld3(Lt.dir));
+    else if (Lt.kind == 2) {
+      const V3 lp = matTvec(Rc, v3((float)((double)Lt.pos[0] - co[0]), (float)((double)Lt.pos[1] - co[1]), (float)((double)Lt.pos[2] - co[2])));
+      const V3 q = lp - ph;
+      const float r = sqrtf(dot(q, q));
+      L = (1.0f / r) * q;
+      const float cs = -dot(L, matTvec(Rc, ld3(Lt.dir)));
+      w = (cs >= Lt.cos_cut ? cam_pow(cs, Lt.expo) : 0.0f) / (Lt.att[0] + Lt.att[1] * r + Lt.att[2] * r * r);
+    }
+    const float nL = dot(n, L), nH = fmaxf(dot(n, cam_unit(L + v)), 0.0f);
+    const float sp = nL > 0.0f ? mat[0] * cam_pow(nH, shin) : 0.0f, df = fmaxf(nL, 0.0f);
+    for (int k = 0; k < 3; k++) out[k] += w * (Lt.amb[k] * col[k] + Lt.dif[k] * col[k] * df + Lt.spe[k] * sp);
+  }
+  return cam_byte(out[0]) | cam_byte(out[1]) << 8 | cam_byte(out[2]) << 16 | 0xff000000u;
 }
 
 }  // namespace gq

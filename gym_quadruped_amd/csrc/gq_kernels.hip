@@ -342,7 +342,11 @@ __global__ void __launch_bounds__(GQ_WAVE) camera_pose_kernel(const GqDevModel* 
   camera_pose_wave(W, *mptr(model), c, (int)blockIdx.x);
 }
 __global__ void __launch_bounds__(GQ_WAVE) camera_pixel_kernel(const GQ_GLOBAL GqDevModel* model, const CamCall c) {
-  camera_tile_wave(*model, c, (int)blockIdx.x, (int)blockIdx.y);
+  camera_tile_wave<false>(*model, c, nullptr, (int)blockIdx.x, (int)blockIdx.y);
+}
+/* gq_camera_shaded: the same pixel pass, plus the RGBA image */
+__global__ void __launch_bounds__(GQ_WAVE) camera_shade_kernel(const GQ_GLOBAL GqDevModel* model, const CamCall c, const CamShade s) {
+  camera_tile_wave<true>(*model, c, &s, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 #endif /* GQ_IN_MISC */
@@ -480,6 +484,11 @@ extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, 
   const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
   hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
   hipLaunchKernelGGL(gq::camera_pixel_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c);
+}
+extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, int n_envs, hipStream_t stream) {
+  const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
+  hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
+  hipLaunchKernelGGL(gq::camera_shade_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c, *s);
 }
 extern "C" void gq_launch_ray(const GQ_GLOBAL GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream) {
   hipLaunchKernelGGL(gq::ray_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, model, origin, dir, total, dist, geom);

@@ -53,6 +53,8 @@ _JOINT_DEF = dict(type='hinge', pos='0 0 0', axis='0 0 1', range='0 0', limited=
 _MOTOR_DEF = dict(ctrlrange='0 0', ctrllimited='auto', forcerange='0 0', forcelimited='auto', gear='1 0 0 0 0 0')
 _SITE_DEF = dict(pos='0 0 0', quat='1 0 0 0')
 _CAMERA_DEF = dict(pos='0 0 0', fovy='45', mode='fixed')
+_MATERIAL_DEF = dict(rgba='1 1 1 1', specular='0.5', shininess='0.5', emission='0')   # MuJoCo's <material> defaults
+GEOM_RGBA_DEFAULT = (0.5, 0.5, 0.5, 1.0)                                            # MuJoCo's geom rgba default
 CAMERA_MODES = {'fixed': 0, 'track': 1, 'trackcom': 2, 'targetbody': 3, 'targetbodycom': 4}
 
 
@@ -315,6 +317,16 @@ class ModelDesc:
     cam_fovy: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0))   # degrees
     cam_mode: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
 
+    # Appearance of every geom, for the shaded camera - plain attributes, not dataclass fields: they are not part of the compiled
+    # tables (model_data/ holds physics and cameras only), so a loaded table has MuJoCo's defaults and compile_mjcf sets what the MJCF
+    # says.  geom_rgba (ngeom, 4): geom rgba > material rgba > default class rgba > (0.5, 0.5, 0.5, 1); geom_specular / geom_shininess /
+    # geom_emission (ngeom,): the geom's <material>, else MuJoCo's material defaults (0.5, 0.5, 0).
+    def __post_init__(self):
+        self.geom_rgba = np.tile(np.asarray(GEOM_RGBA_DEFAULT), (self.ngeom, 1))
+        self.geom_specular = np.full(self.ngeom, float(_MATERIAL_DEF['specular']))
+        self.geom_shininess = np.full(self.ngeom, float(_MATERIAL_DEF['shininess']))
+        self.geom_emission = np.full(self.ngeom, float(_MATERIAL_DEF['emission']))
+
     # ---- (de)serialisation: plain JSON tables
     def to_json(self) -> str:
         d = {}
@@ -357,6 +369,7 @@ class _Compiler:
         self.mesh_hulls = mesh_hulls
         self.defaults = _Defaults()
         self.meshes: dict[str, dict] = {}
+        self.materials: dict[str, dict] = {}
         self.root = self._load_with_includes(self.xml_path)
 
     def _load_with_includes(self, path: Path):
@@ -397,6 +410,9 @@ class _Compiler:
                 attr = self.defaults.resolve('mesh', m, None, {})
                 name = attr.get('name') or Path(attr['file']).stem
                 self.meshes[name] = attr
+            for m in a.findall('material'):
+                attr = self.defaults.resolve('material', m, None, _MATERIAL_DEF)
+                self.materials[attr.get('name', '')] = attr
 
         B = dict(names=['world'], parent=[0], pos=[np.zeros(3)], quat=[np.array([1.0, 0, 0, 0])],
                  ipos=[np.zeros(3)], iquat=[np.array([1.0, 0, 0, 0])], mass=[0.0], inertia=[np.zeros(3)],
@@ -405,7 +421,7 @@ class _Compiler:
                  margin=[], solref=[], solimp=[], afl=[], afr=[], qpos0=[], ref=[])
         D = dict(body=[], jnt=[], parent=[], damping=[], armature=[], frictionloss=[], solref=[], solimp=[])
         G = dict(names=[], type=[], body=[], pos=[], quat=[], size=[], friction=[], margin=[], gap=[], condim=[],
-                 contype=[], conaffinity=[], priority=[], solref=[], solimp=[], solmix=[], group=[], mesh=[])
+                 contype=[], conaffinity=[], priority=[], solref=[], solimp=[], solmix=[], group=[], mesh=[], rgba=[], matl=[])
         S = dict(names=[], body=[], pos=[], quat=[])
         CAM = dict(names=[], body=[], pos=[], quat=[], fovy=[], mode=[])
         self.B, self.J, self.D, self.G, self.S, self.CAM = B, J, D, G, S, CAM
@@ -491,6 +507,8 @@ class _Compiler:
             cam_names=CAM['names'], cam_bodyid=arr(CAM['body'], np.int32), cam_pos=arr(CAM['pos']).reshape(len(CAM['names']), 3),
             cam_quat=arr(CAM['quat']).reshape(len(CAM['names']), 4), cam_fovy=arr(CAM['fovy']), cam_mode=arr(CAM['mode'], np.int32),
         )
+        matl = arr(G['matl']).reshape(ng, 3)
+        md.geom_rgba, md.geom_specular, md.geom_shininess, md.geom_emission = arr(G['rgba']).reshape(ng, 4), matl[:, 0], matl[:, 1], matl[:, 2]
         set_const(md)
         return md
 
@@ -540,6 +558,15 @@ class _Compiler:
                 G['solmix'].append(float(a['solmix']))
                 G['group'].append(int(a['group']))
                 G['mesh'].append(a.get('mesh'))
+                mat = None
+                if 'material' in a:
+                    if a['material'] not in self.materials:
+                        raise ValueError(f'geom {a.get("name", "")!r}: unknown material {a["material"]!r}')
+                    mat = self.materials[a['material']]
+                rgba = ch.attrib['rgba'] if 'rgba' in ch.attrib else mat['rgba'] if mat else a.get('rgba', ' '.join(map(str, GEOM_RGBA_DEFAULT)))
+                G['rgba'].append(_f(rgba, 4))
+                m = mat or _MATERIAL_DEF
+                G['matl'].append([float(m['specular']), float(m['shininess']), float(m['emission'])])
             elif ch.tag == 'site':
                 a = self.defaults.resolve('site', ch, childclass, _SITE_DEF)
                 S['names'].append(a.get('name', ''))

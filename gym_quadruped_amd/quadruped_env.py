@@ -55,7 +55,7 @@ class QuadrupedEnv(AccessorsMixin):
 
     _DEFAULT_OBS = ('qpos', 'qvel', 'tau_ctrl_setpoint', 'feet_pos:base', 'feet_vel:base')
     ALL_OBS = list(_ALL_OBS)
-    metadata = {'render.modes': [], 'version': 0}
+    metadata = {'render.modes': ['rgb_array'], 'version': 0}
 
     def __init__(
         self,
@@ -607,8 +607,30 @@ class QuadrupedEnv(AccessorsMixin):
     def enable_debug(self, n_envs: int):
         _lib.check(self._L.gq_debug_enable(self._hbatch, int(n_envs)), 'gq_debug_enable')
 
-    def render(self, *a, **k):
-        raise NotImplementedError('interactive MuJoCo viewer rendering is out of scope of the batched GPU path')
+    def render(self, mode: str = 'human', *, width: int = 320, height: int = 240, distance: float = 2.0, azimuth: float = 90.0,
+               elevation: float = -45.0):
+        """``mode='rgb_array'``: ``[N, H, W, 3]`` uint8 on the env's device, one frame per env (a fresh tensor) from a camera that tracks
+        the base: it looks along ``f = (cos el cos az, cos el sin az, sin el)`` (degrees, world axes) from ``base - distance f``, world
+        up, 45 degree fovy (``sensors.Camera(rgb=True, track=True)``, cached per argument set).  Every other mode raises: an interactive
+        viewer is out of scope of the batched GPU path."""
+        if mode != 'rgb_array':
+            raise NotImplementedError(f'render(mode={mode!r}): only mode="rgb_array" is available (an interactive viewer is out of scope '
+                                      'of the batched GPU path)')
+        key = (int(width), int(height), float(distance), float(azimuth), float(elevation))
+        cams = self.__dict__.setdefault('_render_cams', {})
+        if key not in cams:
+            from .mjcf import mat_to_quat
+            from .sensors import Camera
+            az, el = np.deg2rad(azimuth), np.deg2rad(elevation)
+            f = np.array([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
+            right = np.cross(f, [0.0, 0.0, 1.0])
+            if np.linalg.norm(right) < 1e-6:
+                raise ValueError(f'render: elevation {elevation} looks straight up or down, the world up is undefined')
+            right /= np.linalg.norm(right)
+            R = np.stack([right, np.cross(right, f), -f], 1)   # columns: camera x (right), y (up), z (backwards)
+            cams[key] = Camera(width, height, 30, self.robot_model, self.sim_data, body=1, pos=-distance * f, quat=mat_to_quat(R), fovy=45.0,
+                               rgb=True, track=True)
+        return cams[key].image.contiguous()
 
     def close(self):
         if getattr(self, '_hbatch', None):

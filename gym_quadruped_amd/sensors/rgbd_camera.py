@@ -3,8 +3,10 @@
 The reference renders one ``mujoco.Renderer`` image per call.  Here ``gq_camera`` ray casts the images of every env in two kernel
 launches (csrc/gq_camera.h), against the collision geometry the device model holds: the robot's foot spheres and link geoms, the floor,
 the world boxes and the height field.  Visual-only geoms (``contype = conaffinity = 0``, group-2 meshes) have no geometry in this
-package, so silhouettes follow the collision shapes; each env is its own world (other envs' robots are never drawn).  There is no
-rasteriser and no material: ``image`` (RGB) raises.  DESIGN.md §2 pins the pixel rays, the depth rules and the segmentation ids.
+package, so silhouettes follow the collision shapes; each env is its own world (other envs' robots are never drawn).  With ``rgb=True``
+the same rays are shaded (``gq_camera_shaded``: per-geom colours, a floor checker, a headlight and up to seven lights, see ``Appearance``)
+and ``image`` is the RGB image; without it ``image`` raises.  DESIGN.md §2 pins the pixel rays, the depth rules, the segmentation ids and
+the lighting model.
 
 The pose is that of the ``qpos`` the images are cast from - the env's current state by default.  MuJoCo's ``update_scene`` after
 ``mj_step`` shows the kinematics of the step's START (mjData.xpos is not updated by the integrator): a caller who wants that timing
@@ -12,6 +14,8 @@ passes a ``qpos`` saved before the step to ``render(qpos=...)``.
 """
 from __future__ import annotations
 
+import ctypes as C
+import dataclasses
 import os
 from datetime import datetime
 
@@ -19,18 +23,95 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..cabi import hull_planes
+from ..cabi import GQ_CAM_MAXLIGHT, GQ_CAM_ROBOT, GQ_CAM_SCENE, GQ_CAM_TRACK, GqCamShade, hull_planes
 from ..mjcf import CAMERA_MODES
+
+
+@dataclasses.dataclass
+class Light:
+    """One light of ``Appearance`` (include/gq.h GqCamLight).  The field defaults are MuJoCo's ``<light>`` defaults; world axes."""
+    pos: tuple = (0.0, 0.0, 0.0)
+    dir: tuple = (0.0, 0.0, -1.0)
+    ambient: tuple = (0.0, 0.0, 0.0)
+    diffuse: tuple = (0.7, 0.7, 0.7)
+    specular: tuple = (0.3, 0.3, 0.3)
+    attenuation: tuple = (1.0, 0.0, 0.0)
+    cutoff: float = 45.0       # degrees, spot lights
+    exponent: float = 10.0     # spot lights
+    directional: bool = False
+
+
+@dataclasses.dataclass
+class Appearance:
+    """What the shaded camera draws with (include/gq.h GqCamShade): ``geom_mat`` [ngeom, 7] (rgba, specular, shininess, emission per
+    ModelDesc geom), the world boxes' material, the floor / height-field checker, the background gradient, the headlight and up to
+    seven more lights.  Colours and material values lie in [0, 1].  ``Appearance.default(model)`` takes the geoms' colours from the
+    model; the scene values are this package's choice, the headlight is MuJoCo's default."""
+    geom_mat: np.ndarray
+    box_mat: tuple = (0.62, 0.52, 0.40, 1.0, 0.2, 0.3, 0.0)
+    floor_rgb1: tuple = (0.42, 0.45, 0.48)
+    floor_rgb2: tuple = (0.30, 0.33, 0.36)
+    floor_square: float = 0.5
+    floor_mark_rgb: tuple = (0.65, 0.67, 0.70)
+    floor_mark_w: float = 0.0
+    floor_specular: float = 0.1
+    floor_shininess: float = 0.2
+    floor_emission: float = 0.0
+    bg_top: tuple = (0.62, 0.75, 0.90)
+    bg_bottom: tuple = (0.20, 0.22, 0.25)
+    head_ambient: tuple = (0.1, 0.1, 0.1)
+    head_diffuse: tuple = (0.4, 0.4, 0.4)
+    head_specular: tuple = (0.5, 0.5, 0.5)
+    head_active: bool = True
+    lights: list = dataclasses.field(default_factory=lambda: [Light(dir=(0.3, 0.2, -1.0), ambient=(0.1, 0.1, 0.1), diffuse=(0.6, 0.6, 0.6),
+                                                                    directional=True)])
+
+    @classmethod
+    def default(cls, model) -> 'Appearance':
+        """The model's geom colours and materials (``ModelDesc.geom_rgba`` etc.) and this package's scene defaults."""
+        return cls(geom_mat=geom_materials(model))
+
+    def struct(self) -> GqCamShade:
+        """The ``GqCamShade`` of these values (``geom_mat`` left NULL: the caller sets the device pointer).  Raises ValueError on a value
+        gq_camera_shaded would refuse."""
+        gm = np.asarray(self.geom_mat, dtype=np.float64)
+        if gm.ndim != 2 or gm.shape[1] != 7 or not np.all(np.isfinite(gm)) or gm.min(initial=0.0) < 0 or gm.max(initial=0.0) > 1:
+            raise ValueError('Appearance.geom_mat must be [ngeom, 7] with values in [0, 1]')
+        if len(self.lights) > GQ_CAM_MAXLIGHT:
+            raise ValueError(f'at most {GQ_CAM_MAXLIGHT} lights besides the headlight (got {len(self.lights)})')
+        s = GqCamShade()
+        s.struct_size = C.sizeof(GqCamShade)
+        s.nlight = len(self.lights)
+        for k in ('box_mat', 'floor_rgb1', 'floor_rgb2', 'floor_mark_rgb', 'bg_top', 'bg_bottom', 'head_ambient', 'head_diffuse', 'head_specular'):
+            v = getattr(self, k)
+            getattr(s, k)[:] = [float(x) for x in v]
+        for k in ('floor_square', 'floor_mark_w', 'floor_specular', 'floor_shininess', 'floor_emission'):
+            setattr(s, k, float(getattr(self, k)))
+        s.head_active = int(bool(self.head_active))
+        for i, L in enumerate(self.lights):
+            o = s.light[i]
+            for k in ('pos', 'dir', 'ambient', 'diffuse', 'specular', 'attenuation'):
+                getattr(o, k)[:] = [float(x) for x in getattr(L, k)]
+            o.cutoff, o.exponent, o.directional = float(L.cutoff), float(L.exponent), int(bool(L.directional))
+        return s
+
+
+def geom_materials(md) -> np.ndarray:
+    """[ngeom, 7] float64: rgba, specular, shininess, emission of every ModelDesc geom."""
+    return np.concatenate([np.asarray(md.geom_rgba, np.float64).reshape(-1, 4), np.stack([md.geom_specular, md.geom_shininess, md.geom_emission], 1)], 1)
 
 
 class Camera:
     """``Camera(width, height, fps, mj_model, mj_data, cam_name='', save_dir='data/img/')`` as in the reference, batched over the envs of
     ``mj_data`` (the ``QuadrupedEnv``; ``env.sim_data``).  Extensions: a camera that is not in the MJCF - ``body`` (name or ModelDesc
     index, 0 = world), ``pos``, ``quat`` (wxyz, MuJoCo's camera frame: looks along -z, y up) and ``fovy`` (degrees) - and the depth range
-    ``znear`` / ``zfar`` (metres; MuJoCo's defaults scaled by a 1 m extent)."""
+    ``znear`` / ``zfar`` (metres; MuJoCo's defaults scaled by a 1 m extent); ``rgb=True``: also shade an RGB image (``image``) with
+    ``appearance`` (default ``Appearance.default(model)``); ``track=True`` (cameras given by ``body=`` only): ``pos`` and ``quat`` are in
+    world axes - the camera follows the body's position and keeps its own orientation (MuJoCo's ``mode="track"`` idea)."""
 
     def __init__(self, width, height, fps, mj_model, mj_data, cam_name: str = '', save_dir='data/img/', *, body=None, pos=None, quat=None,
-                 fovy=None, znear: float = 0.01, zfar: float = 50.0):
+                 fovy=None, znear: float = 0.01, zfar: float = 50.0, rgb: bool = False, appearance: Appearance | None = None,
+                 track: bool = False):
         env = mj_data
         md = env.mjModel
         self._env, self._md = env, md
@@ -49,7 +130,10 @@ class Camera:
             body_id, cpos, cquat, cfovy = (md.body_names.index(body) if isinstance(body, str) else int(body)), (0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0), 45.0
         else:
             raise ValueError('Camera needs cam_name= (a <camera> of the MJCF) or body= (extension: a camera given by body, pos, quat, fovy)')
+        if track and (cam_name or body_id == 0):
+            raise ValueError('track=True is for cameras given by body= (a moving body, not the world)')
         self._body = body_id
+        self._flags = GQ_CAM_ROBOT | GQ_CAM_SCENE | (GQ_CAM_TRACK if track else 0)
         self._pos = np.asarray(cpos if pos is None else pos, dtype=np.float64).reshape(3)
         self._quat = np.asarray(cquat if quat is None else quat, dtype=np.float64).reshape(4)
         self._quat = self._quat / np.linalg.norm(self._quat)
@@ -72,6 +156,15 @@ class Camera:
         self._seg = torch.full((N, H, W), -1, dtype=torch.int32, device=dev)
         self._xpos = torch.zeros(N, 3, dtype=torch.float64, device=dev)
         self._xmat = torch.zeros(N, 9, dtype=torch.float32, device=dev)
+        self._rgb = bool(rgb)
+        if self._rgb:
+            self.appearance = appearance if appearance is not None else Appearance.default(md)
+            if len(self.appearance.geom_mat) != md.ngeom:
+                raise ValueError(f'Appearance.geom_mat has {len(self.appearance.geom_mat)} rows, the model {md.ngeom} geoms')
+            self._shade = self.appearance.struct()
+            self._geom_mat = torch.as_tensor(np.asarray(self.appearance.geom_mat, np.float32), device=dev).contiguous()
+            self._shade.geom_mat = self._geom_mat.data_ptr()
+            self._rgba = torch.zeros(N, H, W, 4, dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------------ the reference's properties
     @property
@@ -152,10 +245,14 @@ class Camera:
         stream = torch.cuda.current_stream(env.device).cuda_stream
         pos = (np.ctypeslib.as_ctypes(self._pos))
         quat = (np.ctypeslib.as_ctypes(self._quat))
-        _lib.check(_lib.lib().gq_camera(env._hbatch, q.data_ptr(), int(q.stride(0)), self._body, pos, quat, self._fovy, self._width, self._height,
-                                        self._znear, self._zfar, 3, None if self._planes is None else self._planes.data_ptr(),
-                                        None if self._plane_adr is None else np.ctypeslib.as_ctypes(self._plane_adr),
-                                        self._depth_plane.data_ptr(), self._seg.data_ptr(), self._xpos.data_ptr(), self._xmat.data_ptr(), stream), 'gq_camera')
+        args = (env._hbatch, q.data_ptr(), int(q.stride(0)), self._body, pos, quat, self._fovy, self._width, self._height, self._znear, self._zfar,
+                self._flags, None if self._planes is None else self._planes.data_ptr(),
+                None if self._plane_adr is None else np.ctypeslib.as_ctypes(self._plane_adr),
+                self._depth_plane.data_ptr(), self._seg.data_ptr(), self._xpos.data_ptr(), self._xmat.data_ptr())
+        if self._rgb:
+            _lib.check(_lib.lib().gq_camera_shaded(*args, C.byref(self._shade), self._rgba.data_ptr(), stream), 'gq_camera_shaded')
+        else:
+            _lib.check(_lib.lib().gq_camera(*args, stream), 'gq_camera')
 
     @property
     def depth_plane(self) -> torch.Tensor:
@@ -203,36 +300,46 @@ class Camera:
         return pts.transpose(1, 2).to(depth_image.dtype)
 
     @property
-    def image(self):
-        raise NotImplementedError('Camera.image (RGB) is not available: the camera is a ray caster - there is no rasteriser and the '
-                                  'models carry no materials.  depth_image, depth_plane, seg_image and point_cloud are.')
+    def image(self) -> torch.Tensor:
+        """``[N, H, W, 3]`` uint8 RGB (a view of the ``[N, H, W, 4]`` RGBA buffer, overwritten by the next render).  Needs ``rgb=True``."""
+        if not self._rgb:
+            raise NotImplementedError('Camera.image (RGB) needs Camera(..., rgb=True): this camera casts depth and segmentation only '
+                                      '(depth_image, depth_plane, seg_image and point_cloud).')
+        self.render()
+        return self._rgba[..., :3]
 
     def shoot(self, autosave: bool = True, img: bool = False, depth: bool = True, seg: bool = True) -> None:
-        """Cast once and keep depth image, point cloud and segmentation (``img=True`` raises: no RGB)."""
-        if img:
+        """Cast once and keep depth image, point cloud and segmentation, and with ``img=True`` the RGB image (needs ``rgb=True``)."""
+        if img and not self._rgb:
             self.image
         self.render()
         self._depth_image = self._range(self._depth_plane)
         self._point_cloud = self._depth_to_point_cloud(self._depth_image)
         self._seg_image = self._seg.clone()
+        if img:
+            self._image = self._rgba[..., :3].clone()
         if autosave:
-            self.save(depth=depth, seg=seg, fresh=False)
+            self.save(img=img, depth=depth, seg=seg, fresh=False)
 
     def save(self, img_name: str = '', img: bool = False, depth: bool = False, seg: bool = False, fresh: bool = True) -> None:
-        """Save depth ``[N, H, W]`` and segmentation ``[N, H, W]`` as ``.npy`` (the reference writes PNGs through cv2, which is not a
-        dependency here).  ``fresh=False``: save what the last ``shoot`` cast instead of casting again."""
-        if img:
+        """Save RGB ``[N, H, W, 3]`` uint8, depth ``[N, H, W]`` and segmentation ``[N, H, W]`` as ``.npy`` (the reference writes PNGs
+        through cv2, which is not a dependency here).  ``fresh=False``: save what the last ``shoot`` cast instead of casting again."""
+        if img and not self._rgb:
             self.image
         os.makedirs(os.path.join(self._save_dir, 'images'), exist_ok=True)
         if fresh:
             self.render()
             self._depth_image, self._seg_image = self._range(self._depth_plane), self._seg
-        print(f'saving {"depth image " if depth else ""}{"segmentation image " if seg else ""}to {self.save_dir}')
+            if img:
+                self._image = self._rgba[..., :3]
+        print(f'saving {"image " if img else ""}{"depth image " if depth else ""}{"segmentation image " if seg else ""}to {self.save_dir}')
         stem = f'{img_name}_' if img_name else ''
         suffix = '' if img_name else f'_{self.save_counter}'
         if seg:
             np.save(os.path.join(self._save_dir, f'{stem}seg{suffix}.npy'), self._seg_image.cpu().numpy())
         if depth:
             np.save(os.path.join(self._save_dir, 'images', f'{stem}depth{suffix}.npy'), self._depth_image.cpu().numpy())
+        if img:
+            np.save(os.path.join(self._save_dir, 'images', f'{stem}image{suffix}.npy'), self._image.cpu().numpy())
         if not img_name:
             self.save_counter += 1

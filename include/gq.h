@@ -20,6 +20,7 @@
  *   mujoco.mj_contactForce         quadruped_env.py:852    gq_contact_force (contact rows of gq_batch_set_outputs); summed per foot: obs epilogue
  *   mujoco.mj_fullM                quadruped_env.py:940    dyn rows of gq_batch_set_outputs (production kernel); gq_full_mass (inspection record)
  *   mujoco.Renderer depth / segmentation  sensors/rgbd_camera.py   gq_camera (ray cast, collision geometry)
+ *   mujoco.Renderer RGB            sensors/rgbd_camera.py   gq_camera_shaded (the same rays, shaded)
  *
  * Conventions
  *  - plain C, no exceptions cross the boundary; every function returns 0 on
@@ -63,8 +64,8 @@ extern "C" {
  * GqModelDesc.plane_* (optional); 510 = gq_batch_set_heightmap (no struct changed); 600 = GqModelDesc.vert_adj* / plane_order (hull
  * graphs: multi-point mesh-plane contacts), the general convex narrow phase (GJK / EPA) behind the same tables; 610 = gq_batch_set_pair_exchange
  * (no struct changed); 620 = GqModelDesc.support_grid (optional); 630 = that grid 16 x 16 cells per face (was 8 x 8); 640 = gq_camera
- * (no struct changed). */
-#define GQ_ABI_VERSION 640
+ * (no struct changed); 650 = gq_camera_shaded + GqCamShade, gq_camera flags bit 2 (GQ_CAM_TRACK). */
+#define GQ_ABI_VERSION 650
 #ifndef GQ_SUPPORT_GRID
 #define GQ_SUPPORT_GRID 16 /* cells per edge of a cube-map face of GqModelDesc.support_grid */
 #endif
@@ -523,7 +524,7 @@ int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float
  * (the kinematics of `qpos`, one wavefront per env) and a pixel pass (one wavefront per 8 x 8 tile of one env).
  *   qpos: device [N][qpos_stride] f64 (the pose drawn); body: ModelDesc body index of the camera, 0 = world; pos / quat: host, the camera
  *   frame in the body frame (MuJoCo's camera frame: looks along -z, y up); fovy_deg: vertical field of view; znear / zfar: depth range;
- *   flags: bit 0 draws the robot, bit 1 the static scene.
+ *   flags: bit 0 draws the robot, bit 1 the static scene, bit 2 (GQ_CAM_TRACK, body cameras only) takes pos / quat in world axes.
  *   hull_planes: device [P][4] f32 face planes (n, d), n.x <= d inside, in the geom frame of the hull (mesh) clouds; hull_plane_adr: host
  *   [ncloud + 1] prefix offsets into it, indexed by GqModelDesc cloud id.  Both may be NULL only for a model without hull geoms (GQ_EINVAL).
  *   depth: device [N][H][W] f32 planar depth (distance along the camera's -z), zfar where nothing is hit in [znear, zfar];
@@ -536,6 +537,53 @@ int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float
 int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
               float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
               float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream);
+/* gq_camera / gq_camera_shaded flags */
+#define GQ_CAM_ROBOT 1   /* draw the robot */
+#define GQ_CAM_SCENE 2   /* draw the static scene */
+#define GQ_CAM_TRACK 4   /* body cameras (body > 0): origin = the body's world position + pos in WORLD axes, orientation = quat in world
+                          * axes (MuJoCo's mode="track" idea); without it pos / quat are in the body frame */
+
+/* Lights and materials of gq_camera_shaded.  Colours are linear RGB in [0, 1]; every value must be finite. */
+#define GQ_CAM_MAXLIGHT 7 /* lights besides the headlight */
+typedef struct {
+  float pos[3];         /* spot light: position, world (m) */
+  float dir[3];         /* direction the light points along, world (need not be unit, not zero) */
+  float ambient[3], diffuse[3], specular[3];
+  float attenuation[3]; /* spot light: 1 / (a0 + a1 r + a2 r^2) at distance r; >= 0, not all zero */
+  float cutoff;         /* spot light: half angle of the cone, degrees, (0, 90] */
+  float exponent;       /* spot light: falloff (-L.dir)^exponent inside the cone, >= 0 */
+  int32_t directional;  /* 1: directional (L = -dir, no attenuation, no cone), 0: spot */
+} GqCamLight;
+typedef struct {
+  int32_t struct_size;  /* = sizeof(GqCamShade) of the caller's header; gq_camera_shaded refuses any other value */
+  int32_t nlight;       /* lights used in light[], 0 .. GQ_CAM_MAXLIGHT */
+  const float* geom_mat;   /* device [ngeom][7] f32 per GqModelDesc geom: rgba (alpha ignored), specular, shininess, emission (each in [0, 1]) */
+  float box_mat[7];     /* the world boxes, same layout */
+  float floor_rgb1[3], floor_rgb2[3];  /* floor and height field: checker of square `floor_square` m in world x / y, rgb1 where */
+  float floor_square;                  /*   floor(x / s) + floor(y / s) is even, rgb2 where odd */
+  float floor_mark_rgb[3], floor_mark_w; /* colour within floor_mark_w m (>= 0; 0: none) of a square's edge */
+  float floor_specular, floor_shininess, floor_emission;
+  float bg_top[3], bg_bottom[3];       /* no hit: mix(bottom, top, (1 + d_z) / 2), d_z: world z of the unit ray */
+  float head_ambient[3], head_diffuse[3], head_specular[3];   /* the headlight: directional, L = the camera's +z */
+  int32_t head_active;  /* 0 / 1 */
+  GqCamLight light[GQ_CAM_MAXLIGHT];
+} GqCamShade;
+
+/* gq_camera plus a shaded RGB image of the same rays: the arguments of gq_camera (depth, seg, cam_xpos and cam_xmat are written exactly as
+ * gq_camera writes them for the same qpos), then
+ *   shade: host, lights and materials (validated: GQ_EINVAL on a struct_size mismatch, a non-finite value, a colour or material value
+ *   outside [0, 1], nlight outside [0, 7], a cutoff outside (0, 90], all-zero or negative attenuation, a zero direction; the device
+ *   table geom_mat is the caller's to fill with values in [0, 1]);
+ *   rgba: device [N][H][W][4] u8, alpha 255.
+ * Per pixel, at the nearest hit and its outward normal n (fp32, camera frame), with base colour c and material (spec, shin, emis):
+ *   out = emis c + sum_l att_l spot_l [A_l c + D_l c max(n.L, 0) + (n.L > 0 ? S_l spec max(n.H, 0)^(128 shin) : 0)],
+ * L the unit vector from the hit towards the light, H = normalize(L + v), v the unit vector towards the camera; a directional light has
+ * L = -dir and att = spot = 1, a spot light att = 1 / (a0 + a1 r + a2 r^2) and spot = (-L.dir >= cos cutoff) ? (-L.dir)^exponent : 0.
+ * Each channel is clamped to [0, 1] and stored as floor(255 x + 0.5).  No shadows, reflections, fog, transparency or textures besides
+ * the checker.  Two launches on hip_stream, as gq_camera: the pose pass, then the shaded pixel pass. */
+int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
+                     int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                     float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, void* hip_stream);
 
 /* mujoco.mj_step1 (quadruped_env.py:376, :384: position + velocity stages) and mujoco.mj_forward (:1321: through the
  * accelerations) for every env WITHOUT advancing the state: stage 1 = mj_step1 (kinematics, inertias, collision,

@@ -1,0 +1,224 @@
+"""Host side of the shaded camera: the MJCF colour and material tables, the GqCamShade mirror and gq_camera_shaded's argument table and
+checks, Appearance, and known answers of the fp64 numpy shader the GPU tests compare against (camera_shading.py)."""
+import ctypes
+import subprocess
+import tempfile
+import types
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from camera_shading import background, checker, lights_of, shade, to_bytes
+
+ROOT = Path(__file__).resolve().parents[1]
+
+
+def _toy_xml(body_geoms, assets='', defaults=''):
+    legs = ''.join(f'''<body name="L{i}_hip" pos="0.1 0 0"><inertial pos="0 0 0" mass="1" diaginertia="1e-3 1e-3 1e-3"/>
+      <joint name="j{i}a" axis="0 1 0"/><body name="L{i}_thigh"><inertial pos="0 0 -0.1" mass="1" diaginertia="1e-3 1e-3 1e-3"/><joint name="j{i}b" axis="0 1 0"/>
+      <body name="L{i}_calf" pos="0 0 -0.2"><inertial pos="0 0 -0.1" mass="0.5" diaginertia="1e-3 1e-3 1e-3"/><joint name="j{i}c" axis="1 0 0"/>
+      <geom name="{n}" size="0.02" pos="0 0 -0.2"/></body></body></body>''' for i, n in enumerate(['FL', 'FR', 'RL', 'RR']))
+    return f'''<mujoco model="toy"><compiler angle="radian"/><default>{defaults}</default><asset>{assets}</asset>
+      <worldbody><body name="base" pos="0 0 0.5"><inertial pos="0 0 0" mass="5" diaginertia="0.1 0.1 0.1"/><freejoint/>{body_geoms}{legs}</body></worldbody>
+      <actuator>{''.join(f'<motor name="m{i}{c}" joint="j{i}{c}"/>' for i in range(4) for c in 'abc')}</actuator></mujoco>'''
+
+
+def test_mjcf_colour_precedence_and_materials(tmp_path):
+    from gym_quadruped_amd.mjcf import compile_mjcf
+    defaults = '<default class="red"><geom rgba="1 0 0 1"/></default><default class="shiny"><geom material="gold"/></default>'
+    assets = ('<material name="gold" rgba="0.9 0.7 0.1 1" specular="0.8" shininess="0.9" emission="0.2"/>'
+              '<material name="plain"/>')
+    geoms = ('<geom name="explicit" type="box" size="0.1 0.1 0.1" rgba="0 1 0 1" material="gold" class="red"/>'   # 1. geom rgba
+             '<geom name="mat" type="box" size="0.1 0.1 0.1" material="gold" class="red"/>'                     # 2. material over class
+             '<geom name="cls" type="box" size="0.1 0.1 0.1" class="red"/>'                                     # 3. class default
+             '<geom name="none" type="box" size="0.1 0.1 0.1"/>'                                                # 4. MuJoCo's default
+             '<geom name="clsmat" type="box" size="0.1 0.1 0.1" class="shiny"/>'                                # material from a class
+             '<geom name="plain" type="box" size="0.1 0.1 0.1" material="plain"/>')                             # material defaults
+    p = tmp_path / 'toy.xml'
+    p.write_text(_toy_xml(geoms, assets, defaults))
+    md = compile_mjcf(p)
+    g = {n: md.geom_names.index(n) for n in ('explicit', 'mat', 'cls', 'none', 'clsmat', 'plain', 'FL')}
+    np.testing.assert_allclose(md.geom_rgba[g['explicit']], [0, 1, 0, 1])
+    np.testing.assert_allclose(md.geom_rgba[g['mat']], [0.9, 0.7, 0.1, 1])
+    np.testing.assert_allclose(md.geom_rgba[g['cls']], [1, 0, 0, 1])
+    np.testing.assert_allclose(md.geom_rgba[g['none']], [0.5, 0.5, 0.5, 1])
+    np.testing.assert_allclose(md.geom_rgba[g['clsmat']], [0.9, 0.7, 0.1, 1])
+    np.testing.assert_allclose(md.geom_rgba[g['plain']], [1, 1, 1, 1])            # MuJoCo's material rgba default
+    np.testing.assert_allclose(md.geom_rgba[g['FL']], [0.5, 0.5, 0.5, 1])
+    for k in ('explicit', 'mat', 'clsmat'):   # the material's fields come with it, whatever sets the colour
+        assert (md.geom_specular[g[k]], md.geom_shininess[g[k]], md.geom_emission[g[k]]) == (0.8, 0.9, 0.2)
+    for k in ('cls', 'none', 'plain', 'FL'):
+        assert (md.geom_specular[g[k]], md.geom_shininess[g[k]], md.geom_emission[g[k]]) == (0.5, 0.5, 0.0)
+    with pytest.raises(ValueError, match='unknown material'):
+        p.write_text(_toy_xml('<geom type="box" size="0.1 0.1 0.1" material="nope"/>'))
+        compile_mjcf(p)
+
+
+@pytest.mark.parametrize('robot', ['aliengo', 'mini_cheetah', 'go2', 'spot'])
+def test_registry_models_load_default_colours(robot):
+    from gym_quadruped_amd.mjcf import load_compiled
+    from gym_quadruped_amd.sensors import Appearance
+    md = load_compiled(robot)
+    assert md.geom_rgba.shape == (md.ngeom, 4)
+    np.testing.assert_array_equal(md.geom_rgba, np.tile([0.5, 0.5, 0.5, 1.0], (md.ngeom, 1)))
+    np.testing.assert_array_equal(md.geom_specular, 0.5)
+    np.testing.assert_array_equal(md.geom_shininess, 0.5)
+    np.testing.assert_array_equal(md.geom_emission, 0.0)
+    app = Appearance.default(md)
+    assert app.geom_mat.shape == (md.ngeom, 7)
+    np.testing.assert_array_equal(app.geom_mat[0], [0.5, 0.5, 0.5, 1.0, 0.5, 0.5, 0.0])
+    assert app.head_active and len(app.lights) == 1 and app.lights[0].directional
+
+
+def test_camshade_mirror_matches_header():
+    from gym_quadruped_amd.cabi import GqCamLight, GqCamShade
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(GqCamShade), sizeof(GqCamLight),'
+           'offsetof(GqCamShade, geom_mat), offsetof(GqCamShade, head_active), offsetof(GqCamShade, light));return 0;}')
+    with tempfile.TemporaryDirectory() as d:
+        (Path(d) / 'a.c').write_text(src)
+        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
+        out = [int(x) for x in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
+    assert out == [ctypes.sizeof(GqCamShade), ctypes.sizeof(GqCamLight), GqCamShade.geom_mat.offset, GqCamShade.head_active.offset,
+                   GqCamShade.light.offset]
+
+
+def _cpu_env(robot, n=2):
+    from gym_quadruped_amd.mjcf import load_compiled
+    return types.SimpleNamespace(mjModel=load_compiled(robot), num_envs=n, device=torch.device('cpu'), simulation_time=torch.zeros(n),
+                                 qpos=torch.zeros(n, 19, dtype=torch.float64), _hbatch=None)
+
+
+@pytest.mark.parametrize('robot,track', [('aliengo', False), ('mini_cheetah', True)])
+def test_camera_shaded_call_matches_argument_table(monkeypatch, robot, track):
+    """Camera(rgb=True).render() on CPU tensors, against the argument table _lib.py declares (test_host_and_abi._TypeCheckedLib)"""
+    from test_host_and_abi import _TypeCheckedLib
+    from gym_quadruped_amd import _lib
+    from gym_quadruped_amd.sensors import Camera
+    proxy = _TypeCheckedLib(_lib.lib())
+    monkeypatch.setattr(_lib, 'lib', lambda: proxy)
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda dev=None: types.SimpleNamespace(cuda_stream=None))
+    env = _cpu_env(robot)
+    cam = Camera(16, 8, 30, env.mjModel, env, body='base', pos=(0.0, -1.0, 0.5), rgb=True, track=track, save_dir='/nonexistent/')
+    cam.render()
+    Camera(16, 8, 30, env.mjModel, env, body='base').render()
+    assert proxy.calls == ['gq_camera_shaded', 'gq_camera']
+    assert cam._flags == (7 if track else 3)
+    assert cam._shade.struct_size == ctypes.sizeof(type(cam._shade)) and cam._shade.geom_mat == cam._geom_mat.data_ptr()
+    assert cam._rgba.shape == (2, 8, 16, 4) and cam._rgba.dtype == torch.uint8
+    with pytest.raises(ValueError, match='track'):
+        Camera(16, 8, 30, env.mjModel, env, body=0, track=True)
+    with pytest.raises(NotImplementedError, match='rgb=True'):
+        Camera(16, 8, 30, env.mjModel, env, body='base').image
+
+
+def _call_shaded(L, shade):
+    """gq_camera_shaded with a null batch: the GqCamShade checks come first, then the null batch is refused"""
+    pos, quat = (ctypes.c_double * 3)(0, 0, 0), (ctypes.c_double * 4)(1, 0, 0, 0)
+    rc = L.gq_camera_shaded(None, None, 19, 0, pos, quat, 45.0, 8, 8, 0.01, 10.0, 3, None, None, None, None, None, None, ctypes.byref(shade), None, None)
+    return rc, L.gq_last_error().decode()
+
+
+def test_gq_camera_shaded_checks_every_field():
+    from gym_quadruped_amd import _lib
+    from gym_quadruped_amd.mjcf import load_compiled
+    from gym_quadruped_amd.sensors import Appearance, Light
+    L = _lib.lib()
+    app = Appearance.default(load_compiled('aliengo'))
+    app.lights.append(Light())   # a spot light of MuJoCo's defaults
+    good = app.struct()
+    good.geom_mat = 16   # any non-null device address: the call stops at the null batch
+    rc, err = _call_shaded(L, good)
+    assert rc == -1 and 'null rgba' in err
+
+    def bad(edit, what):
+        s = app.struct()
+        s.geom_mat = 16
+        edit(s)
+        rc, err = _call_shaded(L, s)
+        assert rc == -1 and what in err, err
+    bad(lambda s: setattr(s, 'struct_size', s.struct_size - 4), 'struct_size')
+    bad(lambda s: setattr(s, 'geom_mat', None), 'geom_mat')
+    bad(lambda s: setattr(s, 'nlight', 8), 'nlight')
+    bad(lambda s: s.floor_rgb1.__setitem__(0, 1.5), 'floor_rgb1')
+    bad(lambda s: s.bg_top.__setitem__(2, float('nan')), 'bg_top')
+    bad(lambda s: s.box_mat.__setitem__(5, -0.1), 'box_mat')
+    bad(lambda s: setattr(s, 'floor_square', 0.0), 'floor_square')
+    bad(lambda s: setattr(s.light[1], 'cutoff', 0.0), 'cutoff')
+    bad(lambda s: setattr(s.light[1], 'cutoff', 91.0), 'cutoff')
+    bad(lambda s: s.light[1].attenuation.__setitem__(0, 0.0), 'attenuation')
+    bad(lambda s: s.light[1].diffuse.__setitem__(1, 2.0), 'colour')
+    bad(lambda s: s.light[0].dir.__setitem__(2, 0.0) or s.light[0].dir.__setitem__(0, 0.0) or s.light[0].dir.__setitem__(1, 0.0), 'zero direction')
+    bad(lambda s: s.light[0].pos.__setitem__(0, float('inf')), 'not finite')
+    with pytest.raises(ValueError):
+        Appearance(geom_mat=np.full((3, 7), 1.2)).struct()
+    with pytest.raises(ValueError):
+        Appearance(geom_mat=np.zeros((3, 7)), lights=[Light()] * 8).struct()
+
+
+# ---- known answers of the numpy shader
+def _app(**kw):
+    from gym_quadruped_amd.sensors import Appearance
+    a = Appearance(geom_mat=np.zeros((1, 7)), lights=[])
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_shader_sphere_under_the_headlight():
+    """camera at the origin looking along -z at a sphere centred on the axis: at the centre pixel n = v = L = +z, so the colour is
+    c (A + D) + S spec (n.H = 1), whatever the shininess"""
+    A, D, S = np.array([0.1, 0.1, 0.1]), np.array([0.4, 0.4, 0.4]), np.array([0.5, 0.5, 0.5])
+    app = _app(head_ambient=tuple(A), head_diffuse=tuple(D), head_specular=tuple(S))
+    c, spec = np.array([0.8, 0.3, 0.2]), 0.5
+    for shin in (0.0, 0.3, 1.0):
+        out = shade([c], [(spec, shin, 0.0)], [(0, 0, 1.0)], [(0, 0, 1.0)], [(0, 0, -2.0)], lights_of(app, np.eye(3)))
+        np.testing.assert_allclose(out[0], c * (A + D) + S * spec, rtol=1e-14)
+    # emission adds emis c; off the axis the diffuse term is D c cos and the highlight falls off
+    out = shade([c], [(spec, 0.5, 0.25)], [(0, 0, 1.0)], [(0, 0, 1.0)], [(0, 0, -2.0)], lights_of(app, np.eye(3)))
+    np.testing.assert_allclose(out[0], 0.25 * c + c * (A + D) + S * spec, rtol=1e-14)
+    n = np.array([np.sin(0.3), 0.0, np.cos(0.3)])
+    out = shade([c], [(spec, 0.5, 0.0)], [n], [(0, 0, 1.0)], [(0, 0, -2.0)], lights_of(app, np.eye(3)))
+    np.testing.assert_allclose(out[0], c * A + c * D * np.cos(0.3) + S * spec * np.cos(0.3) ** 64, rtol=1e-12)
+    assert list(to_bytes(np.array([0.0, 0.5, 1.0, 1.7, -0.2, 0.5 / 255]))) == [0, 128, 255, 255, 0, 1]
+
+
+def test_shader_spot_light_cone_and_attenuation():
+    from gym_quadruped_amd.sensors import Light
+    cut = 30.0
+    lt = Light(pos=(0.0, 0.0, 2.0), dir=(0.0, 0.0, -1.0), ambient=(0.2, 0.2, 0.2), diffuse=(0.5, 0.5, 0.5), specular=(0.0, 0.0, 0.0),
+               attenuation=(1.0, 0.5, 0.25), cutoff=cut, exponent=2.0)
+    app = _app(head_active=False, lights=[lt])
+    c = np.array([0.6, 0.6, 0.6])
+
+    def at(x):   # a floor point at distance x from the foot of the light
+        return shade([c], [(0.0, 0.5, 0.0)], [(0, 0, 1.0)], [(0, 0, 1.0)], [(x, 0.0, 0.0)], lights_of(app, np.eye(3)))[0]
+    edge = 2.0 * np.tan(np.deg2rad(cut))
+    assert np.all(at(edge * 1.001) == 0.0)                 # just outside the cone: nothing, not even its ambient
+    r = np.hypot(edge * 0.999, 2.0)
+    cs = 2.0 / r
+    np.testing.assert_allclose(at(edge * 0.999), cs ** 2 / (1 + 0.5 * r + 0.25 * r * r) * (0.2 * c + 0.5 * c * cs), rtol=1e-12)
+    np.testing.assert_allclose(at(0.0), 1 / (1 + 1 + 1) * (0.2 * c + 0.5 * c), rtol=1e-12)   # r = 2 straight below: spot = 1
+
+
+def test_shader_back_light_has_no_highlight_and_background_gradient():
+    from gym_quadruped_amd.sensors import Light
+    app = _app(head_active=False, lights=[Light(dir=(0.0, 0.0, 1.0), ambient=(0.1, 0.1, 0.1), diffuse=(0.7, 0.7, 0.7), specular=(1.0, 1.0, 1.0),
+                                                directional=True)])
+    c = np.array([0.5, 0.4, 0.3])
+    # lit from behind the surface (n.L < 0): ambient only, no diffuse and no specular even though n.H may be positive
+    out = shade([c], [(1.0, 0.0, 0.0)], [(0, 0, 1.0)], [(0.6, 0, 0.8)], [(0, 0, 0.0)], lights_of(app, np.eye(3)))
+    np.testing.assert_allclose(out[0], 0.1 * c, rtol=1e-14)
+    bg = _app(bg_top=(1.0, 0.5, 0.0), bg_bottom=(0.0, 0.5, 1.0))
+    np.testing.assert_allclose(background(bg, np.array([[0, 0, 3.0], [0, 0, -0.5], [1.0, 0, 0]])),
+                               [[1.0, 0.5, 0.0], [0.0, 0.5, 1.0], [0.5, 0.5, 0.5]], atol=1e-15)
+
+
+def test_checker_parity_and_mark():
+    app = _app(floor_square=0.5, floor_rgb1=(1.0, 1.0, 1.0), floor_rgb2=(0.0, 0.0, 0.0), floor_mark_rgb=(1.0, 0.0, 0.0), floor_mark_w=0.02)
+    x = np.array([0.25, 0.75, -0.25, 0.25, 1e4 + 0.25, 0.49, 0.1])
+    y = np.array([0.25, 0.25, 0.25, -0.25, 0.25, 0.25, 0.00005])
+    col, amb = checker(app, x, y)
+    np.testing.assert_array_equal(col, [[1, 1, 1], [0, 0, 0], [0, 0, 0], [0, 0, 0], [1, 1, 1], [1, 0, 0], [1, 0, 0]])
+    assert list(amb) == [False] * 6 + [True]   # within 1e-4 m of a square edge

@@ -1,6 +1,7 @@
-"""Time gq_camera (sensors.Camera.render: the pose pass and the pixel pass) with HIP events for a batch of envs.
+"""Time gq_camera (sensors.Camera.render: the pose pass and the pixel pass) with HIP events for a batch of envs; with --rgb the shaded
+call gq_camera_shaded (Camera(rgb=True), default Appearance) on the same cases.
 
-    python tools/camera_probe.py [--envs 4096] [--frames 50] [--warmup 5]
+    python tools/camera_probe.py [--envs 4096] [--frames 50] [--warmup 5] [--rgb]
 
 Cases: aliengo robotcam 64 x 64 on flat, random_boxes and perlin; mini_cheetah 64 x 64 with a camera under the trunk looking back at
 the legs; aliengo flat 128 x 128.  Prints one JSON line per case: median and spread of the per-frame time (ms)."""
@@ -25,6 +26,7 @@ def main():
     ap.add_argument('--envs', type=int, default=4096)
     ap.add_argument('--frames', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rgb', action='store_true', help='time the shaded call (depth, segmentation and RGB)')
     a = ap.parse_args()
     for robot, scene, S in CASES:
         env = QuadrupedEnv(robot, scene=scene, num_envs=a.envs, device='cuda:0', state_obs_names=('qpos',), seed=0)
@@ -33,10 +35,10 @@ def main():
         for _ in range(30):
             env.step(torch.randn(a.envs, 12, generator=g, device='cuda:0') * 5.0)
         if robot == 'aliengo':
-            cam = Camera(S, S, 30, env.robot_model, env.sim_data, cam_name='robotcam')
+            cam = Camera(S, S, 30, env.robot_model, env.sim_data, cam_name='robotcam', rgb=a.rgb)
         else:
             q = mat_to_quat(np.stack([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]], 1))
-            cam = Camera(S, S, 30, env.robot_model, env.sim_data, body='base', pos=(0.35, 0.0, -0.12), quat=q, fovy=90.0)
+            cam = Camera(S, S, 30, env.robot_model, env.sim_data, body='base', pos=(0.35, 0.0, -0.12), quat=q, fovy=90.0, rgb=a.rgb)
         for _ in range(a.warmup):
             cam.render()
         torch.cuda.synchronize()
@@ -47,7 +49,7 @@ def main():
             e1.synchronize()
             ms.append(e0.elapsed_time(e1))
         hit = float((cam._depth_plane < cam._zfar).float().mean())
-        print(json.dumps(dict(robot=robot, scene=scene, size=S, envs=a.envs, frames=a.frames, median_ms=float(np.median(ms)),
+        print(json.dumps(dict(robot=robot, scene=scene, size=S, rgb=a.rgb, envs=a.envs, frames=a.frames, median_ms=float(np.median(ms)),
                               p10_ms=float(np.percentile(ms, 10)), p90_ms=float(np.percentile(ms, 90)), hit_fraction=hit)), flush=True)
         env.close()
         del env, cam
