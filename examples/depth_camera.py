@@ -1,16 +1,18 @@
 """The reference's camera example (examples/aliengo_with_camera.py), batched: RGB, depth and segmentation images of every env from the
 ``robotcam`` camera on aliengo's trunk, saved as .npy instead of shown with cv2; and a tracking video frame of every env
-(``env.render('rgb_array')``) at the end.
+(``env.render('rgb_array')``) at the end, and one with two ghosts (20 steps behind and ahead) and the velocity arrows.
 
     python examples/depth_camera.py [scene] [num_envs] [steps]"""
 import sys
 from pathlib import Path
 
 import numpy as np
+import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from gym_quadruped_amd.quadruped_env import QuadrupedEnv  # noqa: E402
 from gym_quadruped_amd.sensors import Camera  # noqa: E402
+from gym_quadruped_amd.utils.visual import velocity_markers  # noqa: E402
 
 robot_name = 'aliengo'
 scene_name = sys.argv[1] if len(sys.argv) > 1 else 'stairs'   # "flat", "stairs", "perlin", "random_boxes", ...
@@ -48,4 +50,18 @@ for _ in range(steps):
 frame = env.render('rgb_array')                         # [N, 240, 320, 3] uint8 from a camera tracking each base
 Path(cam.save_dir).mkdir(parents=True, exist_ok=True)
 np.save(Path(cam.save_dir) / 'render.npy', frame.cpu().numpy())
+
+# ghosts: the pose 20 steps behind and 20 steps ahead of the current one, drawn translucent next to it, with the reference render()'s
+# velocity arrows (commanded: orange, actual: cyan)
+behind = env.qpos.clone()
+for _ in range(20):
+    env.step(action=env.action_space.sample() * 0)
+now = env.state_dict()
+for _ in range(20):
+    env.step(action=env.action_space.sample() * 0)
+ahead = env.qpos.clone()
+env.load_state_dict(now)                                # back to the middle pose
+ghosts = torch.stack([behind, ahead], 1)                # [N, 2, 19]
+frame = env.render('rgb_array', True, ghosts, 0.35, markers=velocity_markers(env))   # tinted robot, two ghosts, two arrows
+np.save(Path(cam.save_dir) / 'render_ghosts.npy', frame.cpu().numpy())
 env.close()

@@ -12,7 +12,7 @@ import numpy as np
 from .mjcf import ModelDesc
 
 GQ_NLEG = 4
-GQ_ABI_VERSION = 650   # include/gq.h
+GQ_ABI_VERSION = 660   # include/gq.h
 # optional extra output rows of the step kernel (include/gq.h gq_batch_set_outputs)
 GQ_DYN = dict(MC=0, MB=108, BIAS=144, XPOS=162, XMAT=201, FOOT=318, STRIDE=336)
 GQ_CON_MAX, GQ_CON_REC = 12, 24
@@ -94,6 +94,14 @@ class GqCamShade(C.Structure):
                 ('floor_mark_w', C.c_float), ('floor_specular', C.c_float), ('floor_shininess', C.c_float), ('floor_emission', C.c_float),
                 ('bg_top', C.c_float * 3), ('bg_bottom', C.c_float * 3), ('head_ambient', C.c_float * 3), ('head_diffuse', C.c_float * 3),
                 ('head_specular', C.c_float * 3), ('head_active', C.c_int32), ('light', GqCamLight * GQ_CAM_MAXLIGHT)]
+
+
+GQ_CAM_MAXGHOST, GQ_CAM_MAXMARKER, GQ_CAM_MAXLAYER = 8, 32, 8   # gq_camera_layered limits
+
+
+class GqCamLayers(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('n_ghost', C.c_int32), ('ghost_qpos', C.c_void_p), ('ghost_stride', C.c_int32),
+                ('ghost_alpha', C.c_void_p), ('ghost_rgb', C.c_void_p), ('n_marker', C.c_int32), ('markers', C.c_void_p)]
 
 
 class GqObsOut(C.Structure):

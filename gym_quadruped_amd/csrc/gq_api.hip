@@ -25,6 +25,9 @@ extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene sc
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, int n_envs, hipStream_t stream);
+extern "C" void gq_launch_camera_layered(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs,
+                                         hipStream_t stream);
+static_assert(GQ_CAM_NLAYER == GQ_CAM_MAXLAYER, "the pixel pass composites GQ_CAM_MAXLAYER layers");
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
                                     float dist_x, float dist_y, float* out, hipStream_t stream);
@@ -77,6 +80,8 @@ struct GqBatch {
   float* sepc;          /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
   float* cam_rec;       /* device: gq_camera's pose-pass records [N][GQ_CAM_REC] (lazily allocated) */
   double* cam_pos;      /* device: ... and camera origins [N][3] */
+  float* cam_grec;      /* device: gq_camera_layered's ghost records [N][cam_nghost][GQ_CAM_GREC] (lazily allocated, grown with n_ghost) */
+  int cam_nghost;       /* ... ghosts per env it holds */
   int stop_stage;       /* profiling aid: GQ_STOP_STAGE at batch creation */
   /* argument block of step_kernel: device copy, host shadow of what the device holds, pinned staging ring for the
    * (rare) stream-ordered re-upload */
@@ -252,7 +257,7 @@ int gq_batch_destroy(GqBatch* b) {
   if (!b) return GQ_OK;
   DeviceGuard guard(b->model->device);
   hipFree(b->dev); hipFree(b->friction_next); hipFree(b->pending); hipFree(b->lift_pending); hipFree(b->load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
-  hipFree(b->cam_rec); hipFree(b->cam_pos);
+  hipFree(b->cam_rec); hipFree(b->cam_pos); hipFree(b->cam_grec);
   if (b->staging) hipHostFree(b->staging);
   if (b->batch_staging) hipHostFree(b->batch_staging);
   mailbox_free(b);
@@ -890,6 +895,45 @@ int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, 
   s.rgba = reinterpret_cast<uint32_t*>(rgba);
   DeviceGuard guard(b->model->device);
   gq_launch_camera_shaded(b->model->dev, &c, &s, b->host.n_envs, (hipStream_t)hip_stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_camera_layered(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
+                      int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                      float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba,
+                      const GqCamLayers* layers, void* hip_stream) {
+  const char* fn = "gq_camera_layered";
+  if (!layers) { SET_ERR("%s: null layers", fn); return GQ_EINVAL; }
+  if (layers->struct_size != (int32_t)sizeof(GqCamLayers)) {
+    SET_ERR("%s: GqCamLayers.struct_size %d != %d (header mismatch)", fn, layers->struct_size, (int)sizeof(GqCamLayers)); return GQ_EINVAL;
+  }
+  if (layers->n_ghost < 0 || layers->n_ghost > GQ_CAM_MAXGHOST) { SET_ERR("%s: n_ghost %d is not in [0, %d]", fn, layers->n_ghost, GQ_CAM_MAXGHOST); return GQ_EINVAL; }
+  if (layers->n_marker < 0 || layers->n_marker > GQ_CAM_MAXMARKER) { SET_ERR("%s: n_marker %d is not in [0, %d]", fn, layers->n_marker, GQ_CAM_MAXMARKER); return GQ_EINVAL; }
+  if (layers->n_ghost > 0 && (!layers->ghost_qpos || !layers->ghost_alpha)) { SET_ERR("%s: n_ghost > 0 with a null ghost_qpos or ghost_alpha", fn); return GQ_EINVAL; }
+  if (layers->n_ghost > 0 && layers->ghost_stride < 19) { SET_ERR("%s: ghost_stride %d < 19", fn, layers->ghost_stride); return GQ_EINVAL; }
+  if (layers->n_marker > 0 && !layers->markers) { SET_ERR("%s: n_marker > 0 with a null markers", fn); return GQ_EINVAL; }
+  gq::CamShade s;
+  int rc = camera_shade(shade, s);
+  if (rc != GQ_OK) return rc;
+  if (!rgba) { SET_ERR("%s: null rgba", fn); return GQ_EINVAL; }
+  gq::CamCall c;
+  rc = camera_call(fn, b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                   depth, seg, cam_xpos, cam_xmat, c);
+  if (rc != GQ_OK) return rc;
+  s.rgba = reinterpret_cast<uint32_t*>(rgba);
+  DeviceGuard guard(b->model->device);
+  if (layers->n_ghost > b->cam_nghost) {
+    hipFree(b->cam_grec);
+    b->cam_grec = nullptr; b->cam_nghost = 0;
+    HIP_TRY(hipMalloc(&b->cam_grec, sizeof(float) * GQ_CAM_GREC * (size_t)layers->n_ghost * b->host.n_envs));
+    b->cam_nghost = layers->n_ghost;
+  }
+  gq::CamLayers l{};
+  l.ghost_qpos = layers->ghost_qpos; l.ghost_stride = layers->ghost_stride; l.n_ghost = layers->n_ghost;
+  l.ghost_alpha = layers->ghost_alpha; l.ghost_rgb = layers->ghost_rgb;
+  l.n_marker = layers->n_marker; l.markers = layers->markers; l.grec = b->cam_grec;
+  gq_launch_camera_layered(b->model->dev, &c, &s, &l, b->host.n_envs, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

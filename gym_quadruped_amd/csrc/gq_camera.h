@@ -5,6 +5,8 @@
  *    geom, every geom's frame relative to the camera (fp32) into the batch's scratch record.  The camera origin in the world is fp64.
  *  - pixel pass, one wavefront per 8 x 8 tile of one env: lane = candidate culls the robot geoms and the world boxes against the tile's
  *    view cone (two ballots, as heightmap_rays does for boxes), then lane = pixel walks the survivors wave-uniformly.
+ * gq_camera_layered adds a ghost pose pass (one wavefront per env and ghost: the robot geoms posed from each ghost qpos, relative to the
+ * env's camera) and composites ghosts and markers over the shaded image in its pixel pass (cam_layers).
  * Also the static-geom ray tests that gq_ray's ray_kernel and the pixel pass share (slab, height-field cell walk).
  * Semantics: pixel (r, c) looks along ((2 (c + .5) / W - 1) tan(fovy / 2) W / H, (1 - 2 (r + .5) / H) tan(fovy / 2), -1) in
  * the camera frame, so a hit's ray parameter is its planar depth; the nearest hit in [znear, zfar] wins, none gives zfar.  Convex geoms are
@@ -50,6 +52,17 @@ struct CamShade {
   float top[3], bottom[3];                     /* background */
   int nlight;
   CamLight light[GQ_CAM_NLIGHT];
+};
+
+/* the layered pixel pass (gq_camera_layered): translucent ghost robots and markers over the shaded image, by value */
+#define GQ_CAM_NLAYER 8                        /* layers composited per pixel (include/gq.h GQ_CAM_MAXLAYER) */
+#define GQ_CAM_GREC (12 * GQ_CAM_NROB)         /* ghost record floats per (env, ghost): per robot geom R (9) t (3), camera frame */
+struct CamLayers {
+  const double* ghost_qpos; int ghost_stride, n_ghost;   /* [N][n_ghost][ghost_stride] */
+  const float* ghost_alpha;                    /* [N][n_ghost] */
+  const float* ghost_rgb;                      /* [N][n_ghost][3], or null: geom_mat's colours */
+  int n_marker; const float* markers;          /* [N][n_marker][16]: type, pos, axis, size, rgba, pad (world) */
+  float* grec;                                 /* [N][n_ghost][GQ_CAM_GREC] batch scratch: ghost pose pass -> pixel pass */
 };
 
 /* ---- static-geom ray tests (T = double: gq_ray; the pixel pass uses float for boxes, origin relative to the camera) */
@@ -203,6 +216,44 @@ __device__ inline float cam_hull(V3 o, V3 d, const float* P, int n, int& part) {
   return !miss && tin <= tout ? tin : -1.0f;
 }
 
+/* the ghost pose pass's pieces of camera_pose_wave: the first 19 entries of one qpos row into the wave's LDS (lane = entry), and the
+ * geom frames below (camera_pose_wave keeps its own copy: through these helpers its code would change) */
+__device__ __forceinline__ void cam_load_qpos(WaveMem& W, const double* qrow, const int lane) {
+  if (lane < 19) {
+    const double q = qrow[lane];
+    if (lane < 2) W.bxy[lane] = q;
+    else if (lane == 2) W.basez = (float)q;
+    else if (lane < 7) W.qb[lane - 3] = (float)q;
+    else W.qj[lane - 7] = (float)q;
+  }
+}
+/* lane = robot geom: its frame relative to the camera (rotation Rc, origin pc relative to the base x/y of W's kinematics), R = Rc' Rg,
+ * t = Rc' (pg - pc), 12 floats per geom from out */
+template <class Mref>
+__device__ __forceinline__ void cam_geom_frames(WaveMem& W, const Mref& m, const float* Rc, const V3 pc, float* out, const int lane) {
+  const int nrob = 4 + m.nlg;
+  if (lane < nrob) {
+    V3 pg;
+    float Rg[9];
+    if (lane < 4) {
+      const FootRec FR = foot_fetch(m, lane);
+      const int b = 3 + 3 * FR.leg;
+      pg = ld3(W.xpos[b]) + matvec(W.xmat[b], ld3(FR.pos));
+      for (int k = 0; k < 9; k++) Rg[k] = (k % 4 == 0) ? 1.0f : 0.0f;
+    } else {
+      const auto& G = m.lg[lane - 4];
+      const int b = G.body;
+      pg = ld3(W.xpos[b]) + matvec(W.xmat[b], ld3(G.pos));
+      for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Rg[3 * i + j] = W.xmat[b][3 * i] * G.mat[j] + W.xmat[b][3 * i + 1] * G.mat[3 + j] + W.xmat[b][3 * i + 2] * G.mat[6 + j];
+    }
+    float* o = out + 12 * lane;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) o[3 * i + j] = Rc[i] * Rg[j] + Rc[3 + i] * Rg[3 + j] + Rc[6 + i] * Rg[6 + j];
+    st3(o + 9, matTvec(Rc, pg - pc));
+  }
+}
+
 /* pose pass: one wavefront per env; W: the wave's LDS */
 template <class Mref>
 __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall& c, const int env) {
@@ -245,7 +296,8 @@ __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall
     c.cpos[(size_t)env * 3 + k] = p;
     if (c.xpos_out) c.xpos_out[(size_t)env * 3 + k] = p;
   }
-  /* lane = robot geom: its frame in the camera frame, R = Rc' Rg, t = Rc' (pg - pc) */
+  /* lane = robot geom: its frame in the camera frame, R = Rc' Rg, t = Rc' (pg - pc).  Twin: cam_geom_frames (the ghost pose pass); a
+   * change here goes there too, or ghosts posed like the robot stop matching it bit for bit */
   const int nrob = 4 + m.nlg;
   if (lane < nrob) {
     V3 pg;
@@ -269,6 +321,26 @@ __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall
   }
 }
 
+/* ghost pose pass (gq_camera_layered): one wavefront per (env, ghost).  The kinematics of the ghost's qpos; the camera stays the one the
+ * pose pass placed from the env's own qpos (rec, cpos), so each ghost geom's frame is taken relative to that camera into L.grec. */
+template <class Mref>
+__device__ inline void camera_ghost_wave(WaveMem& W, const Mref& m, const CamCall& c, const CamLayers& L, const int ghost, const int env) {
+  const int lane = lane_id();
+#if GQ_TICKSET
+  if (lane == 0) W.tk_T = nullptr;
+#endif
+  const size_t row = (size_t)env * L.n_ghost + ghost;
+  cam_load_qpos(W, L.ghost_qpos + row * L.ghost_stride, lane);
+  wave_barrier();
+  stage_kinematics(W, link_fetch(m, lane));
+  const float* rec = c.rec + (size_t)env * GQ_CAM_REC;
+  float Rc[9];
+  for (int k = 0; k < 9; k++) Rc[k] = rec[k];
+  const double* co = c.cpos + (size_t)env * 3;
+  const V3 pc = v3((float)(co[0] - W.bxy[0]), (float)(co[1] - W.bxy[1]), (float)co[2]);   /* relative to the ghost's base x/y */
+  cam_geom_frames(W, m, Rc, pc, L.grec + row * GQ_CAM_GREC, lane);
+}
+
 /* does the sphere (centre ctr, camera frame) meet the cone (unit axis ax, half angle (ca, sa)) within the depth range?  Conservative:
  * behind the apex the distance to the cone is underestimated. */
 __device__ __forceinline__ bool cam_cone_sphere(V3 ctr, float rad, V3 ax, float ca, float sa, float znear, float zfar) {
@@ -279,13 +351,57 @@ __device__ __forceinline__ bool cam_cone_sphere(V3 ctr, float rad, V3 ax, float 
   return sqrtf(dot(p, p)) * ca - a * sa <= rad;
 }
 
+/* may robot geom `lane` (its camera-frame record g) show in the tile's view cone?  This and the three helpers below are the layered pass's
+ * copies of code that stays inline in camera_tile_wave and cam_shade (see there); a change to one copy goes to the other */
 template <class Mref>
-__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
-                                     V3 dw, float best, int id, int slot, int part, int nbox);
-
-/* pixel pass: one wavefront renders tile `tile` of env `env`; SHADE: also its RGBA image (sh) */
+__device__ __forceinline__ bool cam_rob_cull(const Mref& M, const CamCall& c, const float* g, const int lane, V3 ax, float ca, float sa) {
+  V3 ctr = ld3(g + 9);
+  float rad;
+  if (lane < 4) rad = M.foot_radius[lane];
+  else {
+    const auto& G = M.lg[lane - 4];
+    ctr = ctr + matvec(g, ld3(G.aabb_c));
+    rad = sqrtf(G.aabb_h[0] * G.aabb_h[0] + G.aabb_h[1] * G.aabb_h[1] + G.aabb_h[2] * G.aabb_h[2]) + G.radius;
+  }
+  return cam_cone_sphere(ctr, rad, ax, ca, sa, c.znear, c.zfar);
+}
+/* the pixel ray d (camera frame) against robot geom g whose camera-frame record is gr: the entry parameter or -1; pg: the part (SHADE) */
 template <bool SHADE, class Mref>
-__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const CamShade* sh, const int tile, const int env) {
+__device__ __forceinline__ float cam_rob_cast(const Mref& M, const CamCall& c, const float* gr, const int g, V3 d, int& pg) {
+  const V3 t = ld3(gr + 9), o = (-1.0f) * matTvec(gr, t), dl = matTvec(gr, d);
+  float th;
+  if (g < 4) th = cam_sphere(o, dl, M.foot_radius[g]);
+  else {
+    const auto& G = M.lg[g - 4];
+    const int pt = G.ptype;
+    if (pt == 2) th = cam_sphere(o, dl, G.psize[0]);
+    else if (pt == 3) th = cam_capsule(o, dl, G.psize[0], G.psize[1], pg);
+    else if (pt == 5) th = cam_cylinder(o, dl, G.psize[0], G.psize[1], pg);
+    else if (pt == 6) {
+      const float ov[3] = {o.x, o.y, o.z}, dv[3] = {dl.x, dl.y, dl.z}, s[3] = {G.psize[0], G.psize[1], G.psize[2]};
+      float tin = -1e30f, tout = 1e30f;
+      th = ray_slab(ov, dv, s, tin, tout, SHADE ? &pg : nullptr) ? tin : -1.0f;
+    } else {
+      th = cam_hull(o, dl, c.planes + 4 * c.plane_adr[g - 4], c.plane_num[g - 4], pg);
+      pg += c.plane_adr[g - 4];   /* the entry plane, as an index into c.planes */
+    }
+  }
+  return th;
+}
+
+template <bool F, class Mref>
+__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
+                                     V3 dw, float best, int id, int slot, int part, int nbox, float* fout);
+__device__ __forceinline__ uint32_t cam_byte(float x) { return (uint32_t)floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f) + 0.5f); }
+template <class Mref>
+__device__ inline void cam_layers(const Mref& M, const CamCall& c, const CamShade& S, const CamLayers& L, const float* Rc, const double* co, V3 d,
+                                  V3 ax, float ca, float sa, float t0, int env, float* C);
+
+/* pixel pass: one wavefront renders tile `tile` of env `env`; SHADE: also its RGBA image (sh); LAYERS: ghosts and markers composited over
+ * that image (ly, gq_camera_layered) */
+template <bool SHADE, bool LAYERS = false, class Mref>
+__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const CamShade* sh, const int tile, const int env,
+                                        const CamLayers* ly = nullptr) {
   const int lane = lane_id(), W = c.width, H = c.height;
   const int tiles_x = (W + GQ_CAM_TILE - 1) / GQ_CAM_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
   const int row = ty * GQ_CAM_TILE + lane / GQ_CAM_TILE, col = tx * GQ_CAM_TILE + lane % GQ_CAM_TILE;
@@ -313,7 +429,7 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const C
   uint64_t rob = 0, box[2] = {0, 0};
   if (c.flags & 1) {
     bool near = false;
-    if (lane < nrob) {
+    if (lane < nrob) { /* twin: cam_rob_cull (the layered pass); change both */
       const float* g = rec + 12 + 12 * lane;
       V3 ctr = ld3(g + 9);
       float rad;
@@ -369,7 +485,7 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const C
       }
     }
   }
-  for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform */
+  for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform; the cast's twin: cam_rob_cast (the layered pass), change both */
     const int g = ffs64(todo);
     const float* gr = rec + 12 + 12 * g;
     const V3 t = ld3(gr + 9), o = (-1.0f) * matTvec(gr, t), dl = matTvec(gr, d);
@@ -401,30 +517,89 @@ __device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const C
     c.depth[px] = best;
     if (c.seg) c.seg[px] = id;
   }
-  if constexpr (SHADE) {
-    const uint32_t rgba = cam_shade(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox);
+  if constexpr (LAYERS) {
+    float rgb[3];
+    cam_shade<true>(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox, rgb);
+    cam_layers(M, c, *sh, *ly, Rc, co, d, ax, ca, sa, best, env, rgb);
+    const uint32_t rgba = cam_byte(rgb[0]) | cam_byte(rgb[1]) << 8 | cam_byte(rgb[2]) << 16 | 0xff000000u;
+    if (valid) sh->rgba[px] = rgba;
+  } else if constexpr (SHADE) {
+    const uint32_t rgba = cam_shade<false>(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox, nullptr);
     if (valid) sh->rgba[px] = rgba;
   }
 }
 
 /* ---- shading (gq_camera_shaded): the winner's normal, its material and the lights, fp32 in the camera frame */
 __device__ __forceinline__ V3 cam_unit(V3 a) { return (1.0f / sqrtf(dot(a, a))) * a; }
-__device__ __forceinline__ uint32_t cam_byte(float x) { return (uint32_t)floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f) + 0.5f); }
 /* x^e for x in [0, 1], e >= 0 on the transcendental unit (v_log_f32 / v_exp_f32, as fast_pow_ratio; the library powf is hundreds of
  * instructions of special cases); 0^0 = 1 */
 __device__ __forceinline__ float cam_pow(float x, float e) { return e > 0.0f ? __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)) : 1.0f; }
 
+/* outward normal (camera frame, not unit) of robot geom `slot` (camera-frame record gr) at the ray parameter best, entered on `part` */
 template <class Mref>
+__device__ __forceinline__ V3 cam_rob_normal(const Mref& M, const CamCall& c, const float* gr, int slot, int part, V3 d, float best) {
+  const V3 t = ld3(gr + 9), p = (-1.0f) * matTvec(gr, t) + best * matTvec(gr, d);
+  V3 nl = p;   /* spheres */
+  if (slot >= 4) {
+    const auto& G = M.lg[slot - 4];
+    const int pt = G.ptype;
+    const float h = G.psize[1];
+    if (pt == 3) nl = part == 0 ? v3(p.x, p.y, 0.0f) : p - v3(0.0f, 0.0f, part == 1 ? h : -h);
+    else if (pt == 5) nl = part == 0 ? v3(p.x, p.y, 0.0f) : v3(0.0f, 0.0f, p.z > 0.0f ? 1.0f : -1.0f);
+    else if (pt == 6) {
+      const V3 dl = matTvec(gr, d);
+      const float dk = part == 0 ? dl.x : part == 1 ? dl.y : dl.z, s = dk > 0.0f ? -1.0f : 1.0f;
+      nl = v3(part == 0 ? s : 0.0f, part == 1 ? s : 0.0f, part == 2 ? s : 0.0f);
+    } else if (pt != 2) nl = ld3(c.planes + 4 * part);
+  }
+  return matvec(gr, nl);
+}
+
+/* the lights at the hit best d with normal n (camera frame, not unit), base colour col, material (specular, shininess, emission):
+ * out, unclamped */
+__device__ __forceinline__ void cam_light(const CamShade& S, const float* Rc, const double* co, V3 n, const float* col, const float* mat, V3 d,
+                                          float best, float* out) {
+  n = cam_unit(n);
+  const V3 v = (-1.0f) * cam_unit(d), ph = best * d;   /* towards the camera; the hit, camera frame */
+  for (int k = 0; k < 3; k++) out[k] = mat[2] * col[k];
+  const float shin = 128.0f * mat[1];
+  for (int l = 0; l < S.nlight; l++) { /* wave-uniform: each light is taken into the camera frame once per wave */
+    const CamLight& Lt = S.light[l];
+    V3 L = v3(0.0f, 0.0f, 1.0f);
+    float w = 1.0f;   /* attenuation x spot */
+    if (Lt.kind == 1) L = (-1.0f) * matTvec(Rc, ld3(Lt.dir));
+    else if (Lt.kind == 2) {
+      const V3 lp = matTvec(Rc, v3((float)((double)Lt.pos[0] - co[0]), (float)((double)Lt.pos[1] - co[1]), (float)((double)Lt.pos[2] - co[2])));
+      const V3 q = lp - ph;
+      const float r = sqrtf(dot(q, q));
+      L = (1.0f / r) * q;
+      const float cs = -dot(L, matTvec(Rc, ld3(Lt.dir)));
+      w = (cs >= Lt.cos_cut ? cam_pow(cs, Lt.expo) : 0.0f) / (Lt.att[0] + Lt.att[1] * r + Lt.att[2] * r * r);
+    }
+    const float nL = dot(n, L), nH = fmaxf(dot(n, cam_unit(L + v)), 0.0f);
+    const float sp = nL > 0.0f ? mat[0] * cam_pow(nH, shin) : 0.0f, df = fmaxf(nL, 0.0f);
+    for (int k = 0; k < 3; k++) out[k] += w * (Lt.amb[k] * col[k] + Lt.dif[k] * col[k] * df + Lt.spe[k] * sp);
+  }
+}
+
+/* the opaque colour of a pixel: the background, or the winner (id, slot, part) lit; F: unclamped into fout (the layered pass) instead
+ * of the RGBA8 word.  Its robot-normal and lighting code is that of cam_rob_normal and cam_light, which the layered pass uses for its
+ * layers; written out here, the two earlier instantiations of the pixel pass compile to the instructions they had before. */
+template <bool F, class Mref>
 __device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
-                                     V3 dw, float best, int id, int slot, int part, int nbox) {
+                                     V3 dw, float best, int id, int slot, int part, int nbox, float* fout) {
   float col[3], mat[3];   /* base colour; specular, shininess, emission */
   V3 n;                   /* outward normal, camera frame (not yet unit) */
   if (id < 0) { /* background: the gradient over the world z of the unit ray */
     const float s = 0.5f * (1.0f + dw.z / sqrtf(dot(dw, dw)));
-    return cam_byte(S.bottom[0] + (S.top[0] - S.bottom[0]) * s) | cam_byte(S.bottom[1] + (S.top[1] - S.bottom[1]) * s) << 8 |
-           cam_byte(S.bottom[2] + (S.top[2] - S.bottom[2]) * s) << 16 | 0xff000000u;
+    if constexpr (F) {
+      for (int k = 0; k < 3; k++) fout[k] = S.bottom[k] + (S.top[k] - S.bottom[k]) * s;
+      return 0;
+    } else
+      return cam_byte(S.bottom[0] + (S.top[0] - S.bottom[0]) * s) | cam_byte(S.bottom[1] + (S.top[1] - S.bottom[1]) * s) << 8 |
+             cam_byte(S.bottom[2] + (S.top[2] - S.bottom[2]) * s) << 16 | 0xff000000u;
   }
-  if (id < c.ngeom) { /* robot geom `slot`: its frame in the camera frame, the hit in the geom frame */
+  if (id < c.ngeom) { /* robot geom `slot`: its frame in the camera frame, the hit in the geom frame (twin: cam_rob_normal) */
     const float* gr = rec + 12 + 12 * slot;
     const V3 t = ld3(gr + 9), p = (-1.0f) * matTvec(gr, t) + best * matTvec(gr, d);
     V3 nl = p;   /* spheres */
@@ -477,6 +652,7 @@ __device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamS
     }
     n = matTvec(Rc, nw);
   }
+  /* the lights (twin: cam_light, the layers' shading; change both) */
   n = cam_unit(n);
   const V3 v = (-1.0f) * cam_unit(d), ph = best * d;   /* towards the camera; the hit, camera frame */
   float out[3] = {mat[2] * col[0], mat[2] * col[1], mat[2] * col[2]};
@@ -498,7 +674,186 @@ __device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamS
     const float sp = nL > 0.0f ? mat[0] * cam_pow(nH, shin) : 0.0f, df = fmaxf(nL, 0.0f);
     for (int k = 0; k < 3; k++) out[k] += w * (Lt.amb[k] * col[k] + Lt.dif[k] * col[k] * df + Lt.spe[k] * sp);
   }
-  return cam_byte(out[0]) | cam_byte(out[1]) << 8 | cam_byte(out[2]) << 16 | 0xff000000u;
+  if constexpr (F) {
+    for (int k = 0; k < 3; k++) fout[k] = out[k];
+    return 0;
+  } else
+    return cam_byte(out[0]) | cam_byte(out[1]) << 8 | cam_byte(out[2]) << 16 | 0xff000000u;
+}
+
+/* ---- layers (gq_camera_layered): ghost robots and markers, each at most one translucent layer per pixel */
+/* the solid cone with base disc radius rb at z = zb and apex at z = zt > zb (axis z): entry parameter or -1; part 0 side, 1 base.  Within
+ * the slab zb <= z <= zt the solid is {x^2 + y^2 <= k^2 (zt - z)^2}, k = rb / (zt - zb), a convex set, so its ray interval is the slab's
+ * interval cut by the one piece of {f(t) <= 0} that meets it, f(t) = a t^2 + 2 b t + c. */
+__device__ inline float cam_cone(V3 o, V3 d, float rb, float zb, float zt, int& part) {
+  float lo = -1e30f, hi = 1e30f;
+  part = 1;
+  if (fabsf(d.z) < 1e-20f) { if (o.z < zb || o.z > zt) return -1.0f; }
+  else {
+    float t0 = (zb - o.z) / d.z, t1 = (zt - o.z) / d.z;
+    if (t0 > t1) { const float tt = t0; t0 = t1; t1 = tt; }
+    lo = t0; hi = t1;
+  }
+  const float k = rb / (zt - zb), k2 = k * k, hz = zt - o.z;
+  const float a = d.x * d.x + d.y * d.y - k2 * d.z * d.z, b = o.x * d.x + o.y * d.y + k2 * hz * d.z, cc = o.x * o.x + o.y * o.y - k2 * hz * hz;
+  if (fabsf(a) <= 1e-7f * (d.x * d.x + d.y * d.y + k2 * d.z * d.z)) { /* parallel to a generator: 2 b t + c <= 0 */
+    if (fabsf(b) < 1e-30f) { if (cc > 0.0f) return -1.0f; }
+    else {
+      const float r = -0.5f * cc / b;
+      if (b > 0.0f) hi = fminf(hi, r);
+      else if (r > lo) { lo = r; part = 0; }
+    }
+  } else {
+    const float disc = b * b - a * cc;
+    if (disc < 0.0f) { if (a > 0.0f) return -1.0f; }   /* a < 0: f <= 0 everywhere */
+    else {
+      const float s = sqrtf(disc), r0 = (-b - s) / a, r1 = (-b + s) / a, q0 = fminf(r0, r1), q1 = fmaxf(r0, r1);
+      if (a > 0.0f) { /* inside between the roots */
+        if (q0 > lo) { lo = q0; part = 0; }
+        hi = fminf(hi, q1);
+      } else if (lo <= q0) hi = fminf(hi, q0);   /* inside outside the roots: the piece that meets the slab */
+      else if (q1 > lo) { lo = q1; part = 0; }
+    }
+  }
+  return lo <= hi ? lo : -1.0f;
+}
+
+/* marker k of the env (wave-uniform row mk, world axes) in the camera frame: type, centre p (the base for capsules and arrows), unit axis u
+ * with an orthonormal pair e1, e2, length len */
+struct CamMarker {
+  int type;
+  V3 p, u, e1, e2;
+  float len, r0, r1, head;
+};
+__device__ __forceinline__ CamMarker cam_marker(const float* mk, const float* Rc, const double* co) {
+  CamMarker m;
+  m.type = (int)mk[0];
+  m.p = matTvec(Rc, v3((float)((double)mk[1] - co[0]), (float)((double)mk[2] - co[1]), (float)((double)mk[3] - co[2])));
+  const V3 a = matTvec(Rc, v3(mk[4], mk[5], mk[6]));
+  m.len = sqrtf(dot(a, a));
+  m.u = m.len > 0.0f ? (1.0f / m.len) * a : v3(0.0f, 0.0f, 1.0f);
+  const V3 t = fabsf(m.u.x) < 0.6f ? v3(1.0f, 0.0f, 0.0f) : v3(0.0f, 1.0f, 0.0f);
+  m.e1 = cam_unit(t - dot(t, m.u) * m.u);
+  m.e2 = v3(m.u.y * m.e1.z - m.u.z * m.e1.y, m.u.z * m.e1.x - m.u.x * m.e1.z, m.u.x * m.e1.y - m.u.y * m.e1.x);
+  m.r0 = mk[7]; m.r1 = mk[8]; m.head = mk[9];
+  if (m.type != 1 && !(m.len > 0.0f)) m.type = 0;   /* capsules and arrows of zero length are skipped */
+  return m;
+}
+/* a bounding sphere of the marker (camera frame) */
+__device__ __forceinline__ float cam_marker_bound(const CamMarker& m, V3& ctr) {
+  if (m.type == 1) { ctr = m.p; return m.r0; }
+  ctr = m.p + (0.5f * m.len) * m.u;
+  return 0.5f * m.len + (m.type == 3 ? fmaxf(m.r0, m.r1) : m.r0);
+}
+/* the ray d (camera frame, from the camera) against the marker: entry parameter or -1, and the outward normal there (camera frame) */
+__device__ inline float cam_marker_cast(const CamMarker& m, V3 d, V3& n) {
+  if (m.type == 1) {
+    const V3 o = (-1.0f) * m.p;
+    const float t = cam_sphere(o, d, m.r0);
+    n = o + t * d;
+    return t;
+  }
+  const V3 ow = (-1.0f) * m.p;   /* the camera relative to the base, then in the marker frame (e1, e2, u) */
+  const V3 o = v3(dot(ow, m.e1), dot(ow, m.e2), dot(ow, m.u)), dl = v3(dot(d, m.e1), dot(d, m.e2), dot(d, m.u));
+  float t = -1.0f;
+  V3 nl = v3(0.0f, 0.0f, 1.0f);
+  int part = 0;
+  if (m.type == 2) {
+    const float h = 0.5f * m.len;
+    const V3 oc = o - v3(0.0f, 0.0f, h);
+    t = cam_capsule(oc, dl, m.r0, h, part);
+    const V3 p = oc + t * dl;
+    nl = part == 0 ? v3(p.x, p.y, 0.0f) : p - v3(0.0f, 0.0f, part == 1 ? h : -h);
+  } else if (m.type == 3) { /* shaft: cylinder radius r0 over z in [0, zb]; head: cone of base radius r1 from zb to the tip */
+    const float zb = (1.0f - m.head) * m.len, h = 0.5f * zb;
+    const V3 oc = o - v3(0.0f, 0.0f, h);
+    int ps = 0, pc = 0;
+    const float ts = cam_cylinder(oc, dl, m.r0, h, ps), tc = cam_cone(o, dl, m.r1, zb, m.len, pc);
+    if (ts >= 0.0f && (tc < 0.0f || ts <= tc)) {
+      t = ts;
+      const V3 p = oc + t * dl;
+      nl = ps == 0 ? v3(p.x, p.y, 0.0f) : v3(0.0f, 0.0f, p.z > 0.0f ? 1.0f : -1.0f);
+    } else if (tc >= 0.0f) {
+      t = tc;
+      const V3 p = o + t * dl;
+      const float k = m.r1 / (m.len - zb);
+      nl = pc == 0 ? v3(p.x, p.y, k * k * (m.len - p.z)) : v3(0.0f, 0.0f, -1.0f);
+    }
+  }
+  n = nl.x * m.e1 + nl.y * m.e2 + nl.z * m.u;
+  return t;
+}
+
+/* composite the ghosts and markers of env `env` over the opaque colour C (depth t0) of this lane's pixel.  Each layer is shaded when it
+ * enters a depth-sorted list of GQ_CAM_NLAYER (t, rgb, a) entries held in registers (static indices only: the insertion is an unrolled
+ * compare-and-swap chain); layers arrive in index order (ghosts, then markers) and a tie goes behind, so ties sort by index.  Empty
+ * entries have a = 0, which leaves C exactly as it is. */
+template <class Mref>
+__device__ inline void cam_layers(const Mref& M, const CamCall& c, const CamShade& S, const CamLayers& L, const float* Rc, const double* co, V3 d,
+                                  V3 ax, float ca, float sa, float t0, int env, float* C) {
+  const int lane = lane_id(), nrob = 4 + M.nlg;
+  float lt[GQ_CAM_NLAYER], lr[GQ_CAM_NLAYER], lg[GQ_CAM_NLAYER], lb[GQ_CAM_NLAYER], la[GQ_CAM_NLAYER];
+#pragma unroll
+  for (int k = 0; k < GQ_CAM_NLAYER; k++) { lt[k] = 3e38f; lr[k] = lg[k] = lb[k] = la[k] = 0.0f; }
+  auto insert = [&](float t, float r, float g, float b, float a) {
+#pragma unroll
+    for (int k = 0; k < GQ_CAM_NLAYER; k++) {
+      const bool s = t < lt[k];
+      const float t1 = s ? lt[k] : t, r1 = s ? lr[k] : r, g1 = s ? lg[k] : g, b1 = s ? lb[k] : b, a1 = s ? la[k] : a;
+      if (s) { lt[k] = t; lr[k] = r; lg[k] = g; lb[k] = b; la[k] = a; }
+      t = t1; r = r1; g = g1; b = b1; a = a1;
+    }
+  };
+  for (int gh = 0; gh < L.n_ghost; gh++) { /* wave-uniform */
+    const size_t row = (size_t)env * L.n_ghost + gh;
+    const float* grec = L.grec + row * GQ_CAM_GREC;
+    bool near = false;
+    if (lane < nrob) near = cam_rob_cull(M, c, grec + 12 * lane, lane, ax, ca, sa);
+    float tg = t0;   /* the ghost's nearest hit in [znear, t0) */
+    int sg = -1, pb = 0;
+    for (uint64_t todo = ballot(near); todo; todo &= todo - 1) { /* wave-uniform */
+      const int g = ffs64(todo);
+      int pg = 0;
+      const float th = cam_rob_cast<true>(M, c, grec + 12 * g, g, d, pg);
+      if (th >= c.znear && th < tg) { tg = th; sg = g; pb = pg; }
+    }
+    if (sg >= 0) {
+      const float* gm = S.geom_mat + 7 * M.item_geomid[sg];
+      const float* rgb = L.ghost_rgb ? L.ghost_rgb + 3 * row : gm;
+      const float col[3] = {rgb[0], rgb[1], rgb[2]}, mat[3] = {gm[4], gm[5], gm[6]};
+      float o[3];
+      cam_light(S, Rc, co, cam_rob_normal(M, c, grec + 12 * sg, sg, pb, d, tg), col, mat, d, tg, o);
+      insert(tg, o[0], o[1], o[2], L.ghost_alpha[row]);
+    }
+  }
+  if (L.n_marker > 0) {
+    const float* mrow = L.markers + (size_t)env * L.n_marker * 16;
+    bool near = false;
+    if (lane < L.n_marker) {
+      const CamMarker m = cam_marker(mrow + 16 * lane, Rc, co);
+      V3 ctr;
+      const float rad = cam_marker_bound(m, ctr);
+      near = m.type >= 1 && m.type <= 3 && cam_cone_sphere(ctr, rad, ax, ca, sa, c.znear, c.zfar);
+    }
+    for (uint64_t todo = ballot(near); todo; todo &= todo - 1) { /* wave-uniform */
+      const float* mk = mrow + 16 * ffs64(todo);
+      const CamMarker m = cam_marker(mk, Rc, co);
+      V3 n;
+      const float th = cam_marker_cast(m, d, n);
+      if (th >= c.znear && th < t0) {
+        const float col[3] = {mk[10], mk[11], mk[12]}, mat[3] = {0.5f, 0.5f, 0.0f};
+        float o[3];
+        cam_light(S, Rc, co, n, col, mat, d, th, o);
+        insert(th, o[0], o[1], o[2], mk[13]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = GQ_CAM_NLAYER - 1; k >= 0; k--) { /* far to near */
+    C[0] = la[k] * lr[k] + (1.0f - la[k]) * C[0];
+    C[1] = la[k] * lg[k] + (1.0f - la[k]) * C[1];
+    C[2] = la[k] * lb[k] + (1.0f - la[k]) * C[2];
+  }
 }
 
 }  // namespace gq

@@ -348,6 +348,14 @@ __global__ void __launch_bounds__(GQ_WAVE) camera_pixel_kernel(const GQ_GLOBAL G
 __global__ void __launch_bounds__(GQ_WAVE) camera_shade_kernel(const GQ_GLOBAL GqDevModel* model, const CamCall c, const CamShade s) {
   camera_tile_wave<true>(*model, c, &s, (int)blockIdx.x, (int)blockIdx.y);
 }
+/* gq_camera_layered: the ghost pose pass, grid (ghosts, envs), then the shaded pixel pass with the layers composited */
+__global__ void __launch_bounds__(GQ_WAVE) camera_ghost_kernel(const GqDevModel* model, const CamCall c, const CamLayers l) {
+  __shared__ WaveMem W;
+  camera_ghost_wave(W, *mptr(model), c, l, (int)blockIdx.x, (int)blockIdx.y);
+}
+__global__ void __launch_bounds__(GQ_WAVE) camera_layer_kernel(const GQ_GLOBAL GqDevModel* model, const CamCall c, const CamShade s, const CamLayers l) {
+  camera_tile_wave<true, true>(*model, c, &s, (int)blockIdx.x, (int)blockIdx.y, &l);
+}
 
 #endif /* GQ_IN_MISC */
 
@@ -489,6 +497,13 @@ extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCa
   const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
   hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
   hipLaunchKernelGGL(gq::camera_shade_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c, *s);
+}
+extern "C" void gq_launch_camera_layered(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs,
+                                         hipStream_t stream) {
+  const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
+  hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
+  if (l->n_ghost > 0) hipLaunchKernelGGL(gq::camera_ghost_kernel, dim3(l->n_ghost, n_envs), dim3(GQ_WAVE), 0, stream, model, *c, *l);
+  hipLaunchKernelGGL(gq::camera_layer_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c, *s, *l);
 }
 extern "C" void gq_launch_ray(const GQ_GLOBAL GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream) {
   hipLaunchKernelGGL(gq::ray_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, model, origin, dir, total, dist, geom);

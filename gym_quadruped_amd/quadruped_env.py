@@ -607,20 +607,26 @@ class QuadrupedEnv(AccessorsMixin):
     def enable_debug(self, n_envs: int):
         _lib.check(self._L.gq_debug_enable(self._hbatch, int(n_envs)), 'gq_debug_enable')
 
-    def render(self, mode: str = 'human', *, width: int = 320, height: int = 240, distance: float = 2.0, azimuth: float = 90.0,
-               elevation: float = -45.0):
+    def render(self, mode: str = 'human', tint_robot: bool = False, ghost_qpos=None, ghost_alpha=0.5, *, width: int = 320, height: int = 240,
+               distance: float = 2.0, azimuth: float = 90.0, elevation: float = -45.0, markers=None):
         """``mode='rgb_array'``: ``[N, H, W, 3]`` uint8 on the env's device, one frame per env (a fresh tensor) from a camera that tracks
         the base: it looks along ``f = (cos el cos az, cos el sin az, sin el)`` (degrees, world axes) from ``base - distance f``, world
         up, 45 degree fovy (``sensors.Camera(rgb=True, track=True)``, cached per argument set).  Every other mode raises: an interactive
-        viewer is out of scope of the batched GPU path."""
+        viewer is out of scope of the batched GPU path.
+
+        The reference's arguments: ``tint_robot`` recolours the robot's geoms with its palette (``utils.visual.tint_color``: teal body,
+        one colour per leg by body name), on the render camera only; ``ghost_qpos`` (``[19]``, ``[G, 19]`` or ``[N, G, 19]``, G <= 8)
+        draws translucent copies of the robot in the robot's colours (tinted or not) at ``ghost_alpha`` (a float, ``[G]`` or ``[N, G]``).
+        ``markers`` (``utils.visual.Markers`` or ``[N, K, 16]``) adds spheres, lines and arrows; ``utils.visual.velocity_markers(self)``
+        gives the reference's velocity arrows, which are not drawn by default."""
         if mode != 'rgb_array':
             raise NotImplementedError(f'render(mode={mode!r}): only mode="rgb_array" is available (an interactive viewer is out of scope '
                                       'of the batched GPU path)')
-        key = (int(width), int(height), float(distance), float(azimuth), float(elevation))
+        key = (int(width), int(height), float(distance), float(azimuth), float(elevation)) + (('tint',) if tint_robot else ())
         cams = self.__dict__.setdefault('_render_cams', {})
         if key not in cams:
             from .mjcf import mat_to_quat
-            from .sensors import Camera
+            from .sensors import Appearance, Camera
             az, el = np.deg2rad(azimuth), np.deg2rad(elevation)
             f = np.array([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
             right = np.cross(f, [0.0, 0.0, 1.0])
@@ -628,9 +634,14 @@ class QuadrupedEnv(AccessorsMixin):
                 raise ValueError(f'render: elevation {elevation} looks straight up or down, the world up is undefined')
             right /= np.linalg.norm(right)
             R = np.stack([right, np.cross(right, f), -f], 1)   # columns: camera x (right), y (up), z (backwards)
+            app = None
+            if tint_robot:
+                from .utils.visual import tinted_geom_mat
+                app = Appearance.default(self.mjModel)
+                app.geom_mat = tinted_geom_mat(self.mjModel, app.geom_mat)
             cams[key] = Camera(width, height, 30, self.robot_model, self.sim_data, body=1, pos=-distance * f, quat=mat_to_quat(R), fovy=45.0,
-                               rgb=True, track=True)
-        return cams[key].image.contiguous()
+                               rgb=True, track=True, appearance=app)
+        return cams[key].layered_image(ghost_qpos=ghost_qpos, ghost_alpha=ghost_alpha, markers=markers).contiguous()
 
     def close(self):
         if getattr(self, '_hbatch', None):

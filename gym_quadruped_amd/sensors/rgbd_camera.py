@@ -5,8 +5,9 @@ launches (csrc/gq_camera.h), against the collision geometry the device model hol
 the world boxes and the height field.  Visual-only geoms (``contype = conaffinity = 0``, group-2 meshes) have no geometry in this
 package, so silhouettes follow the collision shapes; each env is its own world (other envs' robots are never drawn).  With ``rgb=True``
 the same rays are shaded (``gq_camera_shaded``: per-geom colours, a floor checker, a headlight and up to seven lights, see ``Appearance``)
-and ``image`` is the RGB image; without it ``image`` raises.  DESIGN.md §2 pins the pixel rays, the depth rules, the segmentation ids and
-the lighting model.
+and ``image`` is the RGB image; without it ``image`` raises.  ``layered_image(ghost_qpos=, ghost_alpha=, ghost_rgb=, markers=)`` is
+the RGB image with translucent ghost robots and markers composited over it (``gq_camera_layered``).  DESIGN.md §2 pins the pixel rays,
+the depth rules, the segmentation ids, the lighting model and the layers.
 
 The pose is that of the ``qpos`` the images are cast from - the env's current state by default.  MuJoCo's ``update_scene`` after
 ``mj_step`` shows the kinematics of the step's START (mjData.xpos is not updated by the integrator): a caller who wants that timing
@@ -23,7 +24,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..cabi import GQ_CAM_MAXLIGHT, GQ_CAM_ROBOT, GQ_CAM_SCENE, GQ_CAM_TRACK, GqCamShade, hull_planes
+from ..cabi import (GQ_CAM_MAXGHOST, GQ_CAM_MAXLIGHT, GQ_CAM_MAXMARKER, GQ_CAM_ROBOT, GQ_CAM_SCENE, GQ_CAM_TRACK, GqCamLayers, GqCamShade,
+                    hull_planes)
 from ..mjcf import CAMERA_MODES
 
 
@@ -235,9 +237,17 @@ class Camera:
         return K @ torch.cat([Rcv, t], dim=2)
 
     # ------------------------------------------------------------------ images
-    def render(self, qpos=None):
-        """Cast depth and segmentation of every env from ``qpos`` ([N, 19] float64, default: the env's current state)."""
+    def render(self, qpos=None, *, ghost_qpos=None, ghost_alpha=0.5, ghost_rgb=None, markers=None):
+        """Cast depth and segmentation of every env from ``qpos`` ([N, 19] float64, default: the env's current state).
+
+        Layers (``rgb=True`` cameras; ``gq_camera_layered``), drawn translucent over the RGB image and never into depth or
+        segmentation: ``ghost_qpos`` ``[19]``, ``[G, 19]`` (the same ghosts in every env) or ``[N, G, 19]``, G <= 8: the robot posed from
+        each row, at ``ghost_alpha`` (a float, ``[G]`` or ``[N, G]`` in [0, 1]) and with the camera's colours, or ``ghost_rgb`` (``[3]``,
+        ``[G, 3]`` or ``[N, G, 3]`` in [0, 1]); ``markers``: a ``utils.visual.Markers`` or an ``[N, K, 16]`` tensor, K <= 32.  Bad shapes
+        and values raise ValueError before anything is launched.  Without layers the call is ``gq_camera_shaded``'s.  ``layered_image``
+        renders with layers and returns that frame; ``image``, ``shoot`` and ``save`` render again without layers."""
         env = self._env
+        layers = self._layers(ghost_qpos, ghost_alpha, ghost_rgb, markers)
         q = env.qpos if qpos is None else torch.as_tensor(qpos, dtype=torch.float64, device=env.device).reshape(-1, 19).expand(env.num_envs, 19).contiguous()
         if q.stride(1) != 1:
             q = q.contiguous()
@@ -249,10 +259,86 @@ class Camera:
                 self._flags, None if self._planes is None else self._planes.data_ptr(),
                 None if self._plane_adr is None else np.ctypeslib.as_ctypes(self._plane_adr),
                 self._depth_plane.data_ptr(), self._seg.data_ptr(), self._xpos.data_ptr(), self._xmat.data_ptr())
-        if self._rgb:
+        if layers is not None:
+            _lib.check(_lib.lib().gq_camera_layered(*args, C.byref(self._shade), self._rgba.data_ptr(), C.byref(layers), stream), 'gq_camera_layered')
+        elif self._rgb:
             _lib.check(_lib.lib().gq_camera_shaded(*args, C.byref(self._shade), self._rgba.data_ptr(), stream), 'gq_camera_shaded')
         else:
             _lib.check(_lib.lib().gq_camera(*args, stream), 'gq_camera')
+
+    def _layers(self, ghost_qpos, ghost_alpha, ghost_rgb, markers):
+        """The GqCamLayers of render()'s layer arguments (None: no layers); its device tensors stay alive until the next call.  The value
+        checks are reduced on the device and read back once (one synchronisation per call)."""
+        if ghost_qpos is None and markers is None:
+            if ghost_rgb is not None:
+                raise ValueError('ghost_rgb without ghost_qpos')
+            return None
+        if not self._rgb:
+            raise ValueError('ghosts and markers are drawn into the RGB image: they need Camera(..., rgb=True)')
+        N, dev = self._env.num_envs, self._env.device
+        checks = []   # (device bool scalar, message): all read back at once below
+
+        def per_env(x, width, what, dtype):   # [.., width] -> [N, G, width]: no env axis, or [N, G, width]
+            t = torch.as_tensor(x.detach() if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)).to(device=dev, dtype=torch.float64)
+            if t.ndim == 1:
+                t = t.reshape(1, 1, -1)
+            elif t.ndim == 2:
+                t = t.unsqueeze(0)
+            if t.ndim != 3 or t.shape[2] != width or t.shape[0] not in (1, N):
+                raise ValueError(f'{what}: expected [{width}], [G, {width}] or [{N}, G, {width}], got {tuple(np.shape(x))}')
+            checks.append((torch.isfinite(t).all(), f'{what} has values that are not finite'))
+            return t.expand(N, t.shape[1], width).to(dtype).contiguous()
+
+        L = GqCamLayers()
+        L.struct_size = C.sizeof(GqCamLayers)
+        keep = []
+        if ghost_qpos is not None:
+            q = per_env(ghost_qpos, 19, 'ghost_qpos', torch.float64)
+            G = q.shape[1]
+            if not 1 <= G <= GQ_CAM_MAXGHOST:
+                raise ValueError(f'ghost_qpos: 1 .. {GQ_CAM_MAXGHOST} ghosts per env (got {G})')
+            a = torch.as_tensor(ghost_alpha.detach() if torch.is_tensor(ghost_alpha) else np.asarray(ghost_alpha, np.float64)).to(dev, torch.float64)
+            if a.ndim == 0 or (a.ndim == 1 and a.shape[0] == G):
+                a = a.reshape(1, -1).expand(N, G)
+            elif not (a.ndim == 2 and a.shape == (N, G)):
+                raise ValueError(f'ghost_alpha: expected a float, [{G}] or [{N}, {G}], got {tuple(a.shape)}')
+            checks.append((((a >= 0) & (a <= 1)).all(), 'ghost_alpha must lie in [0, 1]'))
+            a = a.expand(N, G).float().contiguous()
+            L.n_ghost, L.ghost_qpos, L.ghost_stride, L.ghost_alpha = G, q.data_ptr(), 19, a.data_ptr()
+            keep += [q, a]
+            if ghost_rgb is not None:
+                c = per_env(ghost_rgb, 3, 'ghost_rgb', torch.float32)
+                if c.shape[1] == 1 and G > 1:
+                    c = c.expand(N, G, 3).contiguous()
+                if c.shape[1] != G:
+                    raise ValueError(f'ghost_rgb: {c.shape[1]} colours for {G} ghosts')
+                checks.append((((c >= 0) & (c <= 1)).all(), 'ghost_rgb must lie in [0, 1]'))
+                L.ghost_rgb = c.data_ptr()
+                keep.append(c)
+        elif ghost_rgb is not None:
+            raise ValueError('ghost_rgb without ghost_qpos')
+        if markers is not None:
+            m = markers.data if hasattr(markers, 'data') and not torch.is_tensor(markers) else markers
+            m = torch.as_tensor(m).to(dev, torch.float32)
+            if m.ndim != 3 or m.shape[0] != N or m.shape[2] != 16:
+                raise ValueError(f'markers: expected [{N}, K, 16], got {tuple(m.shape)}')
+            if m.shape[1] > GQ_CAM_MAXMARKER:
+                raise ValueError(f'markers: at most {GQ_CAM_MAXMARKER} per env (got {m.shape[1]})')
+            typ = m[..., 0]
+            checks += [(torch.isfinite(m).all(), 'markers has values that are not finite'),
+                       (((typ == 0) | (typ == 1) | (typ == 2) | (typ == 3)).all(), 'marker type must be 0 (none), 1 (sphere), 2 (capsule) or 3 (arrow)'),
+                       (((m[..., 10:14] >= 0) & (m[..., 10:14] <= 1)).all(), 'marker rgba must lie in [0, 1]'),
+                       ((m[..., 7:9] >= 0).all(), 'marker sizes must be >= 0'),
+                       (((m[..., 9] > 0) & (m[..., 9] < 1) | (typ != 3)).all(), 'an arrow marker\'s head share size[2] must lie in (0, 1)')]
+            m = m.contiguous()
+            L.n_marker, L.markers = m.shape[1], (m.data_ptr() if m.shape[1] else None)
+            keep.append(m)
+        ok = torch.stack([c for c, _ in checks]).cpu().tolist()
+        for good, (_, msg) in zip(ok, checks):
+            if not good:
+                raise ValueError(msg)
+        self._keep_layers = keep
+        return L
 
     @property
     def depth_plane(self) -> torch.Tensor:
@@ -306,6 +392,14 @@ class Camera:
             raise NotImplementedError('Camera.image (RGB) needs Camera(..., rgb=True): this camera casts depth and segmentation only '
                                       '(depth_image, depth_plane, seg_image and point_cloud).')
         self.render()
+        return self._rgba[..., :3]
+
+    def layered_image(self, qpos=None, *, ghost_qpos=None, ghost_alpha=0.5, ghost_rgb=None, markers=None) -> torch.Tensor:
+        """``[N, H, W, 3]`` uint8 RGB with ghosts and markers composited over it (``render``'s layer arguments; without any it is
+        ``image`` of ``qpos``).  A view of the RGBA buffer, overwritten by the next render.  Needs ``rgb=True``."""
+        if not self._rgb:
+            raise NotImplementedError('Camera.layered_image (RGB) needs Camera(..., rgb=True)')
+        self.render(qpos, ghost_qpos=ghost_qpos, ghost_alpha=ghost_alpha, ghost_rgb=ghost_rgb, markers=markers)
         return self._rgba[..., :3]
 
     def shoot(self, autosave: bool = True, img: bool = False, depth: bool = True, seg: bool = True) -> None:

@@ -64,8 +64,9 @@ extern "C" {
  * GqModelDesc.plane_* (optional); 510 = gq_batch_set_heightmap (no struct changed); 600 = GqModelDesc.vert_adj* / plane_order (hull
  * graphs: multi-point mesh-plane contacts), the general convex narrow phase (GJK / EPA) behind the same tables; 610 = gq_batch_set_pair_exchange
  * (no struct changed); 620 = GqModelDesc.support_grid (optional); 630 = that grid 16 x 16 cells per face (was 8 x 8); 640 = gq_camera
- * (no struct changed); 650 = gq_camera_shaded + GqCamShade, gq_camera flags bit 2 (GQ_CAM_TRACK). */
-#define GQ_ABI_VERSION 650
+ * (no struct changed); 650 = gq_camera_shaded + GqCamShade, gq_camera flags bit 2 (GQ_CAM_TRACK); 660 = gq_camera_layered + GqCamLayers
+ * (ghost robots and markers). */
+#define GQ_ABI_VERSION 660
 #ifndef GQ_SUPPORT_GRID
 #define GQ_SUPPORT_GRID 16 /* cells per edge of a cube-map face of GqModelDesc.support_grid */
 #endif
@@ -584,6 +585,42 @@ typedef struct {
 int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
                      int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
                      float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, void* hip_stream);
+
+/* Translucent layers of gq_camera_layered: ghost robots (the robot posed from another qpos) and markers.  Device contents are the caller's
+ * to keep in range (alphas and colours in [0, 1], finite values), as geom_mat is. */
+#define GQ_CAM_MAXGHOST 8   /* ghost poses per env */
+#define GQ_CAM_MAXMARKER 32 /* markers per env */
+#define GQ_CAM_MAXLAYER 8   /* translucent layers composited per pixel */
+typedef struct {
+  int32_t struct_size;        /* = sizeof(GqCamLayers) of the caller's header; gq_camera_layered refuses any other value */
+  int32_t n_ghost;            /* 0 .. GQ_CAM_MAXGHOST */
+  const double* ghost_qpos;   /* device [N][n_ghost][ghost_stride] f64 (the first 19 entries of each row are used) */
+  int32_t ghost_stride;       /* >= 19 */
+  const float* ghost_alpha;   /* device [N][n_ghost] f32 in [0, 1] */
+  const float* ghost_rgb;     /* device [N][n_ghost][3] f32 in [0, 1], or NULL: the ghost keeps geom_mat's colours */
+  int32_t n_marker;           /* 0 .. GQ_CAM_MAXMARKER */
+  const float* markers;       /* device [N][n_marker][16] f32: type, pos[3], axis[3], size[3], rgba[4], pad[2], world axes; type 0 none,
+                               * 1 sphere at pos of radius size[0], 2 capsule from pos to pos + axis of radius size[0], 3 arrow from pos to
+                               * pos + axis: a cylinder of radius size[0] along the first 1 - size[2] of the length, then a cone of base
+                               * radius size[1] to the tip (size[2] in (0, 1)); capsules and arrows with |axis| = 0 are skipped */
+} GqCamLayers;
+
+/* gq_camera_shaded plus ghosts and markers composited over its image: the arguments of gq_camera_shaded (depth, seg, cam_xpos, cam_xmat
+ * and, without layers or with every alpha 0, rgba are written exactly as it writes them), then
+ *   layers: host (validated: GQ_EINVAL on NULL, a struct_size mismatch, counts out of range, ghost_stride < 19, a NULL ghost_qpos or
+ *   ghost_alpha with n_ghost > 0, a NULL markers with n_marker > 0).
+ * Per pixel with opaque colour C0 (unclamped) and depth t0 (zfar where the background shows): ghost g gives at most one layer, its
+ * nearest front-face hit t over the robot geoms posed from ghost_qpos[env][g] (the camera stays where the env's own qpos puts it); marker
+ * k gives at most one layer, its nearest front-face hit.  A layer counts if znear <= t < t0.  Its colour S is the lighting formula of
+ * gq_camera_shaded at its own hit and normal (a ghost geom: its geom_mat material, base colour ghost_rgb[env][g] when given; a marker:
+ * base colour rgba[0:3], specular 0.5, shininess 0.5, emission 0), its alpha ghost_alpha[env][g] or rgba[3].  The GQ_CAM_MAXLAYER
+ * nearest layers (ties: the higher layer index is farther; ghosts before markers) are composited far to near, C = a S + (1 - a) C in
+ * fp32 per channel, then clamped and rounded as gq_camera_shaded does.  Ghosts and markers write neither depth nor seg.  Three launches
+ * on hip_stream: the pose pass, the ghost pose pass (n_ghost > 0), the layered pixel pass. */
+int gq_camera_layered(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
+                      int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                      float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba,
+                      const GqCamLayers* layers, void* hip_stream);
 
 /* mujoco.mj_step1 (quadruped_env.py:376, :384: position + velocity stages) and mujoco.mj_forward (:1321: through the
  * accelerations) for every env WITHOUT advancing the state: stage 1 = mj_step1 (kinematics, inertias, collision,
