@@ -23,10 +23,7 @@
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
-extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, int n_envs, hipStream_t stream);
-extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, int n_envs, hipStream_t stream);
-extern "C" void gq_launch_camera_layered(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs,
-                                         hipStream_t stream);
+extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs, hipStream_t stream);
 static_assert(GQ_CAM_NLAYER == GQ_CAM_MAXLAYER, "the pixel pass composites GQ_CAM_MAXLAYER layers");
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
@@ -761,60 +758,6 @@ int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float
   return GQ_OK;
 }
 
-/* gq_camera / gq_camera_shaded: the checks and the call record both share (fn: the entry point's name for the error text); allocates the
- * batch's scratch block on first use */
-static int camera_call(const char* fn, GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg,
-                       int width, int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
-                       float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, gq::CamCall& c) {
-  if (!b || !qpos || !pos || !quat || !depth) { SET_ERR("%s: null argument", fn); return GQ_EINVAL; }
-  if (qpos_stride < 19) { SET_ERR("%s: qpos_stride %d < 19", fn, qpos_stride); return GQ_EINVAL; }
-  if (body < 0 || body > GQ_NB) { SET_ERR("%s: body id %d out of range (0 = world .. %d)", fn, body, GQ_NB); return GQ_EINVAL; }
-  if (width <= 0 || height <= 0 || (size_t)width * height > (1u << 24)) { SET_ERR("%s: bad image size %d x %d", fn, width, height); return GQ_EINVAL; }
-  if (!(fovy_deg > 0.0f && fovy_deg < 180.0f)) { SET_ERR("%s: fovy %g is not in (0, 180) degrees", fn, (double)fovy_deg); return GQ_EINVAL; }
-  if (!(znear > 0.0f && zfar > znear)) { SET_ERR("%s: need 0 < znear < zfar (got %g, %g)", fn, (double)znear, (double)zfar); return GQ_EINVAL; }
-  if (flags & ~(GQ_CAM_ROBOT | GQ_CAM_SCENE | GQ_CAM_TRACK)) { SET_ERR("%s: unknown flags 0x%x", fn, flags); return GQ_EINVAL; }
-  if ((flags & GQ_CAM_TRACK) && body == 0) { SET_ERR("%s: GQ_CAM_TRACK needs a body camera (body > 0)", fn); return GQ_EINVAL; }
-  const double qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
-  if (!(qn > 0.0)) { SET_ERR("%s: zero quaternion", fn); return GQ_EINVAL; }
-  GqModel* m = b->model;
-  c = gq::CamCall{};
-  for (int i = 0; i < m->host.nlg; i++) {
-    if (m->host.lg[i].ptype != 0) continue;
-    if (!hull_planes || !hull_plane_adr) { SET_ERR("%s: the model has hull geoms and no face planes were passed", fn); return GQ_EINVAL; }
-    const int cl = m->lg_cloud[i];
-    if (cl < 0 || cl >= m->ncloud) { SET_ERR("%s: link geom %d has no cloud", fn, i); return GQ_EINVAL; }
-    c.plane_adr[i] = hull_plane_adr[cl]; c.plane_num[i] = hull_plane_adr[cl + 1] - hull_plane_adr[cl];
-    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("%s: cloud %d has %d face planes (a hull has at least 4)", fn, cl, c.plane_num[i]); return GQ_EINVAL; }
-  }
-  DeviceGuard guard(m->device);
-  const int n = b->host.n_envs;
-  if (!b->cam_rec) {
-    HIP_TRY(hipMalloc(&b->cam_rec, sizeof(float) * GQ_CAM_REC * (size_t)n));
-    HIP_TRY(hipMalloc(&b->cam_pos, sizeof(double) * 3 * (size_t)n));
-  }
-  const double th = std::tan(0.5 * (double)fovy_deg * 3.14159265358979323846 / 180.0);
-  c.qpos = qpos; c.qpos_stride = qpos_stride; c.body = body;
-  for (int k = 0; k < 3; k++) c.pos[k] = pos[k];
-  for (int k = 0; k < 4; k++) c.quat[k] = (float)(quat[k] / qn);
-  c.width = width; c.height = height; c.flags = flags; c.ngeom = m->ngeom;
-  c.tan_x = (float)(th * width / height); c.tan_y = (float)th; c.znear = znear; c.zfar = zfar;
-  c.planes = hull_planes; c.rec = b->cam_rec; c.cpos = b->cam_pos; c.xpos_out = cam_xpos; c.xmat_out = cam_xmat; c.depth = depth; c.seg = seg;
-  return GQ_OK;
-}
-
-int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
-              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
-              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream) {
-  gq::CamCall c;
-  const int rc = camera_call("gq_camera", b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
-                             depth, seg, cam_xpos, cam_xmat, c);
-  if (rc != GQ_OK) return rc;
-  DeviceGuard guard(b->model->device);
-  gq_launch_camera(b->model->dev, &c, b->host.n_envs, (hipStream_t)hip_stream);
-  HIP_TRY(hipGetLastError());
-  return GQ_OK;
-}
-
 /* GqCamShade -> the kernel's CamShade: every field checked (include/gq.h gq_camera_shaded), directions normalised, cutoffs as cosines */
 static bool cam_finite(const float* v, int n) {
   for (int k = 0; k < n; k++)
@@ -881,61 +824,98 @@ static int camera_shade(const GqCamShade* in, gq::CamShade& s) {
   return GQ_OK;
 }
 
-int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
-                     int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
-                     float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, void* hip_stream) {
+/* gq_camera (mode 0), gq_camera_shaded (1), gq_camera_layered (2): the checks in the order layers, shade, rgba, camera (fn: the entry
+ * point's name for the error text), the call records, the batch's scratch blocks on first use, the launch */
+static int camera_run(const char* fn, const int mode, GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4],
+                      float fovy_deg, int width, int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                      float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, const GqCamLayers* layers,
+                      void* hip_stream) {
+  if (mode >= 2) {
+    if (!layers) { SET_ERR("%s: null layers", fn); return GQ_EINVAL; }
+    if (layers->struct_size != (int32_t)sizeof(GqCamLayers)) {
+      SET_ERR("%s: GqCamLayers.struct_size %d != %d (header mismatch)", fn, layers->struct_size, (int)sizeof(GqCamLayers)); return GQ_EINVAL;
+    }
+    if (layers->n_ghost < 0 || layers->n_ghost > GQ_CAM_MAXGHOST) { SET_ERR("%s: n_ghost %d is not in [0, %d]", fn, layers->n_ghost, GQ_CAM_MAXGHOST); return GQ_EINVAL; }
+    if (layers->n_marker < 0 || layers->n_marker > GQ_CAM_MAXMARKER) { SET_ERR("%s: n_marker %d is not in [0, %d]", fn, layers->n_marker, GQ_CAM_MAXMARKER); return GQ_EINVAL; }
+    if (layers->n_ghost > 0 && (!layers->ghost_qpos || !layers->ghost_alpha)) { SET_ERR("%s: n_ghost > 0 with a null ghost_qpos or ghost_alpha", fn); return GQ_EINVAL; }
+    if (layers->n_ghost > 0 && layers->ghost_stride < 19) { SET_ERR("%s: ghost_stride %d < 19", fn, layers->ghost_stride); return GQ_EINVAL; }
+    if (layers->n_marker > 0 && !layers->markers) { SET_ERR("%s: n_marker > 0 with a null markers", fn); return GQ_EINVAL; }
+  }
   gq::CamShade s;
-  int rc = camera_shade(shade, s);
-  if (rc != GQ_OK) return rc;
-  if (!rgba) { SET_ERR("gq_camera_shaded: null rgba"); return GQ_EINVAL; }
-  gq::CamCall c;
-  rc = camera_call("gq_camera_shaded", b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
-                   depth, seg, cam_xpos, cam_xmat, c);
-  if (rc != GQ_OK) return rc;
-  s.rgba = reinterpret_cast<uint32_t*>(rgba);
-  DeviceGuard guard(b->model->device);
-  gq_launch_camera_shaded(b->model->dev, &c, &s, b->host.n_envs, (hipStream_t)hip_stream);
+  if (mode >= 1) {
+    const int rc = camera_shade(shade, s);
+    if (rc != GQ_OK) return rc;
+    if (!rgba) { SET_ERR("%s: null rgba", fn); return GQ_EINVAL; }
+    s.rgba = reinterpret_cast<uint32_t*>(rgba);
+  }
+  if (!b || !qpos || !pos || !quat || !depth) { SET_ERR("%s: null argument", fn); return GQ_EINVAL; }
+  if (qpos_stride < 19) { SET_ERR("%s: qpos_stride %d < 19", fn, qpos_stride); return GQ_EINVAL; }
+  if (body < 0 || body > GQ_NB) { SET_ERR("%s: body id %d out of range (0 = world .. %d)", fn, body, GQ_NB); return GQ_EINVAL; }
+  if (width <= 0 || height <= 0 || (size_t)width * height > (1u << 24)) { SET_ERR("%s: bad image size %d x %d", fn, width, height); return GQ_EINVAL; }
+  if (!(fovy_deg > 0.0f && fovy_deg < 180.0f)) { SET_ERR("%s: fovy %g is not in (0, 180) degrees", fn, (double)fovy_deg); return GQ_EINVAL; }
+  if (!(znear > 0.0f && zfar > znear)) { SET_ERR("%s: need 0 < znear < zfar (got %g, %g)", fn, (double)znear, (double)zfar); return GQ_EINVAL; }
+  if (flags & ~(GQ_CAM_ROBOT | GQ_CAM_SCENE | GQ_CAM_TRACK)) { SET_ERR("%s: unknown flags 0x%x", fn, flags); return GQ_EINVAL; }
+  if ((flags & GQ_CAM_TRACK) && body == 0) { SET_ERR("%s: GQ_CAM_TRACK needs a body camera (body > 0)", fn); return GQ_EINVAL; }
+  const double qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
+  if (!(qn > 0.0)) { SET_ERR("%s: zero quaternion", fn); return GQ_EINVAL; }
+  GqModel* m = b->model;
+  gq::CamCall c{};
+  for (int i = 0; i < m->host.nlg; i++) {
+    if (m->host.lg[i].ptype != 0) continue;
+    if (!hull_planes || !hull_plane_adr) { SET_ERR("%s: the model has hull geoms and no face planes were passed", fn); return GQ_EINVAL; }
+    const int cl = m->lg_cloud[i];
+    if (cl < 0 || cl >= m->ncloud) { SET_ERR("%s: link geom %d has no cloud", fn, i); return GQ_EINVAL; }
+    c.plane_adr[i] = hull_plane_adr[cl]; c.plane_num[i] = hull_plane_adr[cl + 1] - hull_plane_adr[cl];
+    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("%s: cloud %d has %d face planes (a hull has at least 4)", fn, cl, c.plane_num[i]); return GQ_EINVAL; }
+  }
+  DeviceGuard guard(m->device);
+  const int n = b->host.n_envs;
+  if (!b->cam_rec) {
+    HIP_TRY(hipMalloc(&b->cam_rec, sizeof(float) * GQ_CAM_REC * (size_t)n));
+    HIP_TRY(hipMalloc(&b->cam_pos, sizeof(double) * 3 * (size_t)n));
+  }
+  const double th = std::tan(0.5 * (double)fovy_deg * 3.14159265358979323846 / 180.0);
+  c.qpos = qpos; c.qpos_stride = qpos_stride; c.body = body;
+  for (int k = 0; k < 3; k++) c.pos[k] = pos[k];
+  for (int k = 0; k < 4; k++) c.quat[k] = (float)(quat[k] / qn);
+  c.width = width; c.height = height; c.flags = flags; c.ngeom = m->ngeom;
+  c.tan_x = (float)(th * width / height); c.tan_y = (float)th; c.znear = znear; c.zfar = zfar;
+  c.planes = hull_planes; c.rec = b->cam_rec; c.cpos = b->cam_pos; c.xpos_out = cam_xpos; c.xmat_out = cam_xmat; c.depth = depth; c.seg = seg;
+  gq::CamLayers l{};
+  if (mode >= 2) {
+    if (layers->n_ghost > b->cam_nghost) {
+      hipFree(b->cam_grec);
+      b->cam_grec = nullptr; b->cam_nghost = 0;
+      HIP_TRY(hipMalloc(&b->cam_grec, sizeof(float) * GQ_CAM_GREC * (size_t)layers->n_ghost * n));
+      b->cam_nghost = layers->n_ghost;
+    }
+    l.ghost_qpos = layers->ghost_qpos; l.ghost_stride = layers->ghost_stride; l.n_ghost = layers->n_ghost;
+    l.ghost_alpha = layers->ghost_alpha; l.ghost_rgb = layers->ghost_rgb;
+    l.n_marker = layers->n_marker; l.markers = layers->markers; l.grec = b->cam_grec;
+  }
+  gq_launch_camera(m->dev, &c, mode >= 1 ? &s : nullptr, mode >= 2 ? &l : nullptr, n, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
 
+int gq_camera(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height,
+              float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+              float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, void* hip_stream) {
+  return camera_run("gq_camera", 0, b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                    depth, seg, cam_xpos, cam_xmat, nullptr, nullptr, nullptr, hip_stream);
+}
+int gq_camera_shaded(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
+                     int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
+                     float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, void* hip_stream) {
+  return camera_run("gq_camera_shaded", 1, b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                    depth, seg, cam_xpos, cam_xmat, shade, rgba, nullptr, hip_stream);
+}
 int gq_camera_layered(GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width,
                       int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
                       float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba,
                       const GqCamLayers* layers, void* hip_stream) {
-  const char* fn = "gq_camera_layered";
-  if (!layers) { SET_ERR("%s: null layers", fn); return GQ_EINVAL; }
-  if (layers->struct_size != (int32_t)sizeof(GqCamLayers)) {
-    SET_ERR("%s: GqCamLayers.struct_size %d != %d (header mismatch)", fn, layers->struct_size, (int)sizeof(GqCamLayers)); return GQ_EINVAL;
-  }
-  if (layers->n_ghost < 0 || layers->n_ghost > GQ_CAM_MAXGHOST) { SET_ERR("%s: n_ghost %d is not in [0, %d]", fn, layers->n_ghost, GQ_CAM_MAXGHOST); return GQ_EINVAL; }
-  if (layers->n_marker < 0 || layers->n_marker > GQ_CAM_MAXMARKER) { SET_ERR("%s: n_marker %d is not in [0, %d]", fn, layers->n_marker, GQ_CAM_MAXMARKER); return GQ_EINVAL; }
-  if (layers->n_ghost > 0 && (!layers->ghost_qpos || !layers->ghost_alpha)) { SET_ERR("%s: n_ghost > 0 with a null ghost_qpos or ghost_alpha", fn); return GQ_EINVAL; }
-  if (layers->n_ghost > 0 && layers->ghost_stride < 19) { SET_ERR("%s: ghost_stride %d < 19", fn, layers->ghost_stride); return GQ_EINVAL; }
-  if (layers->n_marker > 0 && !layers->markers) { SET_ERR("%s: n_marker > 0 with a null markers", fn); return GQ_EINVAL; }
-  gq::CamShade s;
-  int rc = camera_shade(shade, s);
-  if (rc != GQ_OK) return rc;
-  if (!rgba) { SET_ERR("%s: null rgba", fn); return GQ_EINVAL; }
-  gq::CamCall c;
-  rc = camera_call(fn, b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
-                   depth, seg, cam_xpos, cam_xmat, c);
-  if (rc != GQ_OK) return rc;
-  s.rgba = reinterpret_cast<uint32_t*>(rgba);
-  DeviceGuard guard(b->model->device);
-  if (layers->n_ghost > b->cam_nghost) {
-    hipFree(b->cam_grec);
-    b->cam_grec = nullptr; b->cam_nghost = 0;
-    HIP_TRY(hipMalloc(&b->cam_grec, sizeof(float) * GQ_CAM_GREC * (size_t)layers->n_ghost * b->host.n_envs));
-    b->cam_nghost = layers->n_ghost;
-  }
-  gq::CamLayers l{};
-  l.ghost_qpos = layers->ghost_qpos; l.ghost_stride = layers->ghost_stride; l.n_ghost = layers->n_ghost;
-  l.ghost_alpha = layers->ghost_alpha; l.ghost_rgb = layers->ghost_rgb;
-  l.n_marker = layers->n_marker; l.markers = layers->markers; l.grec = b->cam_grec;
-  gq_launch_camera_layered(b->model->dev, &c, &s, &l, b->host.n_envs, (hipStream_t)hip_stream);
-  HIP_TRY(hipGetLastError());
-  return GQ_OK;
+  return camera_run("gq_camera_layered", 2, b, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags, hull_planes, hull_plane_adr,
+                    depth, seg, cam_xpos, cam_xmat, shade, rgba, layers, hip_stream);
 }
 
 int gq_forward(GqBatch* b, int stage, const float* ctrl, GqState st, GqObsOut out, void* hip_stream) {

@@ -6,7 +6,9 @@
  *  - pixel pass, one wavefront per 8 x 8 tile of one env: lane = candidate culls the robot geoms and the world boxes against the tile's
  *    view cone (two ballots, as heightmap_rays does for boxes), then lane = pixel walks the survivors wave-uniformly.
  * gq_camera_layered adds a ghost pose pass (one wavefront per env and ghost: the robot geoms posed from each ghost qpos, relative to the
- * env's camera) and composites ghosts and markers over the shaded image in its pixel pass (cam_layers).
+ * env's camera) and composites ghosts and markers over the shaded image in its pixel pass (cam_layers).  The robot and the ghosts go through
+ * one cull, cast, normal and light routine (cam_rob_cull, cam_rob_cast, cam_rob_normal, cam_light); the file runs from the primitives up to
+ * the pixel pass, camera_tile_wave, at its end.
  * Also the static-geom ray tests that gq_ray's ray_kernel and the pixel pass share (slab, height-field cell walk).
  * Semantics: pixel (r, c) looks along ((2 (c + .5) / W - 1) tan(fovy / 2) W / H, (1 - 2 (r + .5) / H) tan(fovy / 2), -1) in
  * the camera frame, so a hit's ray parameter is its planar depth; the nearest hit in [znear, zfar] wins, none gives zfar.  Convex geoms are
@@ -216,19 +218,9 @@ __device__ inline float cam_hull(V3 o, V3 d, const float* P, int n, int& part) {
   return !miss && tin <= tout ? tin : -1.0f;
 }
 
-/* the ghost pose pass's pieces of camera_pose_wave: the first 19 entries of one qpos row into the wave's LDS (lane = entry), and the
- * geom frames below (camera_pose_wave keeps its own copy: through these helpers its code would change) */
-__device__ __forceinline__ void cam_load_qpos(WaveMem& W, const double* qrow, const int lane) {
-  if (lane < 19) {
-    const double q = qrow[lane];
-    if (lane < 2) W.bxy[lane] = q;
-    else if (lane == 2) W.basez = (float)q;
-    else if (lane < 7) W.qb[lane - 3] = (float)q;
-    else W.qj[lane - 7] = (float)q;
-  }
-}
-/* lane = robot geom: its frame relative to the camera (rotation Rc, origin pc relative to the base x/y of W's kinematics), R = Rc' Rg,
- * t = Rc' (pg - pc), 12 floats per geom from out */
+/* the ghost pose pass's geom frames.  lane = robot geom: its frame relative to the camera (rotation Rc, origin pc relative to the base x/y
+ * of W's kinematics), R = Rc' Rg, t = Rc' (pg - pc), 12 floats per geom from out.  camera_pose_wave holds the same text for the robot: the
+ * one pair left apart, because the compiler contracts the sum for R differently in the two places (see there) */
 template <class Mref>
 __device__ __forceinline__ void cam_geom_frames(WaveMem& W, const Mref& m, const float* Rc, const V3 pc, float* out, const int lane) {
   const int nrob = 4 + m.nlg;
@@ -261,13 +253,7 @@ __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall
 #if GQ_TICKSET
   if (lane == 0) W.tk_T = nullptr;
 #endif
-  if (lane < 19) {
-    const double q = c.qpos[(size_t)env * c.qpos_stride + lane];
-    if (lane < 2) W.bxy[lane] = q;
-    else if (lane == 2) W.basez = (float)q;
-    else if (lane < 7) W.qb[lane - 3] = (float)q;
-    else W.qj[lane - 7] = (float)q;
-  }
+  load_qpos_row(W, c.qpos + (size_t)env * c.qpos_stride, lane);
   wave_barrier();
   stage_kinematics(W, link_fetch(m, lane));
   /* the camera frame relative to the base x/y, like every kinematic quantity */
@@ -296,8 +282,9 @@ __device__ inline void camera_pose_wave(WaveMem& W, const Mref& m, const CamCall
     c.cpos[(size_t)env * 3 + k] = p;
     if (c.xpos_out) c.xpos_out[(size_t)env * 3 + k] = p;
   }
-  /* lane = robot geom: its frame in the camera frame, R = Rc' Rg, t = Rc' (pg - pc).  Twin: cam_geom_frames (the ghost pose pass); a
-   * change here goes there too, or ghosts posed like the robot stop matching it bit for bit */
+  /* lane = robot geom: its frame in the camera frame, the text of cam_geom_frames and not a call to it.  Here the compiler rounds R's sum
+   * a b + c d + e f as fma(e, f, fma(c, d, a b)), inside the helper (called from here or from the ghost pass) as fma(e, f, fma(a, b, c d));
+   * a call moves the robot's depths by an ulp or two (measured).  One explicit order for both changes what is drawn. */
   const int nrob = 4 + m.nlg;
   if (lane < nrob) {
     V3 pg;
@@ -330,7 +317,7 @@ __device__ inline void camera_ghost_wave(WaveMem& W, const Mref& m, const CamCal
   if (lane == 0) W.tk_T = nullptr;
 #endif
   const size_t row = (size_t)env * L.n_ghost + ghost;
-  cam_load_qpos(W, L.ghost_qpos + row * L.ghost_stride, lane);
+  load_qpos_row(W, L.ghost_qpos + row * L.ghost_stride, lane);
   wave_barrier();
   stage_kinematics(W, link_fetch(m, lane));
   const float* rec = c.rec + (size_t)env * GQ_CAM_REC;
@@ -351,8 +338,8 @@ __device__ __forceinline__ bool cam_cone_sphere(V3 ctr, float rad, V3 ax, float 
   return sqrtf(dot(p, p)) * ca - a * sa <= rad;
 }
 
-/* may robot geom `lane` (its camera-frame record g) show in the tile's view cone?  This and the three helpers below are the layered pass's
- * copies of code that stays inline in camera_tile_wave and cam_shade (see there); a change to one copy goes to the other */
+/* may robot geom `lane` (its camera-frame record g) show in the tile's view cone?  The robot and every ghost go through this and the three
+ * helpers below (cast, normal, lights): a ghost posed like the robot then meets the compositor's strict t < t0 with equal bits */
 template <class Mref>
 __device__ __forceinline__ bool cam_rob_cull(const Mref& M, const CamCall& c, const float* g, const int lane, V3 ax, float ca, float sa) {
   V3 ctr = ld3(g + 9);
@@ -389,147 +376,8 @@ __device__ __forceinline__ float cam_rob_cast(const Mref& M, const CamCall& c, c
   return th;
 }
 
-template <bool F, class Mref>
-__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
-                                     V3 dw, float best, int id, int slot, int part, int nbox, float* fout);
-__device__ __forceinline__ uint32_t cam_byte(float x) { return (uint32_t)floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f) + 0.5f); }
-template <class Mref>
-__device__ inline void cam_layers(const Mref& M, const CamCall& c, const CamShade& S, const CamLayers& L, const float* Rc, const double* co, V3 d,
-                                  V3 ax, float ca, float sa, float t0, int env, float* C);
-
-/* pixel pass: one wavefront renders tile `tile` of env `env`; SHADE: also its RGBA image (sh); LAYERS: ghosts and markers composited over
- * that image (ly, gq_camera_layered) */
-template <bool SHADE, bool LAYERS = false, class Mref>
-__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const CamShade* sh, const int tile, const int env,
-                                        const CamLayers* ly = nullptr) {
-  const int lane = lane_id(), W = c.width, H = c.height;
-  const int tiles_x = (W + GQ_CAM_TILE - 1) / GQ_CAM_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
-  const int row = ty * GQ_CAM_TILE + lane / GQ_CAM_TILE, col = tx * GQ_CAM_TILE + lane % GQ_CAM_TILE;
-  const bool valid = row < H && col < W;
-  const int r = row < H ? row : H - 1, cl = col < W ? col : W - 1;   /* lanes past the image edge mirror a pixel and do not store */
-  const V3 d = v3((2.0f * ((float)cl + 0.5f) / (float)W - 1.0f) * c.tan_x, (1.0f - 2.0f * ((float)r + 0.5f) / (float)H) * c.tan_y, -1.0f);
-  const float* rec = c.rec + (size_t)env * GQ_CAM_REC;
-  float Rc[9];
-  for (int k = 0; k < 9; k++) Rc[k] = rec[k];
-  const double co[3] = {c.cpos[(size_t)env * 3], c.cpos[(size_t)env * 3 + 1], c.cpos[(size_t)env * 3 + 2]};
-  /* the tile's view cone: axis through the tile centre, half angle to the farthest corner ray */
-  const int c0 = tx * GQ_CAM_TILE, c1 = imin(c0 + GQ_CAM_TILE, W), r0 = ty * GQ_CAM_TILE, r1 = imin(r0 + GQ_CAM_TILE, H);
-  const float xl = (2.0f * c0 / W - 1.0f) * c.tan_x, xh = (2.0f * c1 / W - 1.0f) * c.tan_x;
-  const float yh = (1.0f - 2.0f * r0 / H) * c.tan_y, yl = (1.0f - 2.0f * r1 / H) * c.tan_y;
-  V3 ax = v3(0.5f * (xl + xh), 0.5f * (yl + yh), -1.0f);
-  ax = (1.0f / sqrtf(dot(ax, ax))) * ax;
-  float ca = 1.0f;
-  for (int k = 0; k < 4; k++) {
-    const V3 q = v3(k & 1 ? xh : xl, k & 2 ? yh : yl, -1.0f);
-    ca = fminf(ca, dot(q, ax) / sqrtf(dot(q, q)));
-  }
-  const float sa = sqrtf(fmaxf(0.0f, 1.0f - ca * ca));
-  /* cull, lane = candidate */
-  const int nrob = 4 + M.nlg, nbox = M.nbox;
-  uint64_t rob = 0, box[2] = {0, 0};
-  if (c.flags & 1) {
-    bool near = false;
-    if (lane < nrob) { /* twin: cam_rob_cull (the layered pass); change both */
-      const float* g = rec + 12 + 12 * lane;
-      V3 ctr = ld3(g + 9);
-      float rad;
-      if (lane < 4) rad = M.foot_radius[lane];
-      else {
-        const auto& G = M.lg[lane - 4];
-        ctr = ctr + matvec(g, ld3(G.aabb_c));
-        rad = sqrtf(G.aabb_h[0] * G.aabb_h[0] + G.aabb_h[1] * G.aabb_h[1] + G.aabb_h[2] * G.aabb_h[2]) + G.radius;
-      }
-      near = cam_cone_sphere(ctr, rad, ax, ca, sa, c.znear, c.zfar);
-    }
-    rob = ballot(near);
-  }
-  if (c.flags & 2)
-    for (int half = 0; half < 2 && half * GQ_WAVE < nbox; half++) { /* wave-uniform */
-      const int b = half * GQ_WAVE + lane;
-      bool near = false;
-      if (b < nbox) {
-        const V3 v = v3((float)((double)M.box[b].pos[0] - co[0]), (float)((double)M.box[b].pos[1] - co[1]), (float)((double)M.box[b].pos[2] - co[2]));
-        near = cam_cone_sphere(matTvec(Rc, v), M.box[b].rad, ax, ca, sa, c.znear, c.zfar);
-      }
-      box[half] = ballot(near);
-    }
-  /* cast, lane = pixel.  The shaded pass also keeps what the winner is: slot (robot geom g / world box b / height-field triangle) and part
-   * (the surface of the primitive the entry is on); its normal is formed once, after the walk.  The depth-only pass never reads them. */
-  float best = c.zfar;
-  int id = -1, slot = 0, part = 0;
-  const V3 dw = matvec(Rc, d);   /* the ray in world axes */
-  if (c.flags & 2) {
-    if (dw.z < 0.0f && co[2] >= 0.0) { /* the floor: a one-sided plane, hit from above */
-      const float t = (float)(-co[2] / (double)dw.z);
-      if (t >= c.znear && t <= best) { best = t; id = c.ngeom; }
-    }
-    const float dv[3] = {dw.x, dw.y, dw.z};
-    for (int half = 0; half < 2; half++)
-      for (uint64_t todo = box[half]; todo; todo &= todo - 1) { /* wave-uniform */
-        const int b = half * GQ_WAVE + ffs64(todo);
-        const float rv[3] = {(float)(co[0] - (double)M.box[b].pos[0]), (float)(co[1] - (double)M.box[b].pos[1]), (float)(co[2] - (double)M.box[b].pos[2])};
-        float tin = -1e30f, tout = 1e30f;
-        int ax_in = 0;
-        if (ray_box(M.box[b], rv, dv, tin, tout, SHADE ? &ax_in : nullptr) && tin >= c.znear && tin <= best) {
-          best = tin; id = c.ngeom + 1 + b;
-          if (SHADE) { slot = b; part = ax_in; }
-        }
-      }
-    if (M.hf_nrow > 0) { /* fp64: the walk runs in the field's own coordinates */
-      const double ol[3] = {co[0] - (double)M.hf_pos[0], co[1] - (double)M.hf_pos[1], co[2] - (double)M.hf_pos[2]}, dd[3] = {dw.x, dw.y, dw.z};
-      int tri = 0;
-      const double t = ray_hfield(M, ol, dd, (double)c.znear, SHADE ? &tri : nullptr);
-      if (t >= 0.0 && t <= (double)best) {
-        best = (float)t; id = c.ngeom + 1 + nbox;
-        if (SHADE) slot = tri;
-      }
-    }
-  }
-  for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform; the cast's twin: cam_rob_cast (the layered pass), change both */
-    const int g = ffs64(todo);
-    const float* gr = rec + 12 + 12 * g;
-    const V3 t = ld3(gr + 9), o = (-1.0f) * matTvec(gr, t), dl = matTvec(gr, d);
-    float th;
-    int pg = 0;
-    if (g < 4) th = cam_sphere(o, dl, M.foot_radius[g]);
-    else {
-      const auto& G = M.lg[g - 4];
-      const int pt = G.ptype;
-      if (pt == 2) th = cam_sphere(o, dl, G.psize[0]);
-      else if (pt == 3) th = cam_capsule(o, dl, G.psize[0], G.psize[1], pg);
-      else if (pt == 5) th = cam_cylinder(o, dl, G.psize[0], G.psize[1], pg);
-      else if (pt == 6) {
-        const float ov[3] = {o.x, o.y, o.z}, dv[3] = {dl.x, dl.y, dl.z}, s[3] = {G.psize[0], G.psize[1], G.psize[2]};
-        float tin = -1e30f, tout = 1e30f;
-        th = ray_slab(ov, dv, s, tin, tout, SHADE ? &pg : nullptr) ? tin : -1.0f;
-      } else {
-        th = cam_hull(o, dl, c.planes + 4 * c.plane_adr[g - 4], c.plane_num[g - 4], pg);
-        pg += c.plane_adr[g - 4];   /* the entry plane, as an index into c.planes */
-      }
-    }
-    if (th >= c.znear && th <= best) {
-      best = th; id = M.item_geomid[g];
-      if (SHADE) { slot = g; part = pg; }
-    }
-  }
-  const size_t px = ((size_t)env * H + row) * W + col;
-  if (valid) {
-    c.depth[px] = best;
-    if (c.seg) c.seg[px] = id;
-  }
-  if constexpr (LAYERS) {
-    float rgb[3];
-    cam_shade<true>(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox, rgb);
-    cam_layers(M, c, *sh, *ly, Rc, co, d, ax, ca, sa, best, env, rgb);
-    const uint32_t rgba = cam_byte(rgb[0]) | cam_byte(rgb[1]) << 8 | cam_byte(rgb[2]) << 16 | 0xff000000u;
-    if (valid) sh->rgba[px] = rgba;
-  } else if constexpr (SHADE) {
-    const uint32_t rgba = cam_shade<false>(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox, nullptr);
-    if (valid) sh->rgba[px] = rgba;
-  }
-}
-
 /* ---- shading (gq_camera_shaded): the winner's normal, its material and the lights, fp32 in the camera frame */
+__device__ __forceinline__ uint32_t cam_byte(float x) { return (uint32_t)floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f) + 0.5f); }
 __device__ __forceinline__ V3 cam_unit(V3 a) { return (1.0f / sqrtf(dot(a, a))) * a; }
 /* x^e for x in [0, 1], e >= 0 on the transcendental unit (v_log_f32 / v_exp_f32, as fast_pow_ratio; the library powf is hundreds of
  * instructions of special cases); 0^0 = 1 */
@@ -582,40 +430,19 @@ __device__ __forceinline__ void cam_light(const CamShade& S, const float* Rc, co
   }
 }
 
-/* the opaque colour of a pixel: the background, or the winner (id, slot, part) lit; F: unclamped into fout (the layered pass) instead
- * of the RGBA8 word.  Its robot-normal and lighting code is that of cam_rob_normal and cam_light, which the layered pass uses for its
- * layers; written out here, the two earlier instantiations of the pixel pass compile to the instructions they had before. */
-template <bool F, class Mref>
-__device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d,
-                                     V3 dw, float best, int id, int slot, int part, int nbox, float* fout) {
+/* the opaque colour of a pixel, unclamped into out: the background, or the winner (id, slot, part) lit */
+template <class Mref>
+__device__ inline void cam_shade(const Mref& M, const CamCall& c, const CamShade& S, const float* rec, const float* Rc, const double* co, V3 d, V3 dw,
+                                 float best, int id, int slot, int part, int nbox, float* out) {
   float col[3], mat[3];   /* base colour; specular, shininess, emission */
-  V3 n;                   /* outward normal, camera frame (not yet unit) */
+  V3 n;                   /* outward normal, camera frame (not unit) */
   if (id < 0) { /* background: the gradient over the world z of the unit ray */
     const float s = 0.5f * (1.0f + dw.z / sqrtf(dot(dw, dw)));
-    if constexpr (F) {
-      for (int k = 0; k < 3; k++) fout[k] = S.bottom[k] + (S.top[k] - S.bottom[k]) * s;
-      return 0;
-    } else
-      return cam_byte(S.bottom[0] + (S.top[0] - S.bottom[0]) * s) | cam_byte(S.bottom[1] + (S.top[1] - S.bottom[1]) * s) << 8 |
-             cam_byte(S.bottom[2] + (S.top[2] - S.bottom[2]) * s) << 16 | 0xff000000u;
+    for (int k = 0; k < 3; k++) out[k] = S.bottom[k] + (S.top[k] - S.bottom[k]) * s;
+    return;
   }
-  if (id < c.ngeom) { /* robot geom `slot`: its frame in the camera frame, the hit in the geom frame (twin: cam_rob_normal) */
-    const float* gr = rec + 12 + 12 * slot;
-    const V3 t = ld3(gr + 9), p = (-1.0f) * matTvec(gr, t) + best * matTvec(gr, d);
-    V3 nl = p;   /* spheres */
-    if (slot >= 4) {
-      const auto& G = M.lg[slot - 4];
-      const int pt = G.ptype;
-      const float h = G.psize[1];
-      if (pt == 3) nl = part == 0 ? v3(p.x, p.y, 0.0f) : p - v3(0.0f, 0.0f, part == 1 ? h : -h);
-      else if (pt == 5) nl = part == 0 ? v3(p.x, p.y, 0.0f) : v3(0.0f, 0.0f, p.z > 0.0f ? 1.0f : -1.0f);
-      else if (pt == 6) {
-        const V3 dl = matTvec(gr, d);
-        const float dk = part == 0 ? dl.x : part == 1 ? dl.y : dl.z, s = dk > 0.0f ? -1.0f : 1.0f;
-        nl = v3(part == 0 ? s : 0.0f, part == 1 ? s : 0.0f, part == 2 ? s : 0.0f);
-      } else if (pt != 2) nl = ld3(c.planes + 4 * part);
-    }
-    n = matvec(gr, nl);
+  if (id < c.ngeom) { /* robot geom `slot` */
+    n = cam_rob_normal(M, c, rec + 12 + 12 * slot, slot, part, d, best);
     const float* gm = S.geom_mat + 7 * id;
     col[0] = gm[0]; col[1] = gm[1]; col[2] = gm[2]; mat[0] = gm[4]; mat[1] = gm[5]; mat[2] = gm[6];
   } else {
@@ -652,33 +479,7 @@ __device__ inline uint32_t cam_shade(const Mref& M, const CamCall& c, const CamS
     }
     n = matTvec(Rc, nw);
   }
-  /* the lights (twin: cam_light, the layers' shading; change both) */
-  n = cam_unit(n);
-  const V3 v = (-1.0f) * cam_unit(d), ph = best * d;   /* towards the camera; the hit, camera frame */
-  float out[3] = {mat[2] * col[0], mat[2] * col[1], mat[2] * col[2]};
-  const float shin = 128.0f * mat[1];
-  for (int l = 0; l < S.nlight; l++) { /* wave-uniform: each light is taken into the camera frame once per wave */
-    const CamLight& Lt = S.light[l];
-    V3 L = v3(0.0f, 0.0f, 1.0f);
-    float w = 1.0f;   /* attenuation x spot */
-    if (Lt.kind == 1) L = (-1.0f) * matTvec(Rc, ld3(Lt.dir));
-    else if (Lt.kind == 2) {
-      const V3 lp = matTvec(Rc, v3((float)((double)Lt.pos[0] - co[0]), (float)((double)Lt.pos[1] - co[1]), (float)((double)Lt.pos[2] - co[2])));
-      const V3 q = lp - ph;
-      const float r = sqrtf(dot(q, q));
-      L = (1.0f / r) * q;
-      const float cs = -dot(L, matTvec(Rc, ld3(Lt.dir)));
-      w = (cs >= Lt.cos_cut ? cam_pow(cs, Lt.expo) : 0.0f) / (Lt.att[0] + Lt.att[1] * r + Lt.att[2] * r * r);
-    }
-    const float nL = dot(n, L), nH = fmaxf(dot(n, cam_unit(L + v)), 0.0f);
-    const float sp = nL > 0.0f ? mat[0] * cam_pow(nH, shin) : 0.0f, df = fmaxf(nL, 0.0f);
-    for (int k = 0; k < 3; k++) out[k] += w * (Lt.amb[k] * col[k] + Lt.dif[k] * col[k] * df + Lt.spe[k] * sp);
-  }
-  if constexpr (F) {
-    for (int k = 0; k < 3; k++) fout[k] = out[k];
-    return 0;
-  } else
-    return cam_byte(out[0]) | cam_byte(out[1]) << 8 | cam_byte(out[2]) << 16 | 0xff000000u;
+  cam_light(S, Rc, co, n, col, mat, d, best, out);
 }
 
 /* ---- layers (gq_camera_layered): ghost robots and markers, each at most one translucent layer per pixel */
@@ -853,6 +654,106 @@ __device__ inline void cam_layers(const Mref& M, const CamCall& c, const CamShad
     C[0] = la[k] * lr[k] + (1.0f - la[k]) * C[0];
     C[1] = la[k] * lg[k] + (1.0f - la[k]) * C[1];
     C[2] = la[k] * lb[k] + (1.0f - la[k]) * C[2];
+  }
+}
+
+/* pixel pass: one wavefront renders tile `tile` of env `env`; SHADE: also its RGBA image (sh); LAYERS: ghosts and markers composited over
+ * that image (ly, gq_camera_layered) */
+template <bool SHADE, bool LAYERS = false, class Mref>
+__device__ inline void camera_tile_wave(const Mref& M, const CamCall& c, const CamShade* sh, const int tile, const int env,
+                                        const CamLayers* ly = nullptr) {
+  const int lane = lane_id(), W = c.width, H = c.height;
+  const int tiles_x = (W + GQ_CAM_TILE - 1) / GQ_CAM_TILE, tx = tile % tiles_x, ty = tile / tiles_x;
+  const int row = ty * GQ_CAM_TILE + lane / GQ_CAM_TILE, col = tx * GQ_CAM_TILE + lane % GQ_CAM_TILE;
+  const bool valid = row < H && col < W;
+  const int r = row < H ? row : H - 1, cl = col < W ? col : W - 1;   /* lanes past the image edge mirror a pixel and do not store */
+  const V3 d = v3((2.0f * ((float)cl + 0.5f) / (float)W - 1.0f) * c.tan_x, (1.0f - 2.0f * ((float)r + 0.5f) / (float)H) * c.tan_y, -1.0f);
+  const float* rec = c.rec + (size_t)env * GQ_CAM_REC;
+  float Rc[9];
+  for (int k = 0; k < 9; k++) Rc[k] = rec[k];
+  const double co[3] = {c.cpos[(size_t)env * 3], c.cpos[(size_t)env * 3 + 1], c.cpos[(size_t)env * 3 + 2]};
+  /* the tile's view cone: axis through the tile centre, half angle to the farthest corner ray */
+  const int c0 = tx * GQ_CAM_TILE, c1 = imin(c0 + GQ_CAM_TILE, W), r0 = ty * GQ_CAM_TILE, r1 = imin(r0 + GQ_CAM_TILE, H);
+  const float xl = (2.0f * c0 / W - 1.0f) * c.tan_x, xh = (2.0f * c1 / W - 1.0f) * c.tan_x;
+  const float yh = (1.0f - 2.0f * r0 / H) * c.tan_y, yl = (1.0f - 2.0f * r1 / H) * c.tan_y;
+  V3 ax = v3(0.5f * (xl + xh), 0.5f * (yl + yh), -1.0f);
+  ax = (1.0f / sqrtf(dot(ax, ax))) * ax;
+  float ca = 1.0f;
+  for (int k = 0; k < 4; k++) {
+    const V3 q = v3(k & 1 ? xh : xl, k & 2 ? yh : yl, -1.0f);
+    ca = fminf(ca, dot(q, ax) / sqrtf(dot(q, q)));
+  }
+  const float sa = sqrtf(fmaxf(0.0f, 1.0f - ca * ca));
+  /* cull, lane = candidate */
+  const int nrob = 4 + M.nlg, nbox = M.nbox;
+  uint64_t rob = 0, box[2] = {0, 0};
+  if (c.flags & 1) {
+    bool near = false;
+    if (lane < nrob) near = cam_rob_cull(M, c, rec + 12 + 12 * lane, lane, ax, ca, sa);
+    rob = ballot(near);
+  }
+  if (c.flags & 2)
+    for (int half = 0; half < 2 && half * GQ_WAVE < nbox; half++) { /* wave-uniform */
+      const int b = half * GQ_WAVE + lane;
+      bool near = false;
+      if (b < nbox) {
+        const V3 v = v3((float)((double)M.box[b].pos[0] - co[0]), (float)((double)M.box[b].pos[1] - co[1]), (float)((double)M.box[b].pos[2] - co[2]));
+        near = cam_cone_sphere(matTvec(Rc, v), M.box[b].rad, ax, ca, sa, c.znear, c.zfar);
+      }
+      box[half] = ballot(near);
+    }
+  /* cast, lane = pixel.  The shaded pass also keeps what the winner is: slot (robot geom g / world box b / height-field triangle) and part
+   * (the surface of the primitive the entry is on); its normal is formed once, after the walk.  The depth-only pass never reads them. */
+  float best = c.zfar;
+  int id = -1, slot = 0, part = 0;
+  const V3 dw = matvec(Rc, d);   /* the ray in world axes */
+  if (c.flags & 2) {
+    if (dw.z < 0.0f && co[2] >= 0.0) { /* the floor: a one-sided plane, hit from above */
+      const float t = (float)(-co[2] / (double)dw.z);
+      if (t >= c.znear && t <= best) { best = t; id = c.ngeom; }
+    }
+    const float dv[3] = {dw.x, dw.y, dw.z};
+    for (int half = 0; half < 2; half++)
+      for (uint64_t todo = box[half]; todo; todo &= todo - 1) { /* wave-uniform */
+        const int b = half * GQ_WAVE + ffs64(todo);
+        const float rv[3] = {(float)(co[0] - (double)M.box[b].pos[0]), (float)(co[1] - (double)M.box[b].pos[1]), (float)(co[2] - (double)M.box[b].pos[2])};
+        float tin = -1e30f, tout = 1e30f;
+        int ax_in = 0;
+        if (ray_box(M.box[b], rv, dv, tin, tout, SHADE ? &ax_in : nullptr) && tin >= c.znear && tin <= best) {
+          best = tin; id = c.ngeom + 1 + b;
+          if (SHADE) { slot = b; part = ax_in; }
+        }
+      }
+    if (M.hf_nrow > 0) { /* fp64: the walk runs in the field's own coordinates */
+      const double ol[3] = {co[0] - (double)M.hf_pos[0], co[1] - (double)M.hf_pos[1], co[2] - (double)M.hf_pos[2]}, dd[3] = {dw.x, dw.y, dw.z};
+      int tri = 0;
+      const double t = ray_hfield(M, ol, dd, (double)c.znear, SHADE ? &tri : nullptr);
+      if (t >= 0.0 && t <= (double)best) {
+        best = (float)t; id = c.ngeom + 1 + nbox;
+        if (SHADE) slot = tri;
+      }
+    }
+  }
+  for (uint64_t todo = rob; todo; todo &= todo - 1) { /* wave-uniform */
+    const int g = ffs64(todo);
+    int pg = 0;
+    const float th = cam_rob_cast<SHADE>(M, c, rec + 12 + 12 * g, g, d, pg);
+    if (th >= c.znear && th <= best) {
+      best = th; id = M.item_geomid[g];
+      if (SHADE) { slot = g; part = pg; }
+    }
+  }
+  const size_t px = ((size_t)env * H + row) * W + col;
+  if (valid) {
+    c.depth[px] = best;
+    if (c.seg) c.seg[px] = id;
+  }
+  if constexpr (SHADE) {
+    float rgb[3];
+    cam_shade(M, c, *sh, rec, Rc, co, d, dw, best, id, slot, part, nbox, rgb);
+    if constexpr (LAYERS) cam_layers(M, c, *sh, *ly, Rc, co, d, ax, ca, sa, best, env, rgb);
+    const uint32_t rgba = cam_byte(rgb[0]) | cam_byte(rgb[1]) << 8 | cam_byte(rgb[2]) << 16 | 0xff000000u;
+    if (valid) sh->rgba[px] = rgba;
   }
 }
 

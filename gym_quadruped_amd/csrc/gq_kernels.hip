@@ -275,15 +275,7 @@ __global__ void __launch_bounds__(GQ_WAVE) jac_kernel(const GqDevModel* model, c
   if (lane == 0) W.tk_T = nullptr;
 #endif
   const GQ_MODEL GqDevModel& m = *mptr(model);
-  double bxy = 0.0;
-  if (lane < 19) {
-    const double q = qpos[(size_t)env * 19 + lane];
-    if (lane < 2) W.bxy[lane] = q;
-    else if (lane == 2) W.basez = (float)q;
-    else if (lane < 7) W.qb[lane - 3] = (float)q;
-    else W.qj[lane - 7] = (float)q;
-  }
-  (void)bxy;
+  load_qpos_row(W, qpos + (size_t)env * 19, lane);
   wave_barrier();
   stage_kinematics(W, link_fetch(m, lane));
   /* the point relative to the base x/y (f64 first, like everything else) */
@@ -488,22 +480,15 @@ extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPd
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream) {
   hipLaunchKernelGGL(gq::jac_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, qpos, body, point, jacp, jacr);
 }
-extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, int n_envs, hipStream_t stream) {
-  const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
+/* s: null for depth / segmentation only (gq_camera); l: null without layers (gq_camera_shaded), needs s */
+extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs, hipStream_t stream) {
+  const dim3 grid(((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE), n_envs);
+  const GQ_GLOBAL GqDevModel* gm = (const GQ_GLOBAL GqDevModel*)model;
   hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
-  hipLaunchKernelGGL(gq::camera_pixel_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c);
-}
-extern "C" void gq_launch_camera_shaded(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, int n_envs, hipStream_t stream) {
-  const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
-  hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
-  hipLaunchKernelGGL(gq::camera_shade_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c, *s);
-}
-extern "C" void gq_launch_camera_layered(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs,
-                                         hipStream_t stream) {
-  const int tiles = ((c->width + GQ_CAM_TILE - 1) / GQ_CAM_TILE) * ((c->height + GQ_CAM_TILE - 1) / GQ_CAM_TILE);
-  hipLaunchKernelGGL(gq::camera_pose_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, *c);
-  if (l->n_ghost > 0) hipLaunchKernelGGL(gq::camera_ghost_kernel, dim3(l->n_ghost, n_envs), dim3(GQ_WAVE), 0, stream, model, *c, *l);
-  hipLaunchKernelGGL(gq::camera_layer_kernel, dim3(tiles, n_envs), dim3(GQ_WAVE), 0, stream, (const GQ_GLOBAL GqDevModel*)model, *c, *s, *l);
+  if (l && l->n_ghost > 0) hipLaunchKernelGGL(gq::camera_ghost_kernel, dim3(l->n_ghost, n_envs), dim3(GQ_WAVE), 0, stream, model, *c, *l);
+  if (l) hipLaunchKernelGGL(gq::camera_layer_kernel, grid, dim3(GQ_WAVE), 0, stream, gm, *c, *s, *l);
+  else if (s) hipLaunchKernelGGL(gq::camera_shade_kernel, grid, dim3(GQ_WAVE), 0, stream, gm, *c, *s);
+  else hipLaunchKernelGGL(gq::camera_pixel_kernel, grid, dim3(GQ_WAVE), 0, stream, gm, *c);
 }
 extern "C" void gq_launch_ray(const GQ_GLOBAL GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream) {
   hipLaunchKernelGGL(gq::ray_kernel, dim3((total + 127) / 128), dim3(128), 0, stream, model, origin, dir, total, dist, geom);

@@ -77,6 +77,18 @@ __device__ inline Q4 stage_kinematics(WaveMem& W, const GqDevLinkRec L) { /* (by
   return qbase;
 }
 
+/* what stage_kinematics reads, from one qpos row outside the step (gq_jac, the camera's pose passes): its first 19 entries into the
+ * wave's LDS, lane = entry; a wave_barrier() follows at the caller */
+__device__ __forceinline__ void load_qpos_row(WaveMem& W, const double* qrow, const int lane) {
+  if (lane < 19) {
+    const double q = qrow[lane];
+    if (lane < 2) W.bxy[lane] = q;
+    else if (lane == 2) W.basez = (float)q;
+    else if (lane < 7) W.qb[lane - 3] = (float)q;
+    else W.qj[lane - 7] = (float)q;
+  }
+}
+
 /* S6 (mj_collision, floor plane z = 0): foot sphere centres and, per link geom, the deepest cloud vertex.
  * calf_only restricts the scan to geoms of the calf bodies (reset lift loop, quadruped_env.py:376-388). */
 /* floor pass scratch in the J block (idle between S5 and the world-box / self-collision passes of S6): per link geom up to two further
