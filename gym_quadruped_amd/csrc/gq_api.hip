@@ -18,7 +18,7 @@
 #include <gq_device.h>
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
-#include "gq_camera.h"
+#include "gq_camera_call.h"
 
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
@@ -825,7 +825,8 @@ static int camera_shade(const GqCamShade* in, gq::CamShade& s) {
 }
 
 /* gq_camera (mode 0), gq_camera_shaded (1), gq_camera_layered (2): the checks in the order layers, shade, rgba, camera (fn: the entry
- * point's name for the error text), the call records, the batch's scratch blocks on first use, the launch */
+ * point's name for the error text), the call record (gq_camera_call.h, shared with the tests' host emulator), the batch's scratch blocks on first
+ * use, the launch */
 static int camera_run(const char* fn, const int mode, GqBatch* b, const double* qpos, int qpos_stride, int body, const double pos[3], const double quat[4],
                       float fovy_deg, int width, int height, float znear, float zfar, int flags, const float* hull_planes, const int32_t* hull_plane_adr,
                       float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, const GqCamShade* shade, uint8_t* rgba, const GqCamLayers* layers,
@@ -856,31 +857,17 @@ static int camera_run(const char* fn, const int mode, GqBatch* b, const double* 
   if (!(znear > 0.0f && zfar > znear)) { SET_ERR("%s: need 0 < znear < zfar (got %g, %g)", fn, (double)znear, (double)zfar); return GQ_EINVAL; }
   if (flags & ~(GQ_CAM_ROBOT | GQ_CAM_SCENE | GQ_CAM_TRACK)) { SET_ERR("%s: unknown flags 0x%x", fn, flags); return GQ_EINVAL; }
   if ((flags & GQ_CAM_TRACK) && body == 0) { SET_ERR("%s: GQ_CAM_TRACK needs a body camera (body > 0)", fn); return GQ_EINVAL; }
-  const double qn = std::sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
-  if (!(qn > 0.0)) { SET_ERR("%s: zero quaternion", fn); return GQ_EINVAL; }
   GqModel* m = b->model;
   gq::CamCall c{};
-  for (int i = 0; i < m->host.nlg; i++) {
-    if (m->host.lg[i].ptype != 0) continue;
-    if (!hull_planes || !hull_plane_adr) { SET_ERR("%s: the model has hull geoms and no face planes were passed", fn); return GQ_EINVAL; }
-    const int cl = m->lg_cloud[i];
-    if (cl < 0 || cl >= m->ncloud) { SET_ERR("%s: link geom %d has no cloud", fn, i); return GQ_EINVAL; }
-    c.plane_adr[i] = hull_plane_adr[cl]; c.plane_num[i] = hull_plane_adr[cl + 1] - hull_plane_adr[cl];
-    if (c.plane_adr[i] < 0 || c.plane_num[i] < 4) { SET_ERR("%s: cloud %d has %d face planes (a hull has at least 4)", fn, cl, c.plane_num[i]); return GQ_EINVAL; }
-  }
+  if (gq::cam_fill_call(c, fn, m->host, m->lg_cloud, m->ncloud, m->ngeom, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar, flags,
+                        hull_planes, hull_plane_adr, depth, seg, cam_xpos, cam_xmat, g_err, sizeof g_err)) return GQ_EINVAL;
   DeviceGuard guard(m->device);
   const int n = b->host.n_envs;
   if (!b->cam_rec) {
     HIP_TRY(hipMalloc(&b->cam_rec, sizeof(float) * GQ_CAM_REC * (size_t)n));
     HIP_TRY(hipMalloc(&b->cam_pos, sizeof(double) * 3 * (size_t)n));
   }
-  const double th = std::tan(0.5 * (double)fovy_deg * 3.14159265358979323846 / 180.0);
-  c.qpos = qpos; c.qpos_stride = qpos_stride; c.body = body;
-  for (int k = 0; k < 3; k++) c.pos[k] = pos[k];
-  for (int k = 0; k < 4; k++) c.quat[k] = (float)(quat[k] / qn);
-  c.width = width; c.height = height; c.flags = flags; c.ngeom = m->ngeom;
-  c.tan_x = (float)(th * width / height); c.tan_y = (float)th; c.znear = znear; c.zfar = zfar;
-  c.planes = hull_planes; c.rec = b->cam_rec; c.cpos = b->cam_pos; c.xpos_out = cam_xpos; c.xmat_out = cam_xmat; c.depth = depth; c.seg = seg;
+  c.rec = b->cam_rec; c.cpos = b->cam_pos;
   gq::CamLayers l{};
   if (mode >= 2) {
     if (layers->n_ghost > b->cam_nghost) {

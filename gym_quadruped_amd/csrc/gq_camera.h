@@ -159,9 +159,10 @@ __device__ inline T ray_hfield(const Mref& M, const T* ol, const T* d, const T t
   return T(-1);
 }
 
-/* ---- robot geoms, in the geom frame (o, d: the ray there).  Each returns the entry parameter (front face), or -1 when the ray starts
- * inside or misses; the caller keeps entries in [znear, best].  part: which surface the entry is on (cam_shade); callers that do not
- * shade pass a local they never read. */
+/* ---- robot geoms, in the geom frame (o, d: the ray there).  Each returns the entry parameter (front face), or -1 when the ray misses.
+ * A ray that starts inside gets -1 from the sphere and the capsule, and from the cylinder, the hull and the cone the entry behind the
+ * origin (negative); so does a ray that points away from the shape.  The caller keeps entries in [znear, best], which drops both.
+ * part: which surface the entry is on (cam_shade); callers that do not shade pass a local they never read. */
 __device__ inline float cam_sphere(V3 o, V3 d, float r) {
   const float a = dot(d, d), b = dot(o, d), c = dot(o, o) - r * r;
   if (c <= 0.0f) return -1.0f;

@@ -5,11 +5,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import marshalled
+import camera_caster as cc
+from camera_caster import ZFAR, Caster, _camera_pose, _oracle_poses, _pixel_dirs, _qmat   # noqa: F401  (the reference: other test modules take it from here)
 
 pytestmark = pytest.mark.gpu
-
-ZFAR = 10.0
 
 
 def _env(robot, n, scene='flat', seed=0, steps=30):
@@ -21,141 +20,6 @@ def _env(robot, n, scene='flat', seed=0, steps=30):
         env.step(torch.randn(n, 12, generator=g, device='cuda:0') * 5.0)
     torch.cuda.synchronize()
     return env
-
-
-def _oracle_poses(robot, qpos):
-    from oracle.oracle import Oracle
-    o = Oracle(marshalled(robot, solver=1))
-    out = []
-    for q in qpos:
-        o.set_state(q, np.zeros(18), np.zeros(18), np.zeros(18)); o.forward(np.zeros(12), stage=1)
-        out.append((o.geom_xpos.copy(), o.geom_xmat.copy(), o.xpos.copy(), o.xmat.copy()))
-    return out
-
-
-def _qmat(q):
-    from gym_quadruped_amd.mjcf import quat_to_mat
-    return quat_to_mat(np.asarray(q, np.float64))
-
-
-def _pixel_dirs(W, H, fovy, pix):
-    t = np.tan(np.deg2rad(fovy) / 2)
-    r, c = pix // W, pix % W
-    return np.stack([(2 * (c + 0.5) / W - 1) * t * W / H, (1 - 2 * (r + 0.5) / H) * t, -np.ones(len(pix))], 1)
-
-
-class Caster:
-    """fp64 reference: nearest front-face entry in [znear, zfar] (robot geoms from the oracle's pose, floor, boxes, height field)."""
-
-    def __init__(self, env):
-        from gym_quadruped_amd.cabi import hull_planes
-        from scipy.spatial.transform import Rotation
-        md = env.mjModel
-        self.md, self.ngeom = md, md.ngeom
-        self.boxes = env.scene_desc.get('boxes') or []
-        self.Rb = [Rotation.from_quat(np.asarray(b['quat']), scalar_first=True).as_matrix() for b in self.boxes]
-        self.planes, self.adr = hull_planes(md)
-        self.robot = [g for g in range(md.ngeom) if md.geom_cloudid[g] >= 0 and md.geom_bodyid[g] > 0]
-        hf = env.scene_desc.get('hfield')
-        self.tris = None
-        if hf is not None:
-            data = np.asarray(hf['data'], np.float64) * hf['size'][2]; sx, sy = hf['size'][0], hf['size'][1]; pz = hf.get('pos', (0, 0, 0))[2]
-            nr, nc = data.shape
-            xs, ys = np.linspace(-sx, sx, nc), np.linspace(-sy, sy, nr)
-            P = np.stack([np.tile(xs, (nr, 1)), np.tile(ys[:, None], (1, nc)), data + pz], -1)
-            A, B, C, D = P[:-1, :-1], P[:-1, 1:], P[1:, :-1], P[1:, 1:]
-            self.tris = np.concatenate([np.stack([A, B, C], -2).reshape(-1, 3, 3), np.stack([D, C, B], -2).reshape(-1, 3, 3)])
-
-    @staticmethod
-    def _slab(o, d, s):
-        with np.errstate(divide='ignore', invalid='ignore'):
-            t0, t1 = (-s - o) / d, (s - o) / d
-        lo, hi = np.minimum(t0, t1), np.maximum(t0, t1)
-        par = np.abs(d) < 1e-14
-        lo = np.where(par, np.where(np.abs(o) <= s, -np.inf, np.inf), lo); hi = np.where(par, np.where(np.abs(o) <= s, np.inf, -np.inf), hi)
-        tin, tout = lo.max(1), hi.min(1)
-        return np.where(tin <= tout, tin, np.nan)
-
-    @staticmethod
-    def _sphere(o, d, r):
-        o = np.broadcast_to(o, d.shape)
-        a, b, c = (d * d).sum(1), (o * d).sum(1), (o * o).sum(1) - r * r
-        disc = b * b - a * c
-        t = (-b - np.sqrt(np.maximum(disc, 0))) / a
-        return np.where((c > 0) & (disc >= 0), t, np.nan)
-
-    @classmethod
-    def _cyl(cls, o, d, r, h):
-        with np.errstate(divide='ignore', invalid='ignore'):
-            z0, z1 = (-h - o[:, 2]) / d[:, 2], (h - o[:, 2]) / d[:, 2]
-            a, b, c = d[:, 0] ** 2 + d[:, 1] ** 2, o[:, 0] * d[:, 0] + o[:, 1] * d[:, 1], o[:, 0] ** 2 + o[:, 1] ** 2 - r * r
-            disc = b * b - a * c
-            s = np.sqrt(np.maximum(disc, 0))
-            c0, c1 = (-b - s) / a, (-b + s) / a
-        tin, tout = np.maximum(np.minimum(z0, z1), c0), np.minimum(np.maximum(z0, z1), c1)
-        return np.where((disc >= 0) & (tin <= tout), tin, np.nan)
-
-    def cast(self, co, Dw, pose, znear, zfar, flags=3):
-        n = len(Dw)
-        best, seg = np.full(n, zfar), np.full(n, -1)
-
-        def take(t, ids):
-            ok = np.isfinite(t) & (t >= znear) & (t <= best)
-            best[ok] = t[ok]; seg[ok] = np.broadcast_to(ids, n)[ok]
-        if flags & 2:
-            with np.errstate(divide='ignore', invalid='ignore'):
-                take(np.where((Dw[:, 2] < 0) & (co[2] >= 0), -co[2] / Dw[:, 2], np.nan), self.ngeom)
-            for b, (bx, Rm) in enumerate(zip(self.boxes, self.Rb)):
-                take(self._slab((co - np.asarray(bx['pos'])) @ Rm, Dw @ Rm, np.asarray(bx['size'])), self.ngeom + 1 + b)
-            if self.tris is not None:
-                e1, e2, a0 = self.tris[:, 1] - self.tris[:, 0], self.tris[:, 2] - self.tris[:, 0], self.tris[:, 0]
-                tv = co - a0
-                qv = np.cross(tv, e1)
-                for i0 in range(0, n, 64):
-                    d_ = Dw[i0:i0 + 64]
-                    pv = np.cross(d_[:, None, :], e2[None])
-                    det = (e1[None] * pv).sum(-1)
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        inv = 1.0 / det; u = (tv[None] * pv).sum(-1) * inv; v = (d_ @ qv.T) * inv; t = (e2 * qv).sum(-1)[None] * inv
-                    ok = (np.abs(det) > 1e-14) & (u >= -1e-9) & (v >= -1e-9) & (u + v <= 1 + 1e-9) & (t >= znear)
-                    tt = np.where(ok, t, np.inf).min(1)
-                    sl = slice(i0, i0 + 64)
-                    good = np.isfinite(tt) & (tt <= best[sl])
-                    best[sl][good] = tt[good]; seg[sl][good] = self.ngeom + 1 + len(self.boxes)
-        if flags & 1:
-            gx, gm = pose[0], pose[1]
-            md = self.md
-            for g in self.robot:
-                o, d = (co - gx[g]) @ gm[g], Dw @ gm[g]
-                typ, s = int(md.geom_type[g]), md.geom_size[g]
-                if typ == 2:
-                    t = self._sphere(o, d, s[0])
-                elif typ == 3:
-                    zc = np.clip(o[2], -s[1], s[1])
-                    if o[0] ** 2 + o[1] ** 2 + (o[2] - zc) ** 2 <= s[0] ** 2:
-                        continue
-                    ts = [self._cyl(o[None].repeat(n, 0), d, s[0], s[1]), self._sphere(o - [0, 0, s[1]], d, s[0]), self._sphere(o + [0, 0, s[1]], d, s[0])]
-                    ts = [np.where(x > 0, x, np.inf) for x in ts]
-                    t = np.minimum(np.minimum(ts[0], ts[1]), ts[2]); t[~np.isfinite(t)] = np.nan
-                elif typ == 5:
-                    t = self._cyl(o[None].repeat(n, 0), d, s[0], s[1])
-                elif typ == 6:
-                    t = self._slab(o[None].repeat(n, 0), d, s)
-                else:
-                    cl = int(md.geom_cloudid[g]); P = self.planes[self.adr[cl]:self.adr[cl + 1]]
-                    den, num = d @ P[:, :3].T, P[:, 3] - P[:, :3] @ o
-                    with np.errstate(divide='ignore', invalid='ignore'):
-                        tk = num / den
-                    tin = np.where(den < 0, tk, -np.inf).max(1); tout = np.where(den > 0, tk, np.inf).min(1)
-                    miss = ((np.abs(den) < 1e-20) & (num < 0)).any(1)
-                    t = np.where(~miss & (tin <= tout), tin, np.nan)
-                take(t, g)
-        return best, seg
-
-
-def _camera_pose(pose, body, pos, quat):
-    xpos, xmat = pose[2], pose[3]
-    return xpos[body] + xmat[body] @ pos, xmat[body] @ _qmat(quat)
 
 
 CASES = [('aliengo', 'flat', 64, 64), ('aliengo', 'stairs', 48, 64), ('aliengo', 'random_boxes', 64, 64), ('aliengo', 'perlin', 48, 64),
@@ -212,6 +76,57 @@ def test_camera_matches_numpy_caster(robot, scene, H, W):
         assert hull_px >= 0.1 * tot_px, hull_px / tot_px
     if scene == 'perlin':
         assert (seg == env.mjModel.ngeom + 1).any()   # the height field is seen
+
+
+def _render_case(case, rgb=False):
+    """the shared case (camera_caster.CASES) on the device: the env of its robot and scene, its camera by body / pos / quat / fovy, its
+    CPU-made qpos rows through Camera.render(qpos=)"""
+    from gym_quadruped_amd.cabi import GQ_CAM_TRACK
+    from gym_quadruped_amd.quadruped_env import QuadrupedEnv
+    from gym_quadruped_amd.sensors import Camera
+    qpos, cam, _, _, _ = cc.case_reference(case)
+    env = QuadrupedEnv(case.robot, num_envs=case.n, device='cuda:0', scene=case.scene, solver='newton', state_obs_names=('qpos', 'qvel'), seed=0)
+    env.reset(seed=0)
+    c = Camera(case.W, case.H, 30, env.robot_model, env.sim_data, body=cam['body'], pos=cam['pos'], quat=cam['quat'], fovy=cam['fovy'], znear=cc.ZNEAR,
+               zfar=ZFAR, track=cam['track'], rgb=rgb)
+    c._flags = case.flags | (GQ_CAM_TRACK if cam['track'] else 0)   # robot only / scene only: gq_camera's flags, which Camera always sets to both
+    c.render(qpos=torch.as_tensor(qpos, dtype=torch.float64, device='cuda:0'))
+    torch.cuda.synchronize()
+    return env, c
+
+
+def test_shared_cases_cover_what_they_claim():
+    cc.check_coverage()
+
+
+@pytest.mark.parametrize('case', cc.CASES, ids=repr)
+def test_camera_matches_numpy_caster_shared_cases(case):
+    """every robot of the registry, partial tiles, robot-only and scene-only flags, a wide fovy, GQ_CAM_TRACK, a far base and the second
+    half of the box walk: the cases and the rule test_camera_emulated.py holds the emulator to, from the same qpos rows"""
+    env, cam = _render_case(case)
+    depth, seg = cam._depth_plane.cpu().numpy(), cam._seg.cpu().numpy()
+    worst, nbad = cc.check_case(case, depth, seg, cam._xpos.cpu().numpy(), cam._xmat.cpu().numpy())
+    print(f'{case}: worst depth error {worst:.3f} of the tolerance, {nbad} ids differ')
+    if case.scene == 'random_boxes':
+        assert (cc.box_ids_seen(case, seg) >= 64).any()
+    if case.flags == 1:   # robot only: no floor, box or height-field id
+        assert (seg < env.mjModel.ngeom).all()
+    if case.flags == 2:   # scene only: no robot geom id
+        assert not ((seg >= 0) & (seg < env.mjModel.ngeom)).any()
+    env.close()
+
+
+def test_shaded_depth_and_seg_equal_depth_only_on_partial_tiles():
+    """gq_camera_shaded's depth and segmentation are gq_camera's bit for bit at 13 x 20 (both edges partial) on a cylinder robot"""
+    case = [c for c in cc.CASES if c.robot == 'b2' and (c.H, c.W) == (13, 20)][0]
+    assert 5 in cc.type_shares(case) and cc.type_shares(case)[5] >= 0.02
+    env, plain = _render_case(case)
+    d0, s0 = plain._depth_plane.clone(), plain._seg.clone()
+    env.close()
+    env, shaded = _render_case(case, rgb=True)
+    assert torch.equal(shaded._depth_plane, d0) and torch.equal(shaded._seg, s0)
+    assert bool((shaded._rgba[..., 3] == 255).all())
+    env.close()
 
 
 def test_camera_sky_and_znear():
