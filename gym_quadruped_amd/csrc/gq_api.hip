@@ -18,6 +18,7 @@
 #include <gq_device.h>
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
+#include "gq_step_call.h"
 #include "gq_camera_call.h"
 
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
@@ -49,29 +50,15 @@ struct GqModel {
   float *vx, *vy, *vz;
   float* hf;            /* device elevations of the scene's height field (NULL: none) */
   int nvert;
-  gq::Scene scene;      /* the step-kernel variants the model runs (model_scene) */
+  gq::Scene scene;      /* the step-kernel variants the model runs (gq_step_call.h model_scene) */
   int ngeom, ncloud;
   int32_t lg_cloud[GQ_MAXLG]; /* GqModelDesc cloud of lg[i] (gq_camera's face-plane table is indexed by cloud) */
 };
-/* world boxes / height field: the world scenes, split by whether the robot has sphere / capsule / box link geoms (exact pair routines
- * compiled in; gq_step_body.h PRIM); flat: the self-collision stage runs for a model with self-collision pairs */
-static gq::Scene model_scene(const GqDevModel& h) {
-  if (h.nbox > 0 || h.hf_nrow > 0) {
-    /* lg[] is indexed by link geom (item[] is in contact order: feet and link geoms interleaved by geom id) */
-    for (int g = 0; g < h.nlg; g++) { const int t = h.lg[g].ptype; if (t == 2 || t == 3 || t == 6) return gq::SCENE_WORLD_PRIM; }
-    return gq::SCENE_WORLD_HULL;
-  }
-  return h.nsp > 0 ? gq::SCENE_FLAT_SELF : gq::SCENE_FLAT;
-}
 struct GqBatch {
   GqModel* model;
   GqDevBatch host;
-  GqDevBatch* dev;
+  gq::BatchPtrs p;    /* device: the batch block and the scratch rows this batch owns, the model's blocks, the rows callers registered */
   float* debug;       /* device, debug_envs * GQ_DBG_SIZE floats (lazily allocated) */
-  float* friction_next; /* device [N]: friction drawn by reset, committed after the reset step */
-  uint8_t* pending;     /* device [N]: next-step auto-reset flags */
-  uint8_t* lift_pending;/* device [N]: reset kernel -> the reset's own step: lift loop still due */
-  uint8_t* load_hint;   /* device [N]: per-env solver load of the previous step (scheduling hint of the step kernel) */
   int32_t* xq;          /* device: convex pair exchange (gq_exchange.h) - models with convex self pairs only, else NULL */
   int xq_slots; bool xq_on;
   float* sepc;          /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
@@ -86,19 +73,14 @@ struct GqBatch {
   gq::FusedArgs shadow;
   gq::FusedArgs* staging;   /* pinned host, GQ_ARG_SLOTS entries */
   int staging_next;
-  /* the batch constants (b->dev): a change made by gq_batch_set_resampling travels with the NEXT launch, on that launch's
+  /* the batch constants (p.batch): a change made by gq_batch_set_resampling travels with the NEXT launch, on that launch's
    * stream, through its own pinned ring - ordered against everything the caller has queued there */
   GqDevBatch* batch_staging; /* pinned host, GQ_ARG_SLOTS entries */
   int batch_staging_next;
   bool batch_dirty;
   bool shadow_valid;
-  float* imu_bias;      /* caller-owned device [N][6], set by gq_batch_set_imu */
-  float* heightmap;     /* caller-owned device [N][rows * cols][3], set by gq_batch_set_heightmap (NULL: off) */
   hipStream_t shard_stream[8]; hipEvent_t shard_event[8]; hipEvent_t fork_event; int n_shard_streams; /* gq_rollout */
-  int32_t* h9;          /* caller-owned device [N][6] resampling counters, set by gq_batch_set_resampling */
-  float* ext_dist;      /* caller-owned device [N][6] */
   int debug_cap;
-  float* dyn_out; float* con_out;  /* caller-owned device rows registered with gq_batch_set_outputs */
   /* closed-loop persistent rollout (gq_rollout_closed): mailboxes, ready queues, the policy's stream; allocated on first use */
   struct {
     gq::MailboxDev host;      /* what the device block holds */
@@ -155,9 +137,9 @@ int gq_model_create(const GqModelDesc* desc, int device, GqModel** out) {
   if (!m) return GQ_ENOMEM;
   std::vector<float> vx, vy, vz;
   if (gq_build_dev_model(desc, &m->host, &vx, &vy, &vz, g_err, sizeof g_err)) { delete m; return GQ_EINVAL; }
-  m->device = device; m->nvert = (int)vx.size(); m->scene = model_scene(m->host);
+  m->device = device; m->nvert = (int)vx.size(); m->scene = gq::model_scene(m->host);
   m->ngeom = desc->ngeom; m->ncloud = desc->ncloud;
-  for (int i = 0; i < m->host.nlg; i++) m->lg_cloud[i] = desc->geom_cloudid[m->host.item_geomid[4 + i]];
+  gq::cam_lg_cloud(m->lg_cloud, m->host, desc);
   DeviceGuard guard(device);
   if (m->host.hf_nrow > 0) {
     std::vector<float> hf;
@@ -192,18 +174,19 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
   GqBatch* b = new (std::nothrow) GqBatch();   /* value-initialised: every pointer starts NULL */
   if (!b) return GQ_ENOMEM;
   b->model = m;
+  b->p.model = m->dev; b->p.vx = m->vx; b->p.vy = m->vy; b->p.vz = m->vz;
   if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &b->host, g_err, sizeof g_err)) { delete b; return GQ_EINVAL; }
   DeviceGuard guard(m->device);
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->dev, sizeof(GqDevBatch)), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemcpy(b->dev, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->friction_next, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->friction_next, 0, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->pending, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->pending, 0, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->lift_pending, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->lift_pending, 0, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->load_hint, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->load_hint, 0, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.batch, sizeof(GqDevBatch)), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.friction_next, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMemset(b->p.friction_next, 0, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.pending, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMemset(b->p.pending, 0, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.lift_pending, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMemset(b->p.lift_pending, 0, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.load_hint, (size_t)n_envs), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMemset(b->p.load_hint, 0, (size_t)n_envs), gq_batch_destroy(b));
   if (m->host.ncvx_self > 0) { /* the pair exchange: two slots per env, rounded up to a power of two (an env publishes what it has beyond its first pair - 0.45 pairs
                                 * per env-step on the benchmark's states: the table stays sparse, which is what its hashing wants) */
     int slots = 256;
@@ -217,7 +200,7 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
     HIP_TRY_OR_DESTROY(hipMalloc(&b->sepc, (size_t)n_envs * m->host.ncvx_self * 3 * sizeof(float)), gq_batch_destroy(b));
     HIP_TRY_OR_DESTROY(hipMemset(b->sepc, 0, (size_t)n_envs * m->host.ncvx_self * 3 * sizeof(float)), gq_batch_destroy(b));
     b->host.sepc = b->sepc; b->host.sepc_stride = m->host.ncvx_self * 3;
-    HIP_TRY_OR_DESTROY(hipMemcpy(b->dev, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
+    HIP_TRY_OR_DESTROY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
   }
   /* profiling knobs of development builds (tools/dev_build.sh defines GQ_DEV_KNOBS; tools/stage_insts.sh, stage_cuts.py): the product library
    * reads no environment variable (tests/test_host_and_abi.py checks its objects for getenv) */
@@ -253,7 +236,7 @@ static void mailbox_free(GqBatch* b) {
 int gq_batch_destroy(GqBatch* b) {
   if (!b) return GQ_OK;
   DeviceGuard guard(b->model->device);
-  hipFree(b->dev); hipFree(b->friction_next); hipFree(b->pending); hipFree(b->lift_pending); hipFree(b->load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
+  hipFree(b->p.batch); hipFree(b->p.friction_next); hipFree(b->p.pending); hipFree(b->p.lift_pending); hipFree(b->p.load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
   hipFree(b->cam_rec); hipFree(b->cam_pos); hipFree(b->cam_grec);
   if (b->staging) hipHostFree(b->staging);
   if (b->batch_staging) hipHostFree(b->batch_staging);
@@ -270,7 +253,7 @@ int gq_batch_obs_dim(const GqBatch* b) { return b ? b->host.obs_dim : GQ_EINVAL;
 int gq_batch_set_imu(GqBatch* b, const GqImuCfg* cfg, float* bias_state) {
   if (!b || !cfg || !bias_state) { SET_ERR("gq_batch_set_imu: null argument"); return GQ_EINVAL; }
   gq_fill_imu(&b->host, cfg);
-  b->imu_bias = bias_state;
+  b->p.imu_bias = bias_state;
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
   return GQ_OK;
 }
@@ -286,10 +269,10 @@ int gq_batch_set_pair_exchange(GqBatch* b, int on) {
 
 int gq_batch_set_heightmap(GqBatch* b, int rows, int cols, float dist_x, float dist_y, float* out) {
   if (!b) { SET_ERR("gq_batch_set_heightmap: null batch"); return GQ_EINVAL; }
-  if (!out) { b->heightmap = nullptr; b->host.hm_rows = b->host.hm_cols = 0; b->batch_dirty = true; return GQ_OK; }
+  if (!out) { b->p.heightmap = nullptr; b->host.hm_rows = b->host.hm_cols = 0; b->batch_dirty = true; return GQ_OK; }
   if (rows <= 0 || cols <= 0 || rows > 4096 || cols > 4096 || rows * cols > 4096 || !(dist_x > 0.0f) || !(dist_y > 0.0f)) { SET_ERR("gq_batch_set_heightmap: bad grid (%d x %d cells of %g x %g m)", rows, cols, (double)dist_x, (double)dist_y); return GQ_EINVAL; }
   if (!gq::scene_boxes(b->model->scene)) { SET_ERR("gq_batch_set_heightmap: the scene has no world boxes / height field - every ray ends on the floor plane; use gq_heightmap"); return GQ_EINVAL; }
-  b->heightmap = out;
+  b->p.heightmap = out;
   b->host.hm_rows = rows; b->host.hm_cols = cols; b->host.hm_dx = dist_x; b->host.hm_dy = dist_y;
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
   return GQ_OK;
@@ -298,7 +281,7 @@ int gq_batch_set_heightmap(GqBatch* b, int rows, int cols, float dist_x, float d
 int gq_batch_set_resampling(GqBatch* b, const GqResampleCfg* cfg, const GqResetCfg* cmd_cfg, int32_t* counters, float* ext_dist) {
   if (!b) { SET_ERR("gq_batch_set_resampling: null batch"); return GQ_EINVAL; }
   GqDevBatch& h = b->host;
-  if (!cfg) { h.rs_cmd_reset = 0; h.rs_dist_reset = 0; b->h9 = nullptr; b->ext_dist = nullptr; }
+  if (!cfg) { h.rs_cmd_reset = 0; h.rs_dist_reset = 0; b->p.h9 = nullptr; b->p.ext_dist = nullptr; }
   else {
     if (!counters || ((cfg->cmd_reset != 0) && !cmd_cfg) || ((cfg->dist_reset != 0) && !ext_dist)) {
       SET_ERR("gq_batch_set_resampling: counters (and the command knobs / wrench tensor of the enabled parts) are required"); return GQ_EINVAL;
@@ -310,7 +293,7 @@ int gq_batch_set_resampling(GqBatch* b, const GqResampleCfg* cfg, const GqResetC
       h.rs_cmd_forward = cmd_cfg->cmd_forward; h.rs_cmd_random = cmd_cfg->cmd_random; h.rs_cmd_rotate = cmd_cfg->cmd_rotate;
     }
     h.rs_seed_lo = (uint32_t)(cfg->seed & 0xffffffffu); h.rs_seed_hi = (uint32_t)(cfg->seed >> 32);
-    b->h9 = counters; b->ext_dist = ext_dist;
+    b->p.h9 = counters; b->p.ext_dist = ext_dist;
   }
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
   return GQ_OK;
@@ -318,17 +301,17 @@ int gq_batch_set_resampling(GqBatch* b, const GqResampleCfg* cfg, const GqResetC
 
 int gq_batch_set_outputs(GqBatch* b, float* dyn, float* contacts) {
   if (!b) { SET_ERR("gq_batch_set_outputs: null batch"); return GQ_EINVAL; }
-  b->dyn_out = dyn; b->con_out = contacts;   /* picked up by the next launch's argument block (ensure_args) */
+  b->p.dyn = dyn; b->p.contacts = contacts;   /* picked up by the next launch's argument block (ensure_args) */
   return GQ_OK;
 }
 
 int gq_contact_force(GqBatch* b, int id, float* result, void* hip_stream) {
   if (!b || !result) { SET_ERR("gq_contact_force: null argument"); return GQ_EINVAL; }
-  if (!b->con_out) { SET_ERR("gq_contact_force: no contact rows registered (gq_batch_set_outputs)"); return GQ_EINVAL; }
+  if (!b->p.contacts) { SET_ERR("gq_contact_force: no contact rows registered (gq_batch_set_outputs)"); return GQ_EINVAL; }
   if (id < 0 || id >= GQ_CON_MAX) { SET_ERR("gq_contact_force: contact id %d out of range (0..%d)", id, GQ_CON_MAX - 1); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   /* records past an env's contact count are written as zeros by the kernel */
-  HIP_TRY(hipMemcpy2DAsync(result, 6 * sizeof(float), b->con_out + 8 + id * GQ_CON_REC + 16, GQ_CON_STRIDE * sizeof(float), 6 * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(result, 6 * sizeof(float), b->p.contacts + 8 + id * GQ_CON_REC + 16, GQ_CON_STRIDE * sizeof(float), 6 * sizeof(float),
                            (size_t)b->host.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
   return GQ_OK;
 }
@@ -348,52 +331,25 @@ int gq_debug_enable(GqBatch* b, int n_debug_envs) {
   return GQ_OK;
 }
 
-static void fill_reset_cfg(gq::ResetCfgDev* d, const GqResetCfg* cfg) {
-  d->seed_lo = (uint32_t)(cfg->seed & 0xffffffffu); d->seed_hi = (uint32_t)(cfg->seed >> 32);
-  d->random = cfg->random; d->q_pos_amp = cfg->q_pos_amp; d->q_vel_amp = cfg->q_vel_amp;
-  d->roll_sweep = cfg->roll_sweep; d->pitch_sweep = cfg->pitch_sweep; d->hip_height = cfg->hip_height;
-  for (int k = 0; k < 2; k++) { d->lin_vel_range[k] = cfg->lin_vel_range[k]; d->ang_vel_range[k] = cfg->ang_vel_range[k]; d->friction_range[k] = cfg->friction_range[k]; }
-  d->cmd_forward = cfg->cmd_forward; d->cmd_random = cfg->cmd_random; d->cmd_rotate = cfg->cmd_rotate; d->cmd_human = cfg->cmd_human;
-  d->env_id_offset = cfg->env_id_offset;
-}
-static void fill_reset_args(gq::ResetArgs* a, GqBatch* b, const uint8_t* mask, const double* qpos_new, const float* qvel_new,
-                            const GqResetCfg* cfg, const GqState& st, const GqObsOut& out, int32_t* episode, uint8_t* lift_failed);
-static void fill_step_args(gq::StepArgs* a, GqBatch* b, const GqState& st, const GqObsOut& out, const int32_t* episode, uint8_t* lift_failed) {
-  GqModel* m = b->model;
-  a->model = m->dev; a->batch = b->dev; a->vx = m->vx; a->vy = m->vy; a->vz = m->vz;
-  a->qpos = st.qpos; a->qvel = st.qvel; a->qacc = st.qacc; a->warm = st.qacc_warmstart;
-  a->applied = st.qfrc_applied; a->time = st.time; a->friction = st.friction; a->cmd = st.cmd;
-  a->friction_next = b->friction_next; a->pending = b->pending; a->load_hint = b->load_hint;
-  a->imu_bias = b->imu_bias; a->heightmap = b->heightmap;
-  a->h9 = b->h9; a->ext_dist = b->ext_dist;
-  a->dyn = b->dyn_out; a->contacts = b->con_out;
-  a->lift_failed = lift_failed; a->lift_pending = b->lift_pending;
-  a->episode_ro = episode;
-  a->obs = out.obs; a->reward = out.reward; a->terminated = out.terminated; a->truncated = out.truncated;
-  a->invalid_contact = out.invalid_contact; a->step_num = out.step_num; a->step_prev = out.step_num_prev;
-  a->contacts_dropped = out.contacts_dropped;
-  a->n_envs = b->host.n_envs;
-  a->timestep = m->host.timestep; a->nlg = m->host.nlg; a->nfl = m->host.nfl; a->pad_ = 0;
-}
-/* Make the device argument block describe (st, out, episode, lift_failed[, auto-reset cfg]).  Steady state: a memcmp.
- * On a change the new block goes through a pinned staging slot with a stream-ordered copy, so launches already queued
- * on `stream` still see the old block.  reset_cfg NULL keeps whatever auto-reset block the device holds. */
 /* batch constants changed since the last launch (gq_batch_set_resampling / _set_imu / gq_debug_enable): stream-ordered upload */
 static int flush_batch(GqBatch* b, hipStream_t stream) {
   if (!b->batch_dirty) return GQ_OK;
   if (b->batch_staging_next == GQ_ARG_SLOTS) { HIP_TRY(hipStreamSynchronize(stream)); b->batch_staging_next = 0; }
   GqDevBatch* slot = b->batch_staging + b->batch_staging_next++;
   std::memcpy(slot, &b->host, sizeof(GqDevBatch));
-  HIP_TRY(hipMemcpyAsync(b->dev, slot, sizeof(GqDevBatch), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(b->p.batch, slot, sizeof(GqDevBatch), hipMemcpyHostToDevice, stream));
   b->batch_dirty = false;
   return GQ_OK;
 }
+/* Make the device argument block describe (st, out, episode, lift_failed[, auto-reset cfg]).  Steady state: a memcmp.
+ * On a change the new block goes through a pinned staging slot with a stream-ordered copy, so launches already queued
+ * on `stream` still see the old block.  reset_cfg NULL keeps whatever auto-reset block the device holds. */
 static int ensure_args(GqBatch* b, const GqState& st, const GqObsOut& out, int32_t* episode, uint8_t* lift_failed,
                        const GqResetCfg* reset_cfg, hipStream_t stream) {
   { const int rcb = flush_batch(b, stream); if (rcb != GQ_OK) return rcb; }
   gq::FusedArgs want = b->shadow; /* struct copy keeps padding bytes identical for the memcmp */
-  fill_step_args(&want.s, b, st, out, episode, lift_failed);
-  if (reset_cfg) fill_reset_args(&want.r, b, nullptr, nullptr, nullptr, reset_cfg, st, out, episode, lift_failed);
+  gq::fill_step_args(&want.s, b->p, b->model->host, b->host.n_envs, st, out, episode, lift_failed);
+  if (reset_cfg) gq::fill_reset_args(&want.r, b->p, b->host.rs_cmd_reset, reset_cfg, st, out, episode, lift_failed);
   if (b->shadow_valid && std::memcmp(&want, &b->shadow, sizeof want) == 0) return GQ_OK;
   if (b->staging_next == GQ_ARG_SLOTS) { /* every slot may still be in flight: drain before reusing the ring */
     HIP_TRY(hipStreamSynchronize(stream));
@@ -404,18 +360,6 @@ static int ensure_args(GqBatch* b, const GqState& st, const GqObsOut& out, int32
   HIP_TRY(hipMemcpyAsync(b->dev_args, slot, sizeof want, hipMemcpyHostToDevice, stream));
   b->shadow = want; b->shadow_valid = true;
   return GQ_OK;
-}
-static void fill_reset_args(gq::ResetArgs* a, GqBatch* b, const uint8_t* mask, const double* qpos_new, const float* qvel_new,
-                            const GqResetCfg* cfg, const GqState& st, const GqObsOut& out, int32_t* episode, uint8_t* lift_failed) {
-  GqModel* m = b->model;
-  a->model = m->dev; a->vx = m->vx; a->vy = m->vy; a->vz = m->vz; a->mask = mask; a->qpos_new = qpos_new; a->qvel_new = qvel_new;
-  a->qpos = st.qpos; a->qvel = st.qvel; a->qacc = st.qacc; a->warm = st.qacc_warmstart; a->applied = st.qfrc_applied;
-  a->time = st.time; a->cmd = st.cmd; a->friction_next = st.friction ? b->friction_next : nullptr;
-  a->step_num = out.step_num; a->episode = episode; a->lift_failed = lift_failed;
-  a->h9 = b->h9;
-  a->lift_pending = nullptr;   /* fused auto-reset: the wave hands the flag to its own step; gq_reset sets the scratch pointer */
-  fill_reset_cfg(&a->cfg, cfg);
-  a->cfg.cmd_reset = b->host.rs_cmd_reset;
 }
 
 /* one launch of the step kernel over n_envs envs from c->env0: the variant follows the batch's model (solver, cone, scene) */
@@ -438,7 +382,7 @@ static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const
   if (count == 0) return GQ_OK;
   gq::StepCall c{};
   c.ctrl = ctrl; c.mask = mask; c.debug = b->host.debug_envs > 0 ? b->debug : nullptr; c.env0 = env0;
-  c.auto_reset = auto_reset ? (auto_reset->autoreset_next_step ? 2 : 1) : 0; c.first_pass = 0; c.stop_stage = b->stop_stage;
+  c.auto_reset = gq::auto_reset_mode(auto_reset); c.first_pass = 0; c.stop_stage = b->stop_stage;
   launch_step_kernel(b, &c, count, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
@@ -468,7 +412,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
     DeviceGuard guard0(b->model->device);
     gq::StepCall c{};
     c.ctrl = ctrl_seq; c.n_steps = n_steps; c.ctrl_stride = b->host.n_envs * 12; c.obs_seq = obs_seq;
-    c.auto_reset = auto_reset ? 2 : 0; c.stop_stage = b->stop_stage;
+    c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = b->stop_stage;
     launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return GQ_OK;
@@ -496,7 +440,7 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
   for (int s = 0; s < shards; s++) RO_TRY(hipStreamWaitEvent(b->shard_stream[s], b->fork_event, 0));
   gq::StepCall c{};
   c.debug = b->host.debug_envs > 0 ? b->debug : nullptr;
-  c.auto_reset = auto_reset ? (auto_reset->autoreset_next_step ? 2 : 1) : 0; c.stop_stage = b->stop_stage;
+  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = b->stop_stage;
   for (int k = 0; k < n_steps && herr == hipSuccess; k++) {
     c.ctrl = ctrl_seq + (size_t)k * N * 12;
     for (int s = 0; s < shards && herr == hipSuccess; s++) {
@@ -622,7 +566,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
     HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
     gq::StepCall ci{};
     ci.n_steps = n_steps; ci.obs_seq = obs_seq; ci.act_seq = act_seq; ci.policy = b->mb.policy_dev;
-    ci.auto_reset = auto_reset ? 2 : 0; ci.stop_stage = 0;
+    ci.auto_reset = gq::auto_reset_mode(auto_reset); ci.stop_stage = 0;
     launch_step_kernel(b, &ci, N, stream);
     HIP_TRY(hipGetLastError());
     return GQ_OK;
@@ -643,7 +587,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   std::memcpy(b->mb.staging, &h, sizeof h);
   HIP_TRY(hipMemcpyAsync(b->mb.dev, b->mb.staging, sizeof h, hipMemcpyHostToDevice, stream));
   gq::StepCall c{};
-  c.auto_reset = auto_reset ? 2 : 0;
+  c.auto_reset = gq::auto_reset_mode(auto_reset);
   if (pd) {
     /* the policy must be RESIDENT before the step wavefronts take every slot of the device: launch it first, on its own stream,
      * and wait until each of its workgroups has reported in */
@@ -699,9 +643,10 @@ int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const floa
   if ((qpos_new == nullptr) != (qvel_new == nullptr)) { SET_ERR("gq_reset: qpos_new and qvel_new must be given together"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   gq::ResetArgs r{};
-  fill_reset_args(&r, b, mask, qpos_new, qvel_new, cfg, st, out, episode, lift_failed);
+  gq::fill_reset_args(&r, b->p, b->host.rs_cmd_reset, cfg, st, out, episode, lift_failed);
+  r.mask = mask; r.qpos_new = qpos_new; r.qvel_new = qvel_new;
   r.clear_terminated = out.terminated; r.clear_truncated = out.truncated; r.clear_invalid = out.invalid_contact;
-  r.lift_pending = b->lift_pending;
+  r.lift_pending = b->p.lift_pending;
   { const int rcb = flush_batch(b, (hipStream_t)hip_stream); if (rcb != GQ_OK) return rcb; }
   gq_launch_reset(&r, b->host.n_envs, b->model->scene, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
@@ -718,8 +663,8 @@ int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const floa
 int gq_batch_set_pending(GqBatch* b, const uint8_t* flags, void* hip_stream) {
   if (!b) { SET_ERR("gq_batch_set_pending: null batch"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  if (flags) HIP_TRY(hipMemcpyAsync(b->pending, flags, (size_t)b->host.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
-  else HIP_TRY(hipMemsetAsync(b->pending, 0, (size_t)b->host.n_envs, (hipStream_t)hip_stream));
+  if (flags) HIP_TRY(hipMemcpyAsync(b->p.pending, flags, (size_t)b->host.n_envs, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+  else HIP_TRY(hipMemsetAsync(b->p.pending, 0, (size_t)b->host.n_envs, (hipStream_t)hip_stream));
   return GQ_OK;
 }
 

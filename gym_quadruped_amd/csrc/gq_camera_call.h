@@ -7,12 +7,17 @@
 #include <cmath>
 #include <cstdio>
 
+#include "gq.h"
 #include "gq_camera.h"
 
 namespace gq {
 
+/* lg_cloud[i] (GQ_MAXLG entries): the GqModelDesc cloud of host.lg[i], -1: none - gq_camera's face-plane table is indexed by cloud */
+inline void cam_lg_cloud(int32_t* lg_cloud, const GqDevModel& host, const GqModelDesc* desc) {
+  for (int i = 0; i < host.nlg; i++) lg_cloud[i] = desc->geom_cloudid[host.item_geomid[4 + i]];
+}
 /* c: zero-initialised by the caller; rec and cpos (the batch's scratch) stay the caller's to set.  host: the model as gq_build_dev_model
- * made it; lg_cloud[i]: the GqModelDesc cloud of lg[i] (-1: none), ncloud / ngeom: the desc's counts.  The arguments are taken as the
+ * made it; lg_cloud: as cam_lg_cloud fills it, ncloud / ngeom: the desc's counts.  The arguments are taken as the
  * entry point's own checks left them.  Returns 0, or 1 with the error text (fn: the entry point's name) in err. */
 inline int cam_fill_call(CamCall& c, const char* fn, const GqDevModel& host, const int32_t* lg_cloud, int ncloud, int ngeom, const double* qpos,
                          int qpos_stride, int body, const double pos[3], const double quat[4], float fovy_deg, int width, int height, float znear,

@@ -351,12 +351,7 @@ __global__ void __launch_bounds__(GQ_WAVE) camera_layer_kernel(const GQ_GLOBAL G
 
 #endif /* GQ_IN_MISC */
 
-/* ---- the kernel variants, the part that builds each, and the run-time dispatch to them.  A variant is a Key: solver (0 PGS, 1 Newton),
- * mode (0 production; 1 debug record + stage timers; 2 stage cut, gq_debug_stop_stage - its early returns cost the production kernel ~8 %
- * when merely compiled in), cone (1 elliptic, Newton only: gq_model_create rejects it with PGS), scene, and mailbox (1: the closed-loop
- * rollout's mailbox_step_kernel, production Newton only; 0: step_kernel, whose production mode also has its PERSIST twin). */
-struct Key { int solver, mode, cone, scene, mailbox; };
-constexpr bool key_exists(Key k) { return !(k.solver == 0 && k.cone) && !(k.mailbox && (k.solver == 0 || k.mode != 0)); }
+/* ---- the kernel variants (Key, gq_step_kernel.h), the part that builds each, and the run-time dispatch to them. */
 /* part 0: the non-template kernels and the launch entry points; 1-18: step variants by solver and cone x mode x flat or world scene;
  * 19-22: mailbox variants by cone x flat or world scene.  Each part is one translation unit (-DGQ_PART=k); the Makefile's NPARTS is checked. */
 constexpr int part_of(Key k) {
@@ -405,27 +400,13 @@ static void launch_variant(const Launch& L) {
     hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
   }
 }
-/* f(std::integral_constant<int, v>{}) for the run-time v in [0, N): turns one field of a key into a template argument */
-template <int N, class F>
-static bool with_const(int v, F&& f) {
-  static_assert(N <= 4, "with_const: add cases");
-  switch (v) {
-    case 0: return f(std::integral_constant<int, 0>{});
-    case 1: if constexpr (N > 1) return f(std::integral_constant<int, 1>{}); break;
-    case 2: if constexpr (N > 2) return f(std::integral_constant<int, 2>{}); break;
-    case 3: if constexpr (N > 3) return f(std::integral_constant<int, 3>{}); break;
-  }
-  return false;
-}
 /* launches L's variant if the unit of part PART instantiates it; false otherwise */
 template <int PART>
 static bool dispatch(const Launch& L) {
-  const Key& k = L.key;
-  return with_const<2>(k.solver, [&](auto S) { return with_const<3>(k.mode, [&](auto M) { return with_const<2>(k.cone, [&](auto C) {
-         return with_const<SCENE_COUNT>(k.scene, [&](auto SC) { return with_const<2>(k.mailbox, [&](auto MB) {
+  return for_variant(L.key, [&](auto S, auto M, auto C, auto SC, auto MB) {
     if constexpr (!compiled_in({S, M, C, SC, MB}, PART)) return false;
     else { launch_variant<S, M, C, SC, MB>(L); return true; }
-  }); }); }); }); });
+  });
 }
 /* the entry point of part PART > 0, instantiated in that part's unit only */
 template <int PART> bool launch_part(const Launch& L);
@@ -451,8 +432,7 @@ static bool launch_key(const Launch& L) {
 
 #if GQ_IN_MISC
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream) {
-  const int newton = solver == 1; /* PGS: pyramidal cones only */
-  const gq::Key k{newton, c->debug != nullptr ? 1 : (c->stop_stage != 0 ? 2 : 0), newton && cone, scene, 0};
+  const gq::Key k = gq::step_key(solver, cone, scene, c->debug != nullptr, c->stop_stage, 0);
   if (!gq::launch_key({k, dev_args, c, nullptr, n_envs, stream})) {
     fprintf(stderr, "libgq: step-kernel variant solver=%d mode=%d cone=%d scene=%d is not compiled into this build\n", k.solver, k.mode, k.cone, k.scene);
     abort();
@@ -460,8 +440,7 @@ extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall
 }
 /* returns 0 if the scene / solver combination has no mailbox variant compiled in */
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream) {
-  const int newton = solver == 1;
-  return gq::launch_key({{newton, 0, newton && cone, scene, 1}, dev_args, c, mb, waves, stream}) ? 1 : 0;
+  return gq::launch_key({gq::step_key(solver, cone, scene, false, 0, 1), dev_args, c, mb, waves, stream}) ? 1 : 0;
 }
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream) {
   if (gq::scene_boxes(scene)) hipLaunchKernelGGL(gq::reset_kernel<true>, dim3(n_envs), dim3(GQ_WAVE), 0, stream, *a);

@@ -28,6 +28,7 @@
 #include <gq_device.h> /* angle brackets: the include path decides (csrc/ for the product, tests/simt_emu/ for the emulator) */
 #include "gq_model_dev.h"
 #include <cstddef>
+#include <type_traits>
 
 namespace gq {
 
@@ -36,7 +37,7 @@ namespace gq {
  * into SGPRs at kernel entry and immediately spilled lane-by-lane into VGPRs (v_writelane / v_readlane: ~10 % of the
  * kernel's VALU issue slots).  What changes from call to call travels by value in StepCall. */
 /* Field order (round 5): the sixteen pointers a wave's PROLOGUE reads (load_rows) are the first 128 bytes - two s_load_dwordx16 - and the
- * ones its EPILOGUE stores through follow in one block (from `qacc` on); the block is filled by name (gq_api.hip). */
+ * ones its EPILOGUE stores through follow in one block (from `qacc` on); the block is filled by name (gq_step_call.h). */
 struct StepArgs {
   const GqDevModel* model;
   const GqDevBatch* batch;
@@ -68,7 +69,7 @@ struct StepArgs {
 #define GQ_XQ_ITEM 64
 #define GQ_XQ_MARGIN 40
 #define GQ_XQ_RES 48 /* hit, dist, normal (3), point (3) */
-/* The scene a model's step-kernel variants are built for (gq_api.hip model_scene; the launch entry points of gq_kernels.hip take it):
+/* The scene a model's step-kernel variants are built for (gq_step_call.h model_scene; the launch entry points of gq_kernels.hip take it):
  * flat (no world geoms beyond the floor), flat + robot self-collision, world boxes / height field for a robot of hulls only, and the
  * same for a robot with sphere / capsule / box link geoms.  The world scenes always carry the self-collision stage (a model without
  * pairs skips it at run time).  scene_boxes / scene_self / scene_prim give the BOXES / SELF / PRIM template arguments of the kernels;
@@ -77,6 +78,38 @@ enum Scene : int { SCENE_FLAT, SCENE_FLAT_SELF, SCENE_WORLD_HULL, SCENE_WORLD_PR
 constexpr bool scene_boxes(Scene s) { return s == SCENE_WORLD_HULL || s == SCENE_WORLD_PRIM; }
 constexpr bool scene_self(Scene s) { return s != SCENE_FLAT; }
 constexpr bool scene_prim(Scene s) { return s != SCENE_WORLD_HULL; }
+/* A step-kernel variant is a Key: solver (0 PGS, 1 Newton), mode (0 production; 1 debug record + stage timers; 2 stage cut,
+ * gq_debug_stop_stage - its early returns cost the production kernel ~8 % when merely compiled in), cone (1 elliptic, Newton only:
+ * gq_model_create rejects it with PGS), scene, and mailbox (1: the closed-loop rollout's mailbox_step_kernel, production Newton only; 0:
+ * step_kernel, whose production mode also has its PERSIST twin).  Plain C++: the launches (gq_kernels.hip) and the tests' host emulator
+ * (tests/simt_emu) pick their instantiation through the same step_key / for_variant. */
+struct Key { int solver, mode, cone, scene, mailbox; };
+constexpr bool key_exists(Key k) { return !(k.solver == 0 && k.cone) && !(k.mailbox && (k.solver == 0 || k.mode != 0)); }
+/* the key of a model's step: PGS knows pyramidal cones only; the debug record wins over a stage cut */
+constexpr Key step_key(int solver, int cone, Scene scene, bool debug, int stop_stage, int mailbox) {
+  return {solver == 1, debug ? 1 : (stop_stage != 0 ? 2 : 0), solver == 1 && cone, scene, mailbox};
+}
+/* f(std::integral_constant<int, v>{}) for the run-time v in [0, N): turns one field of a key into a template argument */
+template <int N, class F>
+bool with_const(int v, F&& f) {
+  static_assert(N <= 4, "with_const: add cases");
+  switch (v) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: if constexpr (N > 1) return f(std::integral_constant<int, 1>{}); break;
+    case 2: if constexpr (N > 2) return f(std::integral_constant<int, 2>{}); break;
+    case 3: if constexpr (N > 3) return f(std::integral_constant<int, 3>{}); break;
+  }
+  return false;
+}
+/* f(solver, mode, cone, scene, mailbox), the fields of k as integral_constants, and its bool; false for a key that does not exist */
+template <class F>
+bool for_variant(Key k, F&& f) {
+  return with_const<2>(k.solver, [&](auto S) { return with_const<3>(k.mode, [&](auto M) { return with_const<2>(k.cone, [&](auto C) {
+         return with_const<SCENE_COUNT>(k.scene, [&](auto SC) { return with_const<2>(k.mailbox, [&](auto MB) {
+    if constexpr (!key_exists({S, M, C, SC, MB})) return false;
+    else return f(S, M, C, SC, MB);
+  }); }); }); }); });
+}
 struct StepCall {
   const float* ctrl;    /* [N][nu] or NULL (zero control) */
   const uint8_t* mask;  /* [N] or NULL */

@@ -5,7 +5,7 @@
 
 #include "gq_device.h"          /* the emulator shim (this directory comes first on the include path) */
 #include "gq_camera_call.h"
-#include "gq_host_model.h"
+#include "emu_model.h"
 
 void emu_run_wave(unsigned block, unsigned nblocks, const std::function<void()>& body);
 
@@ -13,14 +13,11 @@ void emu_run_wave(unsigned block, unsigned nblocks, const std::function<void()>&
 extern "C" int emu_camera(const GqModelDesc* desc, int n_envs, const double* qpos, int qpos_stride, int body, const double* pos, const double* quat,
                           float fovy_deg, int width, int height, float znear, float zfar, int flags, const float* hull_planes,
                           const int32_t* hull_plane_adr, float* depth, int32_t* seg, double* cam_xpos, float* cam_xmat, char* err, int errlen) {
-  static GqDevModel M;
-  std::vector<float> vx, vy, vz;
-  if (gq_build_dev_model(desc, &M, &vx, &vy, &vz, err, (size_t)errlen)) return -1;
-  static std::vector<float> hf_heights;
-  gq_hfield_heights(desc, &hf_heights);
-  M.hf_data = hf_heights.empty() ? nullptr : hf_heights.data();
+  static EmuModel m;
+  if (emu_build_model(desc, m, err, errlen)) return -1;
+  const GqDevModel& M = m.M;
   int32_t lg_cloud[GQ_MAXLG];
-  for (int i = 0; i < M.nlg; i++) lg_cloud[i] = desc->geom_cloudid[M.item_geomid[4 + i]];   /* as gq_model_create */
+  gq::cam_lg_cloud(lg_cloud, M, desc);
   gq::CamCall c{};
   if (gq::cam_fill_call(c, "emu_camera", M, lg_cloud, desc->ncloud, desc->ngeom, qpos, qpos_stride, body, pos, quat, fovy_deg, width, height, znear, zfar,
                         flags, hull_planes, hull_plane_adr, depth, seg, cam_xpos, cam_xmat, err, (size_t)errlen)) return -1;

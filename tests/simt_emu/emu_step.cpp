@@ -1,23 +1,16 @@
 /* TEST INFRASTRUCTURE - runs the unmodified step kernel body (csrc/gq_step_body.h) under the host SIMT emulator.
- * Exposes a C entry point with the same tensors as gq_step, operating on host memory. */
+ * Exposes a C entry point with the same tensors as gq_step, operating on host memory.  The argument blocks are filled by the library's
+ * gq_step_call.h and the instantiation is picked by its step_key / for_variant (gq_step_kernel.h).  The re-spawn loop around step_wave is
+ * still written out here: shared with gq::step_kernel as a function it changed the instruction streams of that kernel's variants. */
 #include <functional>
 #include <vector>
 #include <cstdio>
 
 #include "gq_device.h"          /* the emulator shim (this directory comes first on the include path) */
-#include "gq_step_body.h"
-#include "gq_host_model.h"
+#include "gq_step_call.h"
+#include "emu_model.h"
 
 void emu_run_wave(unsigned block, unsigned nblocks, const std::function<void()>& body);
-
-static void emu_fill_cfg(gq::ResetCfgDev* d, const GqResetCfg* cfg) {
-  d->seed_lo = (uint32_t)(cfg->seed & 0xffffffffu); d->seed_hi = (uint32_t)(cfg->seed >> 32);
-  d->random = cfg->random; d->q_pos_amp = cfg->q_pos_amp; d->q_vel_amp = cfg->q_vel_amp;
-  d->roll_sweep = cfg->roll_sweep; d->pitch_sweep = cfg->pitch_sweep; d->hip_height = cfg->hip_height;
-  for (int k = 0; k < 2; k++) { d->lin_vel_range[k] = cfg->lin_vel_range[k]; d->ang_vel_range[k] = cfg->ang_vel_range[k]; d->friction_range[k] = cfg->friction_range[k]; }
-  d->cmd_forward = cfg->cmd_forward; d->cmd_random = cfg->cmd_random; d->cmd_rotate = cfg->cmd_rotate; d->cmd_human = cfg->cmd_human;
-  d->env_id_offset = cfg->env_id_offset;
-}
 
 /* the convex pair exchange (gq_exchange.h) under emulation: wavefronts run one after the other, so an owner ends up claiming its own items -
  * every queue operation is exercised, concurrency is not (tests/test_gpu_parity.py compares exchange on / off on the device) */
@@ -25,7 +18,14 @@ static int g_emu_xq_on = 0;
 extern "C" void emu_set_exchange(int on) { g_emu_xq_on = on; }
 extern "C" void emu_exchange_stats(int* out) { out[0] = gq::g_emu_cas_ok; out[1] = out[2] = out[3] = 0; }
 
-/* same control flow as gq::step_kernel (csrc/gq_kernels.hip) */
+/* the emulator's batch has neither resampling, a step-time height map nor dyn / contact rows, and no solver-load hint */
+static gq::BatchPtrs emu_ptrs(EmuModel& m, GqDevBatch* B, float* friction_next, uint8_t* pending, uint8_t* lift_pending, float* imu_bias) {
+  gq::BatchPtrs p{};
+  p.model = &m.M; p.batch = B; p.vx = m.vx.data(); p.vy = m.vy.data(); p.vz = m.vz.data();
+  p.friction_next = friction_next; p.pending = pending; p.lift_pending = lift_pending; p.imu_bias = imu_bias;
+  return p;
+}
+
 extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order,
                         const float* ctrl, const uint8_t* mask, double* qpos, float* qvel, float* qacc, float* warm,
                         float* applied, float* time, float* friction, float* cmd, float* obs,
@@ -33,28 +33,13 @@ extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_
                         int32_t* step_num, float* debug, int debug_envs, const GqResetCfg* auto_reset, int32_t* episode,
                         uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
                         uint8_t* pending, uint8_t* lift_pending, char* err, int errlen) {
-  static GqDevModel M;
+  static EmuModel m;
   static GqDevBatch B;
-  std::vector<float> vx, vy, vz;
-  if (gq_build_dev_model(desc, &M, &vx, &vy, &vz, err, (size_t)errlen)) return -1;
-  static std::vector<float> hf_heights;
-  gq_hfield_heights(desc, &hf_heights);
-  M.hf_data = hf_heights.empty() ? nullptr : hf_heights.data();
+  if (emu_build_model(desc, m, err, errlen)) return -1;
+  const GqDevModel& M = m.M;
   if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &B, err, (size_t)errlen)) return -1;
   B.debug_envs = debug_envs;
   if (imu) gq_fill_imu(&B, imu);
-  gq::FusedArgs f{};
-  gq::StepArgs& a = f.s;
-  a.model = &M; a.batch = &B; a.vx = vx.data(); a.vy = vy.data(); a.vz = vz.data();
-  a.qpos = qpos; a.qvel = qvel; a.qacc = qacc; a.warm = warm; a.applied = applied;
-  a.time = time; a.friction = friction; a.cmd = cmd; a.friction_next = friction_next; a.pending = pending; a.obs = obs; a.reward = reward;
-  a.terminated = terminated; a.truncated = truncated; a.invalid_contact = invalid_contact; a.step_num = step_num;
-  a.n_envs = n_envs; a.imu_bias = imu ? imu_bias : nullptr; a.episode_ro = episode;
-  a.lift_failed = lift_failed; a.lift_pending = lift_pending;
-  a.timestep = M.timestep; a.nlg = M.nlg; a.nfl = M.nfl;
-  gq::StepCall call{};
-  call.ctrl = ctrl; call.mask = mask; call.debug = debug;
-  call.auto_reset = auto_reset ? (auto_reset->autoreset_next_step ? 2 : 1) : 0; call.first_pass = first_pass;
   static std::vector<int32_t> xq;
   static std::vector<float> sepc; /* the separating-axis cache (GqDevBatch::sepc): kept across calls like the batch's own */
   if (M.ncvx_self > 0) {
@@ -66,47 +51,45 @@ extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_
     if (xq.empty()) xq.assign((size_t)slots * (1 + GQ_XQ_ITEM), 0);
     B.xq = xq.data(); B.xq_slots = slots;
   }
-  if (auto_reset) {
-    gq::ResetArgs& r = f.r;
-    r.model = &M; r.vx = vx.data(); r.vy = vy.data(); r.vz = vz.data();
-    r.qpos = qpos; r.qvel = qvel; r.qacc = qacc; r.warm = warm; r.applied = applied; r.time = time; r.cmd = cmd;
-    r.friction_next = friction_next; r.step_num = step_num; r.episode = episode; r.lift_failed = lift_failed;
-    emu_fill_cfg(&r.cfg, auto_reset);
-  }
-  for (int e = 0; e < n_envs; e++) {
-    if (mask && !mask[e]) continue;
-    emu_run_wave((unsigned)e, (unsigned)n_envs, [&]() {
-      __shared__ gq::WaveMem W;
-      int pass = call.first_pass;
-      gq::WaveCtx C;
-      const bool boxes = M.nbox > 0 || M.hf_nrow > 0, self = M.nsp > 0;
-      bool prims = false; /* as gq_api.hip model_scene: the PRIM variants serve robots with sphere / capsule / box link geoms */
-      for (int g = 0; g < M.nlg; g++) prims = prims || M.lg[g].ptype == 2 || M.lg[g].ptype == 3 || M.lg[g].ptype == 6;
-      int hint = M.solver == 1 ? gq::load_rows<1>(f.s, call, W, e, pass == 0, C) : gq::load_rows<0>(f.s, call, W, e, pass == 0, C);
-      bool respawn = call.auto_reset == 2 && C.pend;
-      for (;;) {
-        if (respawn) {
-          gq::wave_barrier();
-          boxes ? (prims ? gq::reset_wave<true, true>(f.r, W) : gq::reset_wave<true, false>(f.r, W)) : gq::reset_wave<false>(f.r, W);
-          pass = call.auto_reset;
-          hint = M.solver == 1 ? gq::load_rows<1>(f.s, call, W, e, false, C, true) : gq::load_rows<0>(f.s, call, W, e, false, C, true);
-        }
-        int term;
-        if (M.solver != 1) { /* PGS (pyramidal cones only) */
-          if (boxes && prims) term = gq::step_wave<0, 1, false, true, true, true>(f.s, call, W, pass, hint, C);
-          else if (boxes) term = gq::step_wave<0, 1, false, true, true, false>(f.s, call, W, pass, hint, C);
-          else if (self) term = gq::step_wave<0, 1, false, false, true, true>(f.s, call, W, pass, hint, C);
-          else term = gq::step_wave<0, 1, false, false, false, true>(f.s, call, W, pass, hint, C);
-        }
-        else if (boxes && prims) term = M.cone ? gq::step_wave<1, 1, true, true, true, true>(f.s, call, W, pass, hint, C) : gq::step_wave<1, 1, false, true, true, true>(f.s, call, W, pass, hint, C);
-        else if (boxes) term = M.cone ? gq::step_wave<1, 1, true, true, true, false>(f.s, call, W, pass, hint, C) : gq::step_wave<1, 1, false, true, true, false>(f.s, call, W, pass, hint, C);
-        else if (self) term = M.cone ? gq::step_wave<1, 1, true, false, true, true>(f.s, call, W, pass, hint, C) : gq::step_wave<1, 1, false, false, true, true>(f.s, call, W, pass, hint, C);
-        else term = M.cone ? gq::step_wave<1, 1, true, false, false, true>(f.s, call, W, pass, hint, C) : gq::step_wave<1, 1, false, false, false, true>(f.s, call, W, pass, hint, C);
-        if (pass != 0 || call.auto_reset != 1 || !term) break;
-        respawn = true;
+  const gq::BatchPtrs p = emu_ptrs(m, &B, friction_next, pending, lift_pending, imu ? imu_bias : nullptr);
+  const GqState st{qpos, qvel, qacc, warm, applied, time, friction, cmd};
+  const GqObsOut out{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr};
+  gq::FusedArgs f{};
+  gq::fill_step_args(&f.s, p, M, n_envs, st, out, episode, lift_failed);
+  if (auto_reset) gq::fill_reset_args(&f.r, p, B.rs_cmd_reset, auto_reset, st, out, episode, lift_failed);
+  gq::StepCall call{};
+  call.ctrl = ctrl; call.mask = mask; call.debug = debug; call.auto_reset = gq::auto_reset_mode(auto_reset); call.first_pass = first_pass;
+  /* the instrumented variant of the model's key (mode 1: the one with the debug record), whether or not a record is asked for */
+  const bool known = gq::for_variant(gq::step_key(M.solver, M.cone, gq::model_scene(M), true, 0, 0), [&](auto S, auto MODE, auto CONE, auto SC, auto MB) {
+    if constexpr (MODE != 1 || MB != 0) return false;
+    else {
+      constexpr gq::Scene sc = gq::Scene(int(SC));
+      for (int e = 0; e < n_envs; e++) {
+        if (mask && !mask[e]) continue;
+        emu_run_wave((unsigned)e, (unsigned)n_envs, [&]() { /* the loop of gq::step_kernel (csrc/gq_kernels.hip), kept in step with it by hand */
+          constexpr bool BOXES = gq::scene_boxes(sc), SELF = gq::scene_self(sc), PRIM = gq::scene_prim(sc);
+          __shared__ gq::WaveMem W;
+          gq::WaveCtx C;
+          int pass = call.first_pass;
+          int hint = gq::load_rows<S>(f.s, call, W, e, pass == 0, C);
+          bool respawn = call.auto_reset == 2 && C.pend;
+          for (;;) {
+            if (respawn) {
+              gq::wave_barrier();
+              gq::reset_wave<BOXES, PRIM>(f.r, W);
+              pass = call.auto_reset;
+              hint = gq::load_rows<S>(f.s, call, W, e, false, C, true);
+            }
+            const int term = gq::step_wave<S, 1, CONE != 0, BOXES, SELF, PRIM>(f.s, call, W, pass, hint, C);
+            if (pass != 0 || call.auto_reset != 1 || !term) break;
+            respawn = true;
+          }
+        });
       }
-    });
-  }
+      return true;
+    }
+  });
+  if (!known) { std::snprintf(err, (size_t)errlen, "emu_step: no step-kernel variant for solver %d cone %d", M.solver, M.cone); return -1; }
   return B.obs_dim;
 }
 
@@ -114,23 +97,21 @@ extern "C" int emu_reset(const GqModelDesc* desc, int n_envs, const uint8_t* mas
                          const GqResetCfg* cfg, double* qpos, float* qvel, float* qacc, float* warm, float* applied,
                          float* time, float* cmd, float* friction_next, int32_t* step_num, int32_t* episode,
                          uint8_t* lift_failed, uint8_t* lift_pending, char* err, int errlen) {
-  static GqDevModel M;
-  std::vector<float> vx, vy, vz;
-  if (gq_build_dev_model(desc, &M, &vx, &vy, &vz, err, (size_t)errlen)) return -1;
-  static std::vector<float> hf_heights;
-  gq_hfield_heights(desc, &hf_heights);
-  M.hf_data = hf_heights.empty() ? nullptr : hf_heights.data();
+  static EmuModel m;
+  if (emu_build_model(desc, m, err, errlen)) return -1;
+  const gq::BatchPtrs p = emu_ptrs(m, nullptr, friction_next, nullptr, lift_pending, nullptr);
+  const GqState st{qpos, qvel, qacc, warm, applied, time, /* friction */ nullptr, cmd};
+  GqObsOut out{}; out.step_num = step_num;
   gq::ResetArgs a{};
-  a.model = &M; a.vx = vx.data(); a.vy = vy.data(); a.vz = vz.data(); a.mask = mask; a.qpos_new = qpos_new; a.qvel_new = qvel_new;
-  a.qpos = qpos; a.qvel = qvel; a.qacc = qacc; a.warm = warm; a.applied = applied; a.time = time; a.cmd = cmd;
-  a.friction_next = friction_next; a.step_num = step_num; a.episode = episode; a.lift_failed = lift_failed;
-  a.lift_pending = lift_pending;
-  emu_fill_cfg(&a.cfg, cfg);
+  gq::fill_reset_args(&a, p, 0, cfg, st, out, episode, lift_failed);
+  a.mask = mask; a.qpos_new = qpos_new; a.qvel_new = qvel_new; a.lift_pending = p.lift_pending; /* as gq_reset (no flags to clear here) */
+  a.friction_next = friction_next; /* this entry point takes no friction tensor and always wants the draw */
+  const bool boxes = gq::scene_boxes(gq::model_scene(m.M));
   for (int e = 0; e < n_envs; e++) {
     if (mask && !mask[e]) continue;
-    emu_run_wave((unsigned)e, (unsigned)n_envs, [&]() {
+    emu_run_wave((unsigned)e, (unsigned)n_envs, [&]() { /* as gq::reset_kernel */
       __shared__ gq::WaveMem W;
-      if ((M.nbox > 0 || M.hf_nrow > 0)) gq::reset_wave<true>(a, W); else gq::reset_wave<false>(a, W);
+      if (boxes) gq::reset_wave<true>(a, W); else gq::reset_wave<false>(a, W);
     });
   }
   return 0;
