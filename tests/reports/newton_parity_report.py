@@ -11,7 +11,8 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
-from helpers import ALL_OBS, ParityTally, marshalled, random_states, split_obs  # noqa: E402
+from helpers import ALL_OBS, marshalled, random_states, split_obs  # noqa: E402
+from step_parity import ParityTally  # noqa: E402
 from oracle.oracle import Oracle  # noqa: E402
 from gym_quadruped_amd.quadruped_env import QuadrupedEnv  # noqa: E402
 

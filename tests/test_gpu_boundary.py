@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from helpers import marshalled, random_states
+from step_parity import GPU_FORWARD_ROWS, compare
 
 pytestmark = pytest.mark.gpu
 
@@ -139,8 +140,7 @@ def test_gq_forward_is_mj_forward_without_side_effects():
             assert int(d['nefc'][0]) == ne and int(d['ncon'][0]) == o.ncon
             np.testing.assert_allclose(d['M'].reshape(18, 18), o.M, rtol=1e-4, atol=2e-5)
             np.testing.assert_allclose(d['qfrc_bias'], o.qfrc_bias, rtol=1e-4, atol=2e-3)
-            np.testing.assert_allclose(d['efc_J'].reshape(64, 18)[:ne], o.efc_J, rtol=1e-4, atol=1e-5)
-            np.testing.assert_allclose(d['efc_aref'][:ne], o.efc_aref, rtol=2e-4, atol=2e-2)
+            compare(o, d, GPU_FORWARD_ROWS, e)
             xp = d['xpos'].reshape(13, 3); ref = o.xpos[1:] - np.r_[q0[e, :2], 0.0]     # the record is relative to the base x/y
             np.testing.assert_allclose(xp, ref, atol=5e-6)
             if stage == 0:

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import budgeted_states, oracle_fits_row_budget, ALL_OBS, ParityTally, marshalled, random_states, self_contact_states, split_obs, tally_note
+from helpers import budgeted_states, oracle_fits_row_budget, ALL_OBS, marshalled, random_states, self_contact_states, split_obs, tally_note
+import step_parity as sp
+from step_parity import ParityTally, gpu_records
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +25,27 @@ def _make_env(n, obs=ALL_OBS, iters=50, tol=0.0, solver='pgs', robot='mini_cheet
 def _oracle(env):
     from oracle.oracle import Oracle
     return Oracle(env._mm)
+
+
+def _one_more_step_against_oracle(env, o, g, what, count):
+    """One more step from a rollout's state, checked against the oracle: every env that does not spend the step on its reset is held to
+    ROLLOUT_STATE_STEP - an env over the row budget to the prefix rule: its rows are the oracle's first rows, the flags the oracle's, and the
+    caller is told what was cut.  Returns the sum of count() over the compared envs that have contacts."""
+    n = env.num_envs
+    q0, v0, w0, fr = env.qpos.cpu().numpy().copy(), env.qvel.cpu().numpy().copy(), env._warm.cpu().numpy().copy(), env._friction.cpu().numpy().copy()
+    pend = env._terminated_b.cpu().numpy().copy()
+    act = torch.randn(n, 12, generator=g, device='cuda:0') * 15
+    env.enable_debug(n)
+    env.step(act)
+    kern = gpu_records(env, n, ['qacc', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
+    a = act.cpu().numpy()
+    total = 0
+    tally = ParityTally(env.mjModel.cone == 1, 3e-6)
+    for e in np.where(~pend)[0].tolist():
+        if tally.step_env(e, o, (q0[e], v0[e], w0[e], np.zeros(18), 0.0, float(fr[e])), a[e], kern[e], sp.ROLLOUT_STATE_STEP, prefix=True) == 'ok' and o.ncon:
+            total += count()
+    tally.finish(what, min_checked=0.7, max_tie=0.15, max_budget=0.1)
+    return total
 
 
 def test_loaded_native_lib():
@@ -58,7 +81,7 @@ def test_step_matches_oracle_stagewise():
         o.step(ctrl[e].astype(np.float64))
         # a link geom resting on two hull vertices of (numerically) equal depth has no unique "deepest vertex":
         # fp32 and fp64 may legitimately pick different ones.  Such envs are only checked for sanity.
-        if o.ncon and o.get('contact_tiegap').min() < 3e-7:
+        if sp.has_tie(o, 3e-7):
             n_tie += 1
             assert np.all(np.isfinite(qvel_g[e])) and np.abs(qvel_g[e] - o.qvel).max() < 5.0   # (a tie moves the mesh's whole manifold: up to three contacts)
             continue
@@ -72,9 +95,7 @@ def test_step_matches_oracle_stagewise():
             ne = o.nefc
             np.testing.assert_allclose(d['M'].reshape(18, 18), o.M, rtol=1e-4, atol=2e-5)
             np.testing.assert_allclose(d['qfrc_bias'], o.qfrc_bias, rtol=1e-4, atol=2e-3)
-            np.testing.assert_allclose(d['efc_J'].reshape(64, 18)[:ne], o.efc_J, rtol=1e-4, atol=1e-5)
-            np.testing.assert_allclose(d['efc_aref'][:ne], o.efc_aref, rtol=2e-4, atol=2e-2)
-            np.testing.assert_allclose(d['efc_R'][:ne], o.efc_R, rtol=1e-4)
+            sp.compare(o, d, sp.GPU_STAGE_ROWS, e)
             fmax = max(1.0, np.abs(o.efc_force).max())
             assert np.abs(d['efc_force'][:ne] - o.efc_force).max() < 2e-4 * fmax
             amax = max(1.0, np.abs(o.qacc).max())
@@ -238,36 +259,26 @@ def test_newton_step_matches_converged_oracle(robot):
     env._cmd.copy_(torch.as_tensor(cmd)); env._friction.fill_(0.8)
     env.enable_debug(n)
     obs, rew, term, trunc, info = env.step(torch.as_tensor(ctrl))
-    torch.cuda.synchronize()
-    dbg = env.debug_internals(n, ['qacc', 'niter', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
-    dropped = info['contacts_dropped'].cpu().numpy()
-    qp, qv, ob = env.qpos.cpu().numpy(), env.qvel.cpu().numpy(), env._obs_buf.cpu().numpy()
-    tg, ig = term.cpu().numpy(), info['invalid_contacts'].cpu().numpy()
+    kern = gpu_records(env, n, ['qacc', 'niter', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
     ncon = 0
     tally = ParityTally(env.mjModel.cone == 1, 3e-7)
     cone = env.mjModel.cone == 1
     mg = 9.81 * float(env.mjModel.total_mass)
     ea, ev, ep, eo, ef = [], [], [], [], []
     for e in range(n):
-        o.set_state(qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8)
-        o.step(ctrl[e].astype(np.float64))
-        cls = tally.classify(e, o, dbg[e]['nefc'][0])
-        if cls == 'budget':   # more rows than one wavefront carries: the kernel's rows are the oracle's first rows, the flags the oracle's
-            tally.check_budget_prefix(e, o, dbg[e]['nefc'][0], dbg[e]['efc_J'], dbg[e]['efc_R'], dbg[e]['efc_aref'], (tg[e], ig[e]))
-            # info['contacts_dropped'] says so to the caller: exactly the contacts of MuJoCo's list the kernel did not take
-            assert int(dropped[e]) == o.ncon - int(dbg[e]['ncon'][0]) > 0, (e, int(dropped[e]), o.ncon, int(dbg[e]['ncon'][0]))
-        if cls != 'ok':
-            continue   # tie / over the row budget: counted and bounded below; a row-count mismatch fails the test
-        assert int(dropped[e]) == 0, (e, int(dropped[e]))
+        k = kern[e]
+        # over the row budget: held to the prefix rule, and info['contacts_dropped'] says so to the caller; ties and those are counted and bounded
+        # below; a row-count mismatch fails the test
+        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8), ctrl[e], k, sp.FLAGS, prefix=True) != 'ok':
+            continue
         ncon += o.ncon
-        ea.append(np.abs(dbg[e]['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
-        ev.append(np.abs(qv[e] - o.qvel).max()); ep.append(np.abs(qp[e] - o.qpos).max())
-        ref, t, inv = o.get_obs(ALL_OBS, cmd[e])
-        got = split_obs(ob[e], ALL_OBS)
-        eo.append(max(np.abs(got[k] - ref[k]).max() / max(1.0, np.abs(ref[k]).max()) for k in ALL_OBS if not k.startswith('contact_forces')))
-        ef.append(max(np.abs(got[k] - ref[k]).max() for k in ('contact_forces', 'contact_forces:base')) / max(np.abs(ref['contact_forces']).max(), 0.1 * mg))
-        assert bool(tg[e]) == t and bool(ig[e]) == inv
-        assert dbg[e]['niter'][0] <= (20 if not cone else 100)   # condim-6 cones converge slowly (the fp64 oracle too)
+        ea.append(np.abs(k['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
+        ev.append(np.abs(k['qvel'] - o.qvel).max()); ep.append(np.abs(k['qpos'] - o.qpos).max())
+        ref, _, _ = o.get_obs(ALL_OBS, cmd[e])
+        got = k['obs']
+        eo.append(max(np.abs(got[k_] - ref[k_]).max() / max(1.0, np.abs(ref[k_]).max()) for k_ in ALL_OBS if not k_.startswith('contact_forces')))
+        ef.append(max(np.abs(got[k_] - ref[k_]).max() for k_ in ('contact_forces', 'contact_forces:base')) / max(np.abs(ref['contact_forces']).max(), 0.1 * mg))
+        assert k['niter'][0] <= (20 if not cone else 100)   # condim-6 cones converge slowly (the fp64 oracle too)
     # Asserted bounds = ~10 x the p99 and ~5 x the maximum measured over 512 states per robot on MI355X
     # (profiles/r02_newton_parity_report.txt: tests/reports/newton_parity_report.py).  Elliptic condim-6 contacts (go1, go2,
     # spot): torsional / rolling rows are almost unregularised directions, the forces of a light contact move by ~1e-3 of the
@@ -493,35 +504,9 @@ def test_box_scenes_rollout_and_step_parity(robot, scene):
         obs, rew, term, trunc, info = env.step(torch.randn(n, 12, generator=g, device='cuda:0') * 15)
     torch.cuda.synchronize()
     assert torch.isfinite(env.qpos).all() and torch.isfinite(env.qvel).all() and torch.isfinite(env._obs_buf).all()
-    # one more step, checked against the oracle
-    q0, v0, w0, fr = env.qpos.cpu().numpy().copy(), env.qvel.cpu().numpy().copy(), env._warm.cpu().numpy().copy(), env._friction.cpu().numpy().copy()
-    pend = env._terminated_b.cpu().numpy().copy()
-    act = torch.randn(n, 12, generator=g, device='cuda:0') * 15
-    env.enable_debug(n)
-    obs, rew, term, trunc, info = env.step(act)
-    torch.cuda.synchronize()
-    dbg = env.debug_internals(n, ['qacc', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
     o = Oracle(marshalled(robot, solver=1, iterations=100, tolerance=1e-12, boxes=env.scene_desc['boxes'], terrain_limits=lim))
-    dropped, tg, ig = info['contacts_dropped'].cpu().numpy(), term.cpu().numpy(), info['invalid_contacts'].cpu().numpy()
-    a = act.cpu().numpy()
-    qv = env.qvel.cpu().numpy()
-    nbox = 0
-    tally = ParityTally(env.mjModel.cone == 1, 3e-6)
-    for e in range(n):
-        if pend[e]:
-            continue   # this env spent the step on its reset
-        o.set_state(q0[e], v0[e], w0[e], np.zeros(18), 0.0, float(fr[e])); o.step(a[e].astype(np.float64))
-        cls = tally.classify(e, o, dbg[e]['nefc'][0])
-        if cls == 'budget':   # the kernel's rows are the oracle's first rows, the flags the oracle's, and the caller is told what was cut
-            tally.check_budget_prefix(e, o, dbg[e]['nefc'][0], dbg[e]['efc_J'], dbg[e]['efc_R'], dbg[e]['efc_aref'], (tg[e], ig[e]))
-            assert int(dropped[e]) == o.ncon - int(dbg[e]['ncon'][0]) > 0, (e, int(dropped[e]), o.ncon, int(dbg[e]['ncon'][0]))
-        if cls != 'ok':
-            continue
-        assert int(dropped[e]) == 0, (e, int(dropped[e]))
-        nbox += int((np.abs(o.contact_frame[:, 0, 2] - 1.0) > 1e-9).sum() + (np.abs(o.contact_pos[:, 2]) > 5e-3).sum()) if o.ncon else 0
-        assert np.abs(dbg[e]['qacc'] - o.qacc).max() < 3e-4 * max(1.0, np.abs(o.qacc).max()), e
-        assert np.abs(qv[e] - o.qvel).max() < 1e-3
-    tally.finish(f'box scene one-step parity {robot} {scene}', min_checked=0.7, max_tie=0.15, max_budget=0.1)
+    nbox = _one_more_step_against_oracle(env, o, g, f'box scene one-step parity {robot} {scene}',
+                                         lambda: int((np.abs(o.contact_frame[:, 0, 2] - 1.0) > 1e-9).sum() + (np.abs(o.contact_pos[:, 2]) > 5e-3).sum()))
     assert nbox > 0
 
 
@@ -693,29 +678,18 @@ def test_pgs_on_world_geoms_and_self_collision_matches_oracle_pgs(scene):
     fr = env._friction.cpu().numpy().copy()
     act = torch.randn(n, 12, generator=g, device='cuda:0') * 20
     obs, _, term, _, info = env.step(act)
-    torch.cuda.synchronize()
-    dbgs = env.debug_internals(n, ['nefc', 'ncon', 'qacc', 'efc_J', 'efc_aref'])
+    kern = gpu_records(env, n, ['nefc', 'ncon', 'qacc', 'efc_J', 'efc_aref'])
     o = Oracle(env._mm)
-    a = act.cpu().numpy().astype(np.float64)
-    checked = world = 0
+    a = act.cpu().numpy()
+    world = 0
+    tally = ParityTally(False, 3e-6, lenient_rows=True)
     for e in range(n):
-        o.set_state(q0[e], v0[e], w0[e], np.zeros(18), 0.0, float(fr[e])); o.step(a[e])
-        d = dbgs[e]
-        ne = int(d['nefc'][0])
-        if (o.ncon and o.get('contact_tiegap').min() < 3e-6) or ne != o.nefc:
-            assert ne <= o.nefc
+        if tally.step_env(e, o, (q0[e], v0[e], w0[e], np.zeros(18), 0.0, float(fr[e])), a[e], kern[e], sp.TERRAIN_PGS_STEP_GPU, mass=env.mjModel.total_mass) != 'ok':
+            assert int(kern[e]['nefc'][0]) <= o.nefc
             continue
-        checked += 1
         world += int((np.abs(o.contact_frame[:, 0, 2] - 1.0) > 1e-6).sum()) if o.ncon else 0
-        np.testing.assert_allclose(d['efc_J'].reshape(64, 18)[:ne], o.efc_J, atol=3e-5 * max(1.0, np.abs(o.efc_J).max()))
-        np.testing.assert_allclose(d['efc_aref'][:ne], o.efc_aref, atol=3e-4 * max(1.0, np.abs(o.efc_aref).max()))
-        assert np.abs(d['qacc'] - o.qacc).max() < 3e-4 * max(1.0, np.abs(o.qacc).max()), e
-        ref, t, inv = o.get_obs(ALL_OBS, np.zeros(4))
-        for k in ('contact_forces', 'contact_state'):
-            got = obs[k][e].cpu().numpy().reshape(-1)
-            assert np.abs(got - np.asarray(ref[k]).reshape(-1)).max() < 1e-2 * max(1.0, np.abs(ref[k]).max(), 0.1 * 9.81 * env.mjModel.total_mass), (e, k)
-        assert bool(term[e]) == t
-    assert checked >= n // 2 and world >= 8, (checked, world)
+    tally.finish_count(f'PGS on world geoms {scene}', n // 2)
+    assert world >= 8, world
     env.close()
     big = QuadrupedEnv('aliengo', scene=scene, state_obs_names=ALL_OBS, num_envs=1024, device='cuda:0', solver='pgs', self_collision=True,
                        auto_reset='next_step', seed=2)
@@ -773,35 +747,8 @@ def test_perlin_scene_contract_and_parity(robot):
     ground = np.array([_hfield_height(hf, q[e, 0], q[e, 1]) for e in range(n)])
     assert np.all(q[:, 2] > ground - 0.05), 'a robot fell through the terrain'
     assert float(obs['contact_state'].float().mean()) > 0.03                     # feet on the hills (most robots are mid-fall after a respawn)
-    # one more step, checked against the oracle
-    q0, v0, w0, fr = env.qpos.cpu().numpy().copy(), env.qvel.cpu().numpy().copy(), env._warm.cpu().numpy().copy(), env._friction.cpu().numpy().copy()
-    pend = env._terminated_b.cpu().numpy().copy()
-    act = torch.randn(n, 12, generator=g, device='cuda:0') * 15
-    env.enable_debug(n)
-    obs, rew, term, trunc, info = env.step(act)
-    torch.cuda.synchronize()
-    dbg = env.debug_internals(n, ['qacc', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
     o = Oracle(marshalled(robot, solver=1, iterations=100, tolerance=1e-12, hfield=hf, terrain_limits=lim))
-    dropped, tg, ig = info['contacts_dropped'].cpu().numpy(), term.cpu().numpy(), info['invalid_contacts'].cpu().numpy()
-    a = act.cpu().numpy()
-    qv = env.qvel.cpu().numpy()
-    nhf = 0
-    tally = ParityTally(env.mjModel.cone == 1, 3e-6)
-    for e in range(n):
-        if pend[e]:
-            continue
-        o.set_state(q0[e], v0[e], w0[e], np.zeros(18), 0.0, float(fr[e])); o.step(a[e].astype(np.float64))
-        cls = tally.classify(e, o, dbg[e]['nefc'][0])
-        if cls == 'budget':   # the kernel's rows are the oracle's first rows, the flags the oracle's, and the caller is told what was cut
-            tally.check_budget_prefix(e, o, dbg[e]['nefc'][0], dbg[e]['efc_J'], dbg[e]['efc_R'], dbg[e]['efc_aref'], (tg[e], ig[e]))
-            assert int(dropped[e]) == o.ncon - int(dbg[e]['ncon'][0]) > 0, (e, int(dropped[e]), o.ncon, int(dbg[e]['ncon'][0]))
-        if cls != 'ok':
-            continue
-        assert int(dropped[e]) == 0, (e, int(dropped[e]))
-        nhf += int((np.abs(o.contact_frame[:, 0, 2] - 1.0) > 1e-9).sum()) if o.ncon else 0
-        assert np.abs(dbg[e]['qacc'] - o.qacc).max() < 3e-4 * max(1.0, np.abs(o.qacc).max()), e
-        assert np.abs(qv[e] - o.qvel).max() < 1e-3
-    tally.finish(f'perlin one-step parity {robot}', min_checked=0.7, max_tie=0.15, max_budget=0.1)
+    nhf = _one_more_step_against_oracle(env, o, g, f'perlin one-step parity {robot}', lambda: int((np.abs(o.contact_frame[:, 0, 2] - 1.0) > 1e-9).sum()))
     assert nhf > n // 4, nhf
     # HeightMap: vertical rays against the same surface
     hm = HeightMap(num_rows=5, num_cols=5, dist_x=0.1, dist_y=0.1, mj_model=env.mjModel, mj_data=env)
@@ -883,34 +830,23 @@ def test_robot_self_collision_step_parity(robot):
     env._cmd.copy_(torch.as_tensor(cmd)); env._friction.fill_(0.8)
     env.enable_debug(n)
     obs, rew, term, trunc, info = env.step(torch.as_tensor(ctrl))
-    torch.cuda.synchronize()
-    dbg = env.debug_internals(n, ['qacc', 'niter', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
-    qp, qv, ob = env.qpos.cpu().numpy(), env.qvel.cpu().numpy(), env._obs_buf.cpu().numpy()
-    tg, ig = term.cpu().numpy(), info['invalid_contacts'].cpu().numpy()
-    dropped = info['contacts_dropped'].cpu().numpy()
+    kern = gpu_records(env, n, ['qacc', 'niter', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
     tally = ParityTally(cone, 3e-7)
     nself = ncross = 0
     leg = lambda b: (b - 2) // 3 if b >= 2 else -1
     ea, ev = [], []
     for e in range(n):
-        o.set_state(qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8); o.step(ctrl[e].astype(np.float64))
-        cls = tally.classify(e, o, dbg[e]['nefc'][0])
-        if cls == 'budget':   # held to the prefix rule like everywhere else, and reported to the caller
-            tally.check_budget_prefix(e, o, dbg[e]['nefc'][0], dbg[e]['efc_J'], dbg[e]['efc_R'], dbg[e]['efc_aref'], (tg[e], ig[e]))
-            assert int(dropped[e]) == o.ncon - int(dbg[e]['ncon'][0]) > 0, (e, int(dropped[e]), o.ncon, int(dbg[e]['ncon'][0]))
-        if cls != 'ok':
+        # (over the budget: held to the prefix rule like everywhere else, and reported to the caller; the observables of SELF_STEP_GPU: robot-robot
+        # contacts set no foot contact state and no termination)
+        k = kern[e]
+        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8), ctrl[e], k, sp.SELF_STEP_GPU, prefix=True, cmd=cmd[e]) != 'ok':
             continue
-        assert int(dbg[e]['ncon'][0]) == o.ncon and int(dropped[e]) == 0
         b1, b2 = o.get('contact_body1').astype(int), o.get('contact_body').astype(int)
         nself += int((b1 > 0).any()); ncross += int(any(x > 0 and leg(x) >= 0 and leg(x) != leg(y) for x, y in zip(b1, b2)))
-        ea.append(np.abs(dbg[e]['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
-        ev.append(np.abs(qv[e] - o.qvel).max() / max(1.0, 0.002 * np.abs(o.qacc).max()))   # relative to the step's velocity change once that exceeds 1
+        ea.append(np.abs(k['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
+        ev.append(np.abs(k['qvel'] - o.qvel).max() / max(1.0, 0.002 * np.abs(o.qacc).max()))   # relative to the step's velocity change once that exceeds 1
         # deeply interpenetrating random states reach |qacc| of 1e5 rad/s^2: the position error is dt^2 times the (relative) qacc error
-        assert np.abs(qp[e] - o.qpos).max() < 3.5e-6 + 4e-6 * (2e-4 if cone else 2e-5) * max(1.0, np.abs(o.qacc).max())
-        ref, t, inv = o.get_obs(ALL_OBS, cmd[e]); got = split_obs(ob[e], ALL_OBS)
-        for k in ('contact_state', 'feet_vel', 'base_lin_acc'):   # robot-robot contacts set no foot contact state and no termination
-            assert np.abs(got[k] - ref[k]).max() < 5e-3 * max(1.0, np.abs(ref[k]).max()), (e, k)
-        assert bool(tg[e]) == t and bool(ig[e]) == inv
+        assert np.abs(k['qpos'] - o.qpos).max() < 3.5e-6 + 4e-6 * (2e-4 if cone else 2e-5) * max(1.0, np.abs(o.qacc).max())
     p99 = lambda x: float(np.percentile(x, 99))
     assert p99(ea) < (1e-4 if cone else 2e-5) * 5 and max(ea) < 2e-3, (p99(ea), max(ea))
     assert p99(ev) < (7e-4 if cone else 5e-5) * 5 and max(ev) < 5e-3, (p99(ev), max(ev))
@@ -924,8 +860,7 @@ def test_robot_self_collision_step_parity(robot):
 def test_newton_ends_on_captured_hard_states(robot):
     """The captured go1 states of tests/golden/newton_stagnation_go1.npz (see the emulated twin of this test): the solve
     ends far below the iteration cap, at the oracle's solution."""
-    from pathlib import Path
-    z = np.load(Path(__file__).parent / 'golden' / f'newton_stagnation_{robot}.npz')
+    z = sp.hard_states(robot)
     n = len(z['qpos'])
     env = _make_env(n, solver='newton', iters=100, tol=1e-8, robot=robot)
     env.reset(qpos=z['qpos'], qvel=z['qvel'])
@@ -935,14 +870,7 @@ def test_newton_ends_on_captured_hard_states(robot):
     env.enable_debug(n)
     env.step(torch.as_tensor(z['ctrl']))
     torch.cuda.synchronize()
-    d = env.debug_internals(n, ['niter', 'qacc'])
-    o = _oracle(env)
-    for e in range(n):
-        o.set_state(z['qpos'][e], z['qvel'][e].astype(np.float64), z['warm'][e].astype(np.float64), z['applied'][e].astype(np.float64), 0.0, float(z['friction'][e]))
-        o.step(z['ctrl'][e].astype(np.float64))
-        assert d[e]['niter'][0] <= 20, (e, d[e]['niter'][0], o.solver_niter)
-        qa = np.array(o.qacc)
-        assert np.abs(d[e]['qacc'] - qa).max() <= 2e-5 * max(1.0, np.abs(qa).max()), e
+    sp.hold_hard_states(z, _oracle(env), env.debug_internals(n, ['niter', 'qacc']))
 
 
 @pytest.mark.parametrize('robot,scene', [('mini_cheetah', 'flat'), ('go2', 'flat'), ('aliengo', 'flat'), ('hyqreal1', 'flat'), ('b2', 'flat'),
@@ -965,27 +893,21 @@ def test_step_parity_on_benchmark_rollout_states(robot, scene):
     a = torch.randn(n, 12, generator=g, device='cuda') * 50
     env.enable_debug(n)
     env.step(a)
-    torch.cuda.synchronize()
     ctrl = a.cpu().numpy()
-    d = env.debug_internals(int(idx.max()) + 1, ['qacc', 'nefc', 'ncon', 'niter', 'efc_J', 'efc_R', 'efc_aref'])
-    qv = env.qvel.cpu().numpy()
-    tg, ig = env._terminated.cpu().numpy(), env._invalid.cpu().numpy()
-    dropped = env._contacts_dropped.cpu().numpy()
+    d = gpu_records(env, int(idx.max()) + 1, ['qacc', 'nefc', 'ncon', 'niter', 'efc_J', 'efc_R', 'efc_aref'])
     o = _oracle(env)
     cone = env.mjModel.cone == 1
     tally = ParityTally(cone, 3e-7 if scene == 'flat' else 3e-6)
     ea, ev, nit = [], [], []
     for e in idx:
-        o.set_state(qpos[e], qvel[e].astype(np.float64), warm[e].astype(np.float64), app[e].astype(np.float64), 0.0, float(fr[e]))
-        o.step(ctrl[e].astype(np.float64))
-        cls = tally.classify(e, o, d[e]['nefc'][0])
+        cls = tally.step_env(e, o, (qpos[e], qvel[e], warm[e], app[e], 0.0, float(fr[e])), ctrl[e], d[e], sp.CONTACT_COUNT)
         if cls == 'budget':
-            tally.check_budget_prefix(e, o, d[e]['nefc'][0], d[e]['efc_J'], d[e]['efc_R'], d[e]['efc_aref'], (tg[e], ig[e]))
+            tally.check_budget_prefix(e, o, d[e])
         if cls != 'ok':
             continue
-        assert int(d[e]['ncon'][0]) == o.ncon and int(dropped[e]) == 0   # the benchmark's states are played with every contact
+        assert d[e]['dropped'] == 0   # the benchmark's states are played with every contact
         ea.append(np.abs(d[e]['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
-        ev.append(np.abs(qv[e] - o.qvel).max() / max(1.0, 0.002 * np.abs(o.qacc).max()))
+        ev.append(np.abs(d[e]['qvel'] - o.qvel).max() / max(1.0, 0.002 * np.abs(o.qacc).max()))
         nit.append((int(d[e]['niter'][0]), o.solver_niter))
     p99 = lambda x: float(np.percentile(x, 99))
     tally_note(f'benchmark-state errors {robot} {scene}: qacc rel p50 {np.median(ea):.2e} p99 {p99(ea):.2e} max {max(ea):.2e}; qvel p99 {p99(ev):.2e} max {max(ev):.2e}; '
