@@ -68,6 +68,19 @@ def emu_lib():
     return _EMU
 
 
+_PROBE = None
+
+
+def probe_lib():
+    """tests/device_probe: the product's device routines behind one C entry point each, built with the product's device flags"""
+    global _PROBE
+    if _PROBE is None:
+        d = ROOT / 'tests' / 'device_probe'
+        subprocess.run(['make', '-s', '-C', str(d)], check=True, capture_output=True)
+        _PROBE = C.CDLL(str(d / 'libgq_probe.so'))
+    return _PROBE
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 

@@ -89,7 +89,7 @@ static inline int imax(int a, int b) { return a > b ? a : b; }
 #define __builtin_amdgcn_exp2f(x) exp2f(x)   /* v_exp_f32 / v_log_f32 (gq_camera.h cam_pow) */
 #define __builtin_amdgcn_logf(x) log2f(x)
 static inline float fast_rcp(float x) { return 1.0f / x; }
-static inline float fast_rsqrt(float x) { return 1.0f / std::sqrt(x); }
+static inline float fast_rsqrt(float x) { return (float)(1.0 / std::sqrt((double)x)); } /* one rounding, like v_rsq_f32's 1 ulp: 1.0f / sqrtf(x) rounds twice, up to 1.5 ulp */
 static inline float fdiv(float a, float b) { return a / b; }
 static inline float fast_sqrt(float x) { return std::sqrt(x); }
 static inline float fast_cos_turns(float x) { return std::cos(6.283185307179586f * x); }

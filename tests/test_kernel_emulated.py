@@ -614,63 +614,10 @@ def test_pair_routines_kernel_equals_oracle():
     """csrc/gq_pairs.h (capsule_box, box_box: fp32, called directly under the emulator) against the oracle's restatement
     (oracle/gq_oracle.c, fp64) on random and on resting configurations: same number of points, same order, distances /
     positions / normals to fp32 accuracy.  The oracle versions are pinned against brute-force geometry in
-    tests/test_oracle_invariants.py."""
-    import ctypes as C
-    from scipy.spatial.transform import Rotation
-    from helpers import emu_lib
-    from test_oracle_invariants import _pair_lib, _np_ptr
-    Lo, Le = _pair_lib(), emu_lib()
-    P = C.c_void_p
-    Le.emu_capsule_box.argtypes = [P, P, C.c_float, P, P, P, C.c_float, P]
-    Le.emu_box_box.argtypes = [P, P, P, P, P, P, C.c_float, P]
-    rng = np.random.default_rng(12)
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    ncap = nbox = multi = 0
-    for trial in range(1500):
-        h = rng.uniform(0.02, 0.3, 3); R = Rotation.random(random_state=int(rng.integers(1 << 30))).as_matrix(); c = rng.uniform(-1, 1, 3)
-        margin = 0.001
-        if trial % 2 == 0:   # capsule - box
-            r = rng.uniform(0.005, 0.05)
-            if trial % 8 == 0:
-                a = np.array([rng.uniform(-h[0], h[0]), rng.uniform(-h[1], h[1]), h[2] + r + rng.uniform(-0.002, 0.0005)])
-                b = np.array([rng.uniform(-h[0], h[0]), rng.uniform(-h[1], h[1]), a[2] + rng.uniform(-2e-4, 2e-4)])
-                p0, p1 = c + R @ a, c + R @ b
-            else:
-                p0 = c + R @ (rng.uniform(-1.3, 1.3, 3) * h); p1 = p0 + rng.normal(0, 0.1, 3)
-            # fp32 inputs for both, so that the comparison is about the arithmetic only
-            p0, p1, cc, Rc, hc = (f32(x).astype(np.float64) for x in (p0, p1, c, R, h))
-            rr = float(np.float32(r))
-            oo, oe = np.zeros(28), np.zeros(28, np.float32)
-            Rc = np.ascontiguousarray(Rc)
-            fa = [f32(x) for x in (p0, p1, cc, Rc, hc)]   # keep the fp32 copies alive across the call
-            no = Lo.gqo_test_capsule_box(_np_ptr(p0), _np_ptr(p1), rr, _np_ptr(cc), _np_ptr(Rc), _np_ptr(hc), margin, _np_ptr(oo))
-            ne = Le.emu_capsule_box(_np_ptr(fa[0]), _np_ptr(fa[1]), rr, _np_ptr(fa[2]), _np_ptr(fa[3]), _np_ptr(fa[4]), margin, _np_ptr(oe))
-            ncap += no > 0
-        else:
-            hb = rng.uniform(0.02, 0.3, 3)
-            if trial % 6 == 1:
-                hb[:2] = rng.uniform(0.2, 0.9, 2) * h[:2]
-                Rb = R @ Rotation.from_euler('z', rng.uniform(-0.3, 0.3)).as_matrix()
-                cb = c + R @ np.array([*(rng.uniform(-0.05, 0.05, 2) * h[:2]), h[2] + hb[2] + rng.uniform(-0.003, 0.0008)])
-            else:
-                Rb = Rotation.random(random_state=int(rng.integers(1 << 30))).as_matrix()
-                cb = c + rng.normal(0, 1, 3) * (h + hb) * 0.8
-            cc, Rc, hc, cb, Rb, hb = (f32(x).astype(np.float64) for x in (c, R, h, cb, Rb, hb))
-            oo, oe = np.zeros(28), np.zeros(28, np.float32)
-            Rc, Rb = np.ascontiguousarray(Rc), np.ascontiguousarray(Rb)
-            fa = [f32(x) for x in (cc, Rc, hc, cb, Rb, hb)]
-            no = Lo.gqo_test_box_box(_np_ptr(cc), _np_ptr(Rc), _np_ptr(hc), _np_ptr(cb), _np_ptr(Rb), _np_ptr(hb), margin, _np_ptr(oo))
-            ne = Le.emu_box_box(_np_ptr(fa[0]), _np_ptr(fa[1]), _np_ptr(fa[2]), _np_ptr(fa[3]), _np_ptr(fa[4]), _np_ptr(fa[5]), margin, _np_ptr(oe))
-            nbox += no > 0
-        if no and abs(oo[0::7][:no]).max() > 0.02:
-            continue   # centimetres of overlap: decisions between nearly equal axes / deepest samples may differ; contacts are created at the margin
-        assert no == ne, (trial, no, ne, oo[:7], oe[:7])
-        multi += no > 1
-        for q in range(no):
-            assert abs(oo[7 * q] - oe[7 * q]) < 2e-6, (trial, q, oo[7 * q:7 * q + 7], oe[7 * q:7 * q + 7])
-            np.testing.assert_allclose(oe[7 * q + 1:7 * q + 4], oo[7 * q + 1:7 * q + 4], atol=5e-6, err_msg=f'trial {trial} point {q} pos')
-            np.testing.assert_allclose(oe[7 * q + 4:7 * q + 7], oo[7 * q + 4:7 * q + 7], atol=2e-4, err_msg=f'trial {trial} point {q} normal')
-    assert ncap > 100 and nbox > 100 and multi > 60, (ncap, nbox, multi)
+    tests/test_oracle_invariants.py.  Cases and asserts: tests/contact_cases.py, shared with the GPU probe."""
+    import contact_cases as cc
+    cases = cc.pair_cases()
+    cc.check_pairs(cases, cc.emu_pairs(cases))
 
 
 @pytest.mark.parametrize('robot', [None, 'mini_cheetah', 'hyqreal1', 'go1'])
@@ -680,65 +627,11 @@ def test_convex_routine_kernel_equals_oracle(robot):
     against the exact Minkowski-difference hull in tests/test_oracle_invariants.py): random polytopes and the robots' own mesh /
     cylinder clouds, against an analytic box and against each other, from 12 mm apart to 30 mm deep, with and without an inflation
     radius.  Same contacts; distance to 1e-6 m, normal to 0.1 degree, point to 2e-5 m wherever the oracle says the point is determined
-    (not face on face / edge in face) and the polytope did not run into the iteration cap both sides share."""
-    import ctypes as C
-    from scipy.spatial.transform import Rotation as Rot
-    from helpers import emu_lib
-    from test_oracle_invariants import _box_corners, _support, convex_oracle
-    Le = emu_lib()
-    P = C.c_void_p
-    Le.emu_convex.argtypes = [P, C.c_int, P, P, P, C.c_float] * 2 + [C.c_float, P]
-
-    def emu(VA, hA, RA, tA, rA, VB, hB, RB, tB, rB, margin):
-        arrs = [None if x is None else np.ascontiguousarray(x, dtype=np.float32) for x in (VA, hA, RA, tA, VB, hB, RB, tB)]
-        p = [None if a is None else a.ctypes.data_as(P) for a in arrs]
-        out = np.zeros(7, np.float32)
-        rc = Le.emu_convex(p[0], 0 if arrs[0] is None else len(arrs[0]), p[1], p[2], p[3], rA, p[4], 0 if arrs[4] is None else len(arrs[4]), p[5], p[6], p[7], rB, margin,
-                           out.ctypes.data_as(P))
-        return rc, float(out[0]), out[1:4].astype(float), out[4:7].astype(float)
-
-    rng = np.random.default_rng(0)
-    md = marshalled(robot, solver=1).md if robot else None
-    clouds = [c for c in range(len(md.cloud_vertnum)) if md.cloud_vertnum[c] >= 8] if md else None
-    cloud = lambda c: md.vert_pos[md.cloud_vertadr[c]:md.cloud_vertadr[c] + md.cloud_vertnum[c]]
-    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)   # both sides see the same (fp32) inputs
-    n = capped = deep = 0
-    for trial in range(240 if robot is None else 120):
-        if md is None:
-            VA = rng.normal(size=(rng.integers(4, 60), 3)) * rng.uniform(0.02, 0.15, size=3)
-            VB, hB = (None, rng.uniform(0.05, 0.5, size=3)) if trial % 2 == 0 else (rng.normal(size=(rng.integers(4, 60), 3)) * rng.uniform(0.02, 0.15, size=3), None)
-        else:
-            VA = cloud(clouds[trial % len(clouds)])
-            VB, hB = (None, rng.uniform(0.1, 0.6, size=3)) if trial % 2 == 0 else (cloud(clouds[int(rng.integers(len(clouds)))]), None)
-        VA = f32(VA); VB = None if VB is None else f32(VB); hB = None if hB is None else f32(hB)
-        RA, RB = (f32(Rot.random(random_state=int(rng.integers(1 << 30))).as_matrix()) for _ in range(2))
-        WA, WB0 = VA @ RA.T, (_box_corners(hB) if VB is None else VB) @ RB.T
-        u = rng.normal(size=3); u /= np.linalg.norm(u)
-        want = rng.uniform(-0.03, 0.012)
-        tB = u * (_support(WA, u) + _support(WB0, -u) + 0.05)
-        rc0, d0, _, n0, _, _ = convex_oracle(VA, None, RA, np.zeros(3), 0.0, VB, hB, RB, tB, 0.0, 10.0)
-        tB = f32(tB - (d0 - want) * n0)
-        rA = float(np.float32(rng.choice([0.0, 0.01])))
-        rc, dist, pos, nrm, git, eit = convex_oracle(VA, None, RA, np.zeros(3), rA, VB, hB, RB, tB, 0.0, 0.01)
-        rk, dk, pk, nk = emu(VA, None, RA, np.zeros(3), rA, VB, hB, RB, tB, 0.0, 0.01)
-        if rc != rk:
-            assert rc and abs(dist - 0.01) < 2e-6, (trial, rc, rk, dist)   # only a pair AT the margin may be seen by one side alone
-            continue
-        if not rc:
-            continue
-        n += 1; deep += dist < -1e-3
-        if eit >= 24:   # the shared iteration cap: both sides report the state of an unfinished iteration, which round-off steers
-            capped += 1
-            assert abs(dk - dist) < 1e-4
-            continue
-        assert abs(dk - dist) < 1e-6, (trial, dk, dist)
-        assert np.degrees(np.arccos(np.clip(nk @ nrm, -1, 1))) < 0.1, (trial, nk, nrm)
-        # the point: compared where it is determined (support sets along the normal: not two faces, a face and an edge, parallel edges)
-        WB = WB0 + tB
-        da = int((WA @ nrm > (WA @ nrm).max() - 1e-6).sum()); db = int((WB @ -nrm > (WB @ -nrm).max() - 1e-6).sum())
-        if min(da, db) == 1 or (da == 2 and db == 2):
-            assert np.linalg.norm(pk - pos) < 2e-5, (trial, pk, pos, da, db)
-    assert n >= 80 and deep >= 30 and capped <= 0.05 * n, (n, deep, capped)
+    (not face on face / edge in face) and the polytope did not run into the iteration cap both sides share.  Cases and asserts:
+    tests/contact_cases.py, shared with the GPU probe."""
+    import contact_cases as cc
+    cases = cc.convex_cases(robot)
+    cc.check_convex(cases, cc.emu_convex(cases))
 
 
 def test_capsule_proxy_mode_matches_oracle():
