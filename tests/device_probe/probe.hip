@@ -2,7 +2,8 @@
  *
  * Built with the product's own device flags (csrc/Makefile print-flags) against the product's headers, so what runs here is what the step
  * kernels inline: the DPP ladders and permutes of csrc/gq_device.h, its transcendental-unit shortcuts, the hand-written small math and the
- * tree factor / solve of csrc/gq_step_kernel.h, and the contact routines of csrc/gq_pairs.h and csrc/gq_convex.h.  The host emulator
+ * tree factor / solve of csrc/gq_step_kernel.h, the contact routines of csrc/gq_pairs.h and csrc/gq_convex.h, and the Newton solver's solves,
+ * row laws and elliptic routines of csrc/gq_newton.h (bodies in newton_probe.h, shared with the emulator).  The host emulator
  * (tests/simt_emu) shadows gq_device.h and compiles with g++, so none of this is reached by the CPU suite.
  *
  * Every entry point takes device pointers and a case count, launches once with 64-thread blocks on the null stream, synchronises and returns
@@ -13,6 +14,7 @@
 #include "gq_step_kernel.h"
 #include "gq_pairs.h"
 #include "gq_convex.h"
+#include "newton_probe.h"
 
 #define PROBE_K __global__ void __launch_bounds__(64)
 
@@ -266,5 +268,42 @@ PROBE_K k_convex(const float* vx, const float* vy, const float* vz, const float*
 }
 extern "C" int probe_convex(const float* vx, const float* vy, const float* vz, const float* desc, float margin, int npair, int32_t* hit, float* out) {
   if (npair > 0) hipLaunchKernelGGL(k_convex, dim3(npair), dim3(64), 0, 0, vx, vy, vz, desc, margin, hit, out);
+  return probe_done();
+}
+
+/* ------------------------------------------------------------------ csrc/gq_newton.h: the bodies and the argument layouts are in newton_probe.h */
+template <int MODE> PROBE_K k_newton_solve(const float* Sc, const float* Sb, const float* damping, float hd, const float* rhs, const float* rhs2, int nrhs, int alias,
+                                           float* out, float* out2, int32_t* touched) {
+  nprobe::np_solve<MODE>(blockIdx.x, threadIdx.x, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+}
+PROBE_K k_newton_dense(const float* Hc, const float* Hb, const float* J, const float* w, const int32_t* r01, const float* rhs, int nrhs, int alias, float* out, int32_t* touched) {
+  nprobe::np_dense(blockIdx.x, threadIdx.x, Hc, Hb, J, w, r01, rhs, nrhs, alias, out, touched);
+}
+PROBE_K k_newton_rows(const int32_t* rtype, const float* in, int n, float* out, int32_t* piece) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n) nprobe::np_rows(i, n, rtype, in, out, piece);
+}
+PROBE_K k_newton_ell(const int32_t* code, const int32_t* r0, const float* par, const float* alpha, int na, float* st, float* dd) {
+  nprobe::np_ell(blockIdx.x, threadIdx.x, code, r0, par, alpha, na, st, dd);
+}
+extern "C" int probe_newton_solve(int mode, const float* Sc, const float* Sb, const float* damping, float hd, const float* rhs, const float* rhs2, int nsys, int nrhs, int alias,
+                                  float* out, float* out2, int32_t* touched) {
+  if (mode < 0 || mode > 3) return -1;
+  if (nsys > 0 && nrhs > 0) {
+    if (mode == 0) hipLaunchKernelGGL(k_newton_solve<0>, dim3(nsys), dim3(64), 0, 0, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    if (mode == 1) hipLaunchKernelGGL(k_newton_solve<1>, dim3(nsys), dim3(64), 0, 0, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    if (mode == 2) hipLaunchKernelGGL(k_newton_solve<2>, dim3(nsys), dim3(64), 0, 0, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    if (mode == 3) hipLaunchKernelGGL(k_newton_solve<3>, dim3(nsys), dim3(64), 0, 0, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+  }
+  return probe_done();
+}
+extern "C" int probe_newton_dense(const float* Hc, const float* Hb, const float* J, const float* w, const int32_t* r01, const float* rhs, int nsys, int nrhs, int alias,
+                                  float* out, int32_t* touched) {
+  if (nsys > 0 && nrhs > 0) hipLaunchKernelGGL(k_newton_dense, dim3(nsys), dim3(64), 0, 0, Hc, Hb, J, w, r01, rhs, nrhs, alias, out, touched);
+  return probe_done();
+}
+extern "C" int probe_newton_rows(const int32_t* rtype, const float* in, int n, float* out, int32_t* piece) { PROBE_LANES(k_newton_rows, n, rtype, in, n, out, piece); }
+extern "C" int probe_newton_ell(const int32_t* code, const int32_t* r0, const float* par, const float* alpha, int npat, int na, float* st, float* dd) {
+  if (npat > 0) hipLaunchKernelGGL(k_newton_ell, dim3(npat), dim3(64), 0, 0, code, r0, par, alpha, na, st, dd);
   return probe_done();
 }

@@ -1,9 +1,11 @@
 /* TEST INFRASTRUCTURE - the emulator shim's wave primitives and fast-math stand-ins (gq_device.h in this directory) and the kernel's small math
  * (csrc/gq_step_kernel.h, compiled against the shim) behind the entry points of tests/device_probe/probe.hip, on host memory: the same case
- * tables (tests/device_cases.py) pin the shim and the hardware to the same float64 references. */
+ * tables (tests/device_cases.py) pin the shim and the hardware to the same float64 references.  The Newton solver's routines (csrc/gq_newton.h,
+ * tests/newton_cases.py) run through the bodies of tests/device_probe/newton_probe.h, the ones the probe launches. */
 #include <functional>
 #include "gq_device.h"
 #include "gq_step_kernel.h"
+#include "newton_probe.h"
 
 void emu_run_wave(unsigned block, unsigned nblocks, const std::function<void()>& body);
 
@@ -78,4 +80,29 @@ extern "C" int emu_philox(const uint32_t* ck, int n, uint32_t* words, float* nor
     normal[i] = gq::philox_normal(c[0], c[1], c[2], c[3], c[4], c[5]);
   }
   return 0;
+}
+
+/* ------------------------------------------------------------------ csrc/gq_newton.h (argument layouts: tests/device_probe/newton_probe.h) */
+extern "C" int emu_newton_solve(int mode, const float* Sc, const float* Sb, const float* damping, float hd, const float* rhs, const float* rhs2, int nsys, int nrhs, int alias,
+                                float* out, float* out2, int32_t* touched) {
+  if (mode < 0 || mode > 3) return -1;
+  if (nrhs <= 0) return 0;
+  return waves(nsys, [&](int, int b, int l) {
+    if (mode == 0) nprobe::np_solve<0>(b, l, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    else if (mode == 1) nprobe::np_solve<1>(b, l, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    else if (mode == 2) nprobe::np_solve<2>(b, l, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+    else nprobe::np_solve<3>(b, l, Sc, Sb, damping, hd, rhs, rhs2, nrhs, alias, out, out2, touched);
+  });
+}
+extern "C" int emu_newton_dense(const float* Hc, const float* Hb, const float* J, const float* w, const int32_t* r01, const float* rhs, int nsys, int nrhs, int alias,
+                                float* out, int32_t* touched) {
+  if (nrhs <= 0) return 0;
+  return waves(nsys, [&](int, int b, int l) { nprobe::np_dense(b, l, Hc, Hb, J, w, r01, rhs, nrhs, alias, out, touched); });
+}
+extern "C" int emu_newton_rows(const int32_t* rtype, const float* in, int n, float* out, int32_t* piece) {
+  for (int i = 0; i < n; i++) nprobe::np_rows(i, n, rtype, in, out, piece);
+  return 0;
+}
+extern "C" int emu_newton_ell(const int32_t* code, const int32_t* r0, const float* par, const float* alpha, int npat, int na, float* st, float* dd) {
+  return waves(npat, [&](int, int b, int l) { nprobe::np_ell(b, l, code, r0, par, alpha, na, st, dd); });
 }

@@ -12,7 +12,9 @@ import pytest
 
 import contact_cases as cc
 import device_cases as dc
+import newton_cases as nc
 from helpers import ROOT, probe_lib
+from newton_first_step import REPORT_KEY
 
 pytestmark = pytest.mark.gpu
 
@@ -31,9 +33,11 @@ def report():
     path = os.environ.get('GQ_PROBE_REPORT', str(ROOT / 'profiles' / 'device_probe_report.txt'))
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
+        # the first-step lines are tests/test_gpu_parity.py's (newton_first_step.merge_report): kept, whichever module ran first
+        kept = [ln for ln in open(path).read().splitlines() if ln.startswith(REPORT_KEY)] if os.path.exists(path) else []
         with open(path, 'w') as fh:
             fh.write('Device probe: the routines called alone on the GPU against float64 references (tests/test_gpu_device_probe.py)\n')
-            fh.write('\n'.join(lines) + '\n')
+            fh.write('\n'.join(lines + kept) + '\n')
     except OSError:
         pass
 
@@ -44,10 +48,11 @@ def _note(report, lines):
         report.append(line)
 
 
-@pytest.mark.parametrize('name', list(dc.CHECKS) + ['tree'])
+@pytest.mark.parametrize('name', list(dc.CHECKS) + ['tree'] + list(nc.CHECKS))
 def test_device_matches_float64_reference(be, report, name):
-    """wave primitives, fast math, small math, Philox, tree factor / solve: see the check of that name in tests/device_cases.py"""
-    check = dc.check_tree if name == 'tree' else dc.CHECKS[name]
+    """wave primitives, fast math, small math, Philox, tree factor / solve: see the check of that name in tests/device_cases.py; the Newton
+    solver's fused solves, dense step, row laws and elliptic routines: tests/newton_cases.py"""
+    check = dc.check_tree if name == 'tree' else (nc.CHECKS[name] if name in nc.CHECKS else dc.CHECKS[name])
     try:
         rows = check(be)
     except AssertionError as e:

@@ -3,11 +3,14 @@ qpos / qvel / ctrl.  Tolerances are fp32-vs-fp64 with the same PGS iteration cou
   stage internals (M, bias, J, aref, R) rel 1e-4; constraint forces 2e-3 of the largest force;
   qacc 1e-3 * max|qacc| ; one-step qvel 1e-4 + 1e-5*|.| ; qpos 1e-6 ; observations 2e-3 * max(1, |obs|).
 """
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from helpers import budgeted_states, oracle_fits_row_budget, ALL_OBS, marshalled, random_states, self_contact_states, split_obs, tally_note
+from helpers import ROOT, budgeted_states, oracle_fits_row_budget, ALL_OBS, marshalled, random_states, self_contact_states, split_obs, tally_note
+import newton_first_step as nfs
 import step_parity as sp
 from step_parity import ParityTally, gpu_records
 
@@ -946,3 +949,31 @@ def test_pair_exchange_is_bit_identical(mode):
         env.close()
     assert torch.isfinite(out[0][0]).all()
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1]) and torch.equal(out[0][2], out[1][2])
+
+
+@pytest.fixture(scope='module')
+def first_step_notes():
+    """the measured lines of the first-step test, merged into the device probe's report when the module is done (one line per configuration)"""
+    notes = []
+    yield notes
+    if notes:
+        try:
+            nfs.merge_report(os.environ.get('GQ_PROBE_REPORT', str(ROOT / 'profiles' / 'device_probe_report.txt')), notes)
+        except OSError:   # a read-only checkout: the lines are printed and in the tally file
+            pass
+
+
+@pytest.mark.parametrize('robot,kind', nfs.CONFIGS)
+def test_first_newton_step_solves_the_exact_hessian(robot, kind, first_step_notes):
+    """One Newton iteration on the GPU (solver_iterations=1; tests/newton_first_step.py): qacc - qacc_smooth solves H d = -alpha g for the float64
+    Hessian of the kernel's own rows - what the converged minimiser of the parity tests above does not depend on."""
+    o = nfs.oracle_for(robot)
+    qpos, qvel, ctrl = nfs.draw_states(robot, kind, o)
+    n = len(qpos)
+    env = _make_env(n, iters=1, tol=1e-8, solver='newton', robot=robot)
+    env._qpos.copy_(torch.as_tensor(qpos)); env._qvel.copy_(torch.as_tensor(qvel)); env._warm.zero_(); env._friction.fill_(nfs.FRICTION)
+    env.enable_debug(n)
+    env.step(torch.as_tensor(ctrl))
+    kern = gpu_records(env, n, nfs.NAMES)
+    env.close()
+    nfs.hold_first_step(robot, kind, o, qpos, qvel, ctrl, kern, 'GPU', notes=first_step_notes)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from helpers import ALL_OBS, dbg, oracle_fits_row_budget, default_reset_cfg, emu_reset, emu_step, marshalled, oracle_fits_self_budget, oracle_reset_lift, random_states, self_contact_states, split_obs
+import newton_first_step as nfs
 import step_parity as sp
 from step_parity import ParityTally, emu_record
 from oracle.oracle import Oracle
@@ -689,3 +690,16 @@ def test_pair_exchange_changes_nothing(robot):
     for e in range(n):
         for f in ('ncon', 'nefc', 'efc_J', 'efc_aref', 'contact_dist', 'contact_geom', 'qacc'):
             assert np.array_equal(dbg(a['debug'][e], f), dbg(b['debug'][e], f)), (e, f)
+
+
+@pytest.mark.parametrize('robot,kind', nfs.CONFIGS)
+def test_first_newton_step_solves_the_exact_hessian(robot, kind):
+    """One Newton iteration of the kernel (tests/newton_first_step.py): qacc - qacc_smooth solves H d = -alpha g for the float64 Hessian of the
+    kernel's own rows - the assembly, the middle-zone virtual rows and the tree-sparse, Sherman-Morrison or dense solve, which the minimiser
+    that the parity tests compare does not depend on."""
+    o = nfs.oracle_for(robot)
+    qpos, qvel, ctrl = nfs.draw_states(robot, kind, o)
+    n = len(qpos)
+    mm = marshalled(robot, solver=1, iterations=1, tolerance=1e-8, noise_floor=0.0)
+    st = emu_step(mm, ctrl, qpos.copy(), qvel.copy(), debug_envs=n, friction=np.full(n, nfs.FRICTION, np.float32))
+    nfs.hold_first_step(robot, kind, o, qpos, qvel, ctrl, [emu_record(st, e) for e in range(n)], 'emulated')
