@@ -119,6 +119,12 @@ class GqMailboxView(C.Structure):
                 ('n_queues', C.c_int32), ('queue_capacity', C.c_int32), ('counter_stride', C.c_int32), ('xcc_queue', C.c_int32 * 16)]
 
 
+class GqJointCmd(C.Structure):
+    """gq_step_joint_cmd's command block; ``struct_size`` must hold ``sizeof(GqJointCmd)`` (the library refuses a stale layout)."""
+    _fields_ = [('struct_size', C.c_int32), ('gain_stride', C.c_int32), ('q_des', C.c_void_p), ('qd_des', C.c_void_p), ('tau_ff', C.c_void_p),
+                ('kp', C.c_void_p), ('kd', C.c_void_p), ('tau_out', C.c_void_p), ('terminated_any', C.c_void_p)]
+
+
 class GqResampleCfg(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('cmd_reset', C.c_int32), ('dist_reset', C.c_int32), ('dist_kind', C.c_int32 * 6),
                 ('dist_range', (C.c_float * 2) * 6), ('env_id_offset', C.c_int32)]

@@ -92,6 +92,10 @@ struct GqBatch {
     hipStream_t stream; hipEvent_t fork, join;
     bool ready;
   } mb;
+  /* gq_step_joint_cmd: device block of the call's command pointers (StepCall::policy, tagged) and the host's copy of what it holds */
+  gq::JointCmdDev* jc_dev;
+  gq::JointCmdDev jc_shadow;
+  bool jc_valid;
 };
 
 /* the launches must be issued with the batch's device current (the caller's stream belongs to it); restore the caller's
@@ -213,6 +217,7 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
   HIP_TRY_OR_DESTROY(hipHostMalloc(&b->staging, sizeof(gq::FusedArgs) * GQ_ARG_SLOTS, hipHostMallocDefault), gq_batch_destroy(b));
   b->staging_next = 0; b->shadow_valid = false;
   HIP_TRY_OR_DESTROY(hipHostMalloc(&b->batch_staging, sizeof(GqDevBatch) * GQ_ARG_SLOTS, hipHostMallocDefault), gq_batch_destroy(b));
+  HIP_TRY_OR_DESTROY(hipMalloc(&b->jc_dev, sizeof(gq::JointCmdDev)), gq_batch_destroy(b));
   b->batch_staging_next = 0; b->batch_dirty = false;
   std::memset(&b->shadow, 0, sizeof b->shadow);
   *out = b;
@@ -237,7 +242,7 @@ int gq_batch_destroy(GqBatch* b) {
   if (!b) return GQ_OK;
   DeviceGuard guard(b->model->device);
   hipFree(b->p.batch); hipFree(b->p.friction_next); hipFree(b->p.pending); hipFree(b->p.lift_pending); hipFree(b->p.load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
-  hipFree(b->cam_rec); hipFree(b->cam_pos); hipFree(b->cam_grec);
+  hipFree(b->cam_rec); hipFree(b->cam_pos); hipFree(b->cam_grec); hipFree(b->jc_dev);
   if (b->staging) hipHostFree(b->staging);
   if (b->batch_staging) hipHostFree(b->batch_staging);
   mailbox_free(b);
@@ -616,6 +621,41 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   }
   HIP_TRY(hipGetLastError());
   if (pd) HIP_TRY(hipStreamWaitEvent(stream, b->mb.join, 0)); /* the caller's stream resumes when both kernels are done */
+  return GQ_OK;
+}
+
+int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                      int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
+  if (!cmd) { SET_ERR("gq_step_joint_cmd: bad argument"); return GQ_EINVAL; }
+  if (cmd->struct_size != (int32_t)sizeof(GqJointCmd)) { SET_ERR("gq_step_joint_cmd: GqJointCmd.struct_size is %d, this library's struct has %d bytes: stale binding", cmd->struct_size, (int)sizeof(GqJointCmd)); return GQ_EINVAL; }
+  if (!b) { SET_ERR("gq_step_joint_cmd: bad argument"); return GQ_EINVAL; }
+  if (decimation < 1) { SET_ERR("gq_step_joint_cmd: decimation must be >= 1 (got %d)", decimation); return GQ_EINVAL; }
+  if (!cmd->q_des || !cmd->kp || !cmd->kd) { SET_ERR("gq_step_joint_cmd: q_des, kp and kd must be given"); return GQ_EINVAL; }
+  if (cmd->gain_stride != 0 && cmd->gain_stride != 12) { SET_ERR("gq_step_joint_cmd: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", cmd->gain_stride); return GQ_EINVAL; }
+  if (auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("gq_step_joint_cmd needs next-step auto-reset or none"); return GQ_EINVAL; }
+  if (b->model->host.solver != 1) { SET_ERR("gq_step_joint_cmd needs the Newton solver (solver = 1)"); return GQ_EINVAL; }
+  if (b->host.debug_envs > 0 || b->stop_stage != 0) { SET_ERR("gq_step_joint_cmd runs the production kernel: switch the inspection record / stage cut off first"); return GQ_EINVAL; }
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int rc = step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_step_joint_cmd"); /* validate + bind */
+  if (rc != GQ_OK) return rc;
+  DeviceGuard guard(b->model->device);
+  /* the command pointers travel in a device block of their own: uploaded, stream-ordered, only when one of them changed */
+  gq::JointCmdDev J = b->jc_shadow; /* struct copy keeps padding bytes identical for the memcmp */
+  J.q_des = cmd->q_des; J.qd_des = cmd->qd_des; J.tau_ff = cmd->tau_ff; J.kp = cmd->kp; J.kd = cmd->kd;
+  J.tau_out = cmd->tau_out; J.term_any = cmd->terminated_any; J.gain_stride = cmd->gain_stride; J.pad_ = 0;
+  if (!b->jc_valid || std::memcmp(&J, &b->jc_shadow, sizeof J) != 0) {
+    static_assert(sizeof(gq::JointCmdDev) <= sizeof(gq::FusedArgs), "the command block travels through a staging slot of the argument ring");
+    if (b->staging_next == GQ_ARG_SLOTS) { HIP_TRY(hipStreamSynchronize(stream)); b->staging_next = 0; }
+    gq::JointCmdDev* slot = reinterpret_cast<gq::JointCmdDev*>(b->staging + b->staging_next++); /* a pinned staging slot of the argument ring */
+    std::memcpy(slot, &J, sizeof J);
+    HIP_TRY(hipMemcpyAsync(b->jc_dev, slot, sizeof J, hipMemcpyHostToDevice, stream));
+    b->jc_shadow = J; b->jc_valid = true;
+  }
+  gq::StepCall c{};
+  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_joint_cmd(b->jc_dev);
+  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
+  launch_step_kernel(b, &c, b->host.n_envs, stream);
+  HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
 

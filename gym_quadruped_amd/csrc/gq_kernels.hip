@@ -56,6 +56,28 @@ __device__ __forceinline__ void pd_inline(const GQ_MODEL PolicyPdDev& P, const S
   }
 }
 
+/* the second inline policy of the persistent kernel: lanes 0-11 fetch their joint's words of the env's command rows (absent rows -
+ * qd_des, tau_ff - read as 0) and evaluate the joint-impedance law on the joint state load_rows has just staged in LDS (W.qj, W.qvel -
+ * not the observation row: any observation layout works); the same command at every substep of the window (zero-order hold);
+ * replaces what load_rows left in W.ctrl.  Everything happens here, behind load_rows: nothing of it is live in the prologue that
+ * every persistent launch shares. */
+__device__ __forceinline__ void joint_cmd_inline(const GQ_MODEL JointCmdDev& J, const StepArgs& a, const StepCall& c, WaveMem& W, const int env,
+                                                 const int kstep, const bool last, const bool apply /* false: the env spends this substep on its re-spawn and ignores the torque */) {
+  const int lane = lane_id();
+  wave_barrier(); /* W.qj / W.qvel were stored by other lanes (load_rows: lane = word of the row) */
+  if (lane < 12) {
+    const size_t r = (size_t)env * 12 + lane, g = (size_t)env * (size_t)J.gain_stride + lane;
+    const float q_des = gptr(J.q_des)[r];
+    const float qd_des = J.qd_des ? gptr(J.qd_des)[r] : 0.0f;
+    const float tau_ff = J.tau_ff ? gptr(J.tau_ff)[r] : 0.0f;
+    const float kp = gptr(J.kp)[g], kd = gptr(J.kd)[g];
+    const float u = joint_cmd_law(q_des, qd_des, tau_ff, kp, kd, W.qj[lane], W.qvel[6 + lane]);
+    if (apply) W.ctrl[lane] = u;
+    if (c.act_seq) gptr(c.act_seq)[((size_t)kstep * a.n_envs + env) * 12 + lane] = u;
+    if (last && J.tau_out) gptr(J.tau_out)[(size_t)env * 12 + lane] = u;
+  }
+}
+
 /* step (+ in-kernel auto-reset).  Same-step mode: a terminated env is re-spawned by the same wavefront - reset_wave,
  * then the reset's own mj_step as a second pass through step_wave; no extra launches, but the launch lasts as long as
  * its two-pass waves.  Next-step mode: the env waits (pending flag) and spends its next launch on reset_wave + the
@@ -84,7 +106,16 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __res
   int hint = load_rows<SOLVER>(A->s, c, W, env, pass == 0, C);
   bool respawn = c.auto_reset == 2 && C.pend; /* wave-uniform */
   /* (the reset's own step after an explicit gq_reset: the reset kernel left word whether the lift loop is still due - load_rows put it in W.lift_due) */
-  if constexpr (PERSIST) if (c.policy) pd_inline(*mptr(c.policy), A->s, c, W, env, kstep, !respawn); /* wave-uniform */
+  /* the inline policies (PERSIST variants).  The tag bit of the policy pointer - a kernel argument - tells them apart: the built-in PD
+   * policy pays nothing for the second one.  gq_step_joint_cmd (Newton only): the env's command words are fetched here at every
+   * substep, not carried through the window - the kernel has no register to spare (one carried register was 4 to 8 more scratch
+   * bytes per lane in every persistent variant, re-read from there at every substep anyway); the rows stay in the L2 for the window */
+  if constexpr (PERSIST) if (c.policy) { /* wave-uniform */
+    bool jc = false;
+    if constexpr (SOLVER == 1) jc = policy_is_joint_cmd(c.policy);
+    if (jc) joint_cmd_inline(*mptr(policy_joint_cmd(c.policy)), A->s, c, W, env, kstep, kstep + 1 >= c.n_steps, !respawn);
+    else pd_inline(*mptr(c.policy), A->s, c, W, env, kstep, !respawn);
+  }
   for (;;) { /* one call site each for reset_wave / step_wave: both are large and fully inlined */
     if (respawn) {
       wave_priority(3); /* reset + step in one launch: this wave is the longest of its SIMD */
@@ -94,6 +125,14 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __res
       hint = load_rows<SOLVER>(A->s, c, W, env, false, C, true);
     }
     const int term = step_wave<SOLVER, MODE, CONE, BOXES, SELF, PRIM>(A->s, c, W, pass, hint, C, t_entry);
+    if constexpr (PERSIST && SOLVER == 1) { /* gq_step_joint_cmd: the window's OR of `terminated`, kept in memory - stored by the first
+                                             * substep, set by a later one that terminates (a re-spawn's own step reports none) */
+      const int t = pass == 0 ? term : 0;
+      if ((kstep == 0 || t) && policy_is_joint_cmd(c.policy)) { /* wave-uniform; an ordinary substep stops at the first test */
+        uint8_t* const any = mptr(policy_joint_cmd(c.policy))->term_any;
+        if (any && lane_id() == 0) gptr(any)[env] = (uint8_t)t;
+      }
+    }
     if (pass != 0 || c.auto_reset != 1 || !term) break;
     respawn = true;
   }

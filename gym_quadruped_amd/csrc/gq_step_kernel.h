@@ -27,6 +27,7 @@
 #pragma once
 #include <gq_device.h> /* angle brackets: the include path decides (csrc/ for the product, tests/simt_emu/ for the emulator) */
 #include "gq_model_dev.h"
+#include "gq_joint_cmd.h"
 #include <cstddef>
 #include <type_traits>
 
@@ -126,7 +127,8 @@ struct StepCall {
   int32_t ctrl_stride;  /* floats between the control rows of consecutive steps */
   float* obs_seq;
   /* closed loop INSIDE the persistent rollout (gq_rollout_closed, inline mode): the wavefront derives the action of its env's next
-   * step from the observation row it has just written (PolicyPdDev below, device memory); controls are then not read from ctrl */
+   * step from the observation row it has just written (PolicyPdDev below, device memory); controls are then not read from ctrl.
+   * Tagged (bit 0, see PolicyPdDev): a JointCmdDev instead - joint-impedance command held over the window (gq_step_joint_cmd) */
   const struct PolicyPdDev* policy;
   float* act_seq;       /* [n_steps][N][12] every action taken, or NULL */
   int32_t stop_stage;   /* profiling aid (env GQ_STOP_STAGE, tools/stage_insts.sh): return after stage marker i; 0 = run everything */
@@ -164,6 +166,13 @@ struct PolicyPdDev {
    * id, 0x9011), key = seed (0 sigma: none) */
   float sigma; uint32_t seed_lo, seed_hi; int32_t step0, env_id_offset;
 };
+/* StepCall::policy is a TAGGED pointer: bit 0 set = the block behind it is a JointCmdDev (gq_step_joint_cmd, gq_joint_cmd.h: the
+ * second inline policy of the persistent step kernel), clear = a PolicyPdDev.  The tag travels in the kernel arguments, so telling
+ * the two apart costs the built-in PD policy no look at device memory.  (Both blocks come from hipMalloc: 256-byte aligned.) */
+#define GQ_POLICY_JOINT_CMD ((uintptr_t)1)
+__host__ __device__ inline const PolicyPdDev* policy_tag_joint_cmd(const JointCmdDev* j) { return reinterpret_cast<const PolicyPdDev*>(reinterpret_cast<uintptr_t>(j) | GQ_POLICY_JOINT_CMD); }
+__host__ __device__ inline bool policy_is_joint_cmd(const PolicyPdDev* p) { return (reinterpret_cast<uintptr_t>(p) & GQ_POLICY_JOINT_CMD) != 0; }
+__host__ __device__ inline const JointCmdDev* policy_joint_cmd(const PolicyPdDev* p) { return reinterpret_cast<const JointCmdDev*>(reinterpret_cast<uintptr_t>(p) & ~GQ_POLICY_JOINT_CMD); }
 
 /* wave-uniform model scalars of S5 - S9 (and the cloud pointers): one batch of scalar loads in front of S5, pinned */
 struct StepConsts {

@@ -400,6 +400,102 @@ class QuadrupedEnv(AccessorsMixin):
                 sensor.step()
         return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq}
 
+    def step_pd(self, q_des, kp, kd, qd_des=None, tau_ff=None, decimation: int = 4, record_obs: bool = False, record_actions: bool = False):
+        """Joint-impedance action held over a decimation window, in one launch (``gq_step_joint_cmd``): ``decimation`` physics steps
+        of every env under ``tau = kp * (q_des - q) + kd * (qd_des - qd) + tau_ff``, the law evaluated at every substep from the
+        env's fresh joint state with the same command (zero-order hold) - what a robot's low-level interface does with a policy's
+        50-100 Hz joint targets.  Equivalent, bit for bit, to ::
+
+            for _ in range(decimation):
+                tau = kp * (q_des - env.qpos[:, 7:].float()) + kd * (qd_des - env.qvel[:, 6:]) + tau_ff
+                obs, reward, term, trunc, info = env.step(tau)
+
+        without the launch boundaries and the torch kernels in between; every env follows its own command row, and the law reads the
+        state, not the observation row (any ``state_obs_names`` works).
+
+        q_des, qd_des, tau_ff: ``[N, 12]`` float32 tensors on the env's device (hinge order of ``qpos[7:]``); the optional two default
+        to zero.  kp, kd: a scalar, 12 values, or ``[N, 12]`` (host values are uploaded when they change; a tensor on the env's device is
+        used there, without a synchronisation).  Returns ``(obs, reward, terminated, truncated, info)`` like ``step``,
+        with ``terminated`` the OR over the window (a buffer of its own: an env that fell and re-spawned inside the window is not
+        missed; ``env._terminated`` keeps the last substep's flag); ``truncated``, ``reward`` and the observation are the last
+        substep's.  ``info`` also carries 'obs_seq' ``[decimation, N, obs_dim]`` / 'actions' ``[decimation, N, 12]`` when asked for.
+        ``torque_ctrl_setpoint`` is the last substep's torque.  Needs the Newton solver and ``auto_reset='next_step'`` (or none)."""
+        from .cabi import GqJointCmd
+        N, nu = self.num_envs, 12
+        D = int(decimation)
+        if D < 1:
+            raise ValueError(f'decimation must be >= 1, got {decimation}')
+        if self._mm.desc.solver != 1:
+            raise ValueError("step_pd needs the Newton solver (solver='newton')")
+        if self.auto_reset and self.auto_reset_mode != 'next_step':
+            raise ValueError("step_pd needs auto_reset='next_step' (or no auto-reset): a same-step re-spawn does not fit the persistent kernel")
+
+        def rows(x, name):
+            if x is None:
+                return None
+            if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != (N, nu):
+                raise ValueError(f'{name} must be a float32 tensor of shape ({N}, {nu}) on {self.device}, got '
+                                 + (f'{x.dtype} {tuple(x.shape)} on {x.device}' if torch.is_tensor(x) else type(x).__name__))
+            return x.contiguous()
+
+        def gain(x, name, k):
+            if torch.is_tensor(x) and x.dim() == 2:
+                return rows(x, name), 12
+            if torch.is_tensor(x) and x.device == self.device:   # a device tensor stays there: a copy on the stream, no host round trip
+                if x.dim() > 1 or x.numel() not in (1, nu):
+                    raise ValueError(f'{name} must be a scalar, {nu} values or a ({N}, {nu}) tensor, got shape {tuple(x.shape)}')
+                self._pd_gain[k].copy_(x.detach().to(torch.float32).reshape(-1).expand(nu))
+                self._pd_gain_host[k] = None
+                return self._pd_gain[k], 0
+            v = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float32)
+            if v.ndim > 1 or v.size not in (1, nu):
+                raise ValueError(f'{name} must be a scalar, {nu} values or a ({N}, {nu}) tensor, got shape {tuple(v.shape)}')
+            v = np.broadcast_to(v.reshape(-1), (nu,)).copy()
+            if self._pd_gain_host[k] is None or not np.array_equal(self._pd_gain_host[k], v):   # the shared row is uploaded when it changes
+                self._pd_gain[k].copy_(torch.from_numpy(v))
+                self._pd_gain_host[k] = v
+            return self._pd_gain[k], 0
+
+        if getattr(self, '_pd_tau', None) is None:
+            self._pd_gain = torch.zeros(2, nu, dtype=torch.float32, device=self.device)
+            self._pd_gain_host = [None, None]
+            self._pd_tau = torch.zeros(N, nu, dtype=torch.float32, device=self.device)
+            self._pd_term_any = torch.zeros(N, dtype=torch.uint8, device=self.device)
+            self._pd_term_any_b = self._pd_term_any.view(torch.bool)
+        q = rows(q_des, 'q_des')
+        if q is None:
+            raise ValueError('q_des must be given')
+        qd, ff = rows(qd_des, 'qd_des'), rows(tau_ff, 'tau_ff')
+        (p, sp), (d, sd) = gain(kp, 'kp', 0), gain(kd, 'kd', 1)
+        if sp != sd:   # one stride serves both rows: the shared one is spread
+            p = p if sp == 12 else p.expand(N, nu).contiguous()
+            d = d if sd == 12 else d.expand(N, nu).contiguous()
+            sp = 12
+        f32 = dict(dtype=torch.float32, device=self.device)
+        obs_seq = torch.empty(D, N, self._obs_dim, **f32) if record_obs else None
+        act_seq = torch.empty(D, N, nu, **f32) if record_actions else None
+        cmd = GqJointCmd(struct_size=C.sizeof(GqJointCmd), gain_stride=sp, q_des=q.data_ptr(), qd_des=None if qd is None else qd.data_ptr(),
+                         tau_ff=None if ff is None else ff.data_ptr(), kp=p.data_ptr(), kd=d.data_ptr(), tau_out=self._pd_tau.data_ptr(),
+                         terminated_any=self._pd_term_any.data_ptr())
+        self._pd_cmd_refs = (q, qd, ff, p, d)   # the launch reads them asynchronously
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._hm_fresh = False
+        _lib.check(self._L.gq_step_joint_cmd(self._hbatch, C.byref(cmd), D, self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
+                                             self._lift_failed.data_ptr(), None if obs_seq is None else obs_seq.data_ptr(),
+                                             None if act_seq is None else act_seq.data_ptr(), stream), 'gq_step_joint_cmd')
+        self._last_action = self._pd_tau
+        self._launches += D
+        self._note_step()
+        for sensor in self.sensors:
+            for _ in range(D):
+                sensor.step()
+        info = dict(self._info)
+        if record_obs:
+            info['obs_seq'] = obs_seq
+        if record_actions:
+            info['actions'] = act_seq
+        return self._obs_views, self._reward, self._pd_term_any_b, self._truncated_b, info
+
     def closed_loop_status(self):
         """Wait for the last ``rollout_closed_loop`` and return (abort code, detail, env-steps played); raises ``GqError`` if it
         was aborted (a wait passed its deadline: missing / stuck policy, or the policy kernel could not become resident)."""

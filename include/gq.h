@@ -472,6 +472,34 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
  * returns GQ_EDEVICE with a message when the rollout was aborted */
 int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream);
 int gq_mailbox_get(GqBatch* b, GqMailboxView* out);
+/* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
+ * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
+ *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)
+ * with every env following ITS OWN command row.  The wavefront that steps an env evaluates the law at every substep from the fresh
+ * joint state with the same command (zero-order hold; float32, every operation rounded like the elementwise expression,
+ * q = (float)qpos[7 + j]) and plays the substeps back to back in the persistent step kernel - no launch boundary, no torque tensor
+ * in between.  The law reads the state rows, not the observation row: any observation layout works.  State, flags and
+ * observation row afterwards are those of `decimation` gq_step calls with these torques, bit for bit (next-step auto-reset
+ * included: an env that terminates inside the window spends its next substep on its re-spawn, ignoring that substep's torque, and
+ * tracks the same command for the rest of the window); GqObsOut.terminated / truncated hold the LAST substep's flags.
+ * tau_out: the torques of the last substep (what the tau_ctrl_setpoint observable of a non-respawning env shows).
+ * terminated_any: OR of `terminated` over the window - an env that fell and re-spawned inside the window is not missed.
+ * obs_seq / act_seq: device [decimation][N][obs_dim] / [decimation][N][12] f32 records of every substep, or NULL.
+ * The pointers of GqJointCmd must stay valid until hip_stream has run the launch.  With qd_des = tau_ff = NULL, one shared gain
+ * row and the same q_des row for every env this is the inline PD policy of gq_rollout_closed without noise, bit for bit.
+ * Needs the Newton solver, next-step auto-reset (or none), the production kernel (no inspection record / stage cut) and
+ * decimation >= 1.  Asynchronous on hip_stream. */
+typedef struct GqJointCmd {
+  int32_t struct_size;        /* sizeof(GqJointCmd): a stale binding is refused */
+  int32_t gain_stride;        /* 0: kp / kd are one row of 12; 12: [N][12] */
+  const float *q_des;         /* device [N][12], hinge order of qpos[7:] */
+  const float *qd_des, *tau_ff;   /* device [N][12] or NULL (= 0) */
+  const float *kp, *kd;       /* device, see gain_stride */
+  float *tau_out;             /* device [N][12] or NULL */
+  uint8_t *terminated_any;    /* device [N] or NULL */
+} GqJointCmd;
+int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                      int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream);
 /* upload the device-resident argument block for (st, out, auto_reset, episode, lift_failed) if it changed; no launch */
 int gq_batch_bind(GqBatch* b, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed,
                   void* hip_stream);

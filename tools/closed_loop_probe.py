@@ -1,12 +1,21 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
-usage: closed_loop_probe.py [robot] [n_envs] [K] [scene]"""
+usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D]
+
+--joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
+against the loop they replace - D x (torch PD expression, env.step) - from the same state with the same per-env commands; K windows
+per timing, five timings of each, alternating.  Prints env-steps/s of both, their spreads and the ratio."""
 import sys, time
 from pathlib import Path
 import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from gym_quadruped_amd.quadruped_env import QuadrupedEnv
 
+JOINT_CMD = 0
+if '--joint-cmd' in sys.argv:
+    i = sys.argv.index('--joint-cmd')
+    JOINT_CMD = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 robot = sys.argv[1] if len(sys.argv) > 1 else 'mini_cheetah'
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 500
@@ -24,6 +33,37 @@ def timed(fn, steps):
     torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return n * steps / dt / 1e6, dt / steps * 1e6
+
+if JOINT_CMD:
+    D = JOINT_CMD
+    W = max(1, K // D)   # windows per timing: about K physics steps
+    key = env._key_qpos[7:19].float()
+    u = lambda lo, hi: lo + (hi - lo) * torch.rand(n, 12, generator=g, device='cuda')
+    cmds = [(key + u(-0.6, 0.6), u(-1.0, 1.0), u(-5.0, 5.0)) for _ in range(16)]   # a policy's targets: keyframe +- 0.6 rad, per env
+    kp, kd = u(20.0, 60.0), u(0.5, 2.0)
+    for i in range(300 // D + 1): env.step_pd(cmds[i % 16][0], kp, kd, decimation=D)   # settle into the tracking regime
+    sd = env.state_dict(); launches = env._launches
+    def restore():
+        env.load_state_dict(sd); env._launches = launches; torch.cuda.synchronize()
+    def windows_pd():
+        for w in range(W):
+            q, qd, ff = cmds[w % 16]
+            env.step_pd(q, kp, kd, qd_des=qd, tau_ff=ff, decimation=D)
+    def windows_loop():
+        for w in range(W):
+            q, qd, ff = cmds[w % 16]
+            for _ in range(D):
+                env.step(kp * (q - env.qpos[:, 7:].float()) + kd * (qd - env.qvel[:, 6:]) + ff)
+    restore(); windows_pd(); restore(); windows_loop()   # warm both paths
+    res = {'step_pd': [], 'loop': []}
+    for r in range(5):
+        for name, fn in (('loop', windows_loop), ('step_pd', windows_pd)):
+            restore(); res[name].append(timed(fn, W * D)[0])
+    for name in ('loop', 'step_pd'):
+        v = sorted(res[name])
+        print(f'{robot} {scene} n={n} D={D}: {name:8s} median {v[2]:7.2f} M env-steps/s  min {v[0]:7.2f} max {v[-1]:7.2f}  ({W} windows x 5 runs)', flush=True)
+    print(f'{robot} {scene} n={n} D={D}: step_pd / loop = {sorted(res["step_pd"])[2] / sorted(res["loop"])[2]:.3f} (medians); episodes max {int(env._episode.max())}', flush=True)
+    sys.exit(0)
 
 m, us = timed(lambda: [env.step(pool[i % 16]) for i in range(K)], K)
 print(f'{robot} {scene} n={n}: step loop, random actions             {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
