@@ -4,10 +4,12 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -20,6 +22,7 @@
 #include "gq_step_body.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
+#include "gq_host_res.h"
 
 extern "C" void gq_launch_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, int n_envs, int solver, int cone, gq::Scene scene, hipStream_t stream);
 extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene scene, hipStream_t stream);
@@ -34,7 +37,6 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
-#define GQ_ARG_SLOTS 8
 static thread_local char g_err[512] = "";
 #define SET_ERR(...) std::snprintf(g_err, sizeof g_err, __VA_ARGS__)
 #define HIP_TRY(expr)                                                                   \
@@ -43,59 +45,50 @@ static thread_local char g_err[512] = "";
     if (e_ != hipSuccess) { SET_ERR("%s: %s", #expr, hipGetErrorString(e_)); return GQ_EDEVICE; } \
   } while (0)
 
+using gq::Buf;
+/* every device / pinned block, stream and event below is owned by its holder (gq_host_res.h): deleting the handle frees it */
 struct GqModel {
   int device;
   GqDevModel host;
-  GqDevModel* dev;
-  float *vx, *vy, *vz;
-  float* hf;            /* device elevations of the scene's height field (NULL: none) */
+  Buf<GqDevModel> dev;
+  Buf<float> vx, vy, vz;
+  Buf<float> hf;        /* device elevations of the scene's height field (empty: none) */
   int nvert;
   gq::Scene scene;      /* the step-kernel variants the model runs (gq_step_call.h model_scene) */
   int ngeom, ncloud;
   int32_t lg_cloud[GQ_MAXLG]; /* GqModelDesc cloud of lg[i] (gq_camera's face-plane table is indexed by cloud) */
 };
+/* closed-loop persistent rollout (gq_rollout_closed): mailboxes, ready queues, the policy's stream; built as a whole on first use (mailbox_setup) */
+struct Mailbox {
+  gq::MailboxDev host{};    /* what the device block holds: the plain pointers of the buffers below */
+  Buf<float> act;
+  Buf<int32_t> steps_done, issued, q_items, q_ctr, status;
+  Buf<gq::MailboxDev> dev; Buf<gq::MailboxDev, gq::PinnedMem> staging;
+  Buf<int32_t, gq::PinnedMem> alive, status_host; /* the word the policy workgroups count themselves into; a copy of the status words (gq_rollout_closed_status) */
+  gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
+  gq::Stream stream; gq::Event fork, join;
+  bool ready = false;
+};
 struct GqBatch {
   GqModel* model;
   GqDevBatch host;
   gq::BatchPtrs p;    /* device: the batch block and the scratch rows this batch owns, the model's blocks, the rows callers registered */
-  float* debug;       /* device, debug_envs * GQ_DBG_SIZE floats (lazily allocated) */
-  int32_t* xq;          /* device: convex pair exchange (gq_exchange.h) - models with convex self pairs only, else NULL */
+  Buf<float> friction_next; Buf<uint8_t> pending, lift_pending, load_hint; /* the scratch rows behind p */
+  Buf<float> debug;     /* device, >= debug_envs * GQ_DBG_SIZE floats (lazily allocated) */
+  Buf<int32_t> xq;      /* device: convex pair exchange (gq_exchange.h) - models with convex self pairs only, else empty */
   int xq_slots; bool xq_on;
-  float* sepc;          /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
-  float* cam_rec;       /* device: gq_camera's pose-pass records [N][GQ_CAM_REC] (lazily allocated) */
-  double* cam_pos;      /* device: ... and camera origins [N][3] */
-  float* cam_grec;      /* device: gq_camera_layered's ghost records [N][cam_nghost][GQ_CAM_GREC] (lazily allocated, grown with n_ghost) */
-  int cam_nghost;       /* ... ghosts per env it holds */
+  Buf<float> sepc;      /* device: separating-axis cache of the convex self pairs (GqDevBatch::sepc) */
+  Buf<float> cam_rec;   /* device: gq_camera's pose-pass records [N][GQ_CAM_REC] (lazily allocated, together with cam_pos) */
+  Buf<double> cam_pos;  /* device: ... and camera origins [N][3] */
+  Buf<float> cam_grec;  /* device: gq_camera_layered's ghost records [N][n_ghost][GQ_CAM_GREC] (lazily allocated, grown with n_ghost) */
   int stop_stage;       /* profiling aid: GQ_STOP_STAGE at batch creation */
-  /* argument block of step_kernel: device copy, host shadow of what the device holds, pinned staging ring for the
-   * (rare) stream-ordered re-upload */
-  gq::FusedArgs* dev_args;
-  gq::FusedArgs shadow;
-  gq::FusedArgs* staging;   /* pinned host, GQ_ARG_SLOTS entries */
-  int staging_next;
-  /* the batch constants (p.batch): a change made by gq_batch_set_resampling travels with the NEXT launch, on that launch's
-   * stream, through its own pinned ring - ordered against everything the caller has queued there */
-  GqDevBatch* batch_staging; /* pinned host, GQ_ARG_SLOTS entries */
-  int batch_staging_next;
+  gq::Staged<gq::FusedArgs> args;   /* argument block of step_kernel; re-uploaded (rarely) when a launch's tensors differ: ensure_args */
+  /* the batch constants (p.batch): a setter's change travels with the NEXT launch, on that launch's stream, behind what the caller has queued there (flush_batch) */
+  gq::Staged<GqDevBatch> batch;
   bool batch_dirty;
-  bool shadow_valid;
-  hipStream_t shard_stream[8]; hipEvent_t shard_event[8]; hipEvent_t fork_event; int n_shard_streams; /* gq_rollout */
-  int debug_cap;
-  /* closed-loop persistent rollout (gq_rollout_closed): mailboxes, ready queues, the policy's stream; allocated on first use */
-  struct {
-    gq::MailboxDev host;      /* what the device block holds */
-    gq::MailboxDev* dev;
-    gq::MailboxDev* staging;  /* pinned */
-    int32_t* alive;           /* pinned host word the policy workgroups count themselves into */
-    int32_t* status_host;     /* pinned copy of the status words (gq_rollout_closed_status) */
-    gq::PolicyPdDev* policy_dev; /* device copy of the built-in policy's parameters (inline mode) */
-    hipStream_t stream; hipEvent_t fork, join;
-    bool ready;
-  } mb;
-  /* gq_step_joint_cmd: device block of the call's command pointers (StepCall::policy, tagged) and the host's copy of what it holds */
-  gq::JointCmdDev* jc_dev;
-  gq::JointCmdDev jc_shadow;
-  bool jc_valid;
+  gq::Stream shard_stream[8]; gq::Event shard_event[8], fork_event; int n_shard_streams; /* gq_rollout */
+  Mailbox mb;
+  gq::Staged<gq::JointCmdDev> jc;   /* gq_step_joint_cmd: the call's command pointers (StepCall::policy, tagged) */
 };
 
 /* the launches must be issued with the batch's device current (the caller's stream belongs to it); restore the caller's
@@ -118,16 +111,7 @@ int gq_struct_sizes(int32_t out[8]) {
   return GQ_OK;
 }
 int gq_obs_dim(int obs_id) { return gq_obs_dim_host(obs_id); }
-int gq_model_destroy(GqModel* m);
-int gq_batch_destroy(GqBatch* b);
-
-/* HIP call inside a constructor: on failure the partially built handle is destroyed (frees whatever was allocated) */
-#define HIP_TRY_OR_DESTROY(expr, destroy_call)                                          \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) { SET_ERR("%s: %s", #expr, hipGetErrorString(e_)); destroy_call; return GQ_EDEVICE; } \
-  } while (0)
-
+/* create: the half-built handle sits in a local owner, so a plain HIP_TRY return frees it - with its device current, the DeviceGuard being declared first */
 int gq_model_create(const GqModelDesc* desc, int device, GqModel** out) {
   if (!desc || !out) { SET_ERR("gq_model_create: null argument"); return GQ_EINVAL; }
   if (desc->struct_size != (int32_t)sizeof(GqModelDesc)) {
@@ -137,74 +121,67 @@ int gq_model_create(const GqModelDesc* desc, int device, GqModel** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { SET_ERR("no HIP device visible"); return GQ_ENODEVICE; }
   if (device < 0 || device >= ndev) { SET_ERR("device %d out of range (have %d)", device, ndev); return GQ_EINVAL; }
-  GqModel* m = new (std::nothrow) GqModel();   /* value-initialised: every pointer starts NULL */
+  DeviceGuard guard(device);
+  std::unique_ptr<GqModel> m(new (std::nothrow) GqModel());   /* value-initialised */
   if (!m) return GQ_ENOMEM;
   std::vector<float> vx, vy, vz;
-  if (gq_build_dev_model(desc, &m->host, &vx, &vy, &vz, g_err, sizeof g_err)) { delete m; return GQ_EINVAL; }
+  if (gq_build_dev_model(desc, &m->host, &vx, &vy, &vz, g_err, sizeof g_err)) return GQ_EINVAL;
   m->device = device; m->nvert = (int)vx.size(); m->scene = gq::model_scene(m->host);
   m->ngeom = desc->ngeom; m->ncloud = desc->ncloud;
   gq::cam_lg_cloud(m->lg_cloud, m->host, desc);
-  DeviceGuard guard(device);
   if (m->host.hf_nrow > 0) {
     std::vector<float> hf;
     gq_hfield_heights(desc, &hf);
-    HIP_TRY_OR_DESTROY(hipMalloc(&m->hf, hf.size() * sizeof(float)), gq_model_destroy(m));
-    HIP_TRY_OR_DESTROY(hipMemcpy(m->hf, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice), gq_model_destroy(m));
-    m->host.hf_data = m->hf;
+    HIP_TRY(m->hf.ensure(hf.size(), false));
+    HIP_TRY(hipMemcpy(m->hf.get(), hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
+    m->host.hf_data = m->hf.get();
   }
-  HIP_TRY_OR_DESTROY(hipMalloc(&m->dev, sizeof(GqDevModel)), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMemcpy(m->dev, &m->host, sizeof(GqDevModel), hipMemcpyHostToDevice), gq_model_destroy(m));
-  size_t vb = vx.size() * sizeof(float);
-  HIP_TRY_OR_DESTROY(hipMalloc(&m->vx, vb), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMalloc(&m->vy, vb), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMalloc(&m->vz, vb), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMemcpy(m->vx, vx.data(), vb, hipMemcpyHostToDevice), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMemcpy(m->vy, vy.data(), vb, hipMemcpyHostToDevice), gq_model_destroy(m));
-  HIP_TRY_OR_DESTROY(hipMemcpy(m->vz, vz.data(), vb, hipMemcpyHostToDevice), gq_model_destroy(m));
-  *out = m;
+  HIP_TRY(m->dev.ensure(1, false));
+  HIP_TRY(hipMemcpy(m->dev.get(), &m->host, sizeof(GqDevModel), hipMemcpyHostToDevice));
+  const size_t nv = vx.size(), vb = nv * sizeof(float);
+  HIP_TRY(m->vx.ensure(nv, false));
+  HIP_TRY(m->vy.ensure(nv, false));
+  HIP_TRY(m->vz.ensure(nv, false));
+  HIP_TRY(hipMemcpy(m->vx.get(), vx.data(), vb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(m->vy.get(), vy.data(), vb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(m->vz.get(), vz.data(), vb, hipMemcpyHostToDevice));
+  *out = m.release();
   return GQ_OK;
 }
 
 int gq_model_destroy(GqModel* m) {
-  if (!m) return GQ_OK;
-  DeviceGuard guard(m->device);
-  hipFree(m->dev); hipFree(m->vx); hipFree(m->vy); hipFree(m->vz); hipFree(m->hf);
-  delete m;
+  if (m) { DeviceGuard guard(m->device); delete m; } /* the frees run with the model's device current */
   return GQ_OK;
 }
 
 int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order, GqBatch** out) {
   if (!m || !out || n_envs <= 0) { SET_ERR("gq_batch_create: bad argument"); return GQ_EINVAL; }
-  GqBatch* b = new (std::nothrow) GqBatch();   /* value-initialised: every pointer starts NULL */
+  DeviceGuard guard(m->device);
+  std::unique_ptr<GqBatch> b(new (std::nothrow) GqBatch());   /* value-initialised */
   if (!b) return GQ_ENOMEM;
   b->model = m;
-  b->p.model = m->dev; b->p.vx = m->vx; b->p.vy = m->vy; b->p.vz = m->vz;
-  if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &b->host, g_err, sizeof g_err)) { delete b; return GQ_EINVAL; }
-  DeviceGuard guard(m->device);
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.batch, sizeof(GqDevBatch)), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.friction_next, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->p.friction_next, 0, sizeof(float) * (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.pending, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->p.pending, 0, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.lift_pending, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->p.lift_pending, 0, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->p.load_hint, (size_t)n_envs), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMemset(b->p.load_hint, 0, (size_t)n_envs), gq_batch_destroy(b));
+  b->p.model = m->dev.get(); b->p.vx = m->vx.get(); b->p.vy = m->vy.get(); b->p.vz = m->vz.get();
+  if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &b->host, g_err, sizeof g_err)) return GQ_EINVAL;
+  const size_t n = (size_t)n_envs;
+  HIP_TRY(b->batch.dev.ensure(1, false));
+  b->p.batch = b->batch.dev.get();
+  HIP_TRY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice));
+  HIP_TRY(b->friction_next.ensure(n, true));
+  HIP_TRY(b->pending.ensure(n, true));
+  HIP_TRY(b->lift_pending.ensure(n, true));
+  HIP_TRY(b->load_hint.ensure(n, true));
+  b->p.friction_next = b->friction_next.get(); b->p.pending = b->pending.get(); b->p.lift_pending = b->lift_pending.get(); b->p.load_hint = b->load_hint.get();
   if (m->host.ncvx_self > 0) { /* the pair exchange: two slots per env, rounded up to a power of two (an env publishes what it has beyond its first pair - 0.45 pairs
                                 * per env-step on the benchmark's states: the table stays sparse, which is what its hashing wants) */
     int slots = 256;
     while (slots < 2 * n_envs && slots < (1 << 21)) slots <<= 1;
-    const size_t words = (size_t)slots * (1 + GQ_XQ_ITEM);
-    HIP_TRY_OR_DESTROY(hipMalloc(&b->xq, words * sizeof(int32_t)), gq_batch_destroy(b));
-    HIP_TRY_OR_DESTROY(hipMemset(b->xq, 0, words * sizeof(int32_t)), gq_batch_destroy(b));
+    HIP_TRY(b->xq.ensure((size_t)slots * (1 + GQ_XQ_ITEM), true));
     b->xq_slots = slots;
     b->xq_on = true;
-    b->host.xq = b->xq; b->host.xq_slots = slots;
-    HIP_TRY_OR_DESTROY(hipMalloc(&b->sepc, (size_t)n_envs * m->host.ncvx_self * 3 * sizeof(float)), gq_batch_destroy(b));
-    HIP_TRY_OR_DESTROY(hipMemset(b->sepc, 0, (size_t)n_envs * m->host.ncvx_self * 3 * sizeof(float)), gq_batch_destroy(b));
-    b->host.sepc = b->sepc; b->host.sepc_stride = m->host.ncvx_self * 3;
-    HIP_TRY_OR_DESTROY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice), gq_batch_destroy(b));
+    b->host.xq = b->xq.get(); b->host.xq_slots = slots;
+    HIP_TRY(b->sepc.ensure(n * m->host.ncvx_self * 3, true));
+    b->host.sepc = b->sepc.get(); b->host.sepc_stride = m->host.ncvx_self * 3;
+    HIP_TRY(hipMemcpy(b->p.batch, &b->host, sizeof(GqDevBatch), hipMemcpyHostToDevice));
   }
   /* profiling knobs of development builds (tools/dev_build.sh defines GQ_DEV_KNOBS; tools/stage_insts.sh, stage_cuts.py): the product library
    * reads no environment variable (tests/test_host_and_abi.py checks its objects for getenv) */
@@ -213,43 +190,16 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
 #else
   b->stop_stage = 0;
 #endif
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->dev_args, sizeof(gq::FusedArgs)), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipHostMalloc(&b->staging, sizeof(gq::FusedArgs) * GQ_ARG_SLOTS, hipHostMallocDefault), gq_batch_destroy(b));
-  b->staging_next = 0; b->shadow_valid = false;
-  HIP_TRY_OR_DESTROY(hipHostMalloc(&b->batch_staging, sizeof(GqDevBatch) * GQ_ARG_SLOTS, hipHostMallocDefault), gq_batch_destroy(b));
-  HIP_TRY_OR_DESTROY(hipMalloc(&b->jc_dev, sizeof(gq::JointCmdDev)), gq_batch_destroy(b));
-  b->batch_staging_next = 0; b->batch_dirty = false;
-  std::memset(&b->shadow, 0, sizeof b->shadow);
-  *out = b;
+  HIP_TRY(b->args.dev.ensure(1, false));
+  HIP_TRY(b->args.ring.ensure(GQ_ARG_SLOTS, false));
+  HIP_TRY(b->batch.ring.ensure(GQ_ARG_SLOTS, false));
+  HIP_TRY(b->jc.create());
+  *out = b.release();
   return GQ_OK;
 }
 
-/* releases whatever mailbox_setup has allocated so far (every pointer of the block starts out null: GqBatch is value-initialised) */
-static void mailbox_free(GqBatch* b) {
-  auto& m = b->mb;
-  hipFree(m.host.act); hipFree(m.host.steps_done); hipFree(m.host.issued); hipFree(m.host.q_items); hipFree(m.host.q_ctr); hipFree(m.host.status);
-  hipFree(m.dev); hipFree(m.policy_dev);
-  if (m.staging) hipHostFree(m.staging);
-  if (m.alive) hipHostFree(m.alive);
-  if (m.status_host) hipHostFree(m.status_host);
-  if (m.stream) hipStreamDestroy(m.stream);
-  if (m.fork) hipEventDestroy(m.fork);
-  if (m.join) hipEventDestroy(m.join);
-  std::memset(&m, 0, sizeof m);
-}
-
 int gq_batch_destroy(GqBatch* b) {
-  if (!b) return GQ_OK;
-  DeviceGuard guard(b->model->device);
-  hipFree(b->p.batch); hipFree(b->p.friction_next); hipFree(b->p.pending); hipFree(b->p.lift_pending); hipFree(b->p.load_hint); hipFree(b->xq); hipFree(b->sepc); hipFree(b->dev_args);
-  hipFree(b->cam_rec); hipFree(b->cam_pos); hipFree(b->cam_grec); hipFree(b->jc_dev);
-  if (b->staging) hipHostFree(b->staging);
-  if (b->batch_staging) hipHostFree(b->batch_staging);
-  mailbox_free(b);
-  for (int i = 0; i < b->n_shard_streams; i++) { hipStreamDestroy(b->shard_stream[i]); hipEventDestroy(b->shard_event[i]); }
-  if (b->n_shard_streams) hipEventDestroy(b->fork_event);
-  if (b->debug) hipFree(b->debug);
-  delete b;
+  if (b) { DeviceGuard guard(b->model->device); delete b; }
   return GQ_OK;
 }
 
@@ -265,9 +215,9 @@ int gq_batch_set_imu(GqBatch* b, const GqImuCfg* cfg, float* bias_state) {
 
 int gq_batch_set_pair_exchange(GqBatch* b, int on) {
   if (!b) { SET_ERR("gq_batch_set_pair_exchange: null batch"); return GQ_EINVAL; }
-  if (on && !b->xq) { SET_ERR("gq_batch_set_pair_exchange: the model has no convex self pairs - nothing to exchange"); return GQ_EINVAL; }
+  if (on && !b->xq.get()) { SET_ERR("gq_batch_set_pair_exchange: the model has no convex self pairs - nothing to exchange"); return GQ_EINVAL; }
   b->xq_on = on != 0;
-  b->host.xq = b->xq_on ? b->xq : nullptr; b->host.xq_slots = b->xq_on ? b->xq_slots : 0;
+  b->host.xq = b->xq_on ? b->xq.get() : nullptr; b->host.xq_slots = b->xq_on ? b->xq_slots : 0;
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
   return GQ_OK;
 }
@@ -325,12 +275,7 @@ int gq_debug_enable(GqBatch* b, int n_debug_envs) {
   if (!b) return GQ_EINVAL;
   if (n_debug_envs > b->host.n_envs) n_debug_envs = b->host.n_envs;
   DeviceGuard guard(b->model->device);
-  if (n_debug_envs > b->debug_cap) {
-    if (b->debug) hipFree(b->debug);
-    HIP_TRY(hipMalloc(&b->debug, (size_t)n_debug_envs * GQ_DBG_SIZE * sizeof(float)));
-    HIP_TRY(hipMemset(b->debug, 0, (size_t)n_debug_envs * GQ_DBG_SIZE * sizeof(float)));
-    b->debug_cap = n_debug_envs;
-  }
+  if (n_debug_envs > 0) HIP_TRY(b->debug.ensure((size_t)n_debug_envs * GQ_DBG_SIZE, true));
   b->host.debug_envs = n_debug_envs;
   b->batch_dirty = true; /* uploaded by the next launch, stream-ordered (ensure_args) */
   return GQ_OK;
@@ -339,57 +284,59 @@ int gq_debug_enable(GqBatch* b, int n_debug_envs) {
 /* batch constants changed since the last launch (gq_batch_set_resampling / _set_imu / gq_debug_enable): stream-ordered upload */
 static int flush_batch(GqBatch* b, hipStream_t stream) {
   if (!b->batch_dirty) return GQ_OK;
-  if (b->batch_staging_next == GQ_ARG_SLOTS) { HIP_TRY(hipStreamSynchronize(stream)); b->batch_staging_next = 0; }
-  GqDevBatch* slot = b->batch_staging + b->batch_staging_next++;
-  std::memcpy(slot, &b->host, sizeof(GqDevBatch));
-  HIP_TRY(hipMemcpyAsync(b->p.batch, slot, sizeof(GqDevBatch), hipMemcpyHostToDevice, stream));
+  HIP_TRY(b->batch.push(b->host, stream, true)); /* the dirty flag is the gate: no memcmp of the block */
   b->batch_dirty = false;
   return GQ_OK;
 }
-/* Make the device argument block describe (st, out, episode, lift_failed[, auto-reset cfg]).  Steady state: a memcmp.
- * On a change the new block goes through a pinned staging slot with a stream-ordered copy, so launches already queued
- * on `stream` still see the old block.  reset_cfg NULL keeps whatever auto-reset block the device holds. */
+/* Make the device argument block describe (st, out, episode, lift_failed[, auto-reset cfg]).  Steady state: a memcmp (Staged::push).
+ * reset_cfg NULL keeps whatever auto-reset block the device holds. */
 static int ensure_args(GqBatch* b, const GqState& st, const GqObsOut& out, int32_t* episode, uint8_t* lift_failed,
                        const GqResetCfg* reset_cfg, hipStream_t stream) {
-  { const int rcb = flush_batch(b, stream); if (rcb != GQ_OK) return rcb; }
-  gq::FusedArgs want = b->shadow; /* struct copy keeps padding bytes identical for the memcmp */
+  if (const int rc = flush_batch(b, stream); rc != GQ_OK) return rc;
+  gq::FusedArgs want = b->args.shadow; /* a copy of the shadow, then the fields: see Staged */
   gq::fill_step_args(&want.s, b->p, b->model->host, b->host.n_envs, st, out, episode, lift_failed);
   if (reset_cfg) gq::fill_reset_args(&want.r, b->p, b->host.rs_cmd_reset, reset_cfg, st, out, episode, lift_failed);
-  if (b->shadow_valid && std::memcmp(&want, &b->shadow, sizeof want) == 0) return GQ_OK;
-  if (b->staging_next == GQ_ARG_SLOTS) { /* every slot may still be in flight: drain before reusing the ring */
-    HIP_TRY(hipStreamSynchronize(stream));
-    b->staging_next = 0;
-  }
-  gq::FusedArgs* slot = b->staging + b->staging_next++;
-  std::memcpy(slot, &want, sizeof want);
-  HIP_TRY(hipMemcpyAsync(b->dev_args, slot, sizeof want, hipMemcpyHostToDevice, stream));
-  b->shadow = want; b->shadow_valid = true;
+  HIP_TRY(b->args.push(want, stream, false));
   return GQ_OK;
 }
 
-/* one launch of the step kernel over n_envs envs from c->env0: the variant follows the batch's model (solver, cone, scene) */
-static void launch_step_kernel(const GqBatch* b, const gq::StepCall* c, int n_envs, hipStream_t stream) {
-  const GqModel* m = b->model;
-  gq_launch_step(b->dev_args, c, n_envs, m->host.solver, m->host.cone, m->scene, stream);
+/* one launch of the step kernel over n_envs envs from c->env0: the variant follows the batch's model (solver, cone, scene); returns the launch's error */
+static hipError_t launch_step_kernel(const GqBatch* b, const gq::StepCall* c, int n_envs, hipStream_t stream) {
+  gq_launch_step(b->args.dev.get(), c, n_envs, b->model->host.solver, b->model->host.cone, b->model->scene, stream);
+  return hipGetLastError();
 }
-static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const uint8_t* mask, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
-                       int32_t* episode, uint8_t* lift_failed, void* hip_stream, const char* who) {
-  if (!b || !st.qpos || !st.qvel || !st.qacc || !st.qacc_warmstart || !st.time || !out.obs || !out.reward ||
-      !out.terminated || !out.truncated || !out.invalid_contact || !out.step_num) {
-    SET_ERR("%s: null tensor", who); return GQ_EINVAL;
-  }
-  if (env0 < 0 || count < 0 || env0 + count > b->host.n_envs) { SET_ERR("%s: env range [%d, %d) outside the batch of %d", who, env0, env0 + count, b->host.n_envs); return GQ_EINVAL; }
+/* the checks that several entry points share: one definition each, the entry point's name (who) in front of the text */
+static bool have_tensors(const GqState& st, const GqObsOut& out) {
+  return st.qpos && st.qvel && st.qacc && st.qacc_warmstart && st.time && out.obs && out.reward && out.terminated && out.truncated && out.invalid_contact && out.step_num;
+}
+/* what the persistent production launches (several steps per env in one launch, the policy inline) need */
+static bool persistent_ok(const GqBatch* b, const GqResetCfg* auto_reset, const char* who) {
+  if (auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("%s needs next-step auto-reset or none", who); return false; }
+  if (b->model->host.solver != 1) { SET_ERR("%s needs the Newton solver (solver = 1)", who); return false; }
+  if (b->host.debug_envs > 0 || b->stop_stage != 0) { SET_ERR("%s runs the production kernel: switch the inspection record / stage cut off first", who); return false; }
+  return true;
+}
+/* validate a launch's tensors and make the device argument block describe them (ensure_args), stream-ordered; launches nothing */
+static int bind(GqBatch* b, const GqState& st, const GqObsOut& out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, hipStream_t stream,
+                const char* who) {
+  if (!b || !have_tensors(st, out)) { SET_ERR("%s: null tensor", who); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (auto_reset && (!episode || !st.cmd)) { SET_ERR("%s: auto-reset needs the episode counters and the command tensor", who); return GQ_EINVAL; }
   if (b->host.rs_cmd_reset && !st.cmd) { SET_ERR("%s: command resampling is on (gq_batch_set_resampling) but the state has no command tensor", who); return GQ_EINVAL; }
-  const int rc = ensure_args(b, st, out, episode, lift_failed, auto_reset, (hipStream_t)hip_stream);
-  if (rc != GQ_OK) return rc;
-  if (count == 0) return GQ_OK;
+  return ensure_args(b, st, out, episode, lift_failed, auto_reset, stream);
+}
+static int step_launch(GqBatch* b, int env0, int count, const float* ctrl, const uint8_t* mask, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                       int32_t* episode, uint8_t* lift_failed, void* hip_stream, const char* who) {
+  if (b && have_tensors(st, out) && (env0 < 0 || count < 0 || env0 + count > b->host.n_envs)) { /* a missing tensor is reported first (bind) */
+    SET_ERR("%s: env range [%d, %d) outside the batch of %d", who, env0, env0 + count, b->host.n_envs); return GQ_EINVAL;
+  }
+  const int rc = bind(b, st, out, auto_reset, episode, lift_failed, (hipStream_t)hip_stream, who);
+  if (rc != GQ_OK || count == 0) return rc;
+  DeviceGuard guard(b->model->device);
   gq::StepCall c{};
-  c.ctrl = ctrl; c.mask = mask; c.debug = b->host.debug_envs > 0 ? b->debug : nullptr; c.env0 = env0;
+  c.ctrl = ctrl; c.mask = mask; c.debug = b->host.debug_envs > 0 ? b->debug.get() : nullptr; c.env0 = env0;
   c.auto_reset = gq::auto_reset_mode(auto_reset); c.first_pass = 0; c.stop_stage = b->stop_stage;
-  launch_step_kernel(b, &c, count, (hipStream_t)hip_stream);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_step_kernel(b, &c, count, (hipStream_t)hip_stream));
   return GQ_OK;
 }
 
@@ -408,115 +355,102 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
   if (!b || !ctrl_seq || n_steps < 0) { SET_ERR("gq_rollout: bad argument"); return GQ_EINVAL; }
   /* the persistent kernel exists for the production variant only: with the inspection record or a stage cut active the rollout is
    * played as the step loop (one shard), so that the record describes the last step and the cut applies to every step */
-  if (shards == 0 && b && (b->host.debug_envs > 0 || b->stop_stage != 0)) shards = 1;
+  if (shards == 0 && (b->host.debug_envs > 0 || b->stop_stage != 0)) shards = 1;
+  if (shards == 0 && auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("gq_rollout: the persistent rollout (shards = 0) needs next-step auto-reset or none"); return GQ_EINVAL; }
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_rollout"); rc != GQ_OK) return rc;
+  DeviceGuard guard(b->model->device);
   if (shards == 0) { /* persistent: ONE launch, every wavefront plays the whole sequence of its env (StepCall::n_steps) */
-    if (auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("gq_rollout: the persistent rollout (shards = 0) needs next-step auto-reset or none"); return GQ_EINVAL; }
-    int rc0 = step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_rollout"); /* validate + bind */
-    if (rc0 != GQ_OK) return rc0;
     if (n_steps == 0) return GQ_OK;
-    DeviceGuard guard0(b->model->device);
     gq::StepCall c{};
     c.ctrl = ctrl_seq; c.n_steps = n_steps; c.ctrl_stride = b->host.n_envs * 12; c.obs_seq = obs_seq;
     c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = b->stop_stage;
-    launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
     return GQ_OK;
   }
-  if (shards < 1) shards = 1;
-  if (shards > 8) shards = 8;
-  if (shards > b->host.n_envs) shards = b->host.n_envs;
-  int rc = step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_rollout"); /* validate + bind */
-  if (rc != GQ_OK) return rc;
-  DeviceGuard guard(b->model->device);
+  shards = std::clamp(shards, 1, std::min(8, b->host.n_envs));
   while (b->n_shard_streams < shards) {
     const int i = b->n_shard_streams;
-    if (i == 0) HIP_TRY(hipEventCreateWithFlags(&b->fork_event, hipEventDisableTiming));
-    HIP_TRY(hipStreamCreateWithFlags(&b->shard_stream[i], hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&b->shard_event[i], hipEventDisableTiming));
+    if (i == 0) HIP_TRY(hipEventCreateWithFlags(b->fork_event.put(), hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithFlags(b->shard_stream[i].put(), hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(b->shard_event[i].put(), hipEventDisableTiming));
     b->n_shard_streams = i + 1;
   }
   const int N = b->host.n_envs, od = b->host.obs_dim;
-  HIP_TRY(hipEventRecord(b->fork_event, (hipStream_t)hip_stream));
+  HIP_TRY(hipEventRecord(b->fork_event.get(), stream));
   /* from here on work may sit on the library's shard streams: whatever fails, the caller's stream is made to wait for them
    * before the error is returned - the caller may free ctrl_seq / obs_seq as soon as ITS stream is done with them */
   hipError_t herr = hipSuccess;
   const char* what = "";
 #define RO_TRY(x) do { if (herr == hipSuccess) { herr = (x); if (herr != hipSuccess) what = #x; } } while (0)
-  for (int s = 0; s < shards; s++) RO_TRY(hipStreamWaitEvent(b->shard_stream[s], b->fork_event, 0));
+  for (int s = 0; s < shards; s++) RO_TRY(hipStreamWaitEvent(b->shard_stream[s].get(), b->fork_event.get(), 0));
   gq::StepCall c{};
-  c.debug = b->host.debug_envs > 0 ? b->debug : nullptr;
+  c.debug = b->host.debug_envs > 0 ? b->debug.get() : nullptr;
   c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = b->stop_stage;
   for (int k = 0; k < n_steps && herr == hipSuccess; k++) {
     c.ctrl = ctrl_seq + (size_t)k * N * 12;
     for (int s = 0; s < shards && herr == hipSuccess; s++) {
       const int e0 = (int)((long long)s * N / shards), e1 = (int)((long long)(s + 1) * N / shards);
       c.env0 = e0;
-      launch_step_kernel(b, &c, e1 - e0, b->shard_stream[s]);
-      RO_TRY(hipGetLastError());
-      if (obs_seq) RO_TRY(hipMemcpyAsync(obs_seq + ((size_t)k * N + e0) * od, out.obs + (size_t)e0 * od, (size_t)(e1 - e0) * od * sizeof(float), hipMemcpyDeviceToDevice, b->shard_stream[s]));
+      RO_TRY(launch_step_kernel(b, &c, e1 - e0, b->shard_stream[s].get()));
+      if (obs_seq) RO_TRY(hipMemcpyAsync(obs_seq + ((size_t)k * N + e0) * od, out.obs + (size_t)e0 * od, (size_t)(e1 - e0) * od * sizeof(float), hipMemcpyDeviceToDevice, b->shard_stream[s].get()));
     }
   }
   for (int s = 0; s < shards; s++) { /* join - also on the error path (a stream that cannot even record its event is drained on the host) */
-    hipError_t j = hipEventRecord(b->shard_event[s], b->shard_stream[s]);
-    if (j == hipSuccess) j = hipStreamWaitEvent((hipStream_t)hip_stream, b->shard_event[s], 0);
-    if (j != hipSuccess) { (void)hipStreamSynchronize(b->shard_stream[s]); if (herr == hipSuccess) { herr = j; what = "joining the shard streams"; } }
+    hipError_t j = hipEventRecord(b->shard_event[s].get(), b->shard_stream[s].get());
+    if (j == hipSuccess) j = hipStreamWaitEvent(stream, b->shard_event[s].get(), 0);
+    if (j != hipSuccess) { (void)hipStreamSynchronize(b->shard_stream[s].get()); if (herr == hipSuccess) { herr = j; what = "joining the shard streams"; } }
   }
 #undef RO_TRY
   if (herr != hipSuccess) { SET_ERR("gq_rollout: HIP error '%s' at %s", hipGetErrorString(herr), what); return GQ_EDEVICE; }
   return GQ_OK;
 }
 
-/* mailboxes, queues and the policy stream of a batch; which XCDs the device exposes (one probe launch) */
-static int mailbox_setup_impl(GqBatch* b);
+/* mailboxes, queues and the policy stream of a batch; which XCDs the device exposes (one probe launch).  Built in a local block that the batch
+ * takes over when it is complete: a failed setup keeps nothing, the next call starts from scratch */
 static int mailbox_setup(GqBatch* b) {
   if (b->mb.ready) return GQ_OK;
-  const int rc = mailbox_setup_impl(b);
-  if (rc != GQ_OK) mailbox_free(b); /* a failed setup keeps nothing: the next call starts from scratch */
-  return rc;
-}
-static int mailbox_setup_impl(GqBatch* b) {
-  const int N = b->host.n_envs;
-  gq::MailboxDev& h = b->mb.host;
-  std::memset(&h, 0, sizeof h);
+  const size_t N = (size_t)b->host.n_envs;
+  Mailbox t;
+  gq::MailboxDev& h = t.host;
   int qcap = 64;
-  while (qcap < N) qcap <<= 1;
+  while ((size_t)qcap < N) qcap <<= 1;
   /* which XCC ids do the workgroups of this device report?  (8 on an MI355X in SPX mode; a partitioned device shows fewer) */
-  int32_t* mask_dev = nullptr;
-  HIP_TRY(hipMalloc(&mask_dev, sizeof(int32_t)));
-  HIP_TRY(hipMemset(mask_dev, 0, sizeof(int32_t)));
-  gq_launch_xcc_probe(mask_dev, 0);
+  Buf<int32_t> mask_dev;
+  HIP_TRY(mask_dev.ensure(1, true));
+  gq_launch_xcc_probe(mask_dev.get(), 0);
   int32_t mask = 0;
-  HIP_TRY(hipMemcpy(&mask, mask_dev, sizeof mask, hipMemcpyDeviceToHost));
-  hipFree(mask_dev);
+  HIP_TRY(hipMemcpy(&mask, mask_dev.get(), sizeof mask, hipMemcpyDeviceToHost));
+  mask_dev.reset();
   if (mask == 0) { SET_ERR("gq_rollout_closed: the XCD probe saw no workgroup"); return GQ_EDEVICE; }
   int nq = 0;
   for (int x = 0; x < 16; x++) h.xcc_queue[x] = ((mask >> x) & 1) ? nq++ : 0;
-  h.nq = nq; h.qcap = qcap; h.n_envs = N;
-  HIP_TRY(hipMalloc(&h.act, sizeof(float) * 12 * (size_t)N));
-  HIP_TRY(hipMalloc(&h.steps_done, sizeof(int32_t) * (size_t)N));
-  HIP_TRY(hipMalloc(&h.issued, sizeof(int32_t) * (size_t)N));
-  HIP_TRY(hipMalloc(&h.q_items, sizeof(int32_t) * (size_t)nq * qcap));
-  HIP_TRY(hipMalloc(&h.q_ctr, sizeof(int32_t) * (size_t)nq * 3 * GQ_MB_QSTRIDE));
-  HIP_TRY(hipMalloc(&h.status, sizeof(int32_t) * 8));
-  HIP_TRY(hipMemset(h.status, 0, sizeof(int32_t) * 8));
-  HIP_TRY(hipMalloc(&b->mb.dev, sizeof(gq::MailboxDev)));
-  HIP_TRY(hipMalloc(&b->mb.policy_dev, sizeof(gq::PolicyPdDev)));
-  HIP_TRY(hipHostMalloc(&b->mb.staging, sizeof(gq::MailboxDev), hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc(&b->mb.alive, sizeof(int32_t), hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc(&b->mb.status_host, sizeof(int32_t) * 8, hipHostMallocDefault));
-  h.alive = b->mb.alive;
-  HIP_TRY(hipStreamCreateWithFlags(&b->mb.stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&b->mb.fork, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&b->mb.join, hipEventDisableTiming));
-  b->mb.ready = true;
+  h.nq = nq; h.qcap = qcap; h.n_envs = (int)N;
+  HIP_TRY(t.act.ensure(12 * N, false));
+  HIP_TRY(t.steps_done.ensure(N, false));
+  HIP_TRY(t.issued.ensure(N, false));
+  HIP_TRY(t.q_items.ensure((size_t)nq * qcap, false));
+  HIP_TRY(t.q_ctr.ensure((size_t)nq * 3 * GQ_MB_QSTRIDE, false));
+  HIP_TRY(t.status.ensure(8, true));
+  HIP_TRY(t.dev.ensure(1, false));
+  HIP_TRY(t.policy.create());
+  HIP_TRY(t.staging.ensure(1, false));
+  HIP_TRY(t.alive.ensure(1, false));
+  HIP_TRY(t.status_host.ensure(8, false));
+  h.act = t.act.get(); h.steps_done = t.steps_done.get(); h.issued = t.issued.get(); h.q_items = t.q_items.get(); h.q_ctr = t.q_ctr.get();
+  h.status = t.status.get(); h.alive = t.alive.get();
+  HIP_TRY(hipStreamCreateWithFlags(t.stream.put(), hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(t.fork.put(), hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(t.join.put(), hipEventDisableTiming));
+  t.ready = true;
+  b->mb = std::move(t);
   return GQ_OK;
 }
 
 int gq_mailbox_get(GqBatch* b, GqMailboxView* out) {
   if (!b || !out) { SET_ERR("gq_mailbox_get: null argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  const int rc = mailbox_setup(b);
-  if (rc != GQ_OK) return rc;
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
   const gq::MailboxDev& h = b->mb.host;
   out->action = h.act; out->steps_done = h.steps_done; out->queue_items = h.q_items; out->queue_counters = h.q_ctr; out->status = h.status;
   out->n_queues = h.nq; out->queue_capacity = h.qcap; out->counter_stride = GQ_MB_QSTRIDE;
@@ -528,18 +462,15 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
   if (!b || n_steps < 0 || (mode != GQ_CLOSED_MAILBOX && mode != GQ_CLOSED_INLINE)) { SET_ERR("gq_rollout_closed: bad argument"); return GQ_EINVAL; }
   if (mode == GQ_CLOSED_INLINE && !pd) { SET_ERR("gq_rollout_closed: the inline mode runs the built-in policy: pd must be given"); return GQ_EINVAL; }
-  if (auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("gq_rollout_closed needs next-step auto-reset or none"); return GQ_EINVAL; }
-  if (b->model->host.solver != 1) { SET_ERR("gq_rollout_closed needs the Newton solver (solver = 1)"); return GQ_EINVAL; }
-  if (b->host.debug_envs > 0 || b->stop_stage != 0) { SET_ERR("gq_rollout_closed runs the production kernel: switch the inspection record / stage cut off first"); return GQ_EINVAL; }
+  if (!persistent_ok(b, auto_reset, "gq_rollout_closed")) return GQ_EINVAL;
   hipStream_t stream = (hipStream_t)hip_stream;
-  int rc = step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_rollout_closed"); /* validate + bind */
-  if (rc != GQ_OK) return rc;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_rollout_closed"); rc != GQ_OK) return rc;
   DeviceGuard guard(b->model->device);
-  rc = mailbox_setup(b);
-  if (rc != GQ_OK) return rc;
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
   if (n_steps == 0) return GQ_OK;
   const int N = b->host.n_envs, od = b->host.obs_dim;
-  gq::MailboxDev& h = b->mb.host;
+  Mailbox& mb = b->mb;
+  gq::MailboxDev& h = mb.host;
   /* queue tickets are 32-bit: the env-steps that pass through one queue must stay below 2^31 (items carry env + 1 in 24 bits) */
   if (N >= (1 << 24) || (int64_t)((N + h.nq - 1) / h.nq) * (int64_t)n_steps >= ((int64_t)1 << 31) - 65536) {
     SET_ERR("gq_rollout_closed: %d envs x %d steps over %d queues overflows the 32-bit ticket counters: split the rollout", N, n_steps, h.nq); return GQ_EINVAL;
@@ -560,20 +491,15 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
     if (policy_waves < 2 * h.nq) policy_waves = 2 * h.nq; /* every XCD needs policy wavefronts of its own (dispatch is round-robin over the XCDs) */
     P.sigma = pd->noise_sigma; P.seed_lo = (uint32_t)(pd->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(pd->noise_seed >> 32);
     P.step0 = pd->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
-    /* the parameter block lives in device memory for both modes */
-    if (b->staging_next == GQ_ARG_SLOTS) { HIP_TRY(hipStreamSynchronize(stream)); b->staging_next = 0; }
-    gq::PolicyPdDev* slot = reinterpret_cast<gq::PolicyPdDev*>(b->staging + b->staging_next++); /* a pinned staging slot of the argument ring */
-    std::memcpy(slot, &P, sizeof P);
-    HIP_TRY(hipMemcpyAsync(b->mb.policy_dev, slot, sizeof P, hipMemcpyHostToDevice, stream));
+    HIP_TRY(mb.policy.push(P, stream, true)); /* sent with every call, as ever */
   }
   if (mode == GQ_CLOSED_INLINE) {
     /* the persistent rollout kernel with the policy evaluated by the stepping wavefront itself: no mailbox, no second kernel */
     HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
     gq::StepCall ci{};
-    ci.n_steps = n_steps; ci.obs_seq = obs_seq; ci.act_seq = act_seq; ci.policy = b->mb.policy_dev;
+    ci.n_steps = n_steps; ci.obs_seq = obs_seq; ci.act_seq = act_seq; ci.policy = mb.policy.dev.get();
     ci.auto_reset = gq::auto_reset_mode(auto_reset); ci.stop_stage = 0;
-    launch_step_kernel(b, &ci, N, stream);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_step_kernel(b, &ci, N, stream));
     return GQ_OK;
   }
   if (step_waves <= 0) step_waves = N; /* more workgroups than free slots (or than envs) is harmless: pop tickets that run ahead of the pushes
@@ -589,38 +515,39 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * (size_t)h.nq * 3 * GQ_MB_QSTRIDE, stream));
   HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
   HIP_TRY(hipStreamSynchronize(stream)); /* the pinned staging block below is reused per call; a rollout is thousands of launches' worth of work */
-  std::memcpy(b->mb.staging, &h, sizeof h);
-  HIP_TRY(hipMemcpyAsync(b->mb.dev, b->mb.staging, sizeof h, hipMemcpyHostToDevice, stream));
+  std::memcpy(mb.staging.get(), &h, sizeof h);
+  HIP_TRY(hipMemcpyAsync(mb.dev.get(), mb.staging.get(), sizeof h, hipMemcpyHostToDevice, stream));
   gq::StepCall c{};
   c.auto_reset = gq::auto_reset_mode(auto_reset);
   if (pd) {
     /* the policy must be RESIDENT before the step wavefronts take every slot of the device: launch it first, on its own stream,
      * and wait until each of its workgroups has reported in */
-    *b->mb.alive = 0;
-    HIP_TRY(hipEventRecord(b->mb.fork, stream));
-    HIP_TRY(hipStreamWaitEvent(b->mb.stream, b->mb.fork, 0));
-    gq_launch_policy_pd(b->mb.dev, b->mb.policy_dev, out.obs, od, policy_waves, b->mb.stream);
+    volatile int32_t* alive = mb.alive.get();
+    *alive = 0;
+    HIP_TRY(hipEventRecord(mb.fork.get(), stream));
+    HIP_TRY(hipStreamWaitEvent(mb.stream.get(), mb.fork.get(), 0));
+    gq_launch_policy_pd(mb.dev.get(), mb.policy.dev.get(), out.obs, od, policy_waves, mb.stream.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->mb.join, b->mb.stream));
+    HIP_TRY(hipEventRecord(mb.join.get(), mb.stream.get()));
     const auto t0 = std::chrono::steady_clock::now();
-    while (*(volatile int32_t*)b->mb.alive < policy_waves) {
+    while (*alive < policy_waves) {
       std::this_thread::yield();
       if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
         /* it cannot start: tell it to leave as soon as it does, and report */
-        b->mb.status_host[0] = 3; /* pinned: the source of an asynchronous copy must outlive this frame */
-        (void)hipMemcpyAsync(h.status, b->mb.status_host, sizeof(int32_t), hipMemcpyHostToDevice, stream);
+        mb.status_host.get()[0] = 3; /* pinned: the source of an asynchronous copy must outlive this frame */
+        (void)hipMemcpyAsync(h.status, mb.status_host.get(), sizeof(int32_t), hipMemcpyHostToDevice, stream);
         (void)hipStreamSynchronize(stream);
-        (void)hipStreamSynchronize(b->mb.stream); /* the policy kernel has left (or never ran): nothing of this call touches `alive` later */
-        SET_ERR("gq_rollout_closed: the policy kernel did not become resident within 2 s (%d of %d workgroups)", (int)*(volatile int32_t*)b->mb.alive, policy_waves);
+        (void)hipStreamSynchronize(mb.stream.get()); /* the policy kernel has left (or never ran): nothing of this call touches `alive` later */
+        SET_ERR("gq_rollout_closed: the policy kernel did not become resident within 2 s (%d of %d workgroups)", (int)*alive, policy_waves);
         return GQ_EDEVICE;
       }
     }
   }
-  if (!gq_launch_mailbox_step(b->dev_args, &c, b->mb.dev, step_waves, b->model->host.solver, b->model->host.cone, b->model->scene, stream)) {
+  if (!gq_launch_mailbox_step(b->args.dev.get(), &c, mb.dev.get(), step_waves, b->model->host.solver, b->model->host.cone, b->model->scene, stream)) {
     SET_ERR("gq_rollout_closed: no mailbox variant of the step kernel for this model in this build"); return GQ_EINVAL;
   }
   HIP_TRY(hipGetLastError());
-  if (pd) HIP_TRY(hipStreamWaitEvent(stream, b->mb.join, 0)); /* the caller's stream resumes when both kernels are done */
+  if (pd) HIP_TRY(hipStreamWaitEvent(stream, mb.join.get(), 0)); /* the caller's stream resumes when both kernels are done */
   return GQ_OK;
 }
 
@@ -632,30 +559,19 @@ int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState
   if (decimation < 1) { SET_ERR("gq_step_joint_cmd: decimation must be >= 1 (got %d)", decimation); return GQ_EINVAL; }
   if (!cmd->q_des || !cmd->kp || !cmd->kd) { SET_ERR("gq_step_joint_cmd: q_des, kp and kd must be given"); return GQ_EINVAL; }
   if (cmd->gain_stride != 0 && cmd->gain_stride != 12) { SET_ERR("gq_step_joint_cmd: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", cmd->gain_stride); return GQ_EINVAL; }
-  if (auto_reset && !auto_reset->autoreset_next_step) { SET_ERR("gq_step_joint_cmd needs next-step auto-reset or none"); return GQ_EINVAL; }
-  if (b->model->host.solver != 1) { SET_ERR("gq_step_joint_cmd needs the Newton solver (solver = 1)"); return GQ_EINVAL; }
-  if (b->host.debug_envs > 0 || b->stop_stage != 0) { SET_ERR("gq_step_joint_cmd runs the production kernel: switch the inspection record / stage cut off first"); return GQ_EINVAL; }
+  if (!persistent_ok(b, auto_reset, "gq_step_joint_cmd")) return GQ_EINVAL;
   hipStream_t stream = (hipStream_t)hip_stream;
-  const int rc = step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_step_joint_cmd"); /* validate + bind */
-  if (rc != GQ_OK) return rc;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_step_joint_cmd"); rc != GQ_OK) return rc;
   DeviceGuard guard(b->model->device);
   /* the command pointers travel in a device block of their own: uploaded, stream-ordered, only when one of them changed */
-  gq::JointCmdDev J = b->jc_shadow; /* struct copy keeps padding bytes identical for the memcmp */
+  gq::JointCmdDev J = b->jc.shadow; /* a copy of the shadow, then the fields: see Staged */
   J.q_des = cmd->q_des; J.qd_des = cmd->qd_des; J.tau_ff = cmd->tau_ff; J.kp = cmd->kp; J.kd = cmd->kd;
   J.tau_out = cmd->tau_out; J.term_any = cmd->terminated_any; J.gain_stride = cmd->gain_stride; J.pad_ = 0;
-  if (!b->jc_valid || std::memcmp(&J, &b->jc_shadow, sizeof J) != 0) {
-    static_assert(sizeof(gq::JointCmdDev) <= sizeof(gq::FusedArgs), "the command block travels through a staging slot of the argument ring");
-    if (b->staging_next == GQ_ARG_SLOTS) { HIP_TRY(hipStreamSynchronize(stream)); b->staging_next = 0; }
-    gq::JointCmdDev* slot = reinterpret_cast<gq::JointCmdDev*>(b->staging + b->staging_next++); /* a pinned staging slot of the argument ring */
-    std::memcpy(slot, &J, sizeof J);
-    HIP_TRY(hipMemcpyAsync(b->jc_dev, slot, sizeof J, hipMemcpyHostToDevice, stream));
-    b->jc_shadow = J; b->jc_valid = true;
-  }
+  HIP_TRY(b->jc.push(J, stream, false));
   gq::StepCall c{};
-  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_joint_cmd(b->jc_dev);
+  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_joint_cmd(b->jc.dev.get());
   c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
-  launch_step_kernel(b, &c, b->host.n_envs, stream);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
   return GQ_OK;
 }
 
@@ -663,23 +579,20 @@ int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream) {
   if (!b || !out) { SET_ERR("gq_rollout_closed_status: null argument"); return GQ_EINVAL; }
   if (!b->mb.ready) { out[0] = out[1] = out[2] = out[3] = 0; return GQ_OK; }
   DeviceGuard guard(b->model->device);
-  HIP_TRY(hipMemcpyAsync(b->mb.status_host, b->mb.host.status, sizeof(int32_t) * 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+  HIP_TRY(hipMemcpyAsync(b->mb.status_host.get(), b->mb.host.status, sizeof(int32_t) * 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-  for (int i = 0; i < 4; i++) out[i] = b->mb.status_host[i];
+  for (int i = 0; i < 4; i++) out[i] = b->mb.status_host.get()[i];
   if (out[0] != 0) { SET_ERR("closed-loop rollout aborted: code %d (1: a step wavefront waited past the deadline for ticket %d; 2: policy lane %d waited past the deadline; 3: policy not resident; 4: no policy wavefront on XCD queue %d), %d env-steps were played", out[0], out[1], out[1], out[1], out[2]); return GQ_EDEVICE; }
   return GQ_OK;
 }
 
 int gq_batch_bind(GqBatch* b, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, void* hip_stream) {
-  return step_launch(b, 0, 0, nullptr, nullptr, st, out, auto_reset, episode, lift_failed, hip_stream, "gq_batch_bind");
+  return bind(b, st, out, auto_reset, episode, lift_failed, (hipStream_t)hip_stream, "gq_batch_bind");
 }
 
 int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const float* qvel_new, const GqResetCfg* cfg,
              GqState st, GqObsOut out, int32_t* episode, uint8_t* lift_failed, void* hip_stream) {
-  if (!b || !cfg || !st.qpos || !st.qvel || !st.qacc || !st.qacc_warmstart || !st.time || !out.step_num || !out.obs ||
-      !out.reward || !out.terminated || !out.truncated || !out.invalid_contact) {
-    SET_ERR("gq_reset: null tensor"); return GQ_EINVAL;
-  }
+  if (!b || !cfg || !have_tensors(st, out)) { SET_ERR("gq_reset: null tensor"); return GQ_EINVAL; }
   if ((qpos_new == nullptr) != (qvel_new == nullptr)) { SET_ERR("gq_reset: qpos_new and qvel_new must be given together"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   gq::ResetArgs r{};
@@ -687,16 +600,14 @@ int gq_reset(GqBatch* b, const uint8_t* mask, const double* qpos_new, const floa
   r.mask = mask; r.qpos_new = qpos_new; r.qvel_new = qvel_new;
   r.clear_terminated = out.terminated; r.clear_truncated = out.truncated; r.clear_invalid = out.invalid_contact;
   r.lift_pending = b->p.lift_pending;
-  { const int rcb = flush_batch(b, (hipStream_t)hip_stream); if (rcb != GQ_OK) return rcb; }
+  if (const int rc = flush_batch(b, (hipStream_t)hip_stream); rc != GQ_OK) return rc;
   gq_launch_reset(&r, b->host.n_envs, b->model->scene, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   /* the reset's own mj_step with zero control (quadruped_env.py:334, :397); friction committed after it (:403-404) */
-  const int rc = ensure_args(b, st, out, episode, lift_failed, nullptr, (hipStream_t)hip_stream);
-  if (rc != GQ_OK) return rc;
+  if (const int rc = ensure_args(b, st, out, episode, lift_failed, nullptr, (hipStream_t)hip_stream); rc != GQ_OK) return rc;
   gq::StepCall c{};
-  c.mask = mask; c.first_pass = 1; c.debug = b->host.debug_envs > 0 ? b->debug : nullptr;
-  launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
-  HIP_TRY(hipGetLastError());
+  c.mask = mask; c.first_pass = 1; c.debug = b->host.debug_envs > 0 ? b->debug.get() : nullptr;
+  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream));
   return GQ_OK;
 }
 
@@ -712,7 +623,7 @@ int gq_heightmap(GqBatch* b, const double* center, const float* yaw, int rows, i
                  float* out, void* hip_stream) {
   if (!b || !center || !yaw || !out || rows <= 0 || cols <= 0) { SET_ERR("gq_heightmap: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  gq_launch_heightmap(b->model->dev, center, 3, yaw, 1, b->host.n_envs, rows, cols, dist_x, dist_y, out, (hipStream_t)hip_stream);
+  gq_launch_heightmap(b->model->dev.get(), center, 3, yaw, 1, b->host.n_envs, rows, cols, dist_x, dist_y, out, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -721,7 +632,7 @@ int gq_heightmap_strided(GqBatch* b, const double* center, int center_stride, co
                          float dist_y, float* out, void* hip_stream) {
   if (!b || !center || !yaw || !out || rows <= 0 || cols <= 0 || center_stride < 0 || yaw_stride < 0) { SET_ERR("gq_heightmap_strided: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  gq_launch_heightmap(b->model->dev, center, center_stride, yaw, yaw_stride, b->host.n_envs, rows, cols, dist_x, dist_y, out, (hipStream_t)hip_stream);
+  gq_launch_heightmap(b->model->dev.get(), center, center_stride, yaw, yaw_stride, b->host.n_envs, rows, cols, dist_x, dist_y, out, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -730,7 +641,7 @@ int gq_jac(GqBatch* b, const double* qpos, int body, const double* point, float*
   if (!b || !qpos || !point || (!jacp && !jacr)) { SET_ERR("gq_jac: null argument"); return GQ_EINVAL; }
   if (body < 1 || body > GQ_NB) { SET_ERR("gq_jac: body id %d out of range (1 = base .. %d)", body, GQ_NB); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  gq_launch_jac(b->model->dev, qpos, body, point, jacp, jacr, b->host.n_envs, (hipStream_t)hip_stream);
+  gq_launch_jac(b->model->dev.get(), qpos, body, point, jacp, jacr, b->host.n_envs, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -738,7 +649,7 @@ int gq_jac(GqBatch* b, const double* qpos, int body, const double* point, float*
 int gq_ray(GqBatch* b, const double* origin, const float* dir, int n_rays, float* dist, int32_t* geom, void* hip_stream) {
   if (!b || !origin || !dir || !dist || n_rays <= 0) { SET_ERR("gq_ray: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  gq_launch_ray(b->model->dev, origin, dir, b->host.n_envs * n_rays, dist, geom, (hipStream_t)hip_stream);
+  gq_launch_ray(b->model->dev.get(), origin, dir, b->host.n_envs * n_rays, dist, geom, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -848,24 +759,16 @@ static int camera_run(const char* fn, const int mode, GqBatch* b, const double* 
                         hull_planes, hull_plane_adr, depth, seg, cam_xpos, cam_xmat, g_err, sizeof g_err)) return GQ_EINVAL;
   DeviceGuard guard(m->device);
   const int n = b->host.n_envs;
-  if (!b->cam_rec) {
-    HIP_TRY(hipMalloc(&b->cam_rec, sizeof(float) * GQ_CAM_REC * (size_t)n));
-    HIP_TRY(hipMalloc(&b->cam_pos, sizeof(double) * 3 * (size_t)n));
-  }
-  c.rec = b->cam_rec; c.cpos = b->cam_pos;
+  HIP_TRY(gq::ensure_both(b->cam_rec, (size_t)GQ_CAM_REC * n, b->cam_pos, (size_t)3 * n, false));
+  c.rec = b->cam_rec.get(); c.cpos = b->cam_pos.get();
   gq::CamLayers l{};
   if (mode >= 2) {
-    if (layers->n_ghost > b->cam_nghost) {
-      hipFree(b->cam_grec);
-      b->cam_grec = nullptr; b->cam_nghost = 0;
-      HIP_TRY(hipMalloc(&b->cam_grec, sizeof(float) * GQ_CAM_GREC * (size_t)layers->n_ghost * n));
-      b->cam_nghost = layers->n_ghost;
-    }
+    HIP_TRY(b->cam_grec.ensure((size_t)GQ_CAM_GREC * layers->n_ghost * n, false));
     l.ghost_qpos = layers->ghost_qpos; l.ghost_stride = layers->ghost_stride; l.n_ghost = layers->n_ghost;
     l.ghost_alpha = layers->ghost_alpha; l.ghost_rgb = layers->ghost_rgb;
-    l.n_marker = layers->n_marker; l.markers = layers->markers; l.grec = b->cam_grec;
+    l.n_marker = layers->n_marker; l.markers = layers->markers; l.grec = b->cam_grec.get();
   }
-  gq_launch_camera(m->dev, &c, mode >= 1 ? &s : nullptr, mode >= 2 ? &l : nullptr, n, (hipStream_t)hip_stream);
+  gq_launch_camera(m->dev.get(), &c, mode >= 1 ? &s : nullptr, mode >= 2 ? &l : nullptr, n, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -891,18 +794,15 @@ int gq_camera_layered(GqBatch* b, const double* qpos, int qpos_stride, int body,
 }
 
 int gq_forward(GqBatch* b, int stage, const float* ctrl, GqState st, GqObsOut out, void* hip_stream) {
-  if (!b || !st.qpos || !st.qvel || !st.qacc || !st.qacc_warmstart || !st.time || !out.obs || !out.reward || !out.terminated ||
-      !out.truncated || !out.invalid_contact || !out.step_num) { SET_ERR("gq_forward: null tensor"); return GQ_EINVAL; }
+  if (!b || !have_tensors(st, out)) { SET_ERR("gq_forward: null tensor"); return GQ_EINVAL; }
   if (stage != 0 && stage != 1) { SET_ERR("gq_forward: stage must be 0 (mj_forward) or 1 (mj_step1)"); return GQ_EINVAL; }
-  if (b->host.debug_envs <= 0 || !b->debug) { SET_ERR("gq_forward: no inspection record to write to (call gq_debug_enable first)"); return GQ_EINVAL; }
+  if (b->host.debug_envs <= 0 || !b->debug.get()) { SET_ERR("gq_forward: no inspection record to write to (call gq_debug_enable first)"); return GQ_EINVAL; }
   if (b->model->host.solver != 1) { SET_ERR("gq_forward needs the Newton solver (solver = 1)"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
-  const int rc = ensure_args(b, st, out, nullptr, nullptr, nullptr, (hipStream_t)hip_stream);
-  if (rc != GQ_OK) return rc;
+  if (const int rc = ensure_args(b, st, out, nullptr, nullptr, nullptr, (hipStream_t)hip_stream); rc != GQ_OK) return rc;
   gq::StepCall c{};
-  c.ctrl = ctrl; c.debug = b->debug; c.forward = stage == 1 ? 1 : 2;
-  launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream);
-  HIP_TRY(hipGetLastError());
+  c.ctrl = ctrl; c.debug = b->debug.get(); c.forward = stage == 1 ? 1 : 2;
+  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, (hipStream_t)hip_stream));
   return GQ_OK;
 }
 
@@ -931,31 +831,31 @@ int gq_debug_field(const char* name, int32_t* offset, int32_t* count) {
 
 int gq_debug_device_buffer(GqBatch* b, float** dev, int32_t* n_envs, int32_t* stride) {
   if (!b || !dev || !n_envs || !stride) { SET_ERR("gq_debug_device_buffer: null argument"); return GQ_EINVAL; }
-  *dev = b->host.debug_envs > 0 ? b->debug : nullptr; *n_envs = b->host.debug_envs; *stride = GQ_DBG_SIZE;
+  *dev = b->host.debug_envs > 0 ? b->debug.get() : nullptr; *n_envs = b->host.debug_envs; *stride = GQ_DBG_SIZE;
   return GQ_OK;
 }
 
 int gq_full_mass(GqBatch* b, int n_envs, float* M, void* hip_stream) {
   if (!b || !M || n_envs <= 0) { SET_ERR("gq_full_mass: null / empty argument"); return GQ_EINVAL; }
-  if (!b->debug || n_envs > b->host.debug_envs) {
+  if (!b->debug.get() || n_envs > b->host.debug_envs) {
     SET_ERR("gq_full_mass: the inspection record covers %d envs, %d requested (gq_debug_enable first, then gq_step / gq_forward)", b->host.debug_envs, n_envs);
     return GQ_EINVAL;
   }
   DeviceGuard guard(b->model->device);
-  HIP_TRY(hipMemcpy2DAsync(M, 324 * sizeof(float), b->debug + GQ_DBG_M, GQ_DBG_SIZE * sizeof(float), 324 * sizeof(float), (size_t)n_envs,
+  HIP_TRY(hipMemcpy2DAsync(M, 324 * sizeof(float), b->debug.get() + GQ_DBG_M, GQ_DBG_SIZE * sizeof(float), 324 * sizeof(float), (size_t)n_envs,
                            hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
   return GQ_OK;
 }
 
 int gq_debug_get(GqBatch* b, int env, const char* name, double* out, int max_n) {
-  if (!b || !name || !out || env < 0 || env >= b->host.debug_envs || !b->debug) { SET_ERR("gq_debug_get: bad argument / debug not enabled"); return GQ_EINVAL; }
+  if (!b || !name || !out || env < 0 || env >= b->host.debug_envs || !b->debug.get()) { SET_ERR("gq_debug_get: bad argument / debug not enabled"); return GQ_EINVAL; }
   for (const auto& f : kDbg)
     if (!std::strcmp(f.name, name)) {
       int n = f.n < max_n ? f.n : max_n;
       std::vector<float> tmp((size_t)n);
       DeviceGuard guard(b->model->device);
       HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemcpy(tmp.data(), b->debug + (size_t)env * GQ_DBG_SIZE + f.off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(tmp.data(), b->debug.get() + (size_t)env * GQ_DBG_SIZE + f.off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
       for (int i = 0; i < n; i++) out[i] = tmp[(size_t)i];
       return n;
     }

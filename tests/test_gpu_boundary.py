@@ -281,3 +281,62 @@ def test_bench_plain_run_dumps_the_same_outputs_with_and_without_the_process_gro
         a, b = np.load(tmp_path / 'solo' / f), np.load(tmp_path / 'pg' / f)
         assert a.dtype in (np.float32, np.float64) and a.shape[0] == 4096 and np.isfinite(a).all(), f
         np.testing.assert_array_equal(a, b, err_msg=f)
+
+
+def test_argument_rings_wrap_without_a_sync():
+    """The small argument blocks the kernels read from device memory (FusedArgs, the batch constants, JointCmdDev, PolicyPdDev) reach the
+    device through pinned rings of 8 slots each, stream-ordered, with nothing between two calls but the stream's own order.  Two identical envs
+    play the same 60 calls, which keep re-sending every one of those blocks: 20 uploads of FusedArgs and 10 of each of the other three, so every
+    ring wraps at least once (32 calls would do for a ring that all four share; with a ring per block they wrap FusedArgs' only).  One env never
+    synchronises and makes no host round trip between its calls, the other synchronises after every call.  State, flags and every call's
+    observation row must be equal bit for bit."""
+    import ctypes as C
+    from gym_quadruped_amd import _lib
+    from gym_quadruped_amd.cabi import GqObsOut
+    from gym_quadruped_amd.quadruped_env import QuadrupedEnv
+    n, calls, dev = 5, 60, 'cuda:0'
+    g = torch.Generator(device=dev).manual_seed(7)
+    act = torch.randn(calls, 2, n, 12, generator=g, device=dev) * 20
+    kp, kd = torch.full((12,), 30.0, device=dev), torch.full((12,), 1.0, device=dev)
+
+    def play(sync):
+        env = QuadrupedEnv('mini_cheetah', state_obs_names=('qpos', 'qvel'), scene='flat', base_vel_command_type='forward+reset', num_envs=n, device=dev,
+                           solver='newton', auto_reset='next_step', seed=11)
+        env.reset(random=True)
+        q_home = env._key_qpos[7:19].float().cpu().numpy()   # a host copy, made before the loop: rollout_closed_loop(q_des=None) would fetch it in every call
+        q_des = [env._key_qpos[7:19].float().expand(n, 12) + 0.1 * k * act[0, 0] / 20 for k in (1, 2)]
+        obs2 = torch.zeros_like(env._obs_buf)
+        out2 = GqObsOut(obs2.data_ptr(), env._reward.data_ptr(), env._terminated.data_ptr(), env._truncated.data_ptr(), env._invalid.data_ptr(),
+                        env._step_num.data_ptr(), env._step_num_prev.data_ptr(), env._contacts_dropped.data_ptr())
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        rows = []
+        for k in range(calls):
+            kind, row = k % 6, env._obs_buf
+            if kind == 0:
+                env.step(act[k, 0])
+            elif kind == 1:    # the same step through the C ABI, its observation row in a second buffer: the argument block changes, and changes back
+                _lib.check(env._L.gq_step(env._hbatch, act[k, 0].data_ptr(), None, env._st, out2, env._auto_cfg, env._episode.data_ptr(),
+                                          env._lift_failed.data_ptr(), stream), 'gq_step')
+                row = obs2
+            elif kind == 2:
+                env.step_pd(q_des[(k // 6) % 2], kp, kd, decimation=2)
+            elif kind == 3:
+                env.rollout_closed_loop(1, 30.0, 1.0, q_home, mode='inline', check=False)
+            elif kind == 4:
+                env.rollout(act[k], shards=2)
+            else:              # the env's own resampling block once more: marks the batch constants dirty, changes nothing
+                _lib.check(env._L.gq_batch_set_resampling(env._hbatch, C.byref(env._resample_cfg), C.byref(env._reset_cfg), env._h9.data_ptr(),
+                                                          env._ext_dist.data_ptr()), 'gq_batch_set_resampling')
+            rows.append(row.clone())
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return env, rows
+
+    (a, rows_a), (b, rows_b) = play(False), play(True)
+    for name in ('_qpos', '_qvel', '_reward', '_terminated'):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert torch.isfinite(a._qpos).all() and int(a._step_num.max()) >= 1
+    for k, (ra, rb) in enumerate(zip(rows_a, rows_b)):
+        assert torch.equal(ra, rb), f'observation row after call {k}'
