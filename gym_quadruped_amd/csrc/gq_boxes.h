@@ -773,23 +773,29 @@ __device__ inline bool self_hulls_apart(const WaveMem& W, const GQ_MODEL GqDevMo
 }
 
 /* COLD: tell the register allocator that the convex block is rarely entered (see there) - the world-box variants, whose robots mostly have no hull
- * pair (aliengo perlin + 8 %), do; the flat-scene variants, whose launch on the headline workload IS the convex routine, do not (- 4 % with it) */
-template <bool CONE, bool PRIM = true, bool COLD = false>
+ * pair (aliengo perlin + 8 %), do; the flat-scene variants, whose launch on the headline workload IS the convex routine, do not (- 4 % with it).
+ * CVX false (SCENE_FLAT_SELF_PRIM: the model's pair table holds no kind 4): the convex mid phase, the convex routine and everything of the pair
+ * exchange - the fetches up here, publication, claim / linger loop, collect - are not compiled in; PRIM false (SCENE_FLAT_SELF_HULL, world hull
+ * scenes: no kind 1 - 3): nor are the exact box routines.  gq_step_call.h model_scene picks the scene from the same table that pass B walks. */
+template <bool CONE, bool PRIM = true, bool COLD = false, bool CVX = true>
 __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevModel& m, float mu_env, WorldAppend& S, const SelfPrefetch& pre, const StepConsts& K, const int nlg, const GQ_MODEL GqDevBatch& Bt, float* xdbg = nullptr, const int env = 0) {
   constexpr int NP = PRIM ? 4 : 1; /* points per pair: only the exact pair routines return more than one */
   const int lane = lane_id();
   const int nsp = K.nsp;
   if (nsp == 0) return;
-#ifdef GQ_XQ_OFF /* experiment builds: the pair exchange compiled out */
-  int32_t* const xq_tab = nullptr; const int xq_slots = 0; const int xq_pre = 0; (void)Bt;
-#else
-  int32_t* const xq_tab = Bt.xq; const int xq_slots = Bt.xq_slots; /* (fetched here: the scalar loads return behind the end points and the pair cull) */
-  /* the first half of this wavefront's window of the table - its word 31: when a pair was last published into the window, its word 63: when
-   * an env without convex work (a potential helper) last passed by - fetched here, so that the latency passes behind the end points and the cull */
-  float* const sepc = Bt.sepc ? Bt.sepc + (size_t)env * Bt.sepc_stride : nullptr; /* this env's rows of the separating-axis cache */
+  int32_t* xq_tab = nullptr; int xq_slots = 0; /* the pair exchange: none without the convex block - and none in the experiment builds with -DGQ_XQ_OFF */
+  float* sepc = nullptr; /* this env's rows of the separating-axis cache */
   int xq_pre = 0;
-  if (xq_tab) { Xq X0; X0.q = xq_tab; X0.slots = xq_slots; xq_pre = ld_pub(xq_tab + xq_window(X0, wave_index()) + lane); }
+  (void)Bt; (void)env; (void)xdbg;
+  if constexpr (CVX) {
+#ifndef GQ_XQ_OFF
+    xq_tab = Bt.xq; xq_slots = Bt.xq_slots; /* (fetched here: the scalar loads return behind the end points and the pair cull) */
 #endif
+    /* the first half of this wavefront's window of the table - its word 31: when a pair was last published into the window, its word 63: when
+     * an env without convex work (a potential helper) last passed by - fetched here, so that the latency passes behind the end points and the cull */
+    sepc = Bt.sepc ? Bt.sepc + (size_t)env * Bt.sepc_stride : nullptr;
+    if (xq_tab) { Xq X0; X0.q = xq_tab; X0.slots = xq_slots; xq_pre = ld_pub(xq_tab + xq_window(X0, wave_index()) + lane); }
+  }
   const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   /* world end points of every item's proxy capsule, once: lane = collision item; scratch in the J block, which is free
    * until S7 (the spatial-dynamics scratch it overlays is dead since S5) */
@@ -862,13 +868,17 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
     ncand += popc64(cm);
   }
   GQ_SUB(W, 1, 11); /* pair cull */
-  const int xq_act = bcast(xq_pre, 31), xq_hlp = bcast(xq_pre, 63);
+  int xq_act = 0, xq_hlp = 0;
+  if constexpr (CVX) { xq_act = bcast(xq_pre, 31); xq_hlp = bcast(xq_pre, 63); }
   if (K.self_cut == 2) return;
   if (ncand == 0) { /* nothing of its own to do here: leave word of that, and stay only if pairs have come this way lately */
-    if (xq_tab == nullptr) return;
-    Xq X0; X0.q = xq_tab; X0.slots = xq_slots;
-    xq_mark_helper(X0, wave_index(), xq_hlp);
-    if (!xq_is_hot(xq_act, wall_clock64())) return;
+    if constexpr (!CVX) return;
+    else {
+      if (xq_tab == nullptr) return;
+      Xq X0; X0.q = xq_tab; X0.slots = xq_slots;
+      xq_mark_helper(X0, wave_index(), xq_hlp);
+      if (!xq_is_hot(xq_act, wall_clock64())) return;
+    }
   }
   if (ncand > 2 * GQ_WAVE) ncand = 2 * GQ_WAVE; /* more than 128 close pairs: the robot is a knot; the row budget is long spent */
   wave_barrier();
@@ -897,7 +907,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
           const V3 nrm = fast_rcp(len) * d;
           H.n = 1; H.dist[0] = dist; H.nrm[0] = nrm; H.pos[0] = c1 + (k1[6] + 0.5f * dist) * nrm;
         }
-      } else if (kind == 4) { /* a hull / cylinder is involved: the convex routine, one pair at a time below - here its mid phase, the two shapes' oriented boxes */
+      } else if (kind == 4) { if constexpr (CVX) { /* a hull / cylinder is involved: the convex routine, one pair at a time below - here its mid phase, the two shapes' oriented boxes */
         V3 c1, h1, c2, h2; float R1[9], R2[9];
         self_item_obb(W, m, it1, k1, c1, R1, h1);
         self_item_obb(W, m, it2, k2, c2, R2, h2);
@@ -908,7 +918,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
           const V3 dw = matvec(W.xmat[0], v3(c[0], c[1], c[2]));
           if (dot(dw, dw) > 0.25f) cvx = !self_hulls_apart(W, m, K.vx, it1, k1, R1, it2, k2, R2, marg, true, dw);
         }
-      } else if constexpr (PRIM) { /* a box is involved: exact routines (gq_pairs.h); the box of kind 1 / 3 is item 1, of kind 2 item 2 */
+      } } else if constexpr (PRIM) { /* a box is involved: exact routines (gq_pairs.h); the box of kind 1 / 3 is item 1, of kind 2 item 2 */
         const int ib = kind == 2 ? it2 : it1;
         bool continue_pair = true;
         const GQ_MODEL GqDevGeom& G = m.lg[ib - 4];
@@ -944,7 +954,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
         }
       }
     }
-    { /* the convex pairs that passed their mid phase, one after the other on the whole wavefront (gq_convex.h) - or, when the batch has a
+    if constexpr (CVX) { /* the convex pairs that passed their mid phase, one after the other on the whole wavefront (gq_convex.h) - or, when the batch has a
        * pair exchange and this env several pairs, shared with wavefronts that have time (gq_exchange.h).  ONE call site of the routine
        * serves the pairs computed here and the published pairs taken back. */
       uint64_t cm = ballot(cvx);
@@ -964,7 +974,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
       if (X.q != nullptr && cm == 0 && ncand != 0 && c0 + GQ_WAVE >= npass) xq_mark_helper(X, wave_index(), xq_hlp);
       if (GQ_COLD_HINT(X.q != nullptr && (cm & (cm - 1)) != 0 && xq_is_hot(xq_hlp, wall_clock64()))) { /* two pairs or more - and envs with time on their hands around (hyqreal1 on boxes: every env has four or five pairs, publishing would be pure overhead): keep the first, publish the others - at once, helpers come by only so often */
         const uint64_t rest = cm & (cm - 1);
-        if ((rest >> lane) & 1ull) myslot = xq_reserve(X, wave_index(), lane);
+        if ((rest >> lane) & 1ull) myslot = xq_reserve(X, wave_index(), opaque_lane(lane)); /* (opaque: the four candidate slots' addresses depend on wavefront and lane alone, and were computed in front of pass B and kept across it in scratch memory - 7 64-bit stores there, as many reloads in front of the reservation) */
         own = ballot(myslot >= 0);
         local = cm & ~own; /* (no free slot among a pair's candidates: it stays here) */
         for (uint64_t r = own; r;) {
@@ -1120,7 +1130,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
 
 /* S6 for a scene without world boxes / height field but with robot self-collision: general frames for the floor
  * contacts the floor pass left in W, then the robot-robot contacts.  Ends with a barrier. */
-template <bool CONE>
+template <bool CONE, bool PRIM = true, bool CVX = true>
 __device__ __forceinline__ void stage_self_contacts(WaveMem& W, const GQ_MODEL GqDevModel& m, float mu_env, const SelfPrefetch& pre, const StepConsts& K, const int nlg, const GQ_MODEL GqDevBatch& Bt, float* xdbg = nullptr, const int env = 0) {
   const int lane = lane_id();
   WorldAppend S;
@@ -1133,7 +1143,7 @@ __device__ __forceinline__ void stage_self_contacts(WaveMem& W, const GQ_MODEL G
   }
   if constexpr (CONE)
     for (int c = 0; c < ncon; c++) { const int d = uniform(W.con_dim[c]); S.reserve += d > 1 ? d - 1 : 0; }
-  append_self_contacts<CONE>(W, m, mu_env, S, pre, K, nlg, Bt, xdbg, env);
+  append_self_contacts<CONE, PRIM, false, CVX>(W, m, mu_env, S, pre, K, nlg, Bt, xdbg, env);
   { W.ncon = S.ncon; W.nefc = S.rows; W.nself = S.nself; W.ndrop = S.ndrop; } /* (every lane: the same words) */
   wave_barrier();
 }

@@ -81,9 +81,11 @@ __device__ __forceinline__ void joint_cmd_inline(const GQ_MODEL JointCmdDev& J, 
 /* step (+ in-kernel auto-reset).  Same-step mode: a terminated env is re-spawned by the same wavefront - reset_wave,
  * then the reset's own mj_step as a second pass through step_wave; no extra launches, but the launch lasts as long as
  * its two-pass waves.  Next-step mode: the env waits (pending flag) and spends its next launch on reset_wave + the
- * reset's mj_step instead of a user step - every wave runs exactly one mj_step per launch. */
-template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST = false>
-__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __restrict__ A, const StepCall c) {
+ * reset's mj_step instead of a user step - every wave runs exactly one mj_step per launch.
+ * The body of step_kernel and of step_kernel_prim below, which differ in CVX alone (gq_step_kernel.h scene_cvx): the scenes that existed
+ * before the flat self-collision scene was split keep their kernels' names, template arguments included. */
+template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST, bool CVX>
+__device__ __forceinline__ void step_kernel_body(const FusedArgs* __restrict__ A, const StepCall c) {
   const long long t_entry = (GQ_TICKSET && MODE == 1) ? cycles() : 0; /* sub-stage builds (gq_step_kernel.h GQ_TICKSET) count from here */
   const int env = wave_index() + c.env0;
   if (c.mask && !gptr(c.mask)[env]) return; /* wave-uniform */
@@ -124,7 +126,7 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __res
       pass = c.auto_reset;
       hint = load_rows<SOLVER>(A->s, c, W, env, false, C, true);
     }
-    const int term = step_wave<SOLVER, MODE, CONE, BOXES, SELF, PRIM>(A->s, c, W, pass, hint, C, t_entry);
+    const int term = step_wave<SOLVER, MODE, CONE, BOXES, SELF, PRIM, false, CVX>(A->s, c, W, pass, hint, C, t_entry);
     if constexpr (PERSIST && SOLVER == 1) { /* gq_step_joint_cmd: the window's OR of `terminated`, kept in memory - stored by the first
                                              * substep, set by a later one that terminates (a re-spawn's own step reports none) */
       const int t = pass == 0 ? term : 0;
@@ -141,11 +143,20 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __res
   wave_barrier();
   }
 }
+template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST = false>
+__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __restrict__ A, const StepCall c) {
+  step_kernel_body<SOLVER, MODE, CONE, BOXES, SELF, PRIM, PERSIST, true>(A, c);
+}
+/* SCENE_FLAT_SELF_PRIM: the self-collision stage without the convex block and the pair exchange */
+template <int SOLVER, int MODE, bool CONE, bool PERSIST = false>
+__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel_prim(const FusedArgs* __restrict__ A, const StepCall c) {
+  step_kernel_body<SOLVER, MODE, CONE, false, true, true, PERSIST, false>(A, c);
+}
 
 /* Closed-loop persistent rollout, the stepping side (protocol: gq_step_kernel.h MailboxDev).  grid = any number of one-wave workgroups:
  * each pops tickets of ITS XCD's ready queue until every env-step of the rollout has been claimed.  Production Newton variants only. */
-template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM>
-__global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
+template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM, bool CVX>
+__device__ __forceinline__ void mailbox_step_body(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
   __shared__ WaveMem W;
 #if GQ_TICKSET
   if (lane_id() == 0) W.tk_T = nullptr;
@@ -200,13 +211,21 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArg
       pass = c.auto_reset;
       hint = load_rows<SOLVER, true>(A->s, c, W, env, false, C, true);
     }
-    step_wave<SOLVER, 0, CONE, BOXES, SELF, PRIM, true>(A->s, c, W, pass, hint, C);
+    step_wave<SOLVER, 0, CONE, BOXES, SELF, PRIM, true, CVX>(A->s, c, W, pass, hint, C);
     publish_fence(); /* state rows are in this XCD's L2, the observation row has been written through */
     if (lane_id() == 0) add_pub(MB.steps_done + env, 1);
     wave_barrier();
     played++;
   }
   if (lane_id() == 0 && played) add_pub(MB.status + 2, played);
+}
+template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM>
+__global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
+  mailbox_step_body<SOLVER, CONE, BOXES, SELF, PRIM, true>(A, c0, MBp);
+}
+template <int SOLVER, bool CONE> /* SCENE_FLAT_SELF_PRIM, as step_kernel_prim */
+__global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel_prim(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
+  mailbox_step_body<SOLVER, CONE, false, true, true, false>(A, c0, MBp);
 }
 
 #if GQ_IN_MISC
@@ -392,18 +411,24 @@ __global__ void __launch_bounds__(GQ_WAVE) camera_layer_kernel(const GQ_GLOBAL G
 
 /* ---- the kernel variants (Key, gq_step_kernel.h), the part that builds each, and the run-time dispatch to them. */
 /* part 0: the non-template kernels and the launch entry points; 1-18: step variants by solver and cone x mode x flat or world scene;
- * 19-22: mailbox variants by cone x flat or world scene.  Each part is one translation unit (-DGQ_PART=k); the Makefile's NPARTS is checked. */
+ * 19-22: mailbox variants by cone x flat or world scene; 23-31: step variants of the two split flat self-collision scenes (_HULL, _PRIM)
+ * by solver and cone x mode; 32-33: their mailbox variants by cone.  Each part is one translation unit (-DGQ_PART=k); the Makefile's
+ * NPARTS is checked. */
+constexpr bool scene_split(Scene s) { return s == SCENE_FLAT_SELF_HULL || s == SCENE_FLAT_SELF_PRIM; }
 constexpr int part_of(Key k) {
   const int world = scene_boxes(Scene(k.scene));
+  if (scene_split(Scene(k.scene))) return k.mailbox ? 32 + k.cone : 23 + (k.solver + k.cone) * 3 + k.mode;
   return k.mailbox ? 19 + 2 * k.cone + world : 1 + ((k.solver + k.cone) * 3 + k.mode) * 2 + world;
 }
-constexpr int kParts = part_of({1, 0, 1, SCENE_WORLD_PRIM, 1}) + 1;
+constexpr int kParts = part_of({1, 0, 1, SCENE_FLAT_SELF_PRIM, 1}) + 1;
 #ifdef GQ_NPARTS
 static_assert(GQ_NPARTS == kParts, "csrc/Makefile NPARTS does not match part_of()");
 #endif
 /* Development builds (make dev, tools/dev_build.sh: -DGQ_DEV_ONLY=<cone>, one unit, a 15 s build for A/B timing of kernel experiments
  * through GQ_LIBGQ_PATH) carry the Newton step variants of one cone and one scene - flat + self-collision, -DGQ_DEV_BOXES=1 world hull,
- * =2 world prim - without the stage cut unless -DGQ_DEV_CUTS=1, and the flat self-collision mailbox variant; any other step launch aborts. */
+ * =2 world prim - without the stage cut unless -DGQ_DEV_CUTS=1, and the flat self-collision mailbox variant; any other step launch aborts.
+ * The flat self-collision scene is the one -DGQ_DEV_SELF names: 0 both pair routines (b2, go1 - and every robot when the build also has
+ * -DGQ_SCENE_SPLIT_OFF), 1 SCENE_FLAT_SELF_HULL (mini_cheetah, hyqreal1, spot), 2 SCENE_FLAT_SELF_PRIM (go2, aliengo, hyqreal2, capsule mode). */
 #ifdef GQ_DEV_ONLY
 #ifndef GQ_DEV_BOXES
 #define GQ_DEV_BOXES 0
@@ -411,9 +436,13 @@ static_assert(GQ_NPARTS == kParts, "csrc/Makefile NPARTS does not match part_of(
 #ifndef GQ_DEV_CUTS
 #define GQ_DEV_CUTS 0
 #endif
-constexpr Scene kDevScene = GQ_DEV_BOXES == 2 ? SCENE_WORLD_PRIM : GQ_DEV_BOXES ? SCENE_WORLD_HULL : SCENE_FLAT_SELF;
+#ifndef GQ_DEV_SELF
+#define GQ_DEV_SELF 0
+#endif
+constexpr Scene kDevFlat = GQ_DEV_SELF == 2 ? SCENE_FLAT_SELF_PRIM : GQ_DEV_SELF ? SCENE_FLAT_SELF_HULL : SCENE_FLAT_SELF;
+constexpr Scene kDevScene = GQ_DEV_BOXES == 2 ? SCENE_WORLD_PRIM : GQ_DEV_BOXES ? SCENE_WORLD_HULL : kDevFlat;
 constexpr bool in_build(Key k) {
-  return k.solver == 1 && k.cone == (GQ_DEV_ONLY != 0) && (k.mode != 2 || GQ_DEV_CUTS) && k.scene == (k.mailbox ? SCENE_FLAT_SELF : kDevScene);
+  return k.solver == 1 && k.cone == (GQ_DEV_ONLY != 0) && (k.mode != 2 || GQ_DEV_CUTS) && k.scene == (k.mailbox ? kDevFlat : kDevScene);
 }
 #else
 constexpr bool in_build(Key) { return true; }
@@ -425,18 +454,23 @@ struct Launch { Key key; const FusedArgs* args; const StepCall* c; const Mailbox
 template <int S, int M, int CONE, int SC, int MB>
 static void launch_variant(const Launch& L) {
   constexpr bool C = CONE, B = scene_boxes(Scene(SC)), SF = scene_self(Scene(SC)), P = scene_prim(Scene(SC));
+  constexpr bool NOCVX = SF && !scene_cvx(Scene(SC)); /* the self stage without the convex block: the _prim kernels (SCENE_FLAT has no self stage at all) */
+  static_assert(!NOCVX || (!B && P), "step_kernel_prim is the flat scene with the box routines");
   StepCall call = *L.c;
   if constexpr (MB) {
-    hipLaunchKernelGGL((mailbox_step_kernel<S, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call, L.mb);
+    if constexpr (NOCVX) hipLaunchKernelGGL((mailbox_step_kernel_prim<S, C>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call, L.mb);
+    else hipLaunchKernelGGL((mailbox_step_kernel<S, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call, L.mb);
   } else {
     if constexpr (M == 0) {
       if (call.n_steps > 1 || call.policy) { /* persistent rollout (also a one-step one with the policy inline: only this variant evaluates it): production kernel only */
-        hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+        if constexpr (NOCVX) hipLaunchKernelGGL((step_kernel_prim<S, M, C, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+        else hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
         return;
       }
     }
     call.n_steps = 1;
-    hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+    if constexpr (NOCVX) hipLaunchKernelGGL((step_kernel_prim<S, M, C>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+    else hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
   }
 }
 /* launches L's variant if the unit of part PART instantiates it; false otherwise */

@@ -521,8 +521,8 @@ __device__ __forceinline__ int load_rows(const StepArgs& a, const StepCall& call
  * PRIM (BOXES variants): the robot has sphere / capsule / box link geoms, whose contacts with world boxes and with each other
  * come from the exact pair routines (gq_pairs.h); robots of hulls only get the variant without that code - merely compiled
  * in, it cost them 17 % (registers spilled across the box loop). */
-template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PUB = false> /* PUB: the observation row is published to a
-                                                                                                   * concurrently running reader (st_pub) */
+template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PUB = false /* the observation row is published to a concurrently
+          * running reader (st_pub) */, bool CVX = true /* flat self-collision scenes: the self stage carries the convex block (scene_cvx) */>
 __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call, WaveMem& W, const int pass, const int hint, const WaveCtx& C, const long long t_entry = 0) {
   /* lane / env are made opaque so that per-lane address arithmetic is not hoisted out of the (rarely taken) second
    * pass loop of the kernel and kept live - that hoisting alone cost > 250 spilled VGPRs */
@@ -952,7 +952,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
     stage_box_contacts<CONE, SELF, PRIM>(W, m, vx_p, vy_p, vz_p, bx0, by0, mu_b, self_pre, IT, K, nlg, Bt, (DBG && timing) ? call.debug + (size_t)env * GQ_DBG_SIZE + GQ_DBG_XQ : nullptr, env);
   } else if constexpr (SELF) {
     const float mu_b = W.mu_env;
-    stage_self_contacts<CONE>(W, m, mu_b, self_pre, K, nlg, Bt, (DBG && timing) ? call.debug + (size_t)env * GQ_DBG_SIZE + GQ_DBG_XQ : nullptr, env);
+    stage_self_contacts<CONE, PRIM, CVX>(W, m, mu_b, self_pre, K, nlg, Bt, (DBG && timing) ? call.debug + (size_t)env * GQ_DBG_SIZE + GQ_DBG_XQ : nullptr, env);
   }
   const int nefc = uniform(W.nefc), ncon = uniform(W.ncon), nlim = uniform(W.nlim), nfl = C.nfl; /* SGPRs */
   if (timing) { /* body poses go to the debug record now: xmat's LDS is reused by the Newton solver */

@@ -9,14 +9,28 @@
 
 namespace gq {
 /* world boxes / height field: the world scenes, split by whether the robot has sphere / capsule / box link geoms (exact pair routines
- * compiled in; gq_step_body.h PRIM); flat: the self-collision stage runs for a model with self-collision pairs */
+ * compiled in; gq_step_body.h PRIM); flat: the self-collision stage runs for a model with self-collision pairs, built with the pair
+ * routines its pair table names and no others (gq_step_kernel.h Scene).  The table read here, sp[0 .. nsp), is the one pass B of
+ * append_self_contacts walks (gq_boxes.h): a kind it holds always has its routine in the kernel.  -DGQ_SCENE_SPLIT_OFF (host code only,
+ * for tests and A/B builds): every flat self-collision model runs the kernel with all the routines. */
 inline Scene model_scene(const GqDevModel& h) {
   if (h.nbox > 0 || h.hf_nrow > 0) {
     /* lg[] is indexed by link geom (item[] is in contact order: feet and link geoms interleaved by geom id) */
     for (int g = 0; g < h.nlg; g++) { const int t = h.lg[g].ptype; if (t == 2 || t == 3 || t == 6) return SCENE_WORLD_PRIM; }
     return SCENE_WORLD_HULL;
   }
-  return h.nsp > 0 ? SCENE_FLAT_SELF : SCENE_FLAT;
+  if (h.nsp <= 0) return SCENE_FLAT;
+#ifdef GQ_SCENE_SPLIT_OFF
+  return SCENE_FLAT_SELF;
+#else
+  bool box = false, cvx = h.ncvx_self > 0;
+  for (int p = 0; p < h.nsp; p++) {
+    const int k = h.sp[p].kind;
+    if (k >= 1 && k <= 3) box = true;
+    else if (k != 0) cvx = true; /* kind 4 (counted by ncvx_self) - and anything this function does not know gets the full kernel */
+  }
+  return box && cvx ? SCENE_FLAT_SELF : cvx ? SCENE_FLAT_SELF_HULL : SCENE_FLAT_SELF_PRIM;
+#endif
 }
 /* StepCall::auto_reset of a launch that is given this auto-reset configuration (NULL: none) */
 inline int auto_reset_mode(const GqResetCfg* cfg) { return cfg ? (cfg->autoreset_next_step ? 2 : 1) : 0; }

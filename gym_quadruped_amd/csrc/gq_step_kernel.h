@@ -73,12 +73,17 @@ struct StepArgs {
 /* The scene a model's step-kernel variants are built for (gq_step_call.h model_scene; the launch entry points of gq_kernels.hip take it):
  * flat (no world geoms beyond the floor), flat + robot self-collision, world boxes / height field for a robot of hulls only, and the
  * same for a robot with sphere / capsule / box link geoms.  The world scenes always carry the self-collision stage (a model without
- * pairs skips it at run time).  scene_boxes / scene_self / scene_prim give the BOXES / SELF / PRIM template arguments of the kernels;
- * the flat scenes keep PRIM = true, the default their kernel names were first instantiated with. */
-enum Scene : int { SCENE_FLAT, SCENE_FLAT_SELF, SCENE_WORLD_HULL, SCENE_WORLD_PRIM, SCENE_COUNT };
+ * pairs skips it at run time).  The flat self-collision scene comes in three builds, chosen from the model's own pair table: with both
+ * the exact box routines (gq_pairs.h, pair kinds 1-3) and the convex block with its pair exchange (gq_convex.h / gq_exchange.h, kind 4),
+ * _HULL without the box routines (a robot of hulls and foot spheres), _PRIM without the convex block (a robot of boxes, capsules and
+ * spheres, or any robot in capsule-proxy mode).  The new scenes stand at the end: the values of the others are part of the launch ABI.
+ * scene_boxes / scene_self / scene_prim give the BOXES / SELF / PRIM template arguments of the kernels, scene_cvx whether the self stage
+ * carries the convex block (it is compiled in unless the kernel says otherwise: CVX of step_wave defaults to true). */
+enum Scene : int { SCENE_FLAT, SCENE_FLAT_SELF, SCENE_WORLD_HULL, SCENE_WORLD_PRIM, SCENE_FLAT_SELF_HULL, SCENE_FLAT_SELF_PRIM, SCENE_COUNT };
 constexpr bool scene_boxes(Scene s) { return s == SCENE_WORLD_HULL || s == SCENE_WORLD_PRIM; }
 constexpr bool scene_self(Scene s) { return s != SCENE_FLAT; }
-constexpr bool scene_prim(Scene s) { return s != SCENE_WORLD_HULL; }
+constexpr bool scene_prim(Scene s) { return s != SCENE_WORLD_HULL && s != SCENE_FLAT_SELF_HULL; }
+constexpr bool scene_cvx(Scene s) { return s != SCENE_FLAT_SELF_PRIM && s != SCENE_FLAT; }
 /* A step-kernel variant is a Key: solver (0 PGS, 1 Newton), mode (0 production; 1 debug record + stage timers; 2 stage cut,
  * gq_debug_stop_stage - its early returns cost the production kernel ~8 % when merely compiled in), cone (1 elliptic, Newton only:
  * gq_model_create rejects it with PGS), scene, and mailbox (1: the closed-loop rollout's mailbox_step_kernel, production Newton only; 0:
@@ -93,12 +98,14 @@ constexpr Key step_key(int solver, int cone, Scene scene, bool debug, int stop_s
 /* f(std::integral_constant<int, v>{}) for the run-time v in [0, N): turns one field of a key into a template argument */
 template <int N, class F>
 bool with_const(int v, F&& f) {
-  static_assert(N <= 4, "with_const: add cases");
+  static_assert(N <= 6, "with_const: add cases");
   switch (v) {
     case 0: return f(std::integral_constant<int, 0>{});
     case 1: if constexpr (N > 1) return f(std::integral_constant<int, 1>{}); break;
     case 2: if constexpr (N > 2) return f(std::integral_constant<int, 2>{}); break;
     case 3: if constexpr (N > 3) return f(std::integral_constant<int, 3>{}); break;
+    case 4: if constexpr (N > 4) return f(std::integral_constant<int, 4>{}); break;
+    case 5: if constexpr (N > 5) return f(std::integral_constant<int, 5>{}); break;
   }
   return false;
 }

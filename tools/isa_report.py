@@ -46,7 +46,7 @@ def main(solver='1'):
                 continue
             m = re.match(r'^(_Z\w+):', line)
             if m:
-                infn = m.group(1).startswith(f'_ZN2gq11step_kernelILi{solver}ELi0ELb0ELb0ELb1ELb1ELb0EEE')
+                infn = m.group(1).startswith(f'_ZN2gq11step_kernelILi{solver}ELi0ELb0ELb0ELb1ELb0ELb0EEE')   # the headline's kernel: flat self-collision, hulls (SCENE_FLAT_SELF_HULL)
                 continue
             m = re.match(r'\s*\.loc\s+(\d+)\s+(\d+)', line)
             if m:

@@ -1,11 +1,14 @@
 """Register / scratch / LDS / occupancy table of every kernel of libgq as the COMPILER allocates them (rocprofv3's kernel-trace
 `vgpr` column reports the allocation granule, not the allocation).
 
-    python tools/kernel_resources.py [out.md] [--keep-asm /tmp/gq_kernels.s]
+    python tools/kernel_resources.py [out.md] [--keep-asm /tmp/gq_kernels.s] [--parts JOBS]
 
-Compiles csrc/gq_kernels.hip for gfx950 with the product's flags plus -Rpass-analysis=kernel-resource-usage (device side only,
-~3 min), parses the remarks and counts the scratch_load / scratch_store instructions of each kernel in the assembly."""
-import collections, re, subprocess, sys, tempfile
+Compiles csrc/gq_kernels.hip for gfx950 with the product's flags plus -Rpass-analysis=kernel-resource-usage (device side only), parses
+the remarks and counts the scratch_load / scratch_store instructions of each kernel in the assembly.  As ONE translation unit holding every
+variant (the default: a quarter of an hour since the flat self-collision scene comes in three builds) - or, with --parts JOBS, as the
+product library is built: one unit per part of csrc/Makefile (-DGQ_PART=k), JOBS of them side by side, a few minutes; the allocator sees
+what it sees in the product, and the table is the library's."""
+import collections, concurrent.futures, re, subprocess, sys, tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -27,14 +30,23 @@ def short(name):
 def main(argv):
     out_md = Path(argv[0]) if argv and not argv[0].startswith('--') else None
     keep = Path(argv[argv.index('--keep-asm') + 1]).resolve() if '--keep-asm' in argv else None
+    jobs = int(argv[argv.index('--parts') + 1]) if '--parts' in argv else 0
+    nparts = int(re.search(r'^NPARTS = (\d+)', (CSRC / 'Makefile').read_text(), re.M).group(1))
+    units = [[f'-DGQ_PART={k}', f'-DGQ_NPARTS={nparts}'] for k in range(nparts)] if jobs else [[]]
     with tempfile.TemporaryDirectory() as td:
-        asm = keep or Path(td) / 'k.s'
-        r = subprocess.run(['/opt/rocm/bin/hipcc', *product_flags(), '-gline-tables-only', '-Rpass-analysis=kernel-resource-usage', '-S', '--cuda-device-only',
-                            '-o', str(asm), 'gq_kernels.hip'], capture_output=True, text=True, cwd=CSRC)
-        if r.returncode:
-            sys.exit(r.stderr[-3000:])
+        def compile_unit(k):
+            asm = Path(td) / f'k{k}.s'
+            r = subprocess.run(['/opt/rocm/bin/hipcc', *product_flags(), *units[k], '-gline-tables-only', '-Rpass-analysis=kernel-resource-usage', '-S',
+                                '--cuda-device-only', '-o', str(asm), 'gq_kernels.hip'], capture_output=True, text=True, cwd=CSRC)
+            if r.returncode:
+                sys.exit(r.stderr[-3000:])
+            return r.stderr, asm.read_text()
+        with concurrent.futures.ThreadPoolExecutor(max(jobs, 1)) as pool:
+            done = list(pool.map(compile_unit, range(len(units))))
+        if keep:
+            keep.write_text(''.join(a for _, a in done))
         rows, cur = collections.OrderedDict(), None
-        for line in r.stderr.splitlines():
+        for line in ''.join(e for e, _ in done).splitlines():
             m = re.search(r'remark: Function Name: (\S+)', line)
             if m:
                 cur = m.group(1); rows[cur] = {}
@@ -43,7 +55,7 @@ def main(argv):
             if m and cur:
                 rows[cur][m.group(1).strip()] = int(m.group(2))
         scratch, fn = collections.Counter(), None
-        for line in asm.read_text().splitlines():
+        for line in ''.join(a for _, a in done).splitlines():
             m = re.match(r'^(_Z\w+):', line)
             if m:
                 fn = m.group(1)
@@ -53,9 +65,12 @@ def main(argv):
     for fn, d in rows.items():
         lines.append(f"| `{short(fn)}` | {d.get('VGPRs', '?')} | {d.get('AGPRs', '?')} | {d.get('TotalSGPRs', '?')} | {d.get('ScratchSize', '?')} | {scratch.get(fn, 0)} | "
                      f"{d.get('LDS Size', '?')} | {d.get('Occupancy', '?')} |")
-    text = ('# Kernel resources as allocated by the compiler (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, product flags)\n\n'
+    text = ('# Kernel resources as allocated by the compiler (hipcc -Rpass-analysis=kernel-resource-usage, gfx950, product flags; '
+            + (f'the {nparts} build parts of csrc/Makefile, as in the product library' if jobs else 'ONE translation unit holding every variant') + ')\n\n'
             'step_kernel<SOLVER, MODE, CONE, BOXES, SELF, PRIM, PERSIST>: SOLVER 1 Newton / 0 PGS; MODE 0 production, 1 instrumented, 2 stage cut.\n'
-            'mailbox_step_kernel<SOLVER, CONE, BOXES, SELF, PRIM>: the closed-loop persistent rollout.\n\n' + '\n'.join(lines) + '\n')
+            'mailbox_step_kernel<SOLVER, CONE, BOXES, SELF, PRIM>: the closed-loop persistent rollout.\n'
+            'step_kernel_prim<SOLVER, MODE, CONE, PERSIST> / mailbox_step_kernel_prim<SOLVER, CONE>: the flat self-collision scene without the convex block '
+            '(SCENE_FLAT_SELF_PRIM); the one without the box routines (SCENE_FLAT_SELF_HULL) is step_kernel<.., BOXES false, SELF true, PRIM false, ..>.\n\n' + '\n'.join(lines) + '\n')
     if out_md:
         out_md.write_text(text)
     print(text)
