@@ -125,6 +125,13 @@ class GqJointCmd(C.Structure):
                 ('kp', C.c_void_p), ('kd', C.c_void_p), ('tau_out', C.c_void_p), ('terminated_any', C.c_void_p)]
 
 
+class GqFootCmd(C.Structure):
+    """gq_step_foot_cmd's command block; ``struct_size`` must hold ``sizeof(GqFootCmd)`` (the library refuses a stale layout)."""
+    _fields_ = [('struct_size', C.c_int32), ('gain_stride', C.c_int32), ('frame', C.c_int32), ('pad_', C.c_int32), ('p_des', C.c_void_p),
+                ('v_des', C.c_void_p), ('f_ff', C.c_void_p), ('tau_ff', C.c_void_p), ('kp', C.c_void_p), ('kd', C.c_void_p),
+                ('tau_out', C.c_void_p), ('terminated_any', C.c_void_p)]
+
+
 class GqResampleCfg(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('cmd_reset', C.c_int32), ('dist_reset', C.c_int32), ('dist_kind', C.c_int32 * 6),
                 ('dist_range', (C.c_float * 2) * 6), ('env_id_offset', C.c_int32)]

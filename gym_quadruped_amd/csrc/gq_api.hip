@@ -20,6 +20,7 @@
 #include <gq_device.h>
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
+#include "gq_foot_cmd.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
 #include "gq_host_res.h"
@@ -89,6 +90,7 @@ struct GqBatch {
   gq::Stream shard_stream[8]; gq::Event shard_event[8], fork_event; int n_shard_streams; /* gq_rollout */
   Mailbox mb;
   gq::Staged<gq::JointCmdDev> jc;   /* gq_step_joint_cmd: the call's command pointers (StepCall::policy, tagged) */
+  gq::Staged<gq::FootCmdDev> fc;    /* gq_step_foot_cmd: the same for a foot-space command (tag bit 1) */
 };
 
 /* the launches must be issued with the batch's device current (the caller's stream belongs to it); restore the caller's
@@ -194,6 +196,7 @@ int gq_batch_create(GqModel* m, int n_envs, const int32_t* obs_ids, int n_obs, c
   HIP_TRY(b->args.ring.ensure(GQ_ARG_SLOTS, false));
   HIP_TRY(b->batch.ring.ensure(GQ_ARG_SLOTS, false));
   HIP_TRY(b->jc.create());
+  HIP_TRY(b->fc.create());
   *out = b.release();
   return GQ_OK;
 }
@@ -570,6 +573,30 @@ int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState
   HIP_TRY(b->jc.push(J, stream, false));
   gq::StepCall c{};
   c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_joint_cmd(b->jc.dev.get());
+  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
+  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
+  return GQ_OK;
+}
+
+int gq_step_foot_cmd(GqBatch* b, const GqFootCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                     int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
+  if (!cmd) { SET_ERR("gq_step_foot_cmd: bad argument"); return GQ_EINVAL; }
+  if (cmd->struct_size != (int32_t)sizeof(GqFootCmd)) { SET_ERR("gq_step_foot_cmd: GqFootCmd.struct_size is %d, this library's struct has %d bytes: stale binding", cmd->struct_size, (int)sizeof(GqFootCmd)); return GQ_EINVAL; }
+  if (!b) { SET_ERR("gq_step_foot_cmd: bad argument"); return GQ_EINVAL; }
+  if (decimation < 1) { SET_ERR("gq_step_foot_cmd: decimation must be >= 1 (got %d)", decimation); return GQ_EINVAL; }
+  if (!cmd->p_des || !cmd->kp || !cmd->kd) { SET_ERR("gq_step_foot_cmd: p_des, kp and kd must be given"); return GQ_EINVAL; }
+  if (cmd->gain_stride != 0 && cmd->gain_stride != 12) { SET_ERR("gq_step_foot_cmd: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", cmd->gain_stride); return GQ_EINVAL; }
+  if (cmd->frame != 0 && cmd->frame != 1) { SET_ERR("gq_step_foot_cmd: frame must be 0 (base) or 1 (world axes), got %d", cmd->frame); return GQ_EINVAL; }
+  if (!persistent_ok(b, auto_reset, "gq_step_foot_cmd")) return GQ_EINVAL;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_step_foot_cmd"); rc != GQ_OK) return rc;
+  DeviceGuard guard(b->model->device);
+  gq::FootCmdDev F = b->fc.shadow; /* a copy of the shadow, then the fields: see Staged */
+  F.p_des = cmd->p_des; F.v_des = cmd->v_des; F.f_ff = cmd->f_ff; F.tau_ff = cmd->tau_ff; F.kp = cmd->kp; F.kd = cmd->kd;
+  F.tau_out = cmd->tau_out; F.term_any = cmd->terminated_any; F.gain_stride = cmd->gain_stride; F.frame = cmd->frame;
+  HIP_TRY(b->fc.push(F, stream, false));
+  gq::StepCall c{};
+  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_foot_cmd(b->fc.dev.get());
   c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
   HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
   return GQ_OK;

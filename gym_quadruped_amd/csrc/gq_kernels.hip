@@ -9,6 +9,7 @@
 #include <utility>
 #include <gq_device.h>
 #include "gq_step_body.h"
+#include "gq_foot_cmd.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -78,13 +79,61 @@ __device__ __forceinline__ void joint_cmd_inline(const GQ_MODEL JointCmdDev& J, 
   }
 }
 
+/* the third inline policy: foot-space actions (gq_step_foot_cmd, the law: gq_foot_cmd.h), on the joint state and the base quaternion
+ * load_rows has just staged in LDS.  Three phases through the `u` overlay, which is dead between load_rows and S1:
+ *   lane = link (12): the link's record and its local transform -> W.u.dyn.fkloc (the words S1's first phase leaves there);
+ *   lane = foot (4, FL FR RL RR): the foot's command words, the chain of its leg, tau_leg = J^T F + tau_ff -> the leg's hinges in
+ *     W.u.dyn.anchor (no lane ever holds three link records next to the chain's intermediates: the persistent variants have no
+ *     register to spare);
+ *   lane = hinge (12): W.ctrl / act_seq / tau_out, exactly as joint_cmd_inline.
+ * Fetched at every substep, nothing carried across step_wave (profiles/joint_cmd_kernel_resources.md).  W.force[0..1] are not
+ * touched: they carry the clock and GQ_LIFT_DUE. */
+__device__ __forceinline__ void foot_cmd_inline(const GQ_MODEL FootCmdDev& F, const GQ_MODEL GqDevModel& m, const StepArgs& a, const StepCall& c, WaveMem& W,
+                                                const int env, const int kstep, const bool last, const bool apply) {
+  const int lane = lane_id();
+  static_assert(sizeof(W.u.dyn.fkloc[0]) == GQ_FOOT_LINK_WORDS * sizeof(float), "foot_cmd_link's words fit a row of fkloc");
+  float* const tq = &W.u.dyn.anchor[0][0]; /* [12], hinge order (anchor does not overlay fkloc) */
+  wave_barrier(); /* W.qj / W.qvel / W.qb were stored by other lanes (load_rows: lane = word of the row) */
+  if (lane < GQ_NJ) {
+    const GqDevLinkRec L = link_fetch(m, lane);
+    foot_cmd_link(L, W.qj[lane], W.u.dyn.fkloc[lane]);
+  }
+  wave_barrier();
+  if (lane < 4) {
+    const int leg = m.foot_leg[lane];
+    const size_t r = (size_t)env * 12 + 3 * lane, g = (size_t)env * (size_t)F.gain_stride + 3 * lane, h = (size_t)env * 12 + 3 * leg;
+    FootCmd cmd;
+    float foot[3], tau[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      cmd.p_des[i] = gptr(F.p_des)[r + i];
+      cmd.v_des[i] = F.v_des ? gptr(F.v_des)[r + i] : 0.0f;
+      cmd.f_ff[i] = F.f_ff ? gptr(F.f_ff)[r + i] : 0.0f;
+      cmd.tau_ff[i] = F.tau_ff ? gptr(F.tau_ff)[h + i] : 0.0f;
+      cmd.kp[i] = gptr(F.kp)[g + i]; cmd.kd[i] = gptr(F.kd)[g + i];
+      foot[i] = m.foot_pos[lane][i];
+    }
+    foot_cmd_chain(W.u.dyn.fkloc[3 * leg], W.u.dyn.fkloc[3 * leg + 1], W.u.dyn.fkloc[3 * leg + 2], foot, &W.qvel[6 + 3 * leg], W.qb, cmd, F.frame, tau);
+#pragma unroll
+    for (int i = 0; i < 3; i++) tq[3 * leg + i] = tau[i];
+  }
+  wave_barrier();
+  if (lane < 12) {
+    const float u = tq[lane];
+    if (apply) W.ctrl[lane] = u;
+    if (c.act_seq) gptr(c.act_seq)[((size_t)kstep * a.n_envs + env) * 12 + lane] = u;
+    if (last && F.tau_out) gptr(F.tau_out)[(size_t)env * 12 + lane] = u;
+  }
+}
+
 /* step (+ in-kernel auto-reset).  Same-step mode: a terminated env is re-spawned by the same wavefront - reset_wave,
  * then the reset's own mj_step as a second pass through step_wave; no extra launches, but the launch lasts as long as
  * its two-pass waves.  Next-step mode: the env waits (pending flag) and spends its next launch on reset_wave + the
  * reset's mj_step instead of a user step - every wave runs exactly one mj_step per launch.
  * The body of step_kernel and of step_kernel_prim below, which differ in CVX alone (gq_step_kernel.h scene_cvx): the scenes that existed
  * before the flat self-collision scene was split keep their kernels' names, template arguments included. */
-template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST, bool CVX>
+template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST, bool CVX, bool FOOT = false /* the persistent variants of
+          * gq_step_foot_cmd (step_kernel_foot below): the foot-space law is their ONLY inline policy, and no other kernel holds it */>
 __device__ __forceinline__ void step_kernel_body(const FusedArgs* __restrict__ A, const StepCall c) {
   const long long t_entry = (GQ_TICKSET && MODE == 1) ? cycles() : 0; /* sub-stage builds (gq_step_kernel.h GQ_TICKSET) count from here */
   const int env = wave_index() + c.env0;
@@ -112,7 +161,9 @@ __device__ __forceinline__ void step_kernel_body(const FusedArgs* __restrict__ A
    * policy pays nothing for the second one.  gq_step_joint_cmd (Newton only): the env's command words are fetched here at every
    * substep, not carried through the window - the kernel has no register to spare (one carried register was 4 to 8 more scratch
    * bytes per lane in every persistent variant, re-read from there at every substep anyway); the rows stay in the L2 for the window */
-  if constexpr (PERSIST) if (c.policy) { /* wave-uniform */
+  if constexpr (FOOT) { /* gq_step_foot_cmd launches these variants with its command block and nothing else (launch_variant) */
+    foot_cmd_inline(*mptr(policy_foot_cmd(c.policy)), *mptr(C.model), A->s, c, W, env, kstep, kstep + 1 >= c.n_steps, !respawn);
+  } else if constexpr (PERSIST) if (c.policy) { /* wave-uniform */
     bool jc = false;
     if constexpr (SOLVER == 1) jc = policy_is_joint_cmd(c.policy);
     if (jc) joint_cmd_inline(*mptr(policy_joint_cmd(c.policy)), A->s, c, W, env, kstep, kstep + 1 >= c.n_steps, !respawn);
@@ -127,6 +178,13 @@ __device__ __forceinline__ void step_kernel_body(const FusedArgs* __restrict__ A
       hint = load_rows<SOLVER>(A->s, c, W, env, false, C, true);
     }
     const int term = step_wave<SOLVER, MODE, CONE, BOXES, SELF, PRIM, false, CVX>(A->s, c, W, pass, hint, C, t_entry);
+    if constexpr (FOOT) { /* the window's OR of `terminated`, as for gq_step_joint_cmd below */
+      const int t = pass == 0 ? term : 0;
+      if (kstep == 0 || t) { /* wave-uniform */
+        uint8_t* const any = mptr(policy_foot_cmd(c.policy))->term_any;
+        if (any && lane_id() == 0) gptr(any)[env] = (uint8_t)t;
+      }
+    } else
     if constexpr (PERSIST && SOLVER == 1) { /* gq_step_joint_cmd: the window's OR of `terminated`, kept in memory - stored by the first
                                              * substep, set by a later one that terminates (a re-spawn's own step reports none) */
       const int t = pass == 0 ? term : 0;
@@ -146,6 +204,17 @@ __device__ __forceinline__ void step_kernel_body(const FusedArgs* __restrict__ A
 template <int SOLVER, int MODE, bool CONE, bool BOXES, bool SELF, bool PRIM, bool PERSIST = false>
 __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel(const FusedArgs* __restrict__ A, const StepCall c) {
   step_kernel_body<SOLVER, MODE, CONE, BOXES, SELF, PRIM, PERSIST, true>(A, c);
+}
+/* gq_step_foot_cmd: the Newton production persistent variants with the foot-space law (gq_foot_cmd.h) as their inline policy.  Kernels of
+ * their own, as PERSIST itself is: one more policy arm in the kernels step_pd and the rollouts run cost those 0.6 - 1 % on some robots
+ * (profiles/foot_cmd_kernel_resources.md), so those kernels stay as they were, byte for byte. */
+template <bool CONE, bool BOXES, bool SELF, bool PRIM>
+__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel_foot(const FusedArgs* __restrict__ A, const StepCall c) {
+  step_kernel_body<1, 0, CONE, BOXES, SELF, PRIM, true, true, true>(A, c);
+}
+template <bool CONE>
+__global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel_prim_foot(const FusedArgs* __restrict__ A, const StepCall c) {
+  step_kernel_body<1, 0, CONE, false, true, true, true, false, true>(A, c);
 }
 /* SCENE_FLAT_SELF_PRIM: the self-collision stage without the convex block and the pair exchange */
 template <int SOLVER, int MODE, bool CONE, bool PERSIST = false>
@@ -463,6 +532,11 @@ static void launch_variant(const Launch& L) {
   } else {
     if constexpr (M == 0) {
       if (call.n_steps > 1 || call.policy) { /* persistent rollout (also a one-step one with the policy inline: only this variant evaluates it): production kernel only */
+        if constexpr (S == 1) if (policy_is_foot_cmd(call.policy)) { /* gq_step_foot_cmd: the variants that hold its law */
+          if constexpr (NOCVX) hipLaunchKernelGGL((step_kernel_prim_foot<C>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+          else hipLaunchKernelGGL((step_kernel_foot<C, B, SF, P>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
+          return;
+        }
         if constexpr (NOCVX) hipLaunchKernelGGL((step_kernel_prim<S, M, C, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
         else hipLaunchKernelGGL((step_kernel<S, M, C, B, SF, P, true>), dim3(L.grid), dim3(GQ_WAVE), 0, L.stream, L.args, call);
         return;

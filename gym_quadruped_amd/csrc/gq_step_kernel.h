@@ -135,7 +135,8 @@ struct StepCall {
   float* obs_seq;
   /* closed loop INSIDE the persistent rollout (gq_rollout_closed, inline mode): the wavefront derives the action of its env's next
    * step from the observation row it has just written (PolicyPdDev below, device memory); controls are then not read from ctrl.
-   * Tagged (bit 0, see PolicyPdDev): a JointCmdDev instead - joint-impedance command held over the window (gq_step_joint_cmd) */
+   * Tagged (bit 0, see PolicyPdDev): a JointCmdDev instead - joint-impedance command held over the window (gq_step_joint_cmd); bit 1: a
+   * FootCmdDev - foot-space command (gq_step_foot_cmd, gq_foot_cmd.h): the launch then picks the variants that hold that law */
   const struct PolicyPdDev* policy;
   float* act_seq;       /* [n_steps][N][12] every action taken, or NULL */
   int32_t stop_stage;   /* profiling aid (env GQ_STOP_STAGE, tools/stage_insts.sh): return after stage marker i; 0 = run everything */

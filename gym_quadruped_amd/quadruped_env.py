@@ -422,58 +422,13 @@ class QuadrupedEnv(AccessorsMixin):
         ``torque_ctrl_setpoint`` is the last substep's torque.  Needs the Newton solver and ``auto_reset='next_step'`` (or none)."""
         from .cabi import GqJointCmd
         N, nu = self.num_envs, 12
-        D = int(decimation)
-        if D < 1:
-            raise ValueError(f'decimation must be >= 1, got {decimation}')
-        if self._mm.desc.solver != 1:
-            raise ValueError("step_pd needs the Newton solver (solver='newton')")
-        if self.auto_reset and self.auto_reset_mode != 'next_step':
-            raise ValueError("step_pd needs auto_reset='next_step' (or no auto-reset): a same-step re-spawn does not fit the persistent kernel")
-
-        def rows(x, name):
-            if x is None:
-                return None
-            if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != (N, nu):
-                raise ValueError(f'{name} must be a float32 tensor of shape ({N}, {nu}) on {self.device}, got '
-                                 + (f'{x.dtype} {tuple(x.shape)} on {x.device}' if torch.is_tensor(x) else type(x).__name__))
-            return x.contiguous()
-
-        def gain(x, name, k):
-            if torch.is_tensor(x) and x.dim() == 2:
-                return rows(x, name), 12
-            if torch.is_tensor(x) and x.device == self.device:   # a device tensor stays there: a copy on the stream, no host round trip
-                if x.dim() > 1 or x.numel() not in (1, nu):
-                    raise ValueError(f'{name} must be a scalar, {nu} values or a ({N}, {nu}) tensor, got shape {tuple(x.shape)}')
-                self._pd_gain[k].copy_(x.detach().to(torch.float32).reshape(-1).expand(nu))
-                self._pd_gain_host[k] = None
-                return self._pd_gain[k], 0
-            v = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float32)
-            if v.ndim > 1 or v.size not in (1, nu):
-                raise ValueError(f'{name} must be a scalar, {nu} values or a ({N}, {nu}) tensor, got shape {tuple(v.shape)}')
-            v = np.broadcast_to(v.reshape(-1), (nu,)).copy()
-            if self._pd_gain_host[k] is None or not np.array_equal(self._pd_gain_host[k], v):   # the shared row is uploaded when it changes
-                self._pd_gain[k].copy_(torch.from_numpy(v))
-                self._pd_gain_host[k] = v
-            return self._pd_gain[k], 0
-
-        if getattr(self, '_pd_tau', None) is None:
-            self._pd_gain = torch.zeros(2, nu, dtype=torch.float32, device=self.device)
-            self._pd_gain_host = [None, None]
-            self._pd_tau = torch.zeros(N, nu, dtype=torch.float32, device=self.device)
-            self._pd_term_any = torch.zeros(N, dtype=torch.uint8, device=self.device)
-            self._pd_term_any_b = self._pd_term_any.view(torch.bool)
-        q = rows(q_des, 'q_des')
+        D = self._window_checks('step_pd', decimation)
+        q = self._cmd_rows(q_des, 'q_des')
         if q is None:
             raise ValueError('q_des must be given')
-        qd, ff = rows(qd_des, 'qd_des'), rows(tau_ff, 'tau_ff')
-        (p, sp), (d, sd) = gain(kp, 'kp', 0), gain(kd, 'kd', 1)
-        if sp != sd:   # one stride serves both rows: the shared one is spread
-            p = p if sp == 12 else p.expand(N, nu).contiguous()
-            d = d if sd == 12 else d.expand(N, nu).contiguous()
-            sp = 12
-        f32 = dict(dtype=torch.float32, device=self.device)
-        obs_seq = torch.empty(D, N, self._obs_dim, **f32) if record_obs else None
-        act_seq = torch.empty(D, N, nu, **f32) if record_actions else None
+        qd, ff = self._cmd_rows(qd_des, 'qd_des'), self._cmd_rows(tau_ff, 'tau_ff')
+        p, d, sp = self._cmd_gains(self._cmd_gain(kp, 'kp', 0), self._cmd_gain(kd, 'kd', 1))
+        obs_seq, act_seq = self._window_records(D, record_obs, record_actions)
         cmd = GqJointCmd(struct_size=C.sizeof(GqJointCmd), gain_stride=sp, q_des=q.data_ptr(), qd_des=None if qd is None else qd.data_ptr(),
                          tau_ff=None if ff is None else ff.data_ptr(), kp=p.data_ptr(), kd=d.data_ptr(), tau_out=self._pd_tau.data_ptr(),
                          terminated_any=self._pd_term_any.data_ptr())
@@ -483,6 +438,77 @@ class QuadrupedEnv(AccessorsMixin):
         _lib.check(self._L.gq_step_joint_cmd(self._hbatch, C.byref(cmd), D, self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
                                              self._lift_failed.data_ptr(), None if obs_seq is None else obs_seq.data_ptr(),
                                              None if act_seq is None else act_seq.data_ptr(), stream), 'gq_step_joint_cmd')
+        return self._window_done(D, obs_seq, act_seq)
+
+    # -- what step_pd and step_feet share: the checks in front of a command window, its command rows and gains, its results
+    def _window_checks(self, who, decimation):
+        D = int(decimation)
+        if D < 1:
+            raise ValueError(f'decimation must be >= 1, got {decimation}')
+        if self._mm.desc.solver != 1:
+            raise ValueError(f"{who} needs the Newton solver (solver='newton')")
+        if self.auto_reset and self.auto_reset_mode != 'next_step':
+            raise ValueError(f"{who} needs auto_reset='next_step' (or no auto-reset): a same-step re-spawn does not fit the persistent kernel")
+        if getattr(self, '_pd_tau', None) is None:
+            N, nu = self.num_envs, 12
+            self._pd_gain = torch.zeros(4, nu, dtype=torch.float32, device=self.device)   # rows 0, 1: step_pd's kp, kd; 2, 3: step_feet's
+            self._pd_gain_host = [None] * 4
+            self._pd_tau = torch.zeros(N, nu, dtype=torch.float32, device=self.device)
+            self._pd_term_any = torch.zeros(N, dtype=torch.uint8, device=self.device)
+            self._pd_term_any_b = self._pd_term_any.view(torch.bool)
+        return D
+
+    def _cmd_rows(self, x, name):
+        N, nu = self.num_envs, 12
+        if x is None:
+            return None
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != (N, nu):
+            raise ValueError(f'{name} must be a float32 tensor of shape ({N}, {nu}) on {self.device}, got '
+                             + (f'{x.dtype} {tuple(x.shape)} on {x.device}' if torch.is_tensor(x) else type(x).__name__))
+        return x.contiguous()
+
+    def _cmd_gain(self, x, name, k, sizes=(1, 12), spread=None):
+        """a gain as (tensor, stride): an ``[N, 12]`` tensor as it is (stride 12), anything smaller as the shared row k of
+        ``_pd_gain`` (stride 0).  sizes: the accepted lengths of a shared gain; spread(v): a vector of such a length -> 12 values"""
+        if torch.is_tensor(x) and x.dim() == 2:   # (the per-env form first: nothing else is done for it)
+            return self._cmd_rows(x, name), 12
+        N, nu = self.num_envs, 12
+
+        def bad(shape):
+            what = ', '.join(['a scalar'] + [f'{n} values' for n in sizes[1:]])
+            return ValueError(f'{name} must be {what} or a ({N}, {nu}) tensor, got shape {tuple(shape)}')
+        if torch.is_tensor(x) and x.device == self.device:   # a device tensor stays there: a copy on the stream, no host round trip
+            if x.dim() > 1 or x.numel() not in sizes:
+                raise bad(x.shape)
+            v = x.detach().to(torch.float32).reshape(-1)
+            self._pd_gain[k].copy_(spread(v) if spread else v.expand(nu))
+            self._pd_gain_host[k] = None
+            return self._pd_gain[k], 0
+        v = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(np.float32)
+        if v.ndim > 1 or v.size not in sizes:
+            raise bad(v.shape)
+        v = v.reshape(-1)
+        v = np.ascontiguousarray(spread(v) if spread else np.broadcast_to(v, (nu,)), dtype=np.float32).copy()
+        if self._pd_gain_host[k] is None or not np.array_equal(self._pd_gain_host[k], v):   # the shared row is uploaded when it changes
+            self._pd_gain[k].copy_(torch.from_numpy(v))
+            self._pd_gain_host[k] = v
+        return self._pd_gain[k], 0
+
+    def _cmd_gains(self, kp, kd):
+        (p, sp), (d, sd) = kp, kd
+        if sp != sd:   # one stride serves both rows: the shared one is spread
+            N, nu = self.num_envs, 12
+            p = p if sp == 12 else p.expand(N, nu).contiguous()
+            d = d if sd == 12 else d.expand(N, nu).contiguous()
+            sp = 12
+        return p, d, sp
+
+    def _window_records(self, D, record_obs, record_actions):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return (torch.empty(D, self.num_envs, self._obs_dim, **f32) if record_obs else None,
+                torch.empty(D, self.num_envs, 12, **f32) if record_actions else None)
+
+    def _window_done(self, D, obs_seq, act_seq):
         self._last_action = self._pd_tau
         self._launches += D
         self._note_step()
@@ -490,11 +516,74 @@ class QuadrupedEnv(AccessorsMixin):
             for _ in range(D):
                 sensor.step()
         info = dict(self._info)
-        if record_obs:
+        if obs_seq is not None:
             info['obs_seq'] = obs_seq
-        if record_actions:
+        if act_seq is not None:
             info['actions'] = act_seq
         return self._obs_views, self._reward, self._pd_term_any_b, self._truncated_b, info
+
+    def step_feet(self, p_des, kp, kd, v_des=None, f_ff=None, tau_ff=None, frame: str = 'base', decimation: int = 4, record_obs: bool = False,
+                  record_actions: bool = False):
+        """Foot-space action held over a decimation window, in one launch (``gq_step_foot_cmd``): ``decimation`` physics steps of
+        every env under, per foot, ::
+
+            F = f_ff + kp * (p_des - p) + kd * (v_des - v)          # virtual force on the foot, 3-vector
+            tau_leg = J^T F + tau_ff
+
+        with ``p`` the foot's position relative to the base origin, ``J`` the 3x3 Jacobian of that position in the leg's three joint
+        angles and ``v = J qd_leg`` (the foot's velocity relative to the base), all evaluated at every substep from the env's fresh
+        state with the same command - the inner loop of a force / whole-body controller between two solver updates, for which ``D`` x
+        (``feet_jacobians``, einsum, ``step``) is the alternative.  frame: 'base' (base axes) or 'world' (world AXES; the origin stays
+        at the base).  A stance leg that should receive ground reaction ``g`` is commanded ``f_ff = -g`` with zero gains; a swing leg
+        gets gains and ``p_des`` / ``v_des``.  Only ``J^T`` is used: no pose is singular.
+
+        p_des, v_des, f_ff: ``[N, 12]`` float32 tensors on the env's device, the feet concatenated in the env's ``legs_order`` (like the
+        ``feet_pos`` observable), or a ``LegsAttr`` of ``[N, 3]`` tensors; the optional ones default to zero.  tau_ff: ``[N, 12]`` in hinge
+        order (``qpos[7:]``).  kp, kd: a scalar, 3 values (per axis), 12 values (per foot and axis, ``legs_order``) or ``[N, 12]``.
+        Everything else - the return value with ``terminated`` the OR over the window, ``info['obs_seq']`` / ``info['actions']`` (the
+        torques of every substep), ``torque_ctrl_setpoint``, the requirements - is ``step_pd``'s.  The law reads the state, not the
+        observation row: any ``state_obs_names`` works, ``accessors=True`` is not needed."""
+        from .cabi import LEG_NAMES, GqFootCmd
+        N = self.num_envs
+        D = self._window_checks('step_feet', decimation)
+        if frame not in ('base', 'world'):
+            raise ValueError(f"frame must be 'base' or 'world', got {frame!r}")
+        inv = [self.legs_order.index(leg) for leg in LEG_NAMES]   # canonical foot k sits at place inv[k] of the caller's rows
+        permuted = inv != [0, 1, 2, 3]
+
+        def feet(x, name):
+            if isinstance(x, LegsAttr):
+                legs = x.to_list(order=LEG_NAMES)
+                if not all(torch.is_tensor(t) and t.dtype == torch.float32 and t.device == self.device and tuple(t.shape) == (N, 3) for t in legs):
+                    raise ValueError(f'{name}: every leg of a LegsAttr must be a float32 tensor of shape ({N}, 3) on {self.device}')
+                return torch.cat(legs, dim=1)
+            x = self._cmd_rows(x, name)
+            return x.view(N, 4, 3)[:, inv].reshape(N, 12) if permuted and x is not None else x
+
+        def spread(v):   # a shared gain: 1, 3 (per axis) or 12 (per foot and axis, legs_order) values -> 12 in canonical order
+            rep = (lambda t, n: t.repeat(n)) if torch.is_tensor(v) else (lambda t, n: np.tile(t, n))
+            v = rep(v, 12 // len(v))
+            return v.reshape(4, 3)[inv].reshape(12) if permuted else v
+
+        def gain(x, name, k):
+            g, stride = self._cmd_gain(x, name, k, sizes=(1, 3, 12), spread=spread)
+            return (g.view(N, 4, 3)[:, inv].reshape(N, 12) if permuted and stride == 12 else g), stride
+
+        p = feet(p_des, 'p_des')
+        if p is None:
+            raise ValueError('p_des must be given')
+        v, f, ff = feet(v_des, 'v_des'), feet(f_ff, 'f_ff'), self._cmd_rows(tau_ff, 'tau_ff')
+        gp, gd, stride = self._cmd_gains(gain(kp, 'kp', 2), gain(kd, 'kd', 3))
+        obs_seq, act_seq = self._window_records(D, record_obs, record_actions)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        cmd = GqFootCmd(struct_size=C.sizeof(GqFootCmd), gain_stride=stride, frame=int(frame == 'world'), p_des=p.data_ptr(), v_des=ptr(v), f_ff=ptr(f),
+                        tau_ff=ptr(ff), kp=gp.data_ptr(), kd=gd.data_ptr(), tau_out=self._pd_tau.data_ptr(), terminated_any=self._pd_term_any.data_ptr())
+        self._pd_cmd_refs = (p, v, f, ff, gp, gd)   # the launch reads them asynchronously
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._hm_fresh = False
+        _lib.check(self._L.gq_step_foot_cmd(self._hbatch, C.byref(cmd), D, self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
+                                            self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), stream), 'gq_step_foot_cmd')
+        return self._window_done(D, obs_seq, act_seq)
 
     def closed_loop_status(self):
         """Wait for the last ``rollout_closed_loop`` and return (abort code, detail, env-steps played); raises ``GqError`` if it

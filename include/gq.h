@@ -19,6 +19,7 @@
  *   mujoco.mj_ray                  sensors/heightmap.py:90-99     gq_ray (general rays), gq_heightmap (the HeightMap grid)
  *   mujoco.mj_contactForce         quadruped_env.py:852    gq_contact_force (contact rows of gq_batch_set_outputs); summed per foot: obs epilogue
  *   mujoco.mj_fullM                quadruped_env.py:940    dyn rows of gq_batch_set_outputs (production kernel); gq_full_mass (inspection record)
+ *   feet_jacobians + tau = J^T F   quadruped_env.py:681-740 gq_step_foot_cmd (a force / impedance controller's loop around step())
  *   mujoco.Renderer depth / segmentation  sensors/rgbd_camera.py   gq_camera (ray cast, collision geometry)
  *   mujoco.Renderer RGB            sensors/rgbd_camera.py   gq_camera_shaded (the same rays, shaded)
  *
@@ -500,6 +501,33 @@ typedef struct GqJointCmd {
 } GqJointCmd;
 int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
                       int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream);
+/* FOOT-SPACE action held over a decimation window, one launch: what a whole-body / MPC controller sends between two solver updates -
+ * per foot a virtual force f_ff and a Cartesian impedance (p_des, v_des, kp, kd per axis), plus joint feed-forward torques - the form of
+ *   for k in range(decimation): J = feet_jacobians(); tau_leg = J_leg^T (f_ff + kp (p_des - p) + kd (v_des - v)) + tau_ff; env.step(tau)
+ * with the Jacobian fresh at every substep.  Per env and foot k (FL FR RL RR), leg l = the foot's kinematic leg:
+ *   p_B, J_B: forward kinematics of leg l alone in the BASE frame from qpos[7 + 3l .. 10 + 3l]: foot geom centre relative to the base
+ *             origin, and the 3x3 Jacobian with column i = a_i x (p_B - o_i) (axis / anchor of the leg's i-th hinge)
+ *   A = I (frame 0: base) or R(base quaternion) (frame 1: world AXES - the origin stays at the base)
+ *   p = A p_B, J = A J_B, v = J qvel[6 + 3l .. 9 + 3l]   (foot velocity relative to the base, from the leg's joint rates only)
+ *   F = f_ff + kp .* (p_des - p) + kd .* (v_des - v);  tau_leg = J^T F + tau_ff
+ * F is the virtual force acting ON the foot: a stance leg that should receive ground reaction g is commanded f_ff = -g with zero gains.
+ * float32; held to an fp64 evaluation within a rounding bound, not to the bits of an expression.  The law reads the state rows, not
+ * the observation row.  The substeps are those of gq_step with these torques, bit for bit (act_seq records them); re-spawns, tau_out,
+ * terminated_any, obs_seq / act_seq, the lifetime of the pointers and the requirements are those of gq_step_joint_cmd.
+ * Foot rows are [foot k][xyz]; tau_ff and tau_out are in hinge order (qpos[7:]). */
+typedef struct GqFootCmd {
+  int32_t struct_size;        /* sizeof(GqFootCmd): a stale binding is refused */
+  int32_t gain_stride;        /* 0: kp / kd are one row of 12; 12: [N][12] */
+  int32_t frame;              /* 0: base frame; 1: world axes, origin at the base */
+  int32_t pad_;
+  const float *p_des;         /* device [N][12] */
+  const float *v_des, *f_ff, *tau_ff;   /* device [N][12] or NULL (= 0) */
+  const float *kp, *kd;       /* device, see gain_stride: per foot and axis */
+  float *tau_out;             /* device [N][12] or NULL */
+  uint8_t *terminated_any;    /* device [N] or NULL */
+} GqFootCmd;
+int gq_step_foot_cmd(GqBatch* b, const GqFootCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                     int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream);
 /* upload the device-resident argument block for (st, out, auto_reset, episode, lift_failed) if it changed; no launch */
 int gq_batch_bind(GqBatch* b, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed,
                   void* hip_stream);

@@ -1,10 +1,14 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
-usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D]
+usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
 against the loop they replace - D x (torch PD expression, env.step) - from the same state with the same per-env commands; K windows
-per timing, five timings of each, alternating.  Prints env-steps/s of both, their spreads and the ratio."""
+per timing, five timings of each, alternating.  Prints env-steps/s of both, their spreads and the ratio.
+
+--foot-cmd D: foot-space actions held over a window of D physics steps (QuadrupedEnv.step_feet, one launch per window: stance forces
+-m g / 4 along world z per foot, a soft Cartesian PD on the keyframe footholds +- 2 cm per env, base frame) against the loop they replace on an
+accessors=True env - D x (feet_jacobians, feet_pos, einsums for tau_leg = J_leg^T F, env.step) - with the same commands; timed the same way."""
 import sys, time
 from pathlib import Path
 import torch
@@ -15,6 +19,11 @@ JOINT_CMD = 0
 if '--joint-cmd' in sys.argv:
     i = sys.argv.index('--joint-cmd')
     JOINT_CMD = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+FOOT_CMD = 0
+if '--foot-cmd' in sys.argv:
+    i = sys.argv.index('--foot-cmd')
+    FOOT_CMD = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
 robot = sys.argv[1] if len(sys.argv) > 1 else 'mini_cheetah'
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
@@ -63,6 +72,66 @@ if JOINT_CMD:
         v = sorted(res[name])
         print(f'{robot} {scene} n={n} D={D}: {name:8s} median {v[2]:7.2f} M env-steps/s  min {v[0]:7.2f} max {v[-1]:7.2f}  ({W} windows x 5 runs)', flush=True)
     print(f'{robot} {scene} n={n} D={D}: step_pd / loop = {sorted(res["step_pd"])[2] / sorted(res["loop"])[2]:.3f} (medians); episodes max {int(env._episode.max())}', flush=True)
+    sys.exit(0)
+
+if FOOT_CMD:
+    D = FOOT_CMD
+    W = max(1, K // D)   # windows per timing: about K physics steps
+    acc = QuadrupedEnv(robot, scene=scene, state_obs_names=tuple(QuadrupedEnv.ALL_OBS), num_envs=n, auto_reset='next_step', seed=1, accessors=True)
+    mg4 = float(env.mjModel.body_mass.sum()) * 9.81 / 4
+    kp = torch.tensor([400.0, 400.0, 1500.0] * 4, device='cuda')
+    kd = torch.tensor([15.0] * 12, device='cuda')
+    key = env.reset(random=False)['feet_pos:base'][0].clone()   # the keyframe footholds, base frame, legs_order
+    cmds = [key + 0.02 * (2 * torch.rand(n, 12, generator=g, device='cuda') - 1) for _ in range(16)]
+    legs = list(env.legs_order)
+    cols = {leg: torch.as_tensor(acc.legs_qvel_idx[leg], device='cuda') for leg in legs}
+
+    def stance_force(e):
+        """the controller's part, once per window: -m g / 4 along world z per foot, in the base axes of the env's current orientation"""
+        w, x, y, z = e.qpos[:, 3:7].float().unbind(1)
+        up = torch.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1)   # world z in base axes
+        return (-mg4 * up).repeat(1, 4)
+
+    def torch_law(e, p_des, f_ff):
+        """tau_leg = J_leg^T (f_ff + kp (p_des - p) - kd J_leg qd_leg) from the env's getters: what a controller writes today"""
+        J, P = e.feet_jacobians(frame='base'), e.feet_pos(frame='base')
+        tau = torch.zeros(n, 12, device='cuda')
+        for i, leg in enumerate(legs):
+            c = cols[leg]
+            Jl = J[leg][:, :, c]
+            v = torch.einsum('nij,nj->ni', Jl, e.qvel[:, c])
+            F = f_ff[:, 3 * i:3 * i + 3] + kp[3 * i:3 * i + 3] * (p_des[:, 3 * i:3 * i + 3] - P[leg]) - kd[3 * i:3 * i + 3] * v
+            tau[:, c - 6] = torch.einsum('nij,ni->nj', Jl, F)
+        return tau
+
+    def window_feet(w):
+        env.step_feet(cmds[w % 16], kp, kd, f_ff=stance_force(env), frame='base', decimation=D)
+
+    def window_loop(w):
+        f_ff = stance_force(acc)
+        for _ in range(D):
+            acc.step(torch_law(acc, cmds[w % 16], f_ff))
+    for e in (env, acc):
+        e.reset(random=True)
+    for i in range(600 // D + 1): window_feet(i)   # settle into the standing regime
+    for i in range(600 // D + 1): window_loop(i)
+    sd = {id(e): (e.state_dict(), e._launches) for e in (env, acc)}
+    def restore(e):
+        e.load_state_dict(sd[id(e)][0]); e._launches = sd[id(e)][1]; torch.cuda.synchronize()
+    def windows_feet():
+        for w in range(W): window_feet(w)
+    def windows_loop():
+        for w in range(W): window_loop(w)
+    windows_feet(); windows_loop()   # warm both paths
+    res = {'step_feet': [], 'loop': []}
+    for r in range(5):
+        for name, fn, e in (('loop', windows_loop, acc), ('step_feet', windows_feet, env)):
+            restore(e); res[name].append(timed(fn, W * D)[0])
+    for name in ('loop', 'step_feet'):
+        v = sorted(res[name])
+        print(f'{robot} {scene} n={n} D={D}: {name:9s} median {v[2]:7.2f} M env-steps/s  min {v[0]:7.2f} max {v[-1]:7.2f}  ({W} windows x 5 runs)', flush=True)
+    print(f'{robot} {scene} n={n} D={D}: step_feet / loop = {sorted(res["step_feet"])[2] / sorted(res["loop"])[2]:.3f} (medians); '
+          f'episodes max {int(env._episode.max())} (step_feet) {int(acc._episode.max())} (loop)', flush=True)
     sys.exit(0)
 
 m, us = timed(lambda: [env.step(pool[i % 16]) for i in range(K)], K)
