@@ -132,6 +132,18 @@ class GqFootCmd(C.Structure):
                 ('tau_out', C.c_void_p), ('terminated_any', C.c_void_p)]
 
 
+GQ_ACT = dict(none=0, relu=1, elu=2, tanh=3)   # GQ_ACT_*
+
+
+class GqPolicyMlp(C.Structure):
+    """gq_rollout_policy's / gq_policy_mlp_eval's block; ``struct_size`` must hold ``sizeof(GqPolicyMlp)`` (the library refuses a stale layout)."""
+    _fields_ = [('struct_size', C.c_int32), ('n_layers', C.c_int32), ('width', C.c_int32 * 4), ('in_obs', C.c_int32), ('feed_last_action', C.c_int32),
+                ('activation', C.c_int32), ('out_activation', C.c_int32), ('decimation', C.c_int32), ('noise_step0', C.c_int32), ('blob', C.c_void_p),
+                ('blob_floats', C.c_int64), ('obs_shift', C.c_void_p), ('obs_scale', C.c_void_p), ('policy_actions', C.c_void_p), ('noise_seed', C.c_uint64),
+                ('kp', C.c_float * 12), ('kd', C.c_float * 12), ('q_default', C.c_float * 12), ('action_scale', C.c_float * 12),
+                ('noise_sigma', C.c_float * 12), ('action_clip', C.c_float), ('pad_', C.c_int32)]
+
+
 class GqResampleCfg(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('cmd_reset', C.c_int32), ('dist_reset', C.c_int32), ('dist_kind', C.c_int32 * 6),
                 ('dist_range', (C.c_float * 2) * 6), ('env_id_offset', C.c_int32)]

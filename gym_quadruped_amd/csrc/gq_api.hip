@@ -21,6 +21,7 @@
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
+#include "gq_policy_mlp.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
 #include "gq_host_res.h"
@@ -36,6 +37,8 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, hipStream_t stream);
+extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
 static thread_local char g_err[512] = "";
@@ -67,6 +70,8 @@ struct Mailbox {
   Buf<gq::MailboxDev> dev; Buf<gq::MailboxDev, gq::PinnedMem> staging;
   Buf<int32_t, gq::PinnedMem> alive, status_host; /* the word the policy workgroups count themselves into; a copy of the status words (gq_rollout_closed_status) */
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
+  gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
+  Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Stream stream; gq::Event fork, join;
   bool ready = false;
 };
@@ -437,6 +442,9 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.status.ensure(8, true));
   HIP_TRY(t.dev.ensure(1, false));
   HIP_TRY(t.policy.create());
+  HIP_TRY(t.mlp.create());
+  HIP_TRY(t.held.ensure(12 * N, true));
+  HIP_TRY(t.last.ensure(12 * N, true));
   HIP_TRY(t.staging.ensure(1, false));
   HIP_TRY(t.alive.ensure(1, false));
   HIP_TRY(t.status_host.ensure(8, false));
@@ -461,34 +469,112 @@ int gq_mailbox_get(GqBatch* b, GqMailboxView* out) {
   return GQ_OK;
 }
 
+/* ---- what the closed-loop rollouts (gq_rollout_closed, gq_rollout_policy) share ---- */
+/* in front of everything: the requirements of the persistent kernels, the tensors, the mailbox, the bound of the ticket counters.  The caller
+ * holds the DeviceGuard. */
+static int closed_begin(GqBatch* b, int n_steps, const GqState& st, const GqObsOut& out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed,
+                        hipStream_t stream, const char* who) {
+  if (!persistent_ok(b, auto_reset, who)) return GQ_EINVAL;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  const int N = b->host.n_envs;
+  const gq::MailboxDev& h = b->mb.host;
+  /* queue tickets are 32-bit: the env-steps that pass through one queue must stay below 2^31 (items carry env + 1 in 24 bits) */
+  if (N >= (1 << 24) || (int64_t)((N + h.nq - 1) / h.nq) * (int64_t)n_steps >= ((int64_t)1 << 31) - 65536) {
+    SET_ERR("%s: %d envs x %d steps over %d queues overflows the 32-bit ticket counters: split the rollout", who, N, n_steps, h.nq); return GQ_EINVAL;
+  }
+  return GQ_OK;
+}
+/* the columns of the joint angles / velocities in this batch's observation row (what both built-in policies read) */
+static int joint_columns(const GqBatch* b, int32_t col_q[12], int32_t col_qd[12], const char* who, const char* what) {
+  const int od = b->host.obs_dim;
+  for (int j = 0; j < 12; j++) {
+    col_q[j] = -1; col_qd[j] = -1;
+    for (int c = 0; c < od; c++) {
+      const int src = b->host.obs_map[c];
+      if (col_q[j] < 0 && (src == gq::OB_QPOS_JS + j || src == gq::OB_QPOS + 7 + j)) col_q[j] = c;
+      if (col_qd[j] < 0 && (src == gq::OB_QVEL_JS + j || src == gq::OB_QVEL + 6 + j)) col_qd[j] = c;
+    }
+    if (col_q[j] < 0 || col_qd[j] < 0) { SET_ERR("%s: the %s policy reads qpos_js / qvel_js (or qpos / qvel): not in this batch's observation row", who, what); return GQ_EINVAL; }
+  }
+  return GQ_OK;
+}
+/* fresh rollout state, ordered on the caller's stream, and the device block that describes the rollout; step_waves: the grid it will get */
+static int mailbox_start(GqBatch* b, int n_steps, int& step_waves, double timeout_s, float* obs_seq, float* act_seq, hipStream_t stream) {
+  Mailbox& mb = b->mb;
+  gq::MailboxDev& h = mb.host;
+  const int N = b->host.n_envs;
+  if (step_waves <= 0) step_waves = N; /* more workgroups than free slots (or than envs) is harmless: pop tickets that run ahead of the pushes
+                                        * wait on lap-tagged slots, the late ones find the queues drained */
+  if (step_waves < 4 * h.nq) step_waves = 4 * h.nq; /* a wavefront pops from ITS XCD's queue only: every XCD needs stepping wavefronts, also for a batch of
+                                                      * one env (workgroups are dealt round-robin over the XCDs; the surplus finds its queue empty and leaves) */
+  h.n_steps = n_steps; h.obs_seq = obs_seq; h.act_seq = act_seq;
+  h.timeout_ticks = (int64_t)((timeout_s > 0.0 ? timeout_s : 5.0) * 1e8);
+  HIP_TRY(hipMemsetAsync(h.steps_done, 0, sizeof(int32_t) * (size_t)N, stream));
+  HIP_TRY(hipMemsetAsync(h.issued, 0, sizeof(int32_t) * (size_t)N, stream));
+  HIP_TRY(hipMemsetAsync(h.q_items, 0, sizeof(int32_t) * (size_t)h.nq * h.qcap, stream));
+  HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * (size_t)h.nq * 3 * GQ_MB_QSTRIDE, stream));
+  HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
+  HIP_TRY(hipStreamSynchronize(stream)); /* the pinned staging block below is reused per call; a rollout is thousands of launches' worth of work */
+  std::memcpy(mb.staging.get(), &h, sizeof h);
+  HIP_TRY(hipMemcpyAsync(mb.dev.get(), mb.staging.get(), sizeof h, hipMemcpyHostToDevice, stream));
+  return GQ_OK;
+}
+/* the policy must be RESIDENT before the step wavefronts take every slot of the device: it is launched first, on its own stream
+ * (policy_fork, the launch, policy_resident), and awaited until each of its workgroups has reported in */
+static int policy_fork(Mailbox& mb, hipStream_t stream) {
+  *(volatile int32_t*)mb.alive.get() = 0;
+  HIP_TRY(hipEventRecord(mb.fork.get(), stream));
+  HIP_TRY(hipStreamWaitEvent(mb.stream.get(), mb.fork.get(), 0));
+  return GQ_OK;
+}
+static int policy_resident(Mailbox& mb, int policy_waves, hipStream_t stream, const char* who) {
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(mb.join.get(), mb.stream.get()));
+  volatile int32_t* alive = mb.alive.get();
+  const auto t0 = std::chrono::steady_clock::now();
+  while (*alive < policy_waves) {
+    std::this_thread::yield();
+    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
+      /* it cannot start: tell it to leave as soon as it does, and report */
+      mb.status_host.get()[0] = 3; /* pinned: the source of an asynchronous copy must outlive this frame */
+      (void)hipMemcpyAsync(mb.host.status, mb.status_host.get(), sizeof(int32_t), hipMemcpyHostToDevice, stream);
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamSynchronize(mb.stream.get()); /* the policy kernel has left (or never ran): nothing of this call touches `alive` later */
+      SET_ERR("%s: the policy kernel did not become resident within 2 s (%d of %d workgroups)", who, (int)*alive, policy_waves);
+      return GQ_EDEVICE;
+    }
+  }
+  return GQ_OK;
+}
+/* the stepping side; join: the caller's stream resumes when both kernels are done */
+static int mailbox_steps(GqBatch* b, const GqResetCfg* auto_reset, int step_waves, bool join, hipStream_t stream, const char* who) {
+  gq::StepCall c{};
+  c.auto_reset = gq::auto_reset_mode(auto_reset);
+  if (!gq_launch_mailbox_step(b->args.dev.get(), &c, b->mb.dev.get(), step_waves, b->model->host.solver, b->model->host.cone, b->model->scene, stream)) {
+    SET_ERR("%s: no mailbox variant of the step kernel for this model in this build", who); return GQ_EINVAL;
+  }
+  HIP_TRY(hipGetLastError());
+  if (join) HIP_TRY(hipStreamWaitEvent(stream, b->mb.join.get(), 0));
+  return GQ_OK;
+}
+
 int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
+  const char* const who = "gq_rollout_closed";
   if (!b || n_steps < 0 || (mode != GQ_CLOSED_MAILBOX && mode != GQ_CLOSED_INLINE)) { SET_ERR("gq_rollout_closed: bad argument"); return GQ_EINVAL; }
   if (mode == GQ_CLOSED_INLINE && !pd) { SET_ERR("gq_rollout_closed: the inline mode runs the built-in policy: pd must be given"); return GQ_EINVAL; }
-  if (!persistent_ok(b, auto_reset, "gq_rollout_closed")) return GQ_EINVAL;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_rollout_closed"); rc != GQ_OK) return rc;
   DeviceGuard guard(b->model->device);
-  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  if (const int rc = closed_begin(b, n_steps, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
   if (n_steps == 0) return GQ_OK;
   const int N = b->host.n_envs, od = b->host.obs_dim;
   Mailbox& mb = b->mb;
   gq::MailboxDev& h = mb.host;
-  /* queue tickets are 32-bit: the env-steps that pass through one queue must stay below 2^31 (items carry env + 1 in 24 bits) */
-  if (N >= (1 << 24) || (int64_t)((N + h.nq - 1) / h.nq) * (int64_t)n_steps >= ((int64_t)1 << 31) - 65536) {
-    SET_ERR("gq_rollout_closed: %d envs x %d steps over %d queues overflows the 32-bit ticket counters: split the rollout", N, n_steps, h.nq); return GQ_EINVAL;
-  }
   gq::PolicyPdDev P{};
-  if (pd) { /* the columns of the joint angles / velocities in this batch's observation row */
-    for (int j = 0; j < 12; j++) {
-      P.kp[j] = pd->kp[j]; P.kd[j] = pd->kd[j]; P.qdes[j] = pd->q_des[j]; P.col_q[j] = -1; P.col_qd[j] = -1;
-      for (int c = 0; c < od; c++) {
-        const int src = b->host.obs_map[c];
-        if (P.col_q[j] < 0 && (src == gq::OB_QPOS_JS + j || src == gq::OB_QPOS + 7 + j)) P.col_q[j] = c;
-        if (P.col_qd[j] < 0 && (src == gq::OB_QVEL_JS + j || src == gq::OB_QVEL + 6 + j)) P.col_qd[j] = c;
-      }
-      if (P.col_q[j] < 0 || P.col_qd[j] < 0) { SET_ERR("gq_rollout_closed: the PD policy reads qpos_js / qvel_js (or qpos / qvel): not in this batch's observation row"); return GQ_EINVAL; }
-    }
+  if (pd) {
+    if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "PD"); rc != GQ_OK) return rc;
+    for (int j = 0; j < 12; j++) { P.kp[j] = pd->kp[j]; P.kd[j] = pd->kd[j]; P.qdes[j] = pd->q_des[j]; }
     if (policy_waves <= 0) policy_waves = 64; /* lane = env: 4096 envs get a lane each */
     if (policy_waves > 256) policy_waves = 256;
     if (policy_waves < 2 * h.nq) policy_waves = 2 * h.nq; /* every XCD needs policy wavefronts of its own (dispatch is round-robin over the XCDs) */
@@ -505,52 +591,90 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
     HIP_TRY(launch_step_kernel(b, &ci, N, stream));
     return GQ_OK;
   }
-  if (step_waves <= 0) step_waves = N; /* more workgroups than free slots (or than envs) is harmless: pop tickets that run ahead of the pushes
-                                        * wait on lap-tagged slots, the late ones find the queues drained */
-  if (step_waves < 4 * h.nq) step_waves = 4 * h.nq; /* a wavefront pops from ITS XCD's queue only: every XCD needs stepping wavefronts, also for a batch of
-                                                      * one env (workgroups are dealt round-robin over the XCDs; the surplus finds its queue empty and leaves) */
-  h.n_steps = n_steps; h.obs_seq = obs_seq; h.act_seq = act_seq;
-  h.timeout_ticks = (int64_t)((timeout_s > 0.0 ? timeout_s : 5.0) * 1e8);
-  /* fresh rollout state, ordered on the caller's stream */
-  HIP_TRY(hipMemsetAsync(h.steps_done, 0, sizeof(int32_t) * (size_t)N, stream));
-  HIP_TRY(hipMemsetAsync(h.issued, 0, sizeof(int32_t) * (size_t)N, stream));
-  HIP_TRY(hipMemsetAsync(h.q_items, 0, sizeof(int32_t) * (size_t)h.nq * h.qcap, stream));
-  HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * (size_t)h.nq * 3 * GQ_MB_QSTRIDE, stream));
-  HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
-  HIP_TRY(hipStreamSynchronize(stream)); /* the pinned staging block below is reused per call; a rollout is thousands of launches' worth of work */
-  std::memcpy(mb.staging.get(), &h, sizeof h);
-  HIP_TRY(hipMemcpyAsync(mb.dev.get(), mb.staging.get(), sizeof h, hipMemcpyHostToDevice, stream));
-  gq::StepCall c{};
-  c.auto_reset = gq::auto_reset_mode(auto_reset);
+  if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (pd) {
-    /* the policy must be RESIDENT before the step wavefronts take every slot of the device: launch it first, on its own stream,
-     * and wait until each of its workgroups has reported in */
-    volatile int32_t* alive = mb.alive.get();
-    *alive = 0;
-    HIP_TRY(hipEventRecord(mb.fork.get(), stream));
-    HIP_TRY(hipStreamWaitEvent(mb.stream.get(), mb.fork.get(), 0));
+    if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
     gq_launch_policy_pd(mb.dev.get(), mb.policy.dev.get(), out.obs, od, policy_waves, mb.stream.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(mb.join.get(), mb.stream.get()));
-    const auto t0 = std::chrono::steady_clock::now();
-    while (*alive < policy_waves) {
-      std::this_thread::yield();
-      if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
-        /* it cannot start: tell it to leave as soon as it does, and report */
-        mb.status_host.get()[0] = 3; /* pinned: the source of an asynchronous copy must outlive this frame */
-        (void)hipMemcpyAsync(h.status, mb.status_host.get(), sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        (void)hipStreamSynchronize(stream);
-        (void)hipStreamSynchronize(mb.stream.get()); /* the policy kernel has left (or never ran): nothing of this call touches `alive` later */
-        SET_ERR("gq_rollout_closed: the policy kernel did not become resident within 2 s (%d of %d workgroups)", (int)*alive, policy_waves);
-        return GQ_EDEVICE;
-      }
-    }
+    if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   }
-  if (!gq_launch_mailbox_step(b->args.dev.get(), &c, mb.dev.get(), step_waves, b->model->host.solver, b->model->host.cone, b->model->scene, stream)) {
-    SET_ERR("gq_rollout_closed: no mailbox variant of the step kernel for this model in this build"); return GQ_EINVAL;
+  return mailbox_steps(b, auto_reset, step_waves, pd != nullptr, stream, who);
+}
+
+static bool mlp_fresh(const GqPolicyMlp* mlp, const char* who) {
+  if (!mlp) { SET_ERR("%s: bad argument", who); return false; }
+  if (mlp->struct_size != (int32_t)sizeof(GqPolicyMlp)) { SET_ERR("%s: GqPolicyMlp.struct_size is %d, this library's struct has %d bytes: stale binding", who, mlp->struct_size, (int)sizeof(GqPolicyMlp)); return false; }
+  return true;
+}
+/* the shape of the network and what the law needs, checked and copied into the device block's form */
+static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who) {
+  if (mlp->n_layers < 1 || mlp->n_layers > GQ_MLP_MAXL) { SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, GQ_MLP_MAXL); return GQ_EINVAL; }
+  const int in_dim = mlp->in_obs + (mlp->feed_last_action ? 12 : 0);
+  if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
+  if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the network's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
+  for (int l = 0; l < mlp->n_layers; l++)
+    if (mlp->width[l] < 1 || mlp->width[l] > GQ_MLP_MAXW) { SET_ERR("%s: layer %d has %d outputs: 1 to %d are supported", who, l, mlp->width[l], GQ_MLP_MAXW); return GQ_EINVAL; }
+  if (mlp->width[mlp->n_layers - 1] != 12) { SET_ERR("%s: the network has %d outputs: 12 (one per hinge) are needed", who, mlp->width[mlp->n_layers - 1]); return GQ_EINVAL; }
+  if (mlp->activation < GQ_ACT_RELU || mlp->activation > GQ_ACT_TANH) { SET_ERR("%s: activation %d: relu (1), elu (2) or tanh (3)", who, mlp->activation); return GQ_EINVAL; }
+  if (mlp->out_activation != GQ_ACT_NONE && mlp->out_activation != GQ_ACT_TANH) { SET_ERR("%s: out_activation %d: none (0) or tanh (3)", who, mlp->out_activation); return GQ_EINVAL; }
+  if (!mlp->blob) { SET_ERR("%s: blob is null", who); return GQ_EINVAL; }
+  P.net.n_layers = mlp->n_layers; P.net.in_dim = in_dim; P.net.act = mlp->activation; P.net.out_act = mlp->out_activation;
+  for (int l = 0; l < GQ_MLP_MAXL; l++) P.net.width[l] = l < mlp->n_layers ? mlp->width[l] : 0;
+  if (mlp->blob_floats != (int64_t)gq::mlp_blob_floats(P.net)) { SET_ERR("%s: blob_floats is %lld, this network's blob has %lld", who, (long long)mlp->blob_floats, (long long)gq::mlp_blob_floats(P.net)); return GQ_EINVAL; }
+  P.in_obs = mlp->in_obs; P.feed_last = mlp->feed_last_action ? 1 : 0; P.decimation = mlp->decimation; P.pad_ = 0; P.pad2_ = 0;
+  P.blob = mlp->blob; P.shift = mlp->obs_shift; P.scale = mlp->obs_scale;
+  return GQ_OK;
+}
+
+int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                      const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
+  const char* const who = "gq_rollout_policy";
+  if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
+  if (!b || n_steps < 0) { SET_ERR("gq_rollout_policy: bad argument"); return GQ_EINVAL; }
+  if (mlp->in_obs > b->host.obs_dim) { SET_ERR("gq_rollout_policy: in_obs = %d, the observation row has %d columns", mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
+  gq::PolicyMlpDev P = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
+  if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
+  if (mlp->decimation < 1) { SET_ERR("gq_rollout_policy: decimation must be >= 1 (got %d)", mlp->decimation); return GQ_EINVAL; }
+  if (n_steps % mlp->decimation != 0) { SET_ERR("gq_rollout_policy: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", n_steps, mlp->decimation); return GQ_EINVAL; }
+  if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "MLP"); rc != GQ_OK) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  DeviceGuard guard(b->model->device);
+  if (const int rc = closed_begin(b, n_steps, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
+  if (n_steps == 0) return GQ_OK;
+  const int N = b->host.n_envs, od = b->host.obs_dim;
+  Mailbox& mb = b->mb;
+  gq::MailboxDev& h = mb.host;
+  if (policy_waves <= 0) policy_waves = 128; /* a wavefront takes its ready envs through the network 16 at a time */
+  if (policy_waves > 1024) policy_waves = 1024;
+  if (policy_waves < 2 * h.nq) policy_waves = 2 * h.nq; /* every XCD needs policy wavefronts of its own (dispatch is round-robin over the XCDs) */
+  for (int j = 0; j < 12; j++) {
+    P.kp[j] = mlp->kp[j]; P.kd[j] = mlp->kd[j]; P.q_default[j] = mlp->q_default[j]; P.action_scale[j] = mlp->action_scale[j]; P.sigma[j] = mlp->noise_sigma[j];
   }
+  P.clip = mlp->action_clip;
+  P.seed_lo = (uint32_t)(mlp->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(mlp->noise_seed >> 32);
+  P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
+  P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
+  HIP_TRY(mb.mlp.push(P, stream, true));
+  HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
+  if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
+  if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
+  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, mb.stream.get());
+  if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
+  return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
+}
+
+int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream) {
+  const char* const who = "gq_policy_mlp_eval";
+  if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
+  if (!b || !rows || !out || n_rows < 0 || (impl != 0 && impl != 1)) { SET_ERR("gq_policy_mlp_eval: bad argument"); return GQ_EINVAL; }
+  DeviceGuard guard(b->model->device);
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  gq::PolicyMlpDev P = b->mb.mlp.shadow;
+  if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
+  if (n_rows == 0) return GQ_OK;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(b->mb.mlp.push(P, stream, true));
+  gq_launch_policy_mlp_eval(b->mb.mlp.dev.get(), rows, n_rows, impl, out, stream);
   HIP_TRY(hipGetLastError());
-  if (pd) HIP_TRY(hipStreamWaitEvent(stream, mb.join.get(), 0)); /* the caller's stream resumes when both kernels are done */
   return GQ_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <gq_device.h>
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
+#include "gq_policy_mlp.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -298,6 +299,30 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel_prim(const Fus
 }
 
 #if GQ_IN_MISC
+/* The head of a policy kernel, shared as TEXT (policy_pd_kernel keeps the code it had when the statements stood in its body: a function
+ * around them changed its register allocation): the wavefront says on which XCD it runs and waits until every policy wavefront of the launch
+ * has - rank = its number among those of its XCD's queue q, mine = how many there are (the stride over the queue's envs); it RETURNS from
+ * the kernel when the abort word is up, the deadline passes or an XCD got no policy wavefront.  Needs MB, lane, nq, q in scope. */
+#define GQ_POLICY_REGISTER()                                                                                                                      \
+  const int P_all = (int)gridDim.x;                                                                                                               \
+  int rank = 0;                                                                                                                                   \
+  if (lane == 0) rank = add_pub(MB.q_ctr + (size_t)(3 * q + 2) * GQ_MB_QSTRIDE, 1);                                                               \
+  rank = __builtin_amdgcn_readfirstlane(rank);                                                                                                    \
+  if (lane == 0) __hip_atomic_fetch_add(MB.alive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);                                                \
+  long long t_last = wall_clock64();                                                                                                              \
+  int mine = 0;                                                                                                                                   \
+  for (;;) { /* every policy wavefront has said where it runs: the stride of this XCD is known */                                                 \
+    int sum = 0;                                                                                                                                  \
+    for (int x = 0; x < nq; x++) { const int c = ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE); sum += c; if (x == q) mine = c; }        \
+    if (sum >= P_all) {                                                                                                                           \
+      for (int x = 0; x < nq; x++)                                                                                                                \
+        if (ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE) == 0) { if (lane == 0) { st_pub(MB.status + 1, x); st_pub(MB.status, 4); } return; } /* an XCD without policy */ \
+      break;                                                                                                                                      \
+    }                                                                                                                                             \
+    nap();                                                                                                                                        \
+    if (ld_pub(MB.status) != 0) return;                                                                                                           \
+    if (wall_clock64() - t_last > MB.timeout_ticks) { if (lane == 0) { st_pub(MB.status + 1, -1 - rank); st_pub(MB.status, 2); } return; }        \
+  }
 /* the built-in policy of the closed-loop rollout.  A policy wavefront serves envs of ITS XCD's queue only (lane = env, strided over the
  * policy wavefronts that landed on the XCD): observation row, action row, count and queue slot of an env are written and read
  * through one L2, like the env's state rows - no hand-off of the rollout depends on coherence between two XCDs' L2s, and none
@@ -306,25 +331,8 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
   const GQ_MODEL PolicyPdDev& P = *mptr(Pp);
   const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
-  const int N = MB.n_envs, K = MB.n_steps, P_all = (int)gridDim.x;
-  int rank = 0;
-  if (lane == 0) rank = add_pub(MB.q_ctr + (size_t)(3 * q + 2) * GQ_MB_QSTRIDE, 1);
-  rank = __builtin_amdgcn_readfirstlane(rank);
-  if (lane == 0) __hip_atomic_fetch_add(MB.alive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  long long t_last = wall_clock64();
-  int mine = 0;
-  for (;;) { /* every policy wavefront has said where it runs: the stride of this XCD is known */
-    int sum = 0;
-    for (int x = 0; x < nq; x++) { const int c = ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE); sum += c; if (x == q) mine = c; }
-    if (sum >= P_all) {
-      for (int x = 0; x < nq; x++)
-        if (ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE) == 0) { if (lane == 0) { st_pub(MB.status + 1, x); st_pub(MB.status, 4); } return; } /* an XCD without policy */
-      break;
-    }
-    nap();
-    if (ld_pub(MB.status) != 0) return;
-    if (wall_clock64() - t_last > MB.timeout_ticks) { if (lane == 0) { st_pub(MB.status + 1, -1 - rank); st_pub(MB.status, 2); } return; }
-  }
+  const int N = MB.n_envs, K = MB.n_steps;
+  GQ_POLICY_REGISTER()
   const int nmine = (N - q + nq - 1) / nq;           /* envs of this queue: e = q + nq * i */
   const int g = rank * GQ_WAVE + lane, G = mine * GQ_WAVE;
   int32_t* const tail = MB.q_ctr + (size_t)(3 * q + 1) * GQ_MB_QSTRIDE;
@@ -361,6 +369,146 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
     nap();
     if (ld_pub(MB.status) != 0) break;
     if (wall_clock64() - t_last > MB.timeout_ticks) { st_pub(MB.status + 1, g); st_pub(MB.status, 2); break; }
+  }
+}
+
+/* A learned policy in the same seat (gq_rollout_policy): an MLP on the matrix cores (gq_policy_mlp.h) gives the env a joint-target action
+ * every `decimation` steps; at EVERY step the env's lane turns the held action into torques with the joint-impedance law and hands them
+ * to the step side exactly as policy_pd_kernel does - same registration, same XCD rule, same deadline on every wait.  Lane = env, strided
+ * as there; the lanes of a pass whose env is ready AND due for a new action are compacted by ballot into tiles of up to 16 rows, which the
+ * whole wavefront stages (device-scope loads: every word of the row is another wavefront's store of this launch) and takes through the
+ * layers.  An env that re-spawns ignores the torque of that step (next-step auto-reset); its held and last action are kept. */
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
+  __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
+  const GQ_MODEL MailboxDev& MB = *mptr(MBp);
+  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+  const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
+  const int N = MB.n_envs, K = MB.n_steps, D = P.decimation;
+  GQ_POLICY_REGISTER()
+  const MlpNet net = mlp_net_load(P.net);
+  const int in_obs = P.in_obs, in_dim = net.in_dim;
+  const float* const shift = P.shift;
+  const float* const scale = P.scale;
+  const int nmine = (N - q + nq - 1) / nq;           /* envs of this queue: e = q + nq * i */
+  const int G = mine * GQ_WAVE;
+  int32_t* const tail = MB.q_ctr + (size_t)(3 * q + 1) * GQ_MB_QSTRIDE;
+  int32_t* const items = MB.q_items + (size_t)q * MB.qcap;
+  t_last = wall_clock64();
+  for (;;) {
+    bool all_done = true, progress = false;
+    for (int base = rank * GQ_WAVE; base < nmine; base += G) { /* wave-uniform: the tile work below needs every lane */
+      const int i = base + lane;
+      const int e = i < nmine ? q + nq * i : q;      /* (a lane without env reads env q's words and does nothing) */
+      const int k = i < nmine ? P.issued[e] : K;
+      const bool live = k < K;
+      if (live) all_done = false;
+      const bool ready = live && ld_pub(MB.steps_done + e) >= k; /* the observation after step k - 1 is out */
+      const bool fresh = ready && k % D == 0;                    /* ... and the env is due for a new action */
+      float a[12];
+      /* (the observation words are read AFTER the count has been seen: the ballot below waits for every lane's count) */
+      for (uint64_t todo = ballot(fresh); todo != 0;) {
+        uint64_t tile = 0, t = todo;
+        int src = -1;                                /* the lane whose env is row lane & 15 of this tile */
+        for (int r = 0; r < GQ_MLP_ROWS && t != 0; r++) {
+          const int f = ffs64(t);
+          if ((lane & 15) == r) src = f;
+          tile |= (uint64_t)1 << f; t &= t - 1;
+        }
+        todo &= ~tile;
+        const int er = shfl_idx(e, src < 0 ? 0 : src);
+        const float* const row = obs + (size_t)er * od;
+        const float* const prev = P.last + (size_t)er * 12;
+        mlp_tile_stage(net, xt[0], [&](const int, const int c) {
+          if (src < 0 || c >= in_dim) return 0.0f;
+          if (c < in_obs) return mlp_obs_in(ld_pub(row + c), shift, scale, c);
+          return ld_pub(prev + (c - in_obs));
+        });
+        const float* const out = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
+        if (fresh && ((tile >> lane) & 1)) {
+          const int slot = popc64(tile & (((uint64_t)1 << lane) - 1));
+          const uint32_t gid = (uint32_t)(e + P.env_id_offset);
+#pragma unroll
+          for (int j = 0; j < 12; j++) {
+#pragma clang fp contract(off)
+            float v = out[j * GQ_MLP_ROWS + slot];
+            const float sg = P.sigma[j];
+            if (sg > 0.0f) {
+              const uint32_t x0 = philox4x32((uint32_t)j, (uint32_t)(P.step0 + k), gid, GQ_MLP_NOISE_STREAM, P.seed_lo, P.seed_hi, 0);
+              const uint32_t x1 = philox4x32((uint32_t)j, (uint32_t)(P.step0 + k), gid, GQ_MLP_NOISE_STREAM, P.seed_lo, P.seed_hi, 1);
+              const float nz = sg * mlp_normal(x0, x1);
+              v = v + nz;
+            }
+            if (P.clip > 0.0f) v = fminf(fmaxf(v, -P.clip), P.clip);
+            a[j] = v;
+            st_pub(P.held + (size_t)e * 12 + j, v);
+            if (P.feed_last) st_pub(P.last + (size_t)e * 12 + j, v);
+            if (P.policy_actions) P.policy_actions[((size_t)(k / D) * N + e) * 12 + j] = v;
+          }
+        }
+      }
+      if (!ready) continue;
+      const float* row = obs + (size_t)e * od;
+      float qj[12], qd[12];
+#pragma unroll
+      for (int j = 0; j < 12; j++) {
+        qj[j] = ld_pub(row + P.col_q[j]); qd[j] = ld_pub(row + P.col_qd[j]);
+        if (!fresh) a[j] = ld_pub(P.held + (size_t)e * 12 + j);
+      }
+      /* the action row and the push ticket travel together */
+      const int s = add_pub(tail, 1);
+#pragma unroll
+      for (int j = 0; j < 12; j++) {
+#pragma clang fp contract(off)
+        const float sa = P.action_scale[j] * a[j];
+        const float q_des = P.q_default[j] + sa;
+        const float u = joint_cmd_law(q_des, 0.0f, 0.0f, P.kp[j], P.kd[j], qj[j], qd[j]);
+        st_pub(MB.act + (size_t)e * 12 + j, u);
+        if (MB.act_seq) MB.act_seq[((size_t)k * N + e) * 12 + j] = u;
+      }
+      publish_fence();
+      st_pub(items + (s & qmask), (((s >> qshift) & 0x7f) << 24) | (e + 1)); /* the item (lap of its ticket | env + 1) - after the action is in place */
+      P.issued[e] = k + 1;
+      progress = true;
+    }
+    /* (all_done / progress are per lane, as in policy_pd_kernel: the wavefront goes on while any lane has work, and a lane that leaves
+     * the loop early would miss the tile work of the others - so the exits below are taken by the whole wavefront) */
+    const bool any_live = ballot(!all_done) != 0, any_progress = ballot(progress) != 0;
+    if (!any_live) break;
+    if (any_progress) { t_last = wall_clock64(); continue; }
+    nap();
+    if (ld_pub(MB.status) != 0) break;
+    if (wall_clock64() - t_last > MB.timeout_ticks) { if (lane == 0) { st_pub(MB.status + 1, rank * GQ_WAVE); st_pub(MB.status, 2); } break; }
+  }
+}
+
+/* the network alone over rows [n][in_dim] (gq_policy_mlp_eval): the two forms of the law side by side, so that their bits can be compared.
+ * shift / scale act on the first in_obs columns, as in the rollout. */
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_row_kernel(const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+  const MlpNet net = mlp_net_load(P.net);
+  const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
+  if (r >= n) return;
+  float x[GQ_MLP_MAXW], y[GQ_MLP_ROWS];
+  for (int c = 0; c < net.in_dim; c++) { const float v = rows[(size_t)r * net.in_dim + c]; x[c] = c < P.in_obs ? mlp_obs_in(v, P.shift, P.scale, c) : v; }
+  mlp_row_forward(net, P.blob, x, y);
+  for (int j = 0; j < 12; j++) out[(size_t)r * 12 + j] = y[j];
+}
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
+  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+  const MlpNet net = mlp_net_load(P.net);
+  const int lane = (int)threadIdx.x, r0 = (int)blockIdx.x * GQ_MLP_ROWS, in_dim = net.in_dim, in_obs = P.in_obs;
+  const float* const shift = P.shift;
+  const float* const scale = P.scale;
+  mlp_tile_stage(net, xt[0], [&](const int r, const int c) {
+    if (r0 + r >= n || c >= in_dim) return 0.0f;
+    const float v = rows[(size_t)(r0 + r) * in_dim + c];
+    return c < in_obs ? mlp_obs_in(v, shift, scale, c) : v;
+  });
+  const float* const y = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
+  for (int w = lane; w < GQ_MLP_ROWS * 12; w += GQ_WAVE) {
+    const int r = w / 12, j = w % 12;
+    if (r0 + r < n) out[(size_t)(r0 + r) * 12 + j] = y[j * GQ_MLP_ROWS + r];
   }
 }
 
@@ -602,6 +750,14 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 }
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
+}
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, hipStream_t stream) {
+  hipLaunchKernelGGL(gq::policy_mlp_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+}
+/* impl 0: mlp_row_forward, a thread per row; 1: mlp_tile_forward, a wavefront per 16 rows */
+extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
+  if (impl == 0) hipLaunchKernelGGL(gq::policy_mlp_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
+  else hipLaunchKernelGGL(gq::policy_mlp_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
 }
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream) {
   hipLaunchKernelGGL(gq::jac_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, qpos, body, point, jacp, jacr);

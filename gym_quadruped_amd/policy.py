@@ -1,0 +1,154 @@
+"""Policies that run INSIDE the closed-loop rollout (``QuadrupedEnv.rollout_policy``): a small MLP evaluated by a resident policy kernel
+on the matrix cores, between the published observation rows and the action mailboxes of ``gq_rollout_closed``'s machinery.
+
+The law and the weight blob are defined in ``csrc/gq_policy_mlp.h``; this module packs a network into that blob (no GPU needed) and
+restates the network in float64 for tests."""
+from __future__ import annotations
+
+import numpy as np
+
+from .cabi import GQ_ACT
+
+MAX_LAYERS, MAX_WIDTH, N_ACTIONS = 4, 256, 12
+
+
+def _kp(k):
+    return (k + 3) & ~3
+
+
+def _np(n):
+    return (n + 15) & ~15
+
+
+def elu64(x):
+    return np.where(x > 0, x, np.expm1(np.minimum(x, 0.0)))
+
+
+_ACT64 = dict(none=lambda x: x, relu=lambda x: np.maximum(x, 0.0), elu=elu64, tanh=np.tanh)
+
+
+class MlpPolicy:
+    """An MLP with up to 4 linear layers (at most 3 hidden layers and the output layer), every width and the input width <= 256, 12 outputs
+    (joint-target actions in the hinge order of ``qpos[7:]``), fp32 weights.
+
+    weights: one ``[in, out]`` array per layer (``y = x @ W + b``; ``torch.nn.Linear.weight`` is its transpose); biases: one ``[out]``
+    array per layer.  activation: 'relu', 'elu' or 'tanh' between the layers; out_activation: None or 'tanh'.  obs_shift / obs_scale:
+    optional per-column ``(o - shift) * scale`` on the observation columns the network reads.  feed_last_action: the env's previous
+    policy action (12 values, zeros at the first policy step of a rollout call) follows the observation columns in the input row, so the
+    first layer has ``in_obs + 12`` inputs."""
+
+    def __init__(self, weights, biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None, feed_last_action=False):
+        self.weights = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        self.biases = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
+        if not 1 <= len(self.weights) <= MAX_LAYERS:
+            raise ValueError(f'{len(self.weights)} linear layers: 1 to {MAX_LAYERS} are supported (3 hidden layers and the output)')
+        if len(self.biases) != len(self.weights):
+            raise ValueError('one bias vector per weight matrix')
+        k = None
+        for l, (w, b) in enumerate(zip(self.weights, self.biases)):
+            if w.ndim != 2 or b.shape != (w.shape[1],) or (k is not None and w.shape[0] != k):
+                raise ValueError(f'layer {l}: weights {w.shape} (expected [in, out] with in = {k}) and bias {b.shape} do not fit')
+            if not (1 <= w.shape[0] <= MAX_WIDTH and 1 <= w.shape[1] <= MAX_WIDTH):
+                raise ValueError(f'layer {l}: {w.shape[0]} inputs, {w.shape[1]} outputs: 1 to {MAX_WIDTH} are supported')
+            k = w.shape[1]
+        if k != N_ACTIONS:
+            raise ValueError(f'the network has {k} outputs: {N_ACTIONS} (one per hinge) are needed')
+        if activation not in ('relu', 'elu', 'tanh'):
+            raise ValueError(f"activation must be 'relu', 'elu' or 'tanh', got {activation!r}")
+        if out_activation not in (None, 'none', 'tanh'):
+            raise ValueError(f"out_activation must be None or 'tanh', got {out_activation!r}")
+        self.activation, self.out_activation = activation, out_activation or 'none'
+        self.feed_last_action = bool(feed_last_action)
+        self.in_dim = self.weights[0].shape[0]
+        self.in_obs = self.in_dim - (N_ACTIONS if self.feed_last_action else 0)
+        if self.in_obs < 0:
+            raise ValueError(f'feed_last_action needs at least {N_ACTIONS} inputs, the first layer has {self.in_dim}')
+        self.widths = [w.shape[1] for w in self.weights]
+
+        def col(v, name):
+            if v is None:
+                return None
+            return np.array(np.broadcast_to(np.asarray(v, dtype=np.float32), (self.in_obs,)), dtype=np.float32)
+        self.obs_shift, self.obs_scale = col(obs_shift, 'obs_shift'), col(obs_scale, 'obs_scale')
+        self._device = {}   # device -> (blob, shift, scale) tensors
+
+    @classmethod
+    def from_torch(cls, module, **kw):
+        """From a ``torch.nn.Sequential`` of ``Linear`` layers with ``ReLU``, ``ELU`` (alpha 1) or ``Tanh`` between them (one kind), optionally a
+        ``Tanh`` at the end; anything else raises ``ValueError``."""
+        import torch.nn as nn
+        if not isinstance(module, nn.Sequential):
+            raise ValueError(f'from_torch takes a torch.nn.Sequential, got {type(module).__name__}')
+        names = {nn.ReLU: 'relu', nn.ELU: 'elu', nn.Tanh: 'tanh'}
+        weights, biases, acts = [], [], []
+        for m in module:
+            if isinstance(m, nn.Linear):
+                if len(acts) < len(weights):
+                    acts.append('none')
+                weights.append(m.weight.detach().cpu().numpy().T)
+                biases.append(m.bias.detach().cpu().numpy() if m.bias is not None else np.zeros(m.out_features, dtype=np.float32))
+            elif type(m) in names and len(acts) == len(weights) - 1:
+                if isinstance(m, nn.ELU) and m.alpha != 1.0:
+                    raise ValueError(f'ELU with alpha = {m.alpha}: only alpha = 1 is supported')
+                acts.append(names[type(m)])
+            else:
+                raise ValueError(f'unsupported module in the Sequential: {m!r} (Linear with ReLU, ELU or Tanh)')
+        if not weights:
+            raise ValueError('the Sequential holds no Linear layer')
+        if len(acts) < len(weights):
+            acts.append('none')
+        hidden, out = set(acts[:-1]), acts[-1]
+        if len(hidden) > 1 or 'none' in hidden:
+            raise ValueError(f'the hidden layers must share one activation out of ReLU, ELU, Tanh; got {acts[:-1]}')
+        if out not in ('none', 'tanh'):
+            raise ValueError(f'the output layer may be followed by Tanh or nothing, got {out}')
+        return cls(weights, biases, activation=hidden.pop() if hidden else 'relu', out_activation=out, **kw)
+
+    def blob_floats(self):
+        return sum(_np(w.shape[1]) * (_kp(w.shape[0]) + 1) for w in self.weights)
+
+    def pack(self):
+        """The padded blob (float32 numpy), layer after layer: weights ``[Np / 16][Kp / 4][64]`` - word ``l`` of block ``(cb, kb)`` is
+        ``w[4 kb + (l >> 4)][16 cb + (l & 15)]`` - then ``Np`` biases; zeros in the padding."""
+        parts = []
+        for w, b in zip(self.weights, self.biases):
+            k, n = w.shape
+            kp, npad = _kp(k), _np(n)
+            wp = np.zeros((kp, npad), dtype=np.float32)
+            wp[:k, :n] = w
+            # [kb, kk, cb, oo] -> [cb, kb, kk, oo]
+            parts.append(wp.reshape(kp // 4, 4, npad // 16, 16).transpose(2, 0, 1, 3).reshape(-1))
+            bp = np.zeros(npad, dtype=np.float32)
+            bp[:n] = b
+            parts.append(bp)
+        return np.ascontiguousarray(np.concatenate(parts))
+
+    def reference(self, x):
+        """float64 forward pass of the same network over rows ``[n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns)."""
+        h = np.array(x, dtype=np.float64).reshape(-1, self.in_dim)
+        if self.obs_shift is not None:
+            h[:, :self.in_obs] -= self.obs_shift.astype(np.float64)
+        if self.obs_scale is not None:
+            h[:, :self.in_obs] *= self.obs_scale.astype(np.float64)
+        for l, (w, b) in enumerate(zip(self.weights, self.biases)):
+            h = h @ w.astype(np.float64) + b.astype(np.float64)
+            h = _ACT64[self.out_activation if l == len(self.weights) - 1 else self.activation](h)
+        return h
+
+    # -- the C struct's network part, with the blob on `device`
+    def _struct(self, device):
+        import ctypes as C
+
+        import torch
+
+        from .cabi import GqPolicyMlp
+        key = str(device)
+        if key not in self._device:
+            up = lambda v: None if v is None else torch.from_numpy(v).to(device)
+            self._device[key] = (up(self.pack()), up(self.obs_shift), up(self.obs_scale))
+        blob, shift, scale = self._device[key]
+        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=self.in_obs, feed_last_action=int(self.feed_last_action),
+                        activation=GQ_ACT[self.activation], out_activation=GQ_ACT[self.out_activation], decimation=1, blob=blob.data_ptr(),
+                        blob_floats=blob.numel(), obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
+        m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))
+        return m

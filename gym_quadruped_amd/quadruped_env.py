@@ -400,6 +400,90 @@ class QuadrupedEnv(AccessorsMixin):
                 sensor.step()
         return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq}
 
+    def _policy_struct(self, policy, rollout=True):
+        """``policy``'s C block for this batch; rollout: after the check only this side can make - the network reads the user's own columns"""
+        from .policy import MlpPolicy
+        if not isinstance(policy, MlpPolicy):
+            raise ValueError(f'policy must be an MlpPolicy, got {type(policy).__name__}')
+        width = sum(int(v.shape[1]) for v in self._obs_views.values())
+        if rollout and policy.in_obs > width:
+            raise ValueError(f"the policy reads {policy.in_obs} observation columns, state_obs_names gives {width} (the accessors' extra columns are not fed to a policy)")
+        return policy._struct(self.device)
+
+    def rollout_policy(self, n_steps: int, policy, kp, kd, q_default=None, action_scale=0.25, action_clip=None, decimation: int = 4, noise_sigma=0.0,
+                       record_obs: bool = False, record_actions: bool = False, policy_waves: int = 0, step_waves: int = 0, timeout_s: float = 5.0,
+                       check: bool = True):
+        """``n_steps`` steps of every env with an MLP policy IN the loop and no launch boundary (``gq_rollout_policy``): the device-side
+        form of ::
+
+            for p in range(n_steps // decimation):
+                a = policy(cat(obs_row[:, :in_obs], a_prev)) + noise_sigma * z;  a = clip(a, -action_clip, action_clip)
+                obs, ... = env.step_pd(q_default + action_scale * a, kp, kd, decimation=decimation)
+
+        on the machinery of ``rollout_closed_loop(mode='mailbox')``: a resident policy kernel takes the ready envs through the network 16
+        at a time on the matrix cores (``policy``: an ``MlpPolicy``), holds each env's action for ``decimation`` steps and turns it into
+        torques at EVERY step with the joint-impedance law of ``step_pd`` on the ``qpos_js`` / ``qvel_js`` (or ``qpos`` / ``qvel``)
+        columns of the observation row; the step side is that of ``rollout_closed_loop``.  State, flags and observations afterwards equal
+        the step loop's with the recorded torques, bit for bit.
+
+        The network reads the first ``policy.in_obs`` columns of the observation row - ``state_obs_names``' columns, never the extras of
+        ``accessors=True`` - and, with ``feed_last_action``, the env's previous policy action (zeros at the first policy step of a
+        call).  ``n_steps`` must be a multiple of ``decimation``: no held action crosses calls.  An env that re-spawns ignores that
+        step's torque (next-step auto-reset) and KEEPS its held and its last action: neither is reset with the env.
+
+        kp, kd, action_scale, noise_sigma: a scalar or 12 values (hinge order of ``qpos[7:]``); q_default: 12 joint angles (default:
+        keyframe 0); action_clip: None or a bound on ``|a|``; noise_sigma: Gaussian exploration noise on the action (counter-based draws
+        keyed by the env's seed, the step and the joint).  Returns a dict: 'obs' (the last observation views), 'obs_seq'
+        ``[K, N, obs_dim]`` / 'actions' ``[K, N, 12]`` (the torques) when asked for, else None, and 'policy_actions'
+        ``[K // decimation, N, 12]`` (the network's actions, when ``record_actions``).  ``check``: as in ``rollout_closed_loop``."""
+        K, D = int(n_steps), int(decimation)
+        if K < 0:
+            raise ValueError('n_steps must be >= 0')
+        if D < 1:
+            raise ValueError(f'decimation must be >= 1, got {decimation}')
+        if K % D:
+            raise ValueError(f'n_steps = {K} must be a multiple of decimation = {D}: no held action crosses calls')
+        m = self._policy_struct(policy)
+        row12 = lambda v: (C.c_float * 12)(*np.broadcast_to(np.asarray(v, dtype=np.float32), (12,)))
+        m.kp, m.kd, m.action_scale, m.noise_sigma = row12(kp), row12(kd), row12(action_scale), row12(noise_sigma)
+        m.q_default = row12(self._key_qpos[7:19].float().cpu().numpy() if q_default is None else np.asarray(q_default, dtype=np.float32).reshape(12))
+        m.action_clip = 0.0 if action_clip is None else float(action_clip)
+        if action_clip is not None and not m.action_clip > 0.0:
+            raise ValueError(f'action_clip must be positive or None, got {action_clip}')
+        m.decimation, m.noise_seed, m.noise_step0 = D, int(self._seed or 0) & (2 ** 64 - 1), int(self._launches) & 0x7fffffff
+        obs_seq, act_seq = self._window_records(K, record_obs, record_actions)
+        pol_seq = torch.empty(K // D, self.num_envs, 12, dtype=torch.float32, device=self.device) if record_actions else None
+        m.policy_actions = None if pol_seq is None else pol_seq.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._hm_fresh = False
+        _lib.check(self._L.gq_rollout_policy(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg,
+                                             self._episode.data_ptr(), self._lift_failed.data_ptr(), None if obs_seq is None else obs_seq.data_ptr(),
+                                             None if act_seq is None else act_seq.data_ptr(), stream), 'gq_rollout_policy')
+        self._launches += K
+        if check:
+            self.closed_loop_status()
+        for sensor in self.sensors:
+            for _ in range(K):
+                sensor.step()
+        return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq, 'policy_actions': pol_seq}
+
+    def policy_eval(self, policy, rows, impl: str = 'tile'):
+        """The network of ``policy`` alone over ``rows`` (``[n, policy.in_dim]`` float32 on the env's device; shift / scale applied to
+        the first ``in_obs`` columns; no noise, no clip, no control law) -> ``[n, 12]``.  impl 'tile': the matrix-core form the rollout
+        runs, a wavefront per 16 rows; 'scalar': the plain ``fmaf`` loop that defines the law, a thread per row.  Both give the same
+        bits (``gq_policy_mlp_eval``)."""
+        if impl not in ('tile', 'scalar'):
+            raise ValueError("impl must be 'tile' or 'scalar'")
+        m = self._policy_struct(policy, rollout=False)
+        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.device != self.device or rows.dim() != 2 or rows.shape[1] != policy.in_dim:
+            raise ValueError(f'rows must be a float32 tensor of shape (n, {policy.in_dim}) on {self.device}')
+        rows = rows.contiguous()
+        out = torch.empty(rows.shape[0], 12, dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._L.gq_policy_mlp_eval(self._hbatch, C.byref(m), rows.data_ptr(), int(rows.shape[0]), int(impl == 'tile'), out.data_ptr(), stream),
+                   'gq_policy_mlp_eval')
+        return out
+
     def step_pd(self, q_des, kp, kd, qd_des=None, tau_ff=None, decimation: int = 4, record_obs: bool = False, record_actions: bool = False):
         """Joint-impedance action held over a decimation window, in one launch (``gq_step_joint_cmd``): ``decimation`` physics steps
         of every env under ``tau = kp * (q_des - q) + kd * (qd_des - qd) + tau_ff``, the law evaluated at every substep from the

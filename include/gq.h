@@ -473,6 +473,59 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
  * returns GQ_EDEVICE with a message when the rollout was aborted */
 int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream);
 int gq_mailbox_get(GqBatch* b, GqMailboxView* out);
+/* A LEARNED policy in the mailbox seat of the closed-loop rollout: an MLP evaluated on the matrix cores by a resident policy kernel, the
+ * form of
+ *   for p in range(n_steps / decimation):
+ *       a = net([(obs[:, :in_obs] - obs_shift) * obs_scale, a_prev]) + noise_sigma * z;  a = clip(a, -action_clip, action_clip)
+ *       for _ in range(decimation): tau = kp * ((q_default + action_scale * a) - q) + kd * (0 - qd) + 0;  obs, ... = env.step(tau)
+ * with no launch boundary: everything of gq_rollout_closed's mailbox mode holds (per-env mailboxes, per-XCD queues, the XCD rule, a deadline
+ * on every wait, gq_rollout_closed_status; final state = that of n_steps gq_step calls with the recorded torques, bit for bit).
+ * The network: n_layers <= 4 linear layers (at most 3 hidden + the output), every width and the input width <= 256, the output width 12
+ * (hinge order of qpos[7:]), fp32 weights; hidden activation relu / elu / tanh, output activation none / tanh.  Its input row is the
+ * first in_obs columns of the env's observation row, optionally (o - shift) * scale per column (each operation rounded), followed - when
+ * feed_last_action - by the 12 values of the env's previous policy action (zeros at the first policy step of a call).
+ * A layer IS  y_o = fmaf(x_{K-1}, w_{K-1,o}, ... fmaf(x_0, w_{0,o}, b_o)),  k ascending, K padded with zeros to a multiple of 4 and the
+ * outputs to a multiple of 16: what v_mfma_f32_16x16x4_f32 computes with the bias as initial accumulator, and what a plain fmaf loop
+ * computes - gq_policy_mlp_eval runs either.  elu and tanh are built from IEEE operations and fmaf (csrc/gq_policy_mlp.h).
+ * blob (device floats), layer after layer: weights [Np / 16][Kp / 4][64] - word l of block (cb, kb) is w[k = 4 kb + (l >> 4)][o = 16 cb + (l & 15)],
+ * zero where k >= K or o >= N - then Np biases (zero behind N).  blob_floats must be the sum of Np (Kp + 1) over the layers.
+ * The torque of EVERY step is the joint-impedance law of gq_step_joint_cmd on the qpos_js / qvel_js (or qpos / qvel) columns of the
+ * observation row with q_des = q_default + action_scale * a (both rounded), a held for `decimation` steps; k, the step index within the
+ * call, selects the policy steps (k % decimation == 0), and n_steps % decimation == 0 is required: no hold state crosses calls.
+ * noise: z from words 0, 1 of the Philox4x32-10 block (joint, noise_step0 + k, global env id, 0x3b1f), key = noise_seed, Box-Muller in
+ * fp64 from IEEE operations alone (reproducible on any host); noise_sigma[j] = 0: no draw.  action_clip <= 0: no clip.
+ * An env that re-spawns ignores that step's torque (next-step auto-reset) and KEEPS its held and last action.
+ * policy_actions: device [n_steps / decimation][N][12] record of a, or NULL; act_seq records the torques.
+ * Refused with a message: a stale struct_size, more than 4 layers or widths out of range, an output width other than 12, in_obs beyond
+ * the observation row, missing joint columns, PGS, same-step auto-reset, n_steps % decimation != 0, a null blob or a wrong blob size. */
+#define GQ_ACT_NONE 0
+#define GQ_ACT_RELU 1
+#define GQ_ACT_ELU 2
+#define GQ_ACT_TANH 3
+typedef struct GqPolicyMlp {
+  int32_t struct_size;        /* sizeof(GqPolicyMlp): a stale binding is refused */
+  int32_t n_layers;           /* 1 .. 4 */
+  int32_t width[4];           /* outputs of layer l; width[n_layers - 1] = 12 */
+  int32_t in_obs;             /* leading columns of the observation row the network reads */
+  int32_t feed_last_action;   /* 1: the env's previous policy action follows them */
+  int32_t activation, out_activation;  /* GQ_ACT_* */
+  int32_t decimation;         /* physics steps per policy step, >= 1 */
+  int32_t noise_step0;
+  const float *blob;          /* device, see above */
+  int64_t blob_floats;
+  const float *obs_shift, *obs_scale;  /* device [in_obs] or NULL */
+  float *policy_actions;      /* device [n_steps / decimation][N][12] or NULL */
+  uint64_t noise_seed;
+  float kp[12], kd[12], q_default[12], action_scale[12], noise_sigma[12];
+  float action_clip;
+  int32_t pad_;
+} GqPolicyMlp;
+int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                      const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream);
+/* the network of `mlp` alone (no noise, no clip, no control law; decimation and the gains are not read) over rows: device
+ * [n_rows][in_obs + 12 feed_last_action] f32 -> out: device [n_rows][12].  impl 0: the plain fmaf loop, a thread per row; impl 1: the
+ * matrix-core form, a wavefront per 16 rows.  Both give the same bits; that is what the call is for.  Asynchronous on hip_stream. */
+int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

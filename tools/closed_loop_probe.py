@@ -1,6 +1,6 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
-usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D]
+usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R]]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
 against the loop they replace - D x (torch PD expression, env.step) - from the same state with the same per-env commands; K windows
@@ -8,7 +8,13 @@ per timing, five timings of each, alternating.  Prints env-steps/s of both, thei
 
 --foot-cmd D: foot-space actions held over a window of D physics steps (QuadrupedEnv.step_feet, one launch per window: stance forces
 -m g / 4 along world z per foot, a soft Cartesian PD on the keyframe footholds +- 2 cm per env, base frame) against the loop they replace on an
-accessors=True env - D x (feet_jacobians, feet_pos, einsums for tau_leg = J_leg^T F, env.step) - with the same commands; timed the same way."""
+accessors=True env - D x (feet_jacobians, feet_pos, einsums for tau_leg = J_leg^T F, env.step) - with the same commands; timed the same way.
+
+--mlp H1,H2,H3: an MLP policy with these hidden widths (elu, torch's default initialisation, 33 observation columns) in the closed-loop
+rollout (QuadrupedEnv.rollout_policy, a new action every D steps: --decimation, default 4) against the loop it replaces on the same
+commit - a = torch_module(obs); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
+network; one timing of the loop, then one of the rollout per entry of --policy-waves (default 64,128,256,512), R times over (--runs,
+default 3).  Prints every run of both sides."""
 import sys, time
 from pathlib import Path
 import torch
@@ -25,6 +31,17 @@ if '--foot-cmd' in sys.argv:
     i = sys.argv.index('--foot-cmd')
     FOOT_CMD = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+def _opt(name, default, conv):
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    v = conv(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    return v
+MLP = _opt('--mlp', None, lambda t: [int(h) for h in t.split(',')])
+MLP_D = _opt('--decimation', 4, int)
+MLP_WAVES = _opt('--policy-waves', [64, 128, 256, 512], lambda t: [int(w) for w in t.split(',')])
+MLP_RUNS = _opt('--runs', 3, int)
 robot = sys.argv[1] if len(sys.argv) > 1 else 'mini_cheetah'
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 500
@@ -42,6 +59,43 @@ def timed(fn, steps):
     torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return n * steps / dt / 1e6, dt / steps * 1e6
+
+if MLP:
+    from gym_quadruped_amd.policy import MlpPolicy
+    D, scale = MLP_D, 0.25
+    names = ('qpos_js', 'qvel_js', 'base_lin_vel:base', 'base_ang_vel:base', 'gravity_vector:base')   # 33 columns
+    env = QuadrupedEnv(robot, scene=scene, state_obs_names=names, num_envs=n, auto_reset='next_step', seed=1)
+    env.reset(random=True)
+    torch.manual_seed(0)
+    dims = [33] + MLP + [12]
+    mods = []
+    for a, b in zip(dims[:-1], dims[1:]):
+        mods += [torch.nn.Linear(a, b), torch.nn.ELU()]
+    module = torch.nn.Sequential(*mods[:-1]).to('cuda')
+    policy = MlpPolicy.from_torch(module)
+    q0 = env._key_qpos[7:19].float()
+    W = max(1, K // D)
+    env.rollout_policy(300 // D * D, policy, KP, KD, action_scale=scale, decimation=D)   # settle into the policy's regime
+    sd = env.state_dict(); launches = env._launches
+    def restore():
+        env.load_state_dict(sd); env._launches = launches; torch.cuda.synchronize()
+    def feature(pw):
+        env.rollout_policy(W * D, policy, KP, KD, action_scale=scale, decimation=D, policy_waves=pw)
+    def loop():
+        with torch.no_grad():
+            for w in range(W):
+                a = module(env._obs_buf)
+                env.step_pd(q0 + scale * a, KP, KD, decimation=D)
+    restore(); feature(0); restore(); loop()   # warm both paths
+    tag = f'{robot} {scene} n={n} mlp={MLP} D={D}'
+    for r in range(MLP_RUNS):
+        restore(); m, us = timed(loop, W * D)
+        print(f'{tag} run {r}: loop (torch module + step_pd)          {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+        for pw in MLP_WAVES:
+            restore(); m, us = timed(lambda: feature(pw), W * D)
+            print(f'{tag} run {r}: rollout_policy, policy waves {pw:4d}       {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
+    print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
+    sys.exit(0)
 
 if JOINT_CMD:
     D = JOINT_CMD
