@@ -144,6 +144,16 @@ class GqPolicyMlp(C.Structure):
                 ('noise_sigma', C.c_float * 12), ('action_clip', C.c_float), ('pad_', C.c_int32)]
 
 
+class GqLearn(C.Structure):
+    """gq_rollout_policy_learn's / gq_reward_eval's block: the reward weights in the order of the law's sum, and the rollout's output
+    pointers; ``struct_size`` must hold ``sizeof(GqLearn)`` (the library refuses a stale layout)."""
+    _fields_ = [('struct_size', C.c_int32), ('pad_', C.c_int32), ('w_track_lin_vel', C.c_float), ('w_track_ang_vel', C.c_float), ('w_lin_vel_z', C.c_float),
+                ('w_ang_vel_xy', C.c_float), ('w_orientation', C.c_float), ('w_base_height', C.c_float), ('w_torques', C.c_float), ('w_joint_vel', C.c_float),
+                ('w_power', C.c_float), ('w_action_rate', C.c_float), ('w_alive', C.c_float), ('w_termination', C.c_float), ('sigma_lin', C.c_float),
+                ('sigma_ang', C.c_float), ('base_height_target', C.c_float), ('pad2_', C.c_int32), ('rewards', C.c_void_p), ('dones', C.c_void_p),
+                ('policy_obs', C.c_void_p), ('policy_means', C.c_void_p)]
+
+
 class GqResampleCfg(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('cmd_reset', C.c_int32), ('dist_reset', C.c_int32), ('dist_kind', C.c_int32 * 6),
                 ('dist_range', (C.c_float * 2) * 6), ('env_id_offset', C.c_int32)]

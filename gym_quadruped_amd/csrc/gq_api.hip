@@ -22,6 +22,7 @@
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
+#include "gq_reward.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
 #include "gq_host_res.h"
@@ -37,7 +38,9 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, hipStream_t stream);
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, bool learn, hipStream_t stream);
+extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                      const uint8_t* terminated, int n, float* out, hipStream_t stream);
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
@@ -72,6 +75,9 @@ struct Mailbox {
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
   gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
+  gq::Staged<gq::LearnDev> learn;           /* gq_rollout_policy_learn's / gq_reward_eval's block */
+  Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
+  Buf<int32_t> learn_state;                 /* [N] the window's flags (gq_reward.h LEARN_*) */
   gq::Stream stream; gq::Event fork, join;
   bool ready = false;
 };
@@ -445,6 +451,10 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.mlp.create());
   HIP_TRY(t.held.ensure(12 * N, true));
   HIP_TRY(t.last.ensure(12 * N, true));
+  HIP_TRY(t.learn.create());
+  HIP_TRY(t.learn_acc.ensure(N, true));
+  HIP_TRY(t.learn_prev.ensure(12 * N, true));
+  HIP_TRY(t.learn_state.ensure(N, true));
   HIP_TRY(t.staging.ensure(1, false));
   HIP_TRY(t.alive.ensure(1, false));
   HIP_TRY(t.status_host.ensure(8, false));
@@ -625,17 +635,78 @@ static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char*
   return GQ_OK;
 }
 
-int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
-                      const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  const char* const who = "gq_rollout_policy";
+/* ---- the reward law's block (gq_reward.h) from the C block: weights checked, columns resolved by observable in this batch's row ---- */
+static bool learn_fresh(const GqLearn* learn, const char* who) {
+  if (learn->struct_size != (int32_t)sizeof(GqLearn)) { SET_ERR("%s: GqLearn.struct_size is %d, this library's struct has %d bytes: stale binding", who, learn->struct_size, (int)sizeof(GqLearn)); return false; }
+  return true;
+}
+static int obs_column(const GqBatch* b, int canonical) {
+  for (int c = 0; c < b->host.obs_dim; c++)
+    if (b->host.obs_map[c] == canonical) return c;
+  return -1;
+}
+static int reward_describe(const GqBatch* b, const GqLearn* learn, gq::RewardLaw& R, bool& on, const char* who) {
+  static const char* const names[GQ_REWARD_TERMS] = {"track_lin_vel", "track_ang_vel", "lin_vel_z", "ang_vel_xy", "orientation", "base_height", "torques", "joint_vel",
+                                                     "power", "action_rate", "alive", "termination"};
+  const float w[GQ_REWARD_TERMS] = {learn->w_track_lin_vel, learn->w_track_ang_vel, learn->w_lin_vel_z, learn->w_ang_vel_xy, learn->w_orientation, learn->w_base_height,
+                                    learn->w_torques, learn->w_joint_vel, learn->w_power, learn->w_action_rate, learn->w_alive, learn->w_termination};
+  on = false;
+  for (int i = 0; i < GQ_REWARD_TERMS; i++) {
+    if (!std::isfinite(w[i])) { SET_ERR("%s: the weight of the reward term %s is not finite", who, names[i]); return GQ_EINVAL; }
+    R.w[i] = w[i];
+    on = on || w[i] != 0.0f;
+  }
+  if (w[gq::RW_TRACK_LIN_VEL] != 0.0f && !(learn->sigma_lin > 0.0f && std::isfinite(learn->sigma_lin))) { SET_ERR("%s: sigma_lin = %g with track_lin_vel on: it must be positive", who, (double)learn->sigma_lin); return GQ_EINVAL; }
+  if (w[gq::RW_TRACK_ANG_VEL] != 0.0f && !(learn->sigma_ang > 0.0f && std::isfinite(learn->sigma_ang))) { SET_ERR("%s: sigma_ang = %g with track_ang_vel on: it must be positive", who, (double)learn->sigma_ang); return GQ_EINVAL; }
+  if (w[gq::RW_BASE_HEIGHT] != 0.0f && !std::isfinite(learn->base_height_target)) { SET_ERR("%s: base_height_target is not finite", who); return GQ_EINVAL; }
+  R.inv_sigma_lin = w[gq::RW_TRACK_LIN_VEL] != 0.0f ? 1.0f / learn->sigma_lin : 0.0f; /* IEEE divisions, here and nowhere else: gq_reward.h */
+  R.inv_sigma_ang = w[gq::RW_TRACK_ANG_VEL] != 0.0f ? 1.0f / learn->sigma_ang : 0.0f;
+  R.base_height_target = w[gq::RW_BASE_HEIGHT] != 0.0f ? learn->base_height_target : 0.0f;
+  R.dt = b->model->host.timestep;
+  R.pad_ = 0;
+  bool ok = true;
+  /* a column of an observable, or -1 when the term is off; a weighted term whose observable is absent is refused by name */
+  auto col = [&](const int term, const int canonical, const char* obs_name) {
+    if (w[term] == 0.0f) return -1;
+    const int c = obs_column(b, canonical);
+    if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads %s: not in this batch's observation row", who, names[term], obs_name); ok = false; }
+    return c;
+  };
+  R.col_lin_err[0] = col(gq::RW_TRACK_LIN_VEL, gq::OB_LIN_VEL_ERR_B + 0, "base_lin_vel_err:base"); R.col_lin_err[1] = col(gq::RW_TRACK_LIN_VEL, gq::OB_LIN_VEL_ERR_B + 1, "base_lin_vel_err:base");
+  R.col_ang_err_z = col(gq::RW_TRACK_ANG_VEL, gq::OB_ANG_VEL_ERR_B + 2, "base_ang_vel_err:base");
+  R.col_vz = col(gq::RW_LIN_VEL_Z, gq::OB_LIN_VEL_B + 2, "base_lin_vel:base");
+  R.col_wxy[0] = col(gq::RW_ANG_VEL_XY, gq::OB_ANG_VEL_B + 0, "base_ang_vel:base"); R.col_wxy[1] = col(gq::RW_ANG_VEL_XY, gq::OB_ANG_VEL_B + 1, "base_ang_vel:base");
+  R.col_gxy[0] = col(gq::RW_ORIENTATION, gq::OB_GRAV_B + 0, "gravity_vector:base"); R.col_gxy[1] = col(gq::RW_ORIENTATION, gq::OB_GRAV_B + 1, "gravity_vector:base");
+  R.col_z = col(gq::RW_BASE_HEIGHT, gq::OB_BASE_POS + 2, "base_pos");
+  const bool need_qd = gq::reward_needs_qd(R);
+  for (int j = 0; j < 12; j++) {
+    R.col_qd[j] = -1;
+    if (!need_qd) continue;
+    int c = obs_column(b, gq::OB_QVEL_JS + j);
+    if (c < 0) c = obs_column(b, gq::OB_QVEL + 6 + j);
+    if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads qvel_js (or qvel): not in this batch's observation row", who, w[gq::RW_JOINT_VEL] != 0.0f ? "joint_vel" : "power"); ok = false; }
+    R.col_qd[j] = c;
+  }
+  return ok ? GQ_OK : GQ_EINVAL;
+}
+
+static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                          const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                          void* hip_stream, const char* const who) {
   if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
-  if (!b || n_steps < 0) { SET_ERR("gq_rollout_policy: bad argument"); return GQ_EINVAL; }
-  if (mlp->in_obs > b->host.obs_dim) { SET_ERR("gq_rollout_policy: in_obs = %d, the observation row has %d columns", mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
+  if (learn && !learn_fresh(learn, who)) return GQ_EINVAL;
+  if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
   gq::PolicyMlpDev P = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
   if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
-  if (mlp->decimation < 1) { SET_ERR("gq_rollout_policy: decimation must be >= 1 (got %d)", mlp->decimation); return GQ_EINVAL; }
-  if (n_steps % mlp->decimation != 0) { SET_ERR("gq_rollout_policy: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", n_steps, mlp->decimation); return GQ_EINVAL; }
+  if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
+  if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "MLP"); rc != GQ_OK) return rc;
+  gq::LearnDev L = b->mb.learn.shadow;
+  bool reward_on = false;
+  if (learn) {
+    if (const int rc = reward_describe(b, learn, L.law, reward_on, who); rc != GQ_OK) return rc;
+  }
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceGuard guard(b->model->device);
   if (const int rc = closed_begin(b, n_steps, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
@@ -653,13 +724,55 @@ int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int polic
   P.seed_lo = (uint32_t)(mlp->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(mlp->noise_seed >> 32);
   P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
   P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
+  P.learn = learn ? mb.learn.dev.get() : nullptr;
   HIP_TRY(mb.mlp.push(P, stream, true));
   HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
+  if (learn) {
+    /* the reward is evaluated when anything of it is asked for (a spec without a weighted term is a reward of zero) */
+    L.has_reward = (learn->rewards || learn->dones) ? 1 : 0; L.pad_ = 0;
+    L.terminated = out.terminated; L.pending = b->p.pending;
+    L.acc = mb.learn_acc.get(); L.wstate = mb.learn_state.get(); L.prev = mb.learn_prev.get();
+    L.rewards = learn->rewards; L.dones = learn->dones; L.policy_obs = learn->policy_obs; L.policy_means = learn->policy_means;
+    HIP_TRY(mb.learn.push(L, stream, true));
+    HIP_TRY(hipMemsetAsync(L.acc, 0, sizeof(float) * (size_t)N, stream));
+    HIP_TRY(hipMemsetAsync(L.wstate, 0, sizeof(int32_t) * (size_t)N, stream));
+  }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, mb.stream.get());
+  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, learn != nullptr, mb.stream.get());
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
+}
+int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                      const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
+  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, hip_stream, "gq_rollout_policy");
+}
+int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                            const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                            void* hip_stream) {
+  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, hip_stream,
+                        learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
+}
+
+int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev, const uint8_t* terminated,
+                   int n, float* out, void* hip_stream) {
+  const char* const who = "gq_reward_eval";
+  if (!learn) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  if (!learn_fresh(learn, who)) return GQ_EINVAL;
+  if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  DeviceGuard guard(b->model->device);
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  gq::LearnDev L = b->mb.learn.shadow;
+  bool on = false;
+  if (const int rc = reward_describe(b, learn, L.law, on, who); rc != GQ_OK) return rc;
+  if (gq::reward_needs_u(L.law) && !torques) { SET_ERR("%s: a weighted term reads the torques: torques is null", who); return GQ_EINVAL; }
+  if (gq::reward_needs_a(L.law) && (!act || !act_prev)) { SET_ERR("%s: action_rate reads act and act_prev: null", who); return GQ_EINVAL; }
+  if (n == 0) return GQ_OK;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(b->mb.learn.push(L, stream, true));
+  gq_launch_reward_eval(b->mb.learn.dev.get(), rows, b->host.obs_dim, torques, act, act_prev, terminated, n, out, stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
 }
 
 int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream) {

@@ -11,6 +11,7 @@
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
+#include "gq_reward.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -377,7 +378,16 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * to the step side exactly as policy_pd_kernel does - same registration, same XCD rule, same deadline on every wait.  Lane = env, strided
  * as there; the lanes of a pass whose env is ready AND due for a new action are compacted by ballot into tiles of up to 16 rows, which the
  * whole wavefront stages (device-scope loads: every word of the row is another wavefront's store of this launch) and takes through the
- * layers.  An env that re-spawns ignores the torque of that step (next-step auto-reset); its held and last action are kept. */
+ * layers.  An env that re-spawns ignores the torque of that step (next-step auto-reset); its held and last action are kept.
+ * LEARN (gq_rollout_policy_learn; false compiles to the kernel as it was): the same seat also records what a learner needs, where the data
+ * passes anyway.  At a fresh policy step the row the network is fed and its output before noise and clip are recorded; at the visit for
+ * step k >= 1 - the observation after step k - 1 is out, the env waits for this wavefront - the reward of step k - 1 is evaluated
+ * (gq_reward.h) from that row, the torques of step k - 1 (still in the env's mailbox), the held action and the one before it, and the
+ * batch's `terminated` byte; every one of them a device-scope load.  Three per-env words (acc, wstate, prev: written by the env's lane
+ * alone) carry the window; at k % D == 0 the window k / D - 1 is flushed.  Every env gets ONE CLOSING VISIT at k = K, when its last
+ * observation is out: it evaluates step K - 1, flushes the last window and pushes nothing - the step side's ticket count is unchanged, and
+ * the wait for that observation is the loop's own wait, with its deadline and the abort word. */
+template <bool LEARN>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
@@ -399,12 +409,54 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
     for (int base = rank * GQ_WAVE; base < nmine; base += G) { /* wave-uniform: the tile work below needs every lane */
       const int i = base + lane;
       const int e = i < nmine ? q + nq * i : q;      /* (a lane without env reads env q's words and does nothing) */
-      const int k = i < nmine ? P.issued[e] : K;
-      const bool live = k < K;
+      constexpr int KL = LEARN ? 1 : 0;             /* LEARN: the closing visit at k = K */
+      const int k = i < nmine ? P.issued[e] : K + KL;
+      const bool live = k < K + KL;
       if (live) all_done = false;
       const bool ready = live && ld_pub(MB.steps_done + e) >= k; /* the observation after step k - 1 is out */
-      const bool fresh = ready && k % D == 0;                    /* ... and the env is due for a new action */
+      const bool fresh = ready && k % D == 0 && (!LEARN || k < K); /* ... and the env is due for a new action */
       float a[12];
+      if constexpr (LEARN) {
+        const GQ_MODEL LearnDev& L = *mptr(P.learn);
+        if (L.has_reward && ready) {
+          int ws = ld_pub(L.wstate + e);
+          float acc = ld_pub(L.acc + e);
+          if (k == 0) {
+            if (L.pending && ld_pub_u8(L.pending + e)) ws |= LEARN_RESPAWN; /* the env spends step 0 on its re-spawn */
+          } else {
+            const int term = ld_pub_u8(L.terminated + e);
+            if (!(ws & (LEARN_DEAD | LEARN_RESPAWN))) {
+              const RewardLaw R = reward_law_load(L.law);
+              const float* const row = obs + (size_t)e * od;
+              RewardIn in;
+              reward_gather_row(R, [&](const int c) { return ld_pub(row + c); }, in);
+              if (reward_needs_u(R)) {
+#pragma unroll
+                for (int j = 0; j < 12; j++) in.u[j] = ld_pub(MB.act + (size_t)e * 12 + j);
+              }
+              if (reward_needs_a(R)) {
+#pragma unroll
+                for (int j = 0; j < 12; j++) { in.a[j] = ld_pub(P.held + (size_t)e * 12 + j); in.a_prev[j] = ld_pub(L.prev + (size_t)e * 12 + j); }
+              }
+              {
+#pragma clang fp contract(off)
+                acc = acc + reward_step(R, in, term);
+              }
+              if (term) ws |= LEARN_DEAD | LEARN_DONE;
+            }
+            ws = (ws & ~LEARN_RESPAWN) | (term ? LEARN_RESPAWN : 0);
+            if (k % D == 0) { /* the window k / D - 1 is complete */
+              const size_t at = (size_t)(k / D - 1) * N + e;
+              if (L.rewards) L.rewards[at] = acc;
+              if (L.dones) L.dones[at] = (uint8_t)((ws & LEARN_DONE) != 0);
+              acc = 0.0f;
+              ws &= LEARN_RESPAWN;
+            }
+          }
+          st_pub(L.acc + e, acc);
+          st_pub(L.wstate + e, ws);
+        }
+      }
       /* (the observation words are read AFTER the count has been seen: the ballot below waits for every lane's count) */
       for (uint64_t todo = ballot(fresh); todo != 0;) {
         uint64_t tile = 0, t = todo;
@@ -418,6 +470,17 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         const int er = shfl_idx(e, src < 0 ? 0 : src);
         const float* const row = obs + (size_t)er * od;
         const float* const prev = P.last + (size_t)er * 12;
+        if constexpr (LEARN) {
+          const int kr = shfl_idx(k, src < 0 ? 0 : src);
+          float* const rec = mptr(P.learn)->policy_obs;
+          float* const rec_row = rec ? rec + ((size_t)(kr / D) * N + er) * in_dim : nullptr;
+          mlp_tile_stage(net, xt[0], [&](const int, const int c) {
+            if (src < 0 || c >= in_dim) return 0.0f;
+            const float o = ld_pub(c < in_obs ? row + c : prev + (c - in_obs));
+            if (rec_row) rec_row[c] = o; /* the row as the network is fed it, before shift / scale */
+            return c < in_obs ? mlp_obs_in(o, shift, scale, c) : o;
+          });
+        } else
         mlp_tile_stage(net, xt[0], [&](const int, const int c) {
           if (src < 0 || c >= in_dim) return 0.0f;
           if (c < in_obs) return mlp_obs_in(ld_pub(row + c), shift, scale, c);
@@ -431,6 +494,10 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           for (int j = 0; j < 12; j++) {
 #pragma clang fp contract(off)
             float v = out[j * GQ_MLP_ROWS + slot];
+            if constexpr (LEARN) {
+              const GQ_MODEL LearnDev& L = *mptr(P.learn);
+              if (L.policy_means) L.policy_means[((size_t)(k / D) * N + e) * 12 + j] = v;
+            }
             const float sg = P.sigma[j];
             if (sg > 0.0f) {
               const uint32_t x0 = philox4x32((uint32_t)j, (uint32_t)(P.step0 + k), gid, GQ_MLP_NOISE_STREAM, P.seed_lo, P.seed_hi, 0);
@@ -440,6 +507,10 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
             }
             if (P.clip > 0.0f) v = fminf(fmaxf(v, -P.clip), P.clip);
             a[j] = v;
+            if constexpr (LEARN) { /* the action before the held one; a_prev := a in the first window of a call */
+              const GQ_MODEL LearnDev& L = *mptr(P.learn);
+              if (L.has_reward) st_pub(L.prev + (size_t)e * 12 + j, k == 0 ? v : ld_pub(P.held + (size_t)e * 12 + j));
+            }
             st_pub(P.held + (size_t)e * 12 + j, v);
             if (P.feed_last) st_pub(P.last + (size_t)e * 12 + j, v);
             if (P.policy_actions) P.policy_actions[((size_t)(k / D) * N + e) * 12 + j] = v;
@@ -447,6 +518,9 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         }
       }
       if (!ready) continue;
+      if constexpr (LEARN) {
+        if (k == K) { P.issued[e] = K + 1; progress = true; continue; } /* the closing visit: nothing is pushed */
+      }
       const float* row = obs + (size_t)e * od;
       float qj[12], qd[12];
 #pragma unroll
@@ -510,6 +584,28 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const Pol
     const int r = w / 12, j = w % 12;
     if (r0 + r < n) out[(size_t)(r0 + r) * 12 + j] = y[j * GQ_MLP_ROWS + r];
   }
+}
+
+/* the reward law alone over rows [n][od] (gq_reward_eval), lane = row: what policy_mlp_eval_* is for the network - the law's bits, to be compared
+ * with the host's.  torques / act / act_prev: [n][12], read only by the terms that need them (may be NULL then); terminated: [n] or NULL. */
+__global__ void __launch_bounds__(GQ_WAVE) reward_eval_kernel(const LearnDev* __restrict__ Lp, const float* __restrict__ rows, const int od, const float* __restrict__ torques,
+                                                              const float* __restrict__ act, const float* __restrict__ act_prev, const uint8_t* __restrict__ terminated, const int n,
+                                                              float* __restrict__ out) {
+  const RewardLaw R = reward_law_load(mptr(Lp)->law);
+  const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
+  if (r >= n) return;
+  const float* const row = rows + (size_t)r * od;
+  RewardIn in;
+  reward_gather_row(R, [&](const int c) { return row[c]; }, in);
+  if (reward_needs_u(R)) {
+#pragma unroll
+    for (int j = 0; j < 12; j++) in.u[j] = torques[(size_t)r * 12 + j];
+  }
+  if (reward_needs_a(R)) {
+#pragma unroll
+    for (int j = 0; j < 12; j++) { in.a[j] = act[(size_t)r * 12 + j]; in.a_prev[j] = act_prev[(size_t)r * 12 + j]; }
+  }
+  out[r] = reward_step(R, in, terminated ? (int)terminated[r] : 0);
 }
 
 /* which XCDs does this device expose?  bit HW_REG_XCC_ID of *mask is set by every workgroup */
@@ -751,10 +847,15 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, hipStream_t stream) {
-  hipLaunchKernelGGL(gq::policy_mlp_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, bool learn, hipStream_t stream) {
+  if (learn) hipLaunchKernelGGL(gq::policy_mlp_kernel<true>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+  else hipLaunchKernelGGL(gq::policy_mlp_kernel<false>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
 }
 /* impl 0: mlp_row_forward, a thread per row; 1: mlp_tile_forward, a wavefront per 16 rows */
+extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                      const uint8_t* terminated, int n, float* out, hipStream_t stream) {
+  hipLaunchKernelGGL(gq::reward_eval_kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, n, out);
+}
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
   if (impl == 0) hipLaunchKernelGGL(gq::policy_mlp_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
   else hipLaunchKernelGGL(gq::policy_mlp_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);

@@ -296,6 +296,7 @@ __device__ __forceinline__ void mlp_tile_stage(const MlpNet& net, float* xt0, F 
 #endif /* __HIPCC__ */
 
 /* what a call of gq_rollout_policy hands to policy_mlp_kernel (device pointers), next to the MailboxDev it shares with the step side */
+struct LearnDev;
 struct PolicyMlpDev {
   MlpNet net;
   int32_t in_obs, feed_last;    /* leading observation columns fed to the net; 1: the env's last action (12) follows them */
@@ -311,5 +312,6 @@ struct PolicyMlpDev {
   float* held;                  /* [N][12] the action the env tracks until its next policy step */
   float* last;                  /* [N][12] the env's previous policy action (feed_last) */
   float* policy_actions;        /* [n_steps / decimation][N][12] record, or NULL */
+  const LearnDev* learn;        /* gq_rollout_policy_learn's block (gq_reward.h): read by policy_mlp_kernel<true> alone */
 };
 }  // namespace gq

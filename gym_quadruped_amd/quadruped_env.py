@@ -412,7 +412,7 @@ class QuadrupedEnv(AccessorsMixin):
 
     def rollout_policy(self, n_steps: int, policy, kp, kd, q_default=None, action_scale=0.25, action_clip=None, decimation: int = 4, noise_sigma=0.0,
                        record_obs: bool = False, record_actions: bool = False, policy_waves: int = 0, step_waves: int = 0, timeout_s: float = 5.0,
-                       check: bool = True):
+                       check: bool = True, reward=None, record_transitions: bool = False):
         """``n_steps`` steps of every env with an MLP policy IN the loop and no launch boundary (``gq_rollout_policy``): the device-side
         form of ::
 
@@ -435,7 +435,25 @@ class QuadrupedEnv(AccessorsMixin):
         keyframe 0); action_clip: None or a bound on ``|a|``; noise_sigma: Gaussian exploration noise on the action (counter-based draws
         keyed by the env's seed, the step and the joint).  Returns a dict: 'obs' (the last observation views), 'obs_seq'
         ``[K, N, obs_dim]`` / 'actions' ``[K, N, 12]`` (the torques) when asked for, else None, and 'policy_actions'
-        ``[K // decimation, N, 12]`` (the network's actions, when ``record_actions``).  ``check``: as in ``rollout_closed_loop``."""
+        ``[K // decimation, N, 12]`` (the network's actions, when ``record_actions``).  ``check``: as in ``rollout_closed_loop``.
+
+        THE LEARNING HALF (``gq_rollout_policy_learn``; with ``reward=None`` and ``record_transitions=False`` the call and the dict's keys
+        are the ones above).  ``reward``: a ``RewardSpec`` - the policy seat evaluates the reward of every physics step from the
+        observation row after it, the torques applied in it, the held action and the one before it and the ``terminated`` flag
+        (``csrc/gq_reward.h``), and sums it per decimation window ``s``, the form of ::
+
+            acc, done, dead = float32(0), 0, False
+            for k in range(D * s, D * s + D):
+                respawn = (k > 0 and terminated_after[k - 1]) or (k == 0 and the env was waiting for its re-spawn before the call)
+                if not dead and not respawn:
+                    acc += r_k;  if terminated_after[k]: done, dead = 1, True
+
+        a re-spawn step earns nothing, and after a termination the rest of the window earns nothing (the new episode starts at window
+        ``s + 1``); ``action_rate`` is 0 in the first window of a call.  The dict gains 'rewards' ``[K // D, N]`` float32 and 'dones'
+        ``[K // D, N]`` bool.  ``record_transitions``: the dict gains 'policy_obs' ``[K // D, N, policy.in_dim]`` - the row the network
+        was fed at each policy step, before shift / scale: the observation columns, then the fed-back action - 'policy_means'
+        ``[K // D, N, 12]`` - the network's output before noise and clip - and 'policy_actions' (as under ``record_actions``): what the old
+        log-probability of a policy-gradient step needs, at the policy's rate."""
         K, D = int(n_steps), int(decimation)
         if K < 0:
             raise ValueError('n_steps must be >= 0')
@@ -452,20 +470,73 @@ class QuadrupedEnv(AccessorsMixin):
             raise ValueError(f'action_clip must be positive or None, got {action_clip}')
         m.decimation, m.noise_seed, m.noise_step0 = D, int(self._seed or 0) & (2 ** 64 - 1), int(self._launches) & 0x7fffffff
         obs_seq, act_seq = self._window_records(K, record_obs, record_actions)
-        pol_seq = torch.empty(K // D, self.num_envs, 12, dtype=torch.float32, device=self.device) if record_actions else None
+        learning = reward is not None or record_transitions
+        f32 = dict(dtype=torch.float32, device=self.device)
+        pol_seq = torch.empty(K // D, self.num_envs, 12, **f32) if record_actions or record_transitions else None
         m.policy_actions = None if pol_seq is None else pol_seq.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        extra = {}
+        if learning:
+            from .reward import RewardSpec
+            if reward is not None and not isinstance(reward, RewardSpec):
+                raise ValueError(f'reward must be a RewardSpec, got {type(reward).__name__}')
+            g = (reward if reward is not None else RewardSpec())._struct()
+            if reward is not None:
+                extra['rewards'] = torch.zeros(K // D, self.num_envs, **f32)
+                extra['dones'] = torch.zeros(K // D, self.num_envs, dtype=torch.bool, device=self.device)
+            if record_transitions:
+                extra['policy_obs'] = torch.zeros(K // D, self.num_envs, policy.in_dim, **f32)
+                extra['policy_means'] = torch.zeros(K // D, self.num_envs, 12, **f32)
+            g.rewards, g.dones = ptr(extra.get('rewards')), ptr(extra.get('dones'))
+            g.policy_obs, g.policy_means = ptr(extra.get('policy_obs')), ptr(extra.get('policy_means'))
         self._hm_fresh = False
-        _lib.check(self._L.gq_rollout_policy(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg,
-                                             self._episode.data_ptr(), self._lift_failed.data_ptr(), None if obs_seq is None else obs_seq.data_ptr(),
-                                             None if act_seq is None else act_seq.data_ptr(), stream), 'gq_rollout_policy')
+        if learning:
+            _lib.check(self._L.gq_rollout_policy_learn(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out,
+                                                       self._auto_cfg, self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), C.byref(g),
+                                                       stream), 'gq_rollout_policy_learn')
+        else:
+            _lib.check(self._L.gq_rollout_policy(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg,
+                                                 self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), stream), 'gq_rollout_policy')
         self._launches += K
         if check:
             self.closed_loop_status()
         for sensor in self.sensors:
             for _ in range(K):
                 sensor.step()
-        return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq, 'policy_actions': pol_seq}
+        return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq, 'policy_actions': pol_seq, **extra}
+
+    def reward_eval(self, spec, rows, torques=None, actions=None, prev_actions=None, terminated=None):
+        """The reward law of ``spec`` (a ``RewardSpec``) alone over ``n`` given steps (``gq_reward_eval``): rows ``[n, obs_dim]`` in this env's
+        observation layout (e.g. ``env._obs_buf`` after a step), torques / actions / prev_actions ``[n, 12]`` (None where no weighted
+        term reads them), terminated ``[n]`` bool or uint8 (None: all False); float32 tensors on the env's device -> ``[n]`` float32.
+        The same routine, hence the same bits, as inside ``rollout_policy(reward=spec)``."""
+        from .reward import RewardSpec
+        if not isinstance(spec, RewardSpec):
+            raise ValueError(f'spec must be a RewardSpec, got {type(spec).__name__}')
+        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.device != self.device or rows.dim() != 2 or rows.shape[1] != self._obs_dim:
+            raise ValueError(f'rows must be a float32 tensor of shape (n, {self._obs_dim}) on {self.device}')
+        n = int(rows.shape[0])
+        rows = rows.contiguous()
+
+        def arg(t, name, dtype, shape):
+            if t is None:
+                return None
+            if not torch.is_tensor(t) or t.device != self.device or tuple(t.shape) != shape:
+                raise ValueError(f'{name} must be a tensor of shape {shape} on {self.device}')
+            if dtype is torch.uint8 and t.dtype == torch.bool:
+                t = t.to(torch.uint8)
+            if t.dtype != dtype:
+                raise ValueError(f'{name} must be {dtype}, got {t.dtype}')
+            return t.contiguous()
+        u, a, ap = (arg(t, nm, torch.float32, (n, 12)) for t, nm in ((torques, 'torques'), (actions, 'actions'), (prev_actions, 'prev_actions')))
+        term = arg(terminated, 'terminated', torch.uint8, (n,))
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        g = spec._struct()
+        _lib.check(self._L.gq_reward_eval(self._hbatch, C.byref(g), rows.data_ptr(), ptr(u), ptr(a), ptr(ap), ptr(term), n, out.data_ptr(), stream), 'gq_reward_eval')
+        return out
 
     def policy_eval(self, policy, rows, impl: str = 'tile'):
         """The network of ``policy`` alone over ``rows`` (``[n, policy.in_dim]`` float32 on the env's device; shift / scale applied to

@@ -526,6 +526,48 @@ int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int polic
  * [n_rows][in_obs + 12 feed_last_action] f32 -> out: device [n_rows][12].  impl 0: the plain fmaf loop, a thread per row; impl 1: the
  * matrix-core form, a wavefront per 16 rows.  Both give the same bits; that is what the call is for.  Asynchronous on hip_stream. */
 int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream);
+/* THE LEARNING HALF of gq_rollout_policy: a task reward and transition records at the POLICY's rate, produced in the policy seat where
+ * the data already passes (the step side is the same kernel, untouched).  The reward of one physics step (csrc/gq_reward.h is the
+ * definition: fp32, contraction off, IEEE operations and fmaf in a fixed order) is
+ *   r = dt * S + w_termination * terminated,   S = sum of w_i * term_i over the terms with w_i != 0, in the order of the fields, dt = the model's time step
+ *   track_lin_vel exp(-(ex^2 + ey^2) / sigma_lin)  base_lin_vel_err:base[0:2]     track_ang_vel exp(-ez^2 / sigma_ang)  base_ang_vel_err:base[2]
+ *   lin_vel_z vz^2  base_lin_vel:base[2]           ang_vel_xy wx^2 + wy^2  base_ang_vel:base[0:2]      orientation gx^2 + gy^2  gravity_vector:base[0:2]
+ *   base_height (z - base_height_target)^2  base_pos[2]      torques sum u_j^2      joint_vel sum qd_j^2  qvel_js (or qvel[6:])
+ *   power sum |u_j qd_j|      action_rate sum (a_j - a_prev_j)^2  the policy's held action and the one before it      alive 1      termination: the flag
+ * read from the env's observation row AFTER the step, the torques applied in it and the `terminated` flag after it.  A term with weight
+ * 0 is off and its observable need not be in the row.  exp is the policy header's mlp_expm1 + 1 with the argument clamped at 87; the
+ * division by sigma is a multiplication by 1.0f / sigma, computed once on the host.
+ * Window s (steps D s .. D s + D - 1 of the call, D = decimation) - rewards[s][e], dones[s][e]:
+ *   acc = 0; done = 0; dead = false
+ *   for k in the window:  respawn = (k > 0 and terminated after step k - 1) or (k == 0 and the env was waiting for its re-spawn before the call)
+ *       if not dead and not respawn:  acc += r_k (fp32, k ascending);  if terminated after step k: done = 1, dead = true
+ * a re-spawn step earns nothing, and after a termination the rest of the window earns nothing (the learner starts the new episode at
+ * window s + 1).  action_rate is 0 in the first window of a call (a_prev := a).
+ * policy_obs[s][e][0:in_dim]: the row the network was fed at policy step s, BEFORE shift / scale (in_obs observation columns, then the
+ * fed-back action); policy_means[s][e][0:12]: the network's output before noise and clip.  Each output pointer may be NULL.
+ * Refused with a message, the batch stays usable: a stale struct_size, a weighted term whose observable is not in the observation row
+ * (the message names it), sigma <= 0 with its term on, a non-finite weight, and everything gq_rollout_policy refuses. */
+typedef struct GqLearn {
+  int32_t struct_size;        /* sizeof(GqLearn): a stale binding is refused */
+  int32_t pad_;
+  float w_track_lin_vel, w_track_ang_vel, w_lin_vel_z, w_ang_vel_xy, w_orientation, w_base_height, w_torques, w_joint_vel, w_power,
+        w_action_rate, w_alive, w_termination;
+  float sigma_lin, sigma_ang, base_height_target;
+  int32_t pad2_;
+  float *rewards;             /* device [n_steps / decimation][N] f32 or NULL */
+  uint8_t *dones;             /* device [n_steps / decimation][N] u8 or NULL */
+  float *policy_obs;          /* device [n_steps / decimation][N][in_obs + 12 feed_last_action] f32 or NULL */
+  float *policy_means;        /* device [n_steps / decimation][N][12] f32 or NULL */
+} GqLearn;
+/* gq_rollout_policy with the learn block (learn = NULL: gq_rollout_policy itself) */
+int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                            const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                            void* hip_stream);
+/* the reward law alone over n given steps: rows device [n][obs_dim] (this batch's observation layout), torques / act / act_prev device
+ * [n][12] (NULL allowed where no weighted term reads them), terminated device [n] u8 or NULL (all 0) -> out device [n] f32.  The output
+ * pointers of `learn` are not read.  Asynchronous on hip_stream. */
+int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev,
+                   const uint8_t* terminated, int n, float* out, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

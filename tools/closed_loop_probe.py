@@ -1,6 +1,6 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
-usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R]]
+usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R] [--learn]]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
 against the loop they replace - D x (torch PD expression, env.step) - from the same state with the same per-env commands; K windows
@@ -14,7 +14,13 @@ accessors=True env - D x (feet_jacobians, feet_pos, einsums for tau_leg = J_leg^
 rollout (QuadrupedEnv.rollout_policy, a new action every D steps: --decimation, default 4) against the loop it replaces on the same
 commit - a = torch_module(obs); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
 network; one timing of the loop, then one of the rollout per entry of --policy-waves (default 64,128,256,512), R times over (--runs,
-default 3).  Prints every run of both sides."""
+default 3).  Prints every run of both sides.
+
+--learn (with --mlp): the learning half instead.  The observation row gets the reward's observables behind the network's 33 columns, and
+three forms are timed in turn, R times over, from the same state with the same network and exploration noise: plain rollout_policy; the
+same call with reward= (every term on) and record_transitions=True; and what that replaces - rollout_policy(record_obs=True,
+record_actions=True), the same reward terms as a torch expression over obs_seq summed per window, and policy_eval on the rows the network
+saw for the means (no termination bookkeeping: obs_seq does not carry the flags).  Policy waves: the first entry of --policy-waves."""
 import sys, time
 from pathlib import Path
 import torch
@@ -42,6 +48,9 @@ MLP = _opt('--mlp', None, lambda t: [int(h) for h in t.split(',')])
 MLP_D = _opt('--decimation', 4, int)
 MLP_WAVES = _opt('--policy-waves', [64, 128, 256, 512], lambda t: [int(w) for w in t.split(',')])
 MLP_RUNS = _opt('--runs', 3, int)
+LEARN = '--learn' in sys.argv
+if LEARN:
+    sys.argv.remove('--learn')
 robot = sys.argv[1] if len(sys.argv) > 1 else 'mini_cheetah'
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 K = int(sys.argv[3]) if len(sys.argv) > 3 else 500
@@ -64,6 +73,8 @@ if MLP:
     from gym_quadruped_amd.policy import MlpPolicy
     D, scale = MLP_D, 0.25
     names = ('qpos_js', 'qvel_js', 'base_lin_vel:base', 'base_ang_vel:base', 'gravity_vector:base')   # 33 columns
+    if LEARN:
+        names += ('base_pos', 'base_lin_vel_err:base', 'base_ang_vel_err:base')
     env = QuadrupedEnv(robot, scene=scene, state_obs_names=names, num_envs=n, auto_reset='next_step', seed=1)
     env.reset(random=True)
     torch.manual_seed(0)
@@ -86,6 +97,49 @@ if MLP:
             for w in range(W):
                 a = module(env._obs_buf)
                 env.step_pd(q0 + scale * a, KP, KD, decimation=D)
+    if LEARN:
+        from gym_quadruped_amd.reward import RewardSpec
+        wt = dict(track_lin_vel=1.0, track_ang_vel=0.5, lin_vel_z=-2.0, ang_vel_xy=-0.05, orientation=-0.2, base_height=-30.0, torques=-1e-5, joint_vel=-1e-3,
+                  power=-2e-5, action_rate=-0.01, alive=0.25)
+        spec = RewardSpec(base_height_target=0.3, **wt)
+        pw, sigma, dt = MLP_WAVES[0], 0.1, env.simulation_dt
+        row0 = env._obs_buf.clone()   # the policy's first action reads the observation row, which is no part of the checkpoint
+        def restore():
+            env.load_state_dict(sd); env._launches = launches; env._obs_buf.copy_(row0); torch.cuda.synchronize()
+        kw = dict(action_scale=scale, decimation=D, noise_sigma=sigma, policy_waves=pw)
+        def plain():
+            env.rollout_policy(W * D, policy, KP, KD, **kw)
+        def learn():
+            return env.rollout_policy(W * D, policy, KP, KD, reward=spec, record_transitions=True, **kw)
+        def replaced():
+            first = env._obs_buf[:, :33].clone()
+            r = env.rollout_policy(W * D, policy, KP, KD, record_obs=True, record_actions=True, **kw)
+            o, u, pol = r['obs_seq'], r['actions'], r['policy_actions']
+            qd, vb, wb, gv, z, el, ea = o[..., 12:24], o[..., 24:27], o[..., 27:30], o[..., 30:33], o[..., 35], o[..., 36:39], o[..., 39:42]
+            a = pol.repeat_interleave(D, dim=0)
+            ap = torch.cat([pol[:1], pol[:-1]]).repeat_interleave(D, dim=0)
+            rew = dt * (wt['track_lin_vel'] * torch.exp(-(el[..., :2] ** 2).sum(-1) / 0.25) + wt['track_ang_vel'] * torch.exp(-ea[..., 2] ** 2 / 0.25)
+                        + wt['lin_vel_z'] * vb[..., 2] ** 2 + wt['ang_vel_xy'] * (wb[..., :2] ** 2).sum(-1) + wt['orientation'] * (gv[..., :2] ** 2).sum(-1)
+                        + wt['base_height'] * (z - 0.3) ** 2 + wt['torques'] * (u ** 2).sum(-1) + wt['joint_vel'] * (qd ** 2).sum(-1)
+                        + wt['power'] * (u * qd).abs().sum(-1) + wt['action_rate'] * ((a - ap) ** 2).sum(-1) + wt['alive'])
+            rewards = rew.view(W, D, n).sum(1)
+            rows = torch.cat([first[None], o[D - 1:-1:D, :, :33]])
+            means = env.policy_eval(policy, rows.reshape(W * n, 33)).view(W, n, 12)
+            return rewards, means
+        forms = (('rollout_policy, plain', plain), ('rollout_policy, reward + record_transitions', learn), ('record_obs + torch reward + policy_eval', replaced))
+        for _, fn in forms:   # warm every path
+            restore(); fn()
+        restore(); got = learn(); restore(); want = replaced()   # the two forms agree where no env terminated inside the window
+        quiet = ~got['dones'].any(0)
+        print(f'learn vs replaced: |rewards| differ by at most {float((got["rewards"] - want[0])[:, quiet].abs().max()):.2e} over the {int(quiet.sum())} envs without a '
+              f'termination (max |reward| {float(want[0].abs().max()):.3f}); means equal: {torch.equal(got["policy_means"], want[1])}', flush=True)
+        tag = f'{robot} {scene} n={n} mlp={MLP} D={D} K={W * D} waves={pw}'
+        for r in range(MLP_RUNS):
+            for name, fn in forms:
+                restore(); m, us = timed(fn, W * D)
+                print(f'{tag} run {r}: {name:46s} {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
+        print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
+        sys.exit(0)
     restore(); feature(0); restore(); loop()   # warm both paths
     tag = f'{robot} {scene} n={n} mlp={MLP} D={D}'
     for r in range(MLP_RUNS):
