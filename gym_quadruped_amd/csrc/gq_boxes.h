@@ -299,7 +299,15 @@ __device__ inline bool box_item_scan(WaveMem& W, const GQ_MODEL GqDevModel& m, c
  * runs from (c,r+1) to (c+1,r)).  MuJoCo collides a convex geom with the prisms under its bounding box, one contact per
  * prism; here every collision item keeps ONE contact with the height field: a foot sphere its closest triangle (exact
  * point-triangle distance, centre above the surface), a link geom its deepest cloud vertex measured against the plane
- * of the triangle under that vertex - the same simplification as for the world boxes, restated in the oracle. */
+ * of the triangle under that vertex - the same simplification as for the world boxes, restated in the oracle.
+ * Which triangles speak for a sphere centre p (sphere_hf_triangle here, sphere_hfield in the oracle): one whose plane p is
+ * on or above (side >= 0), with the exact point-triangle distance (the face normal where p projects into the triangle, else
+ * the direction from the closest edge point or corner); one whose plane p is BELOW (side < 0) only where p projects into
+ * the face AND p has sunk under the surface of its own column (it is below the plane of the triangle under its (x, y)):
+ * depth along that face's normal.  For a centre ABOVE the surface a triangle it is below has no say: the straight line
+ * from the centre to such a triangle's back side crosses the surface first, so it is never the nearest feature - a steep
+ * neighbour whose plane passes above a centre in the air beside it used to report a phantom penetration of centimetres
+ * on rough terrain.  For a centre above the surface the result is the distance to the surface. */
 struct HfTri { V3 a, b, c, n; }; /* corners and unit normal (n.z > 0) */
 /* All height-field geometry is expressed relative to a reference grid corner (cb, rb) next to the robot's base, so that
  * the fp32 coordinates stay small (a foot sphere of 2-3 cm resolved against coordinates of 15 m would lose its normal to
@@ -357,8 +365,12 @@ __device__ __forceinline__ bool sphere_hf_triangle(const GQ_MODEL GqDevModel& m,
   const float side = dot(p - t.a, t.n);
   bool inside;
   const V3 q = closest_on_triangle(p, t.a, t.b, t.c, inside);
-  if (inside) { dd = side - r; nn = t.n; return true; } /* over (or under) the face: distance along its normal, whatever the sign */
-  if (side < 0.0f) return false;                        /* below the plane and outside the column: a neighbour's business */
+  if (side < 0.0f) { /* below the plane: only over the face, and only for a centre that has sunk under the surface of its own column */
+    HfTri tu;
+    if (!inside || !hf_triangle_under(m, H, ref, p.x, p.y, tu) || !(dot(p - tu.a, tu.n) < 0.0f)) return false;
+    dd = side - r; nn = t.n; return true;
+  }
+  if (inside) { dd = side - r; nn = t.n; return true; } /* over the face: distance along its normal */
   const V3 d = p - q;
   const float l2 = dot(d, d);
   if (!(l2 > 1e-12f)) return false;
@@ -400,10 +412,17 @@ __device__ inline bool hfield_item_scan(WaveMem& W, const GQ_MODEL GqDevModel& m
     const int fk = isfoot ? lane - 60 : 0;
     const V3 cl = (isfoot ? ld3(W.foot_world[fk]) : cg) - hp;
     const float rb = isfoot ? m.foot_radius[fk] : rg;
+    /* a centre beside the grid: the item may still reach over the border (the oracle looks at every vertex / the sphere's footprint), so the
+     * surface is taken at the grid point nearest to the centre - every grid point within rb of the centre is within rb of that one */
+    const float fx = cl.x * m.hf_inv_dx, fy = cl.y * m.hf_inv_dy;
+    const int kc = imin(imax((int)floorf(fx), -ref.cb), m.hf_ncol - 2 - ref.cb), kr = imin(imax((int)floorf(fy), -ref.rb), m.hf_nrow - 2 - ref.rb);
+    const float u = med3(fx - (float)kc, 0.0f, 1.0f), v = med3(fy - (float)kr, 0.0f, 1.0f);
+    const float xc = med3(cl.x, (float)kc * m.hf_dx, (float)(kc + 1) * m.hf_dx), yc = med3(cl.y, (float)kr * m.hf_dy, (float)(kr + 1) * m.hf_dy);
     HfTri t;
-    if ((isfoot || isgeom) && hf_triangle_under(m, H, ref, cl.x, cl.y, t)) {
-      const float hc = t.a.z - (t.n.x * (cl.x - t.a.x) + t.n.y * (cl.y - t.a.y)) / t.n.z;
-      needs = cl.z - rb - (hc + m.hf_maxslope * rb) < m.boxmix[cls][isfoot ? fk : 4 + lane].margin;
+    if ((isfoot || isgeom) && hf_cell_triangle(m, H, ref, kc, kr, u + v > 1.0f ? 1 : 0, t)) {
+      const float hc = t.a.z - (t.n.x * (xc - t.a.x) + t.n.y * (yc - t.a.y)) / t.n.z;
+      const float mg = m.boxmix[cls][isfoot ? fk : 4 + lane].margin, out = rb + fmaxf(mg, 0.0f) + 1e-4f;
+      needs = cl.z - rb - (hc + m.hf_maxslope * rb) < mg && fabsf(cl.x - xc) <= out && fabsf(cl.y - yc) <= out;
     }
   }
   if (lane < nlg && !needs) W.u2.c.lg_dist[lane] = 1e30f;

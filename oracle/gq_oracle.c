@@ -593,6 +593,12 @@ static int sphere_hfield(const GqModelDesc* m, const double* p, double r, double
   if (r0 < 0) r0 = 0;
   if (c1 > m->hfield_ncol - 2) c1 = m->hfield_ncol - 2;
   if (r1 > m->hfield_nrow - 2) r1 = m->hfield_nrow - 2;
+  /* has the centre sunk under the surface of its own column (below the plane of the triangle under its (x, y))?  Only then may a triangle
+   * whose plane it is below speak for it.  For a centre above the surface such a triangle has no say - the straight line to its back side
+   * crosses the surface first, so it is never the nearest feature; a steep neighbour used to report a phantom penetration there.  The
+   * kernel's rule (csrc/gq_boxes.h, above HfTri). */
+  int sunk = 0;
+  { HfTri tu; if (hf_triangle_under(m, p[0], p[1], &tu)) { const double pu[3] = {p[0] - tu.a[0], p[1] - tu.a[1], p[2] - tu.a[2]}; sunk = dot3(pu, tu.n) < 0; } }
   *dist = 1e300; n[0] = n[1] = 0; n[2] = 1;
   for (int rr = r0; rr <= r1; rr++)
     for (int cc = c0; cc <= c1; cc++)
@@ -601,9 +607,12 @@ static int sphere_hfield(const GqModelDesc* m, const double* p, double r, double
         hf_cell_triangle(m, cc, rr, up, &t);
         double pa[3] = {p[0] - t.a[0], p[1] - t.a[1], p[2] - t.a[2]}, q[3], d[3], dd, nn[3];
         const double side = dot3(pa, t.n);
-        if (closest_on_triangle(p, t.a, t.b, t.c, q)) { dd = side - r; memcpy(nn, t.n, sizeof nn); } /* over / under the face */
+        const int inside = closest_on_triangle(p, t.a, t.b, t.c, q);
+        if (side < 0) { /* below the plane: only over the face, and only for a centre that has sunk under the surface of its own column */
+          if (!inside || !sunk) continue;
+          dd = side - r; memcpy(nn, t.n, sizeof nn);
+        } else if (inside) { dd = side - r; memcpy(nn, t.n, sizeof nn); } /* over the face */
         else {
-          if (side < 0) continue; /* below the plane and outside the column: a neighbour's business */
           for (int k = 0; k < 3; k++) d[k] = p[k] - q[k];
           const double l2 = dot3(d, d);
           if (!(l2 > 1e-12)) continue;
@@ -823,6 +832,13 @@ int gqo_test_box_box(const double* ca, const double* Ra, const double* ha, const
   const int n = box_box(ca, Ra, ha, cb, Rb, hb, margin, pts);
   for (int q = 0; q < n; q++) { out[7 * q] = pts[q].dist; memcpy(out + 7 * q + 1, pts[q].pos, 24); memcpy(out + 7 * q + 4, pts[q].nrm, 24); }
   return n;
+}
+
+/* the height-field routines (tests/hfield_cases.py): closest point of the triangle and the `interior` flag; n spheres (centres p [n][3] in
+ * hfield-local coordinates, r [n], reach [n]) against the field of m: hit [n], out [n][4] = dist, normal (whatever sphere_hfield left there) */
+int gqo_test_closest_on_triangle(const double* p, const double* a, const double* b, const double* c, double* q) { return closest_on_triangle(p, a, b, c, q); }
+void gqo_test_sphere_hfield(const GqModelDesc* m, int n, const double* p, const double* r, const double* reach, int* hit, double* out) {
+  for (int i = 0; i < n; i++) hit[i] = sphere_hfield(m, p + 3 * i, r[i], reach[i], out + 4 * i, out + 4 * i + 1);
 }
 
 /* counters of the convex routine's work (tools/convex_census.py): calls, contacts, GJK iterations, EPA runs, EPA iterations; not thread-safe */

@@ -15,6 +15,9 @@
 #include "gq_pairs.h"
 #include "gq_convex.h"
 #include "newton_probe.h"
+#include "hfield_probe.h"
+#include <cstring>
+#include <vector>
 
 #define PROBE_K __global__ void __launch_bounds__(64)
 
@@ -269,6 +272,47 @@ PROBE_K k_convex(const float* vx, const float* vy, const float* vz, const float*
 extern "C" int probe_convex(const float* vx, const float* vy, const float* vz, const float* desc, float margin, int npair, int32_t* hit, float* out) {
   if (npair > 0) hipLaunchKernelGGL(k_convex, dim3(npair), dim3(64), 0, 0, vx, vy, vz, desc, margin, hit, out);
   return probe_done();
+}
+
+/* ------------------------------------------------------------------ csrc/gq_boxes.h, the height field: lane = case; the bodies and the argument
+ * layouts are in hfield_probe.h.  probe_sphere_hfield builds the model on the host from the grid's description (grid [8], raw [nrow][ncol]:
+ * device memory like every argument, copied back), uploads it with the elevations, launches once and frees both. */
+PROBE_K k_closest_on_triangle(const float* in, int n, float* out, int32_t* interior) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n) hfprobe::hfp_triangle_case(i, in, out, interior);
+}
+PROBE_K k_sphere_hfield(const GqDevModel* M, const double* base, const float* q, int n, int32_t* hit, float* out, float* under) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n) hfprobe::hfp_sphere_case(i, *gq::mptr(M), base, q, hit, out, under);
+}
+extern "C" int probe_closest_on_triangle(const float* in, int n, float* out, int32_t* interior) { PROBE_LANES(k_closest_on_triangle, n, in, n, out, interior); }
+extern "C" int probe_sphere_hfield(const double* grid, const float* raw, const double* base, const float* q, int n, int32_t* hit, float* out, float* under) {
+  double g[8];
+  hipError_t e = hipMemcpy(g, grid, sizeof g, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  const int nr = (int)g[0], nc = (int)g[1];
+  if (nr < 2 || nc < 2 || nr > 4096 || nc > 4096) return -1;
+  std::vector<float> rawh((size_t)nr * nc), heights;
+  e = hipMemcpy(rawh.data(), raw, rawh.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  static GqDevModel M; /* large: not on the stack */
+  memset(&M, 0, sizeof M);
+  hfprobe::hfp_fill(M, g, rawh.data(), heights);
+  float* dH = nullptr;
+  GqDevModel* dM = nullptr;
+  e = hipMalloc(&dH, heights.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dM, sizeof M);
+  if (e == hipSuccess) e = hipMemcpy(dH, heights.data(), heights.size() * sizeof(float), hipMemcpyHostToDevice);
+  M.hf_data = dH;
+  if (e == hipSuccess) e = hipMemcpy(dM, &M, sizeof M, hipMemcpyHostToDevice);
+  int rc = (int)e;
+  if (e == hipSuccess) {
+    if (n > 0) hipLaunchKernelGGL(k_sphere_hfield, dim3(probe_blocks(n)), dim3(64), 0, 0, dM, base, q, n, hit, out, under);
+    rc = probe_done();
+  }
+  if (dM) hipFree(dM);
+  if (dH) hipFree(dH);
+  return rc;
 }
 
 /* ------------------------------------------------------------------ csrc/gq_newton.h: the bodies and the argument layouts are in newton_probe.h */

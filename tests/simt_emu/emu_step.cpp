@@ -9,6 +9,8 @@
 #include "gq_device.h"          /* the emulator shim (this directory comes first on the include path) */
 #include "gq_step_call.h"
 #include "emu_model.h"
+#include "hfield_probe.h"
+#include <cstring>
 
 void emu_run_wave(unsigned block, unsigned nblocks, const std::function<void()>& body);
 
@@ -130,6 +132,21 @@ extern "C" int emu_box_box(const float* ca, const float* Ra, const float* ha, co
   gq::box_box(gq::v3(ca[0], ca[1], ca[2]), Ra, gq::v3(ha[0], ha[1], ha[2]), gq::v3(cb[0], cb[1], cb[2]), Rb, gq::v3(hb[0], hb[1], hb[2]), margin, H);
   for (int q = 0; q < H.n; q++) { out[7 * q] = H.dist[q]; out[7 * q + 1] = H.pos[q].x; out[7 * q + 2] = H.pos[q].y; out[7 * q + 3] = H.pos[q].z; out[7 * q + 4] = gq::hit_nrm(H, q).x; out[7 * q + 5] = gq::hit_nrm(H, q).y; out[7 * q + 6] = gq::hit_nrm(H, q).z; }
   return H.n;
+}
+/* the kernel's height-field routines (csrc/gq_boxes.h: closest_on_triangle, hf_triangle_under, sphere_hfield) called directly, one case
+ * after the other through the bodies the GPU probe launches (tests/device_probe/hfield_probe.h: argument layouts there) */
+extern "C" int emu_closest_on_triangle(const float* in, int n, float* out, int32_t* interior) {
+  for (int i = 0; i < n; i++) hfprobe::hfp_triangle_case(i, in, out, interior);
+  return 0;
+}
+extern "C" int emu_sphere_hfield(const double* grid, const float* raw, const double* base, const float* q, int n, int32_t* hit, float* out, float* under) {
+  static GqDevModel M;
+  std::vector<float> heights;
+  memset(&M, 0, sizeof M);
+  hfprobe::hfp_fill(M, grid, raw, heights);
+  M.hf_data = heights.data();
+  for (int i = 0; i < n; i++) hfprobe::hfp_sphere_case(i, M, base, q, hit, out, under);
+  return 0;
 }
 /* the kernel's convex routine (csrc/gq_convex.h: GJK + EPA, one wavefront per pair) called directly on two shapes - vertex clouds (h = NULL)
  * or analytic boxes (V = NULL) - for a side-by-side with the oracle's restatement: out = dist, pos[3], nrm[3] */

@@ -12,6 +12,7 @@ import pytest
 
 import contact_cases as cc
 import device_cases as dc
+import hfield_cases as hc
 import newton_cases as nc
 from helpers import ROOT, probe_lib
 from newton_first_step import REPORT_KEY
@@ -76,3 +77,9 @@ def test_convex_routine_on_device_equals_oracle(be, report, robot):
     worst = cc.check_convex(cases, cc.probe_convex(be, cases))
     _note(report, [f'cvx_pair_wave {str(robot):<14s} cases {len(cases):>7d}   max error vs fp64 oracle: ' +
                    ', '.join(f'{k} {v[0]:.3g} (trial {v[1]}, tolerance {cc.CVX_TOL[k]:g})' for k, v in worst.items())])
+
+
+def test_height_field_routines_on_device_equal_oracle(be):
+    """closest_on_triangle, hf_triangle_under and sphere_hfield, one case per lane, the emulated test's tables (tests/hfield_cases.py): same
+    tolerances and coverage; the worst errors go to profiles/hfield_cases_report.txt"""
+    hc.run_backend(be, 'gpu')

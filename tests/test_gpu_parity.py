@@ -545,6 +545,95 @@ def test_heightmap_rays_hit_world_boxes():
     assert nhit > 0
 
 
+def _env_on_grid(monkeypatch, robot, name, n, **kw):
+    """QuadrupedEnv takes scene names only: the grid of tests/hfield_cases.py goes in through generate_terrain"""
+    import gym_quadruped_amd.quadruped_env as qe
+    import hfield_cases as hc
+    monkeypatch.setattr(qe, 'generate_terrain', lambda scene, hip, seed=10: hc.scene(name))
+    env = qe.QuadrupedEnv(robot, scene='perlin', num_envs=n, solver='newton', **kw)
+    assert env.scene_desc['hfield'] is hc.grid(name)
+    return env
+
+
+@pytest.mark.parametrize('rows,cols', [(9, 9), (6, 4)])   # 81 cells: the strided cell loop and its cells - 1 mirror lanes; both dimensions even
+def test_heightmap_and_rays_on_a_non_square_height_field(monkeypatch, rows, cols):
+    """HeightMap and gq_ray (mj_ray) on the mild_coarse grid of tests/hfield_cases.py - cells of 0.11 x 0.07 m, 41 x 57 samples, 40 m from the
+    origin - against the numpy surface (triangle interpolation with the same diagonal): hit heights to 1e-4, the grid layout to the tolerance
+    of test_sensors_imu_and_heightmap_on_gpu; map centres and rays over the grid, beside and beyond its border (there: the floor)."""
+    import hfield_cases as hc
+    from gym_quadruped_amd.sensors import HeightMap
+    n = 32
+    env = _env_on_grid(monkeypatch, 'aliengo', 'mild_coarse', n, state_obs_names=('qpos',), seed=5)
+    hf = hc.grid('mild_coarse')
+    pos, sx, sy = np.asarray(hf['pos']), hf['size'][0], hf['size'][1]
+    rng = np.random.default_rng(8)
+
+    def top(x, y):
+        h, _, inside, _ = hc.surface(hf, x - pos[0], y - pos[1])
+        near = np.minimum(np.abs(np.abs(x - pos[0]) - sx), np.abs(np.abs(y - pos[1]) - sy)) < 1e-5   # on the border line: either answer
+        return np.where(inside, np.maximum(pos[2] + h, 0.0), 0.0), near
+    dx_, dy_ = 0.045, 0.06
+    c = np.stack([pos[0] + rng.uniform(-sx - 0.3, sx + 0.3, n), pos[1] + rng.uniform(-sy - 0.3, sy + 0.3, n), rng.uniform(0.5, 0.9, n)], 1)
+    c[:8, 0] = pos[0] + np.where(np.arange(8) % 2 == 0, -sx, sx) + rng.uniform(-0.1, 0.1, 8)   # maps that straddle the border
+    yaw = rng.uniform(-np.pi, np.pi, n).astype(np.float32)
+    hm = HeightMap(num_rows=rows, num_cols=cols, dist_x=dx_, dist_y=dy_, mj_model=env.mjModel, mj_data=env)
+    d = hm.update_height_map(torch.as_tensor(c, device='cuda:0'), yaw=torch.as_tensor(yaw, device='cuda:0')).cpu().numpy()[:, :, :, 0, :]
+    assert d.shape == (n, rows, cols, 3)
+    ii, jj = np.meshgrid(np.arange(rows), np.arange(cols), indexing='ij')
+    gx, gy = dx_ * ((rows - 1) / 2 - ii), dy_ * ((cols - 1) / 2 - jj)
+    non, noff = 0, 0
+    for e in range(n):
+        cy, sn = np.cos(yaw[e]), np.sin(yaw[e])
+        px, py = c[e, 0] + cy * gx - sn * gy, c[e, 1] + sn * gx + cy * gy
+        assert np.abs(d[e, :, :, 0] - px).max() < 1e-4 + 1e-7 * np.abs(c[e, :2]).max() and np.abs(d[e, :, :, 1] - py).max() < 1e-4 + 1e-7 * np.abs(c[e, :2]).max()
+        ref, near = top(d[e, :, :, 0].astype(np.float64), d[e, :, :, 1].astype(np.float64))
+        assert (np.abs(d[e, :, :, 2] - ref)[~near] < 1e-4).all(), (e, np.abs(d[e, :, :, 2] - ref).max())
+        non += int((ref > 0).sum()); noff += int((ref == 0).sum())
+    assert non > 10 * rows and noff > 10 * rows, (non, noff)
+    # gq_ray: vertical rays from above, over the grid and around it
+    R = 64
+    o = np.stack([pos[0] + rng.uniform(-sx - 0.2, sx + 0.2, (n, R)), pos[1] + rng.uniform(-sy - 0.2, sy + 0.2, (n, R)), np.full((n, R), 2.0)], -1)
+    o[:, :8, 1] = pos[1] + np.where(np.arange(8) % 2 == 0, -sy, sy) + rng.uniform(-0.01, 0.01, (n, 8))
+    vec = np.tile(np.array([0.0, 0.0, -1.0], np.float32), (n, R, 1))
+    dist = env.mj_ray(o, vec).cpu().numpy()
+    ref, near = top(o[..., 0], o[..., 1])
+    assert (np.abs((2.0 - dist) - ref)[~near] < 1e-4).all(), np.abs((2.0 - dist) - ref)[~near].max()
+    assert (ref > 0).sum() > 100 and (ref == 0).sum() > 100
+
+
+@pytest.mark.parametrize('name', ['mild_coarse', 'rough_coarse', 'mild_fine', 'rough_fine'])
+@pytest.mark.parametrize('robot', ['aliengo', 'hyqreal1'])   # primitive geoms, pyramidal cones / hulls, elliptic cones
+def test_height_field_step_on_rough_fine_grids_matches_oracle(monkeypatch, robot, name):
+    """The emulated test of the same name on the device, 64 envs per grid: hfield_item_scan under the STRICT row rule on rough and mild, coarse
+    and fine, non-square grids away from the origin, a quarter of the robots at the border.
+    The states keep every foot at least 0.01 m from the ridge it touches (hfield_cases.min_lever: closer, an fp32 normal cannot hold efc_J)."""
+    import hfield_cases as hc
+    from oracle.oracle import Oracle
+    n = 64
+    env = _env_on_grid(monkeypatch, robot, name, n, state_obs_names=tuple(ALL_OBS), seed=3)
+    hf = hc.grid(name)
+    mmN = marshalled(robot, solver=1, iterations=100, tolerance=1e-13, hfield=hf, terrain_limits=env.terrain_limits)
+    hc.assert_foot_form(mmN, hf, name, robot)
+    rng = np.random.default_rng(32)
+    o = Oracle(mmN)
+    qpos, qvel = hc.step_states(mmN, robot, name, n, rng, o)
+    warm = rng.normal(0, 3, (n, 18)).astype(np.float32)
+    ctrl = (rng.normal(0, 1, (n, 12)) * 20).astype(np.float32)
+    env._qpos.copy_(torch.as_tensor(qpos)); env._qvel.copy_(torch.as_tensor(qvel)); env._warm.copy_(torch.as_tensor(warm))
+    env._cmd.zero_(); env._friction.fill_(0.8)
+    env.enable_debug(n)
+    env.step(torch.as_tensor(ctrl))
+    kern = gpu_records(env, n, ['qacc', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
+    tally = ParityTally(env.mjModel.cone == 1, 3e-6)
+    tot = np.zeros(3, int)
+    for e in range(n):
+        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8), ctrl[e], kern[e], sp.TERRAIN_NEWTON_STEP, mass=float(env.mjModel.total_mass)) == 'ok':
+            tot += hc.count_contacts(o, mmN, hf)
+    sp.tally_note(f'gpu {name} {robot}: height-field contacts {tot[0]} over {tally.checked} compared envs, {tot[1]} foot contacts on an edge or corner, {tot[2]} link-geom contacts')
+    tally.finish_count(f'gpu {name} {robot}', n // 2)
+    assert tot[0] >= 4 * tally.checked and tot[2] >= 1 and (tot[1] >= 1 or 'rough' not in name), tot
+
+
 @pytest.mark.parametrize('robot,scene', [('hyqreal1', 'random_boxes'), ('aliengo', 'perlin'), ('aliengo', 'random_boxes')])
 def test_heightmap_following_the_base_equals_the_ray_kernel(robot, scene):
     """HeightMap(follow_base=True): the step kernel casts the rays of the map centred on the new base position with the new heading

@@ -402,6 +402,35 @@ def test_perlin_height_field_step_matches_oracle(robot):
     assert nhf_con >= 8, nhf_con
 
 
+@pytest.mark.parametrize('name', ['mild_coarse', 'rough_coarse', 'mild_fine', 'rough_fine'])
+@pytest.mark.parametrize('robot', ['aliengo', 'hyqreal1'])   # primitive geoms, pyramidal cones / hulls, elliptic cones
+def test_height_field_step_on_rough_fine_grids_matches_oracle(robot, name):
+    """hfield_item_scan - the phase-A cull with hf_maxslope of non-square cells, the flattened and serial cloud passes, the 2 x 2 parallel foot
+    form (coarse grids) and the serial one (fine grids), the grid's border, a grid far from the origin - on the grids of tests/hfield_cases.py
+    under the STRICT row rule: an env whose row count differs from the oracle's without a tie or the budget explaining it fails the test."""
+    import hfield_cases as hc
+    hf = hc.grid(name)
+    kw = dict(solver=1, iterations=100, hfield=hf, terrain_limits=hc.limits(hf, 0.0))
+    mm = marshalled(robot, tolerance=1e-8, noise_floor=1e-5, **kw)
+    mmN = marshalled(robot, tolerance=1e-13, **kw)
+    hc.assert_foot_form(mm, hf, name, robot)
+    rng = np.random.default_rng(31)
+    n = 12
+    o = Oracle(mmN)
+    qpos, qvel = hc.step_states(mm, robot, name, n, rng, o)
+    warm = rng.normal(0, 3, (n, 18)).astype(np.float32)
+    ctrl = (rng.normal(0, 1, (n, 12)) * 20).astype(np.float32)
+    st = emu_step(mm, ctrl, qpos.copy(), qvel.copy(), warm=warm.copy(), debug_envs=n)
+    tally = ParityTally(mm.md.cone == 1, 3e-6)
+    tot = np.zeros(3, int)
+    for e in range(n):
+        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18)), ctrl[e], emu_record(st, e), sp.TERRAIN_NEWTON_STEP, mass=mm.md.total_mass) == 'ok':
+            tot += hc.count_contacts(o, mm, hf)
+    sp.tally_note(f'emulated {name} {robot}: height-field contacts {tot[0]} over {tally.checked} compared envs, {tot[1]} foot contacts on an edge or corner, {tot[2]} link-geom contacts')
+    tally.finish_count(f'emulated {name} {robot}', n // 2)
+    assert tot[0] >= 4 * tally.checked and tot[2] >= 1 and (tot[1] >= 1 or 'rough' not in name), tot
+
+
 def test_flat_height_field_equals_raised_floor_in_the_kernel():
     H = 1.37
     flat = dict(data=np.zeros((17, 17), np.float32), size=(8.0, 8.0, 1.0, 0.01), pos=(0.0, 0.0, H))
@@ -619,6 +648,18 @@ def test_pair_routines_kernel_equals_oracle():
     import contact_cases as cc
     cases = cc.pair_cases()
     cc.check_pairs(cases, cc.emu_pairs(cases))
+
+
+def test_height_field_routines_kernel_equals_oracle():
+    """csrc/gq_boxes.h's closest_on_triangle, hf_triangle_under and sphere_hfield (fp32, called directly under the emulator with a GqDevModel
+    filled as csrc/gq_host_model.cpp fills it) against the oracle's restatement on the four grids of tests/hfield_cases.py - rough and mild,
+    coarse and fine, non-square cells, away from the origin, queries beside and beyond the border: presence, distance and normal to
+    contact_cases.PAIR_TOL, ties settled among the truth's candidates.  The oracle's routines are pinned against brute force in
+    tests/test_oracle_invariants.py.  Cases and asserts: tests/hfield_cases.py, shared with the GPU probe."""
+    import device_cases as dc
+    import hfield_cases as hc
+    from helpers import emu_lib
+    hc.run_backend(dc.Backend(emu_lib(), 'emu_'), 'emulator')
 
 
 @pytest.mark.parametrize('robot', [None, 'mini_cheetah', 'hyqreal1', 'go1'])
