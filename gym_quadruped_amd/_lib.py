@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-from .cabi import GQ_ABI_VERSION, GqCamLayers, GqCamShade, GqFootCmd, GqImuCfg, GqJointCmd, GqLearn, GqMailboxView, GqModelDesc, GqObsOut, GqPolicyMlp, GqPolicyPd, GqResampleCfg, GqResetCfg, GqState
+from .cabi import GQ_ABI_VERSION, GqCamLayers, GqCamShade, GqFootCmd, GqFootReward, GqImuCfg, GqJointCmd, GqLearn, GqMailboxView, GqModelDesc, GqObsOut, GqPolicyMlp, GqPolicyPd, GqResampleCfg, GqResetCfg, GqState
 
 _LIB = None
 import os
@@ -14,7 +14,7 @@ import os
 LIB_PATH = Path(os.environ.get('GQ_LIBGQ_PATH', Path(__file__).parent / 'libgq.so'))
 
 EXPORTS = ['gq_last_error', 'gq_version', 'gq_struct_sizes', 'gq_obs_dim', 'gq_model_create', 'gq_model_destroy', 'gq_batch_create',
-           'gq_batch_destroy', 'gq_batch_obs_dim', 'gq_batch_set_imu', 'gq_batch_set_heightmap', 'gq_batch_set_pair_exchange', 'gq_batch_set_pending', 'gq_batch_set_resampling', 'gq_heightmap', 'gq_heightmap_strided', 'gq_step_range', 'gq_batch_bind', 'gq_rollout', 'gq_rollout_closed', 'gq_rollout_closed_status', 'gq_mailbox_get', 'gq_rollout_policy', 'gq_policy_mlp_eval', 'gq_rollout_policy_learn', 'gq_reward_eval', 'gq_step_joint_cmd', 'gq_step_foot_cmd', 'gq_jac', 'gq_ray', 'gq_camera', 'gq_camera_shaded', 'gq_camera_layered', 'gq_forward', 'gq_full_mass', 'gq_batch_set_outputs', 'gq_contact_force', 'gq_step', 'gq_reset', 'gq_debug_enable', 'gq_debug_get', 'gq_debug_device_buffer', 'gq_debug_field', 'gq_debug_stop_stage']
+           'gq_batch_destroy', 'gq_batch_obs_dim', 'gq_batch_set_imu', 'gq_batch_set_heightmap', 'gq_batch_set_pair_exchange', 'gq_batch_set_pending', 'gq_batch_set_resampling', 'gq_heightmap', 'gq_heightmap_strided', 'gq_step_range', 'gq_batch_bind', 'gq_rollout', 'gq_rollout_closed', 'gq_rollout_closed_status', 'gq_mailbox_get', 'gq_rollout_policy', 'gq_policy_mlp_eval', 'gq_rollout_policy_learn', 'gq_reward_eval', 'gq_rollout_policy_learn_feet', 'gq_reward_eval_feet', 'gq_step_joint_cmd', 'gq_step_foot_cmd', 'gq_jac', 'gq_ray', 'gq_camera', 'gq_camera_shaded', 'gq_camera_layered', 'gq_forward', 'gq_full_mass', 'gq_batch_set_outputs', 'gq_contact_force', 'gq_step', 'gq_reset', 'gq_debug_enable', 'gq_debug_get', 'gq_debug_device_buffer', 'gq_debug_field', 'gq_debug_stop_stage']
 
 
 class GqError(RuntimeError):
@@ -64,6 +64,9 @@ def lib():
     L.gq_rollout_policy_learn.argtypes = [C.c_void_p, C.c_int, C.POINTER(GqPolicyMlp), C.c_int, C.c_int, C.c_double, GqState, GqObsOut, C.POINTER(GqResetCfg), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GqLearn), C.c_void_p]
     L.gq_reward_eval.argtypes = [C.c_void_p, C.POINTER(GqLearn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gq_rollout_policy_learn_feet.argtypes = L.gq_rollout_policy_learn.argtypes[:-1] + [C.POINTER(GqFootReward), C.c_void_p]
+    L.gq_reward_eval_feet.argtypes = [C.c_void_p, C.POINTER(GqLearn), C.POINTER(GqFootReward), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gq_step_joint_cmd.argtypes = [C.c_void_p, C.POINTER(GqJointCmd), C.c_int, GqState, GqObsOut, C.POINTER(GqResetCfg), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     L.gq_step_foot_cmd.argtypes = [C.c_void_p, C.POINTER(GqFootCmd), C.c_int, GqState, GqObsOut, C.POINTER(GqResetCfg), C.c_void_p, C.c_void_p, C.c_void_p,

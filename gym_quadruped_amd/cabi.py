@@ -154,6 +154,14 @@ class GqLearn(C.Structure):
                 ('policy_obs', C.c_void_p), ('policy_means', C.c_void_p)]
 
 
+class GqFootReward(C.Structure):
+    """gq_rollout_policy_learn_feet's / gq_reward_eval_feet's block: the foot terms' weights in the order they continue the law's sum, their
+    parameters and the air-time state (device ``[N][4]`` float32, in / out); ``struct_size`` must hold ``sizeof(GqFootReward)``."""
+    _fields_ = [('struct_size', C.c_int32), ('pad_', C.c_int32), ('w_air_time', C.c_float), ('w_slip', C.c_float), ('w_impact', C.c_float),
+                ('w_clearance', C.c_float), ('air_time_target', C.c_float), ('min_cmd_speed', C.c_float), ('impact_limit', C.c_float),
+                ('clearance_target', C.c_float), ('air_time', C.c_void_p)]
+
+
 class GqResampleCfg(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('cmd_reset', C.c_int32), ('dist_reset', C.c_int32), ('dist_kind', C.c_int32 * 6),
                 ('dist_range', (C.c_float * 2) * 6), ('env_id_offset', C.c_int32)]

@@ -23,6 +23,7 @@
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
 #include "gq_reward.h"
+#include "gq_reward_feet.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
 #include "gq_host_res.h"
@@ -38,7 +39,9 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, bool learn, hipStream_t stream);
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream);
+extern "C" void gq_launch_reward_eval_feet(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                           const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, hipStream_t stream);
 extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
                                       const uint8_t* terminated, int n, float* out, hipStream_t stream);
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
@@ -75,7 +78,7 @@ struct Mailbox {
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
   gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
-  gq::Staged<gq::LearnDev> learn;           /* gq_rollout_policy_learn's / gq_reward_eval's block */
+  gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
   Buf<int32_t> learn_state;                 /* [N] the window's flags (gq_reward.h LEARN_*) */
   gq::Stream stream; gq::Event fork, join;
@@ -690,11 +693,57 @@ static int reward_describe(const GqBatch* b, const GqLearn* learn, gq::RewardLaw
   return ok ? GQ_OK : GQ_EINVAL;
 }
 
+/* ---- the foot terms' block (gq_reward_feet.h) from the C block: parameters checked, columns resolved per CANONICAL foot (obs_map holds the
+ * canonical index of every column, so legs_order is already undone) ---- */
+static bool feet_fresh(const GqFootReward* feet, const char* who) {
+  if (feet->struct_size != (int32_t)sizeof(GqFootReward)) { SET_ERR("%s: GqFootReward.struct_size is %d, this library's struct has %d bytes: stale binding", who, feet->struct_size, (int)sizeof(GqFootReward)); return false; }
+  return true;
+}
+static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw& F, const char* who) {
+  static const char* const names[GQ_FOOT_TERMS] = {"air_time", "slip", "impact", "clearance"};
+  const float w[GQ_FOOT_TERMS] = {feet->w_air_time, feet->w_slip, feet->w_impact, feet->w_clearance};
+  for (int i = 0; i < GQ_FOOT_TERMS; i++) {
+    if (!std::isfinite(w[i])) { SET_ERR("%s: the weight of the reward term %s is not finite", who, names[i]); return GQ_EINVAL; }
+    F.w[i] = w[i];
+  }
+  if (w[gq::FW_AIR_TIME] != 0.0f && !std::isfinite(feet->air_time_target)) { SET_ERR("%s: air_time_target is not finite with air_time on", who); return GQ_EINVAL; }
+  if (!(feet->min_cmd_speed >= 0.0f && std::isfinite(feet->min_cmd_speed))) { SET_ERR("%s: min_cmd_speed = %g: it must be finite and >= 0", who, (double)feet->min_cmd_speed); return GQ_EINVAL; }
+  if (w[gq::FW_IMPACT] != 0.0f && !(feet->impact_limit > 0.0f && std::isfinite(feet->impact_limit))) { SET_ERR("%s: impact_limit = %g with impact on: it must be positive and finite", who, (double)feet->impact_limit); return GQ_EINVAL; }
+  if (w[gq::FW_CLEARANCE] != 0.0f && !std::isfinite(feet->clearance_target)) { SET_ERR("%s: clearance_target is not finite with clearance on", who); return GQ_EINVAL; }
+  F.air_time_target = w[gq::FW_AIR_TIME] != 0.0f ? feet->air_time_target : 0.0f;
+  F.min_cmd_speed2 = w[gq::FW_AIR_TIME] != 0.0f ? feet->min_cmd_speed * feet->min_cmd_speed : 0.0f; /* squared once, here */
+  F.impact_limit = w[gq::FW_IMPACT] != 0.0f ? feet->impact_limit : 0.0f;
+  F.clearance_target = w[gq::FW_CLEARANCE] != 0.0f ? feet->clearance_target : 0.0f;
+  bool ok = true;
+  auto col = [&](const bool needed, const int term, const int canonical, const char* obs_name) {
+    if (!needed) return -1;
+    const int c = obs_column(b, canonical);
+    if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads %s: not in this batch's observation row", who, names[term], obs_name); ok = false; }
+    return c;
+  };
+  const bool air = w[gq::FW_AIR_TIME] != 0.0f, slip = w[gq::FW_SLIP] != 0.0f, impact = w[gq::FW_IMPACT] != 0.0f, clear = w[gq::FW_CLEARANCE] != 0.0f;
+  const bool gate = gq::foot_needs_cmd(F);
+  for (int i = 0; i < 4; i++) {
+    F.col_c[i] = col(air || slip, air ? gq::FW_AIR_TIME : gq::FW_SLIP, gq::OB_CONTACT_STATE + i, "contact_state");
+    F.col_vx[i] = col(slip || clear, slip ? gq::FW_SLIP : gq::FW_CLEARANCE, gq::OB_FEET_VEL + 3 * i + 0, "feet_vel");
+    F.col_vy[i] = col(slip || clear, slip ? gq::FW_SLIP : gq::FW_CLEARANCE, gq::OB_FEET_VEL + 3 * i + 1, "feet_vel");
+    F.col_fz[i] = col(impact, gq::FW_IMPACT, gq::OB_CONTACT_F + 3 * i + 2, "contact_forces");
+    F.col_zb[i] = col(clear, gq::FW_CLEARANCE, gq::OB_FEET_POS_B + 3 * i + 2, "feet_pos:base");
+  }
+  for (int k = 0; k < 2; k++) {
+    F.col_cmd_err[k] = col(gate, gq::FW_AIR_TIME, gq::OB_LIN_VEL_ERR_B + k, "base_lin_vel_err:base");
+    F.col_cmd_vel[k] = col(gate, gq::FW_AIR_TIME, gq::OB_LIN_VEL_B + k, "base_lin_vel:base");
+  }
+  return ok ? GQ_OK : GQ_EINVAL;
+}
+
 static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
-                          void* hip_stream, const char* const who) {
+                          const GqFootReward* feet, void* hip_stream, const char* const who) {
+  if (feet && !feet_fresh(feet, who)) return GQ_EINVAL;
   if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
   if (learn && !learn_fresh(learn, who)) return GQ_EINVAL;
+  if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
   gq::PolicyMlpDev P = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
@@ -702,10 +751,18 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "MLP"); rc != GQ_OK) return rc;
-  gq::LearnDev L = b->mb.learn.shadow;
+  gq::LearnFeetDev LF = b->mb.learn.shadow;
+  gq::LearnDev& L = LF.learn;
   bool reward_on = false;
   if (learn) {
     if (const int rc = reward_describe(b, learn, L.law, reward_on, who); rc != GQ_OK) return rc;
+  }
+  bool feet_on = false;
+  if (feet) {
+    if (const int rc = foot_describe(b, feet, LF.feet, who); rc != GQ_OK) return rc;
+    feet_on = gq::foot_on(LF.feet) && (learn->rewards || learn->dones); /* without a weighted foot term, or with no reward asked for, the call is gq_rollout_policy_learn's */
+    if (LF.feet.w[gq::FW_AIR_TIME] != 0.0f && !feet->air_time) { SET_ERR("%s: air_time is on and GqFootReward.air_time (the state, device [N][4]) is null", who); return GQ_EINVAL; }
+    LF.air_time = feet->air_time;
   }
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceGuard guard(b->model->device);
@@ -724,7 +781,7 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   P.seed_lo = (uint32_t)(mlp->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(mlp->noise_seed >> 32);
   P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
   P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
-  P.learn = learn ? mb.learn.dev.get() : nullptr;
+  P.learn = learn ? &mb.learn.dev.get()->learn : nullptr;
   HIP_TRY(mb.mlp.push(P, stream, true));
   HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
   if (learn) {
@@ -733,25 +790,32 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
     L.terminated = out.terminated; L.pending = b->p.pending;
     L.acc = mb.learn_acc.get(); L.wstate = mb.learn_state.get(); L.prev = mb.learn_prev.get();
     L.rewards = learn->rewards; L.dones = learn->dones; L.policy_obs = learn->policy_obs; L.policy_means = learn->policy_means;
-    HIP_TRY(mb.learn.push(L, stream, true));
+    HIP_TRY(mb.learn.push(LF, stream, true));
     HIP_TRY(hipMemsetAsync(L.acc, 0, sizeof(float) * (size_t)N, stream));
     HIP_TRY(hipMemsetAsync(L.wstate, 0, sizeof(int32_t) * (size_t)N, stream));
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, learn != nullptr, mb.stream.get());
+  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
 }
 int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, hip_stream, "gq_rollout_policy");
+  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
 }
 int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                             const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                             void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, hip_stream,
+  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
                         learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
+}
+int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                                 const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                                 const GqFootReward* feet, void* hip_stream) {
+  const char* const who = "gq_rollout_policy_learn_feet";
+  if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
 int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev, const uint8_t* terminated,
@@ -762,15 +826,39 @@ int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const fl
   if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
-  gq::LearnDev L = b->mb.learn.shadow;
+  gq::LearnFeetDev LF = b->mb.learn.shadow;
+  gq::LearnDev& L = LF.learn;
   bool on = false;
   if (const int rc = reward_describe(b, learn, L.law, on, who); rc != GQ_OK) return rc;
   if (gq::reward_needs_u(L.law) && !torques) { SET_ERR("%s: a weighted term reads the torques: torques is null", who); return GQ_EINVAL; }
   if (gq::reward_needs_a(L.law) && (!act || !act_prev)) { SET_ERR("%s: action_rate reads act and act_prev: null", who); return GQ_EINVAL; }
   if (n == 0) return GQ_OK;
   hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(b->mb.learn.push(L, stream, true));
-  gq_launch_reward_eval(b->mb.learn.dev.get(), rows, b->host.obs_dim, torques, act, act_prev, terminated, n, out, stream);
+  HIP_TRY(b->mb.learn.push(LF, stream, true));
+  gq_launch_reward_eval(&b->mb.learn.dev.get()->learn, rows, b->host.obs_dim, torques, act, act_prev, terminated, n, out, stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act, const float* act_prev,
+                        const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream) {
+  const char* const who = "gq_reward_eval_feet";
+  if (!learn || !feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  if (!feet_fresh(feet, who) || !learn_fresh(learn, who)) return GQ_EINVAL;
+  if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  DeviceGuard guard(b->model->device);
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  gq::LearnFeetDev LF = b->mb.learn.shadow;
+  bool on = false;
+  if (const int rc = reward_describe(b, learn, LF.learn.law, on, who); rc != GQ_OK) return rc;
+  if (const int rc = foot_describe(b, feet, LF.feet, who); rc != GQ_OK) return rc;
+  if (gq::reward_needs_u(LF.learn.law) && !torques) { SET_ERR("%s: a weighted term reads the torques: torques is null", who); return GQ_EINVAL; }
+  if (gq::reward_needs_a(LF.learn.law) && (!act || !act_prev)) { SET_ERR("%s: action_rate reads act and act_prev: null", who); return GQ_EINVAL; }
+  if (LF.feet.w[gq::FW_AIR_TIME] != 0.0f && (!air_in || !air_out)) { SET_ERR("%s: air_time is on: air_in and air_out (the state before and after, device [n][4]) must not be null", who); return GQ_EINVAL; }
+  if (n == 0) return GQ_OK;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(b->mb.learn.push(LF, stream, true));
+  gq_launch_reward_eval_feet(b->mb.learn.dev.get(), rows, b->host.obs_dim, torques, act, act_prev, terminated, air_in, n, out, air_out, stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

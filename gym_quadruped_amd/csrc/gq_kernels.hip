@@ -12,6 +12,7 @@
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
 #include "gq_reward.h"
+#include "gq_reward_feet.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -386,9 +387,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * batch's `terminated` byte; every one of them a device-scope load.  Three per-env words (acc, wstate, prev: written by the env's lane
  * alone) carry the window; at k % D == 0 the window k / D - 1 is flushed.  Every env gets ONE CLOSING VISIT at k = K, when its last
  * observation is out: it evaluates step K - 1, flushes the last window and pushes nothing - the step side's ticket count is unchanged, and
- * the wait for that observation is the loop's own wait, with its deadline and the abort word. */
-template <bool LEARN>
+ * the wait for that observation is the loop's own wait, with its deadline and the abort word.
+ * MODE 0: gq_rollout_policy; 1: LEARN; 2: LEARN with the foot terms of gq_reward_feet.h (gq_rollout_policy_learn_feet) - P.learn then points at
+ * a LearnFeetDev.  The visit that evaluates step k - 1 also applies the foot law, whose state - the feet's air times, [N][4], read and written
+ * by the env's lane alone like acc and wstate - advances whether or not the window is dead (a dead window's tail holds the re-spawn step and
+ * the new episode's first steps: they earn nothing, but feet leave the ground in them) and is zeroed at the env's re-spawn step. */
+template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
+  constexpr bool LEARN = MODE != 0;
   __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
   const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
@@ -425,6 +431,47 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
             if (L.pending && ld_pub_u8(L.pending + e)) ws |= LEARN_RESPAWN; /* the env spends step 0 on its re-spawn */
           } else {
             const int term = ld_pub_u8(L.terminated + e);
+            if constexpr (MODE == 2) {
+              const GQ_MODEL LearnFeetDev& LF = *mptr((const LearnFeetDev*)P.learn);
+              const FootLaw F = foot_law_load(LF.feet);
+              const bool air_on = F.w[FW_AIR_TIME] != 0.0f;
+              float* const air = LF.air_time + (size_t)e * 4;
+              float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+              if (!(ws & LEARN_RESPAWN)) {
+                const float* const row = obs + (size_t)e * od;
+                const bool earns = !(ws & LEARN_DEAD);
+                const RewardLaw R = reward_law_load(L.law);
+                /* every load of the visit is issued before the first word is used: the foot columns, the state, then the twelve terms' words */
+                FootIn fin;
+                foot_gather_row(F, [&](const int c) { return ld_pub(row + c); }, fin);
+                if (air_on) {
+#pragma unroll
+                  for (int i = 0; i < 4; i++) t[i] = ld_pub(air + i);
+                }
+                RewardIn in;
+                if (earns) {
+                  reward_gather_row(R, [&](const int c) { return ld_pub(row + c); }, in);
+                  if (reward_needs_u(R)) {
+#pragma unroll
+                    for (int j = 0; j < 12; j++) in.u[j] = ld_pub(MB.act + (size_t)e * 12 + j);
+                  }
+                  if (reward_needs_a(R)) {
+#pragma unroll
+                    for (int j = 0; j < 12; j++) { in.a[j] = ld_pub(P.held + (size_t)e * 12 + j); in.a_prev[j] = ld_pub(L.prev + (size_t)e * 12 + j); }
+                  }
+                }
+                {
+#pragma clang fp contract(off)
+                  if (earns) acc = acc + foot_reward_step(R, F, in, fin, term, t);
+                  else (void)foot_sum(F, fin, R.dt, 0.0f, t); /* a dead window's tail: the state advances, nothing is earned */
+                }
+                if (earns && term) ws |= LEARN_DEAD | LEARN_DONE;
+              }
+              if (air_on) { /* (t is still zero at the env's re-spawn step) */
+#pragma unroll
+                for (int i = 0; i < 4; i++) st_pub(air + i, t[i]);
+              }
+            } else
             if (!(ws & (LEARN_DEAD | LEARN_RESPAWN))) {
               const RewardLaw R = reward_law_load(L.law);
               const float* const row = obs + (size_t)e * od;
@@ -606,6 +653,41 @@ __global__ void __launch_bounds__(GQ_WAVE) reward_eval_kernel(const LearnDev* __
     for (int j = 0; j < 12; j++) { in.a[j] = act[(size_t)r * 12 + j]; in.a_prev[j] = act_prev[(size_t)r * 12 + j]; }
   }
   out[r] = reward_step(R, in, terminated ? (int)terminated[r] : 0);
+}
+
+/* the law with the foot terms over rows (gq_reward_eval_feet), lane = row: air_in / air_out [n][4], the state before and after the row's step
+ * (read and written only with air_time on; may be NULL then - and may be the same tensor: a lane reads its row before it writes it) */
+__global__ void __launch_bounds__(GQ_WAVE) reward_eval_feet_kernel(const LearnFeetDev* __restrict__ Lp, const float* __restrict__ rows, const int od, const float* __restrict__ torques,
+                                                                   const float* __restrict__ act, const float* __restrict__ act_prev, const uint8_t* __restrict__ terminated,
+                                                                   const float* air_in, const int n, float* __restrict__ out, float* air_out) {
+  const RewardLaw R = reward_law_load(mptr(Lp)->learn.law);
+  const FootLaw F = foot_law_load(mptr(Lp)->feet);
+  const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
+  if (r >= n) return;
+  const float* const row = rows + (size_t)r * od;
+  FootIn fin;
+  foot_gather_row(F, [&](const int c) { return row[c]; }, fin);
+  float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  const bool air_on = F.w[FW_AIR_TIME] != 0.0f;
+  if (air_on) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) t[i] = air_in[(size_t)r * 4 + i];
+  }
+  RewardIn in;
+  reward_gather_row(R, [&](const int c) { return row[c]; }, in);
+  if (reward_needs_u(R)) {
+#pragma unroll
+    for (int j = 0; j < 12; j++) in.u[j] = torques[(size_t)r * 12 + j];
+  }
+  if (reward_needs_a(R)) {
+#pragma unroll
+    for (int j = 0; j < 12; j++) { in.a[j] = act[(size_t)r * 12 + j]; in.a_prev[j] = act_prev[(size_t)r * 12 + j]; }
+  }
+  out[r] = foot_reward_step(R, F, in, fin, terminated ? (int)terminated[r] : 0, t);
+  if (air_on) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) air_out[(size_t)r * 4 + i] = t[i];
+  }
 }
 
 /* which XCDs does this device expose?  bit HW_REG_XCC_ID of *mask is set by every workgroup */
@@ -847,9 +929,15 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, bool learn, hipStream_t stream) {
-  if (learn) hipLaunchKernelGGL(gq::policy_mlp_kernel<true>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
-  else hipLaunchKernelGGL(gq::policy_mlp_kernel<false>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+/* mode 0: gq_rollout_policy, 1: the learning half, 2: the learning half with the foot terms (mlp->learn is a LearnFeetDev) */
+extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream) {
+  if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<2>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+  else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<1>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+  else hipLaunchKernelGGL(gq::policy_mlp_kernel<0>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+}
+extern "C" void gq_launch_reward_eval_feet(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                           const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, hipStream_t stream) {
+  hipLaunchKernelGGL(gq::reward_eval_feet_kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, air_in, n, out, air_out);
 }
 /* impl 0: mlp_row_forward, a thread per row; 1: mlp_tile_forward, a wavefront per 16 rows */
 extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,

@@ -1,6 +1,7 @@
 /*
  * gq_reward.h - the task reward of the learning rollout (gq_rollout_policy_learn, gq_reward_eval): the law of ONE physics step's reward,
- * the block that carries a call's weights and columns to the device, and the per-env window bookkeeping of policy_mlp_kernel<true>.
+ * the block that carries a call's weights and columns to the device, and the per-env window bookkeeping of policy_mlp_kernel<1> (and <2>,
+ * which adds the foot terms of gq_reward_feet.h).
  * Plain C++ for host and device (tests/reward_host.cpp compiles it with g++): contraction off, IEEE +, -, * and fmaf only - the same
  * bits from any compiler.  The ORDER of the operations below is the definition.
  *
@@ -73,8 +74,8 @@ __host__ __device__ inline void reward_gather_row(const RewardLaw& R, Ld ld, Rew
   }
 }
 
-/* THE LAW */
-__host__ __device__ inline float reward_step(const RewardLaw& R, const RewardIn& in, const int terminated) {
+/* THE LAW, in two halves so that gq_reward_feet.h can continue the sum: S through `alive`, then dt * S and the termination */
+__host__ __device__ inline float reward_sum(const RewardLaw& R, const RewardIn& in) {
 #pragma clang fp contract(off)
   float S = 0.0f;
   if (R.w[RW_TRACK_LIN_VEL] != 0.0f) {
@@ -117,9 +118,14 @@ __host__ __device__ inline float reward_step(const RewardLaw& R, const RewardIn&
     S = fmaf(R.w[RW_ACTION_RATE], t, S);
   }
   if (R.w[RW_ALIVE] != 0.0f) S = S + R.w[RW_ALIVE];
+  return S;
+}
+__host__ __device__ inline float reward_finish(const RewardLaw& R, const float S, const int terminated) {
+#pragma clang fp contract(off)
   const float r = R.dt * S;
   return terminated ? r + R.w[RW_TERMINATION] : r;
 }
+__host__ __device__ inline float reward_step(const RewardLaw& R, const RewardIn& in, const int terminated) { return reward_finish(R, reward_sum(R, in), terminated); }
 
 /* what a call of gq_rollout_policy_learn adds to PolicyMlpDev (device pointers), and gq_reward_eval's whole block */
 struct LearnDev {

@@ -171,6 +171,7 @@ class QuadrupedEnv(AccessorsMixin):
         self._obs_dim = int(sum(OBS_DIMS[i] for i in self._all_ids))   # row width the kernel writes
         self._obs_buf = torch.zeros(N, self._obs_dim, **f32)
         self._reward = torch.zeros(N, **f32)
+        self._feet_air = torch.zeros(N, 4, **f32)   # the foot reward terms' state (feet_air_time)
         self._terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._invalid = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -453,7 +454,12 @@ class QuadrupedEnv(AccessorsMixin):
         ``[K // D, N]`` bool.  ``record_transitions``: the dict gains 'policy_obs' ``[K // D, N, policy.in_dim]`` - the row the network
         was fed at each policy step, before shift / scale: the observation columns, then the fed-back action - 'policy_means'
         ``[K // D, N, 12]`` - the network's output before noise and clip - and 'policy_actions' (as under ``record_actions``): what the old
-        log-probability of a policy-gradient step needs, at the policy's rate."""
+        log-probability of a policy-gradient step needs, at the policy's rate.
+
+        THE FOOT TERMS (``gq_rollout_policy_learn_feet``; a ``reward`` without ``feet``, or with every foot weight 0, is the call above):
+        ``RewardSpec(..., feet=FootRewardSpec(...))`` continues every step's sum with air time, slip, impact and clearance
+        (``csrc/gq_reward_feet.h``).  The air times are ``env.feet_air_time``: they persist across calls, advance at every evaluated step -
+        also in the tail of a window after a fall, which earns nothing - and are zeroed at an env's re-spawn step."""
         K, D = int(n_steps), int(decimation)
         if K < 0:
             raise ValueError('n_steps must be >= 0')
@@ -491,7 +497,12 @@ class QuadrupedEnv(AccessorsMixin):
             g.rewards, g.dones = ptr(extra.get('rewards')), ptr(extra.get('dones'))
             g.policy_obs, g.policy_means = ptr(extra.get('policy_obs')), ptr(extra.get('policy_means'))
         self._hm_fresh = False
-        if learning:
+        if learning and reward is not None and reward.feet_on:
+            gf = reward.feet._struct(self._feet_air.data_ptr())
+            _lib.check(self._L.gq_rollout_policy_learn_feet(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out,
+                                                            self._auto_cfg, self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), C.byref(g),
+                                                            C.byref(gf), stream), 'gq_rollout_policy_learn_feet')
+        elif learning:
             _lib.check(self._L.gq_rollout_policy_learn(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out,
                                                        self._auto_cfg, self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), C.byref(g),
                                                        stream), 'gq_rollout_policy_learn')
@@ -506,11 +517,15 @@ class QuadrupedEnv(AccessorsMixin):
                 sensor.step()
         return {'obs': self._obs_views, 'obs_seq': obs_seq, 'actions': act_seq, 'policy_actions': pol_seq, **extra}
 
-    def reward_eval(self, spec, rows, torques=None, actions=None, prev_actions=None, terminated=None):
+    def reward_eval(self, spec, rows, torques=None, actions=None, prev_actions=None, terminated=None, feet_air=None):
         """The reward law of ``spec`` (a ``RewardSpec``) alone over ``n`` given steps (``gq_reward_eval``): rows ``[n, obs_dim]`` in this env's
         observation layout (e.g. ``env._obs_buf`` after a step), torques / actions / prev_actions ``[n, 12]`` (None where no weighted
         term reads them), terminated ``[n]`` bool or uint8 (None: all False); float32 tensors on the env's device -> ``[n]`` float32.
-        The same routine, hence the same bits, as inside ``rollout_policy(reward=spec)``."""
+        The same routine, hence the same bits, as inside ``rollout_policy(reward=spec)``.
+
+        ``feet_air``: ``[n, 4]`` float32, the feet's air times BEFORE each row's step (``gq_reward_eval_feet``); when given, the result is
+        ``(reward, feet_air_next)``.  A spec whose ``air_time`` term is on needs it; a spec without foot terms ignores the state (it is
+        returned unchanged)."""
         from .reward import RewardSpec
         if not isinstance(spec, RewardSpec):
             raise ValueError(f'spec must be a RewardSpec, got {type(spec).__name__}')
@@ -535,8 +550,17 @@ class QuadrupedEnv(AccessorsMixin):
         ptr = lambda t: None if t is None else t.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         g = spec._struct()
+        air = arg(feet_air, 'feet_air', torch.float32, (n, 4))
+        if spec.feet_on:
+            if spec.feet.air_time != 0.0 and air is None:
+                raise ValueError('the air_time term is on: feet_air ([n, 4], the air times before each step) is needed')
+            air_next = None if air is None else air.clone()   # (with air_time off the state passes through)
+            gf = spec.feet._struct()
+            _lib.check(self._L.gq_reward_eval_feet(self._hbatch, C.byref(g), C.byref(gf), rows.data_ptr(), ptr(u), ptr(a), ptr(ap), ptr(term), ptr(air), n,
+                                                   out.data_ptr(), ptr(air_next), stream), 'gq_reward_eval_feet')
+            return out if air is None else (out, air_next)
         _lib.check(self._L.gq_reward_eval(self._hbatch, C.byref(g), rows.data_ptr(), ptr(u), ptr(a), ptr(ap), ptr(term), n, out.data_ptr(), stream), 'gq_reward_eval')
-        return out
+        return out if air is None else (out, air.clone())
 
     def policy_eval(self, policy, rows, impl: str = 'tile'):
         """The network of ``policy`` alone over ``rows`` (``[n, policy.in_dim]`` float32 on the env's device; shift / scale applied to
@@ -796,6 +820,7 @@ class QuadrupedEnv(AccessorsMixin):
                                     self._episode.data_ptr(), self._lift_failed.data_ptr(), stream), 'gq_reset')
         self._launches += 1
         self._note_step()
+        self._feet_air.masked_fill_(mask.bool().unsqueeze(1), 0.0)   # a new episode starts with no air time behind it
         if mask is self._mask_all:  # the reference zeroes mjData.ctrl in reset (:334): torque_ctrl_setpoint reads zero afterwards
             self._ctrl.zero_()
             self._last_action = self._ctrl
@@ -896,6 +921,17 @@ class QuadrupedEnv(AccessorsMixin):
         """Per-env flag of the reset RuntimeError condition (reference :387-388)."""
         return self._lift_failed.view(torch.bool)
 
+    @property
+    def feet_air_time(self):
+        """``[N, 4]`` float32, FL FR RL RR: how long each foot has been in the air, the state of the reward's ``air_time`` term
+        (``FootRewardSpec``).  ``rollout_policy(reward=spec)`` with that term on reads and advances it at every physics step, and zeroes
+        an env's row at its re-spawn step; ``reset`` zeroes the rows of the envs it resets.  Assigning copies into the same tensor."""
+        return self._feet_air
+
+    @feet_air_time.setter
+    def feet_air_time(self, value):
+        self._feet_air.copy_(torch.as_tensor(value, dtype=torch.float32, device=self.device).reshape(self.num_envs, 4))
+
     def target_base_vel(self):
         """Reference command in the heading frame ``[N,3]`` and yaw rate ``[N]`` (reference :488-499 inputs)."""
         return self._cmd[:, 0:3], self._cmd[:, 3]
@@ -904,7 +940,7 @@ class QuadrupedEnv(AccessorsMixin):
         """Checkpoint: everything needed to resume a rollout bit-for-bit."""
         keys = ['_qpos', '_qvel', '_qacc', '_warm', '_applied', '_time', '_friction', '_cmd', '_step_num', '_episode', '_terminated',
                 '_h9', '_ext_dist', '_step_num_prev']
-        keys.append('_lift_failed')
+        keys += ['_lift_failed', '_feet_air']
         d = {k: getattr(self, k).clone() for k in keys}
         d['rng'] = self._gen.get_state()
         # sensor state the kernel reads and writes every step: the IMU bias random walks

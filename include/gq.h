@@ -568,6 +568,35 @@ int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int
  * pointers of `learn` are not read.  Asynchronous on hip_stream. */
 int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev,
                    const uint8_t* terminated, int n, float* out, void* hip_stream);
+/* THE FOOT TERMS of the learning rollout's reward (additive: GqLearn, gq_rollout_policy_learn and gq_reward_eval are what they were).  They
+ * continue the sum S of the twelve terms after `alive`, before dt * S (csrc/gq_reward_feet.h is the definition), in the order of the
+ * fields, each off at weight 0 (its observables need not be in the row then).  Feet are FL, FR, RL, RR whatever the batch's legs_order; per
+ * physics step, from the row AFTER the step, for foot i: c_i = contact_state[i] != 0, vx_i, vy_i = feet_vel[i][0:2], fz_i =
+ * contact_forces[i][2], zb_i = feet_pos:base[i][2], t_i = air_time[e][i]:
+ *   air_time   A = sum over the feet with c_i and t_i > 0 of (t_i + dt - air_time_target);  then t_i <- c_i ? 0 : t_i + dt;
+ *              with min_cmd_speed > 0, A = 0 unless |base_lin_vel_err:base + base_lin_vel:base|[0:2]^2 > min_cmd_speed^2 (the command)
+ *   slip       sum over the feet with c_i of vx_i^2 + vy_i^2          impact  sum of max(fz_i - impact_limit, 0)
+ *   clearance  sum of (zb_i - clearance_target)^2 (vx_i^2 + vy_i^2)
+ * In the rollout the state advances at EVERY evaluated step, whether or not its window still earns (the tail of a window after a fall), and
+ * is zeroed at the env's re-spawn step: the first contact of an episode earns nothing.  It persists across calls in the caller's tensor.
+ * Refused with a message, the batch stays usable: a stale struct_size (before anything else), a weighted term whose observable is not in the
+ * row, a non-finite weight, impact on with impact_limit not finite or not positive, air_time on with air_time_target not finite,
+ * min_cmd_speed < 0 or not finite, clearance on with a non-finite target, air_time on with a null state pointer. */
+typedef struct GqFootReward {
+  int32_t struct_size;        /* sizeof(GqFootReward): a stale binding is refused */
+  int32_t pad_;
+  float w_air_time, w_slip, w_impact, w_clearance;
+  float air_time_target, min_cmd_speed, impact_limit, clearance_target;
+  float *air_time;            /* device [N][4] f32, in / out: the feet's air times; required in the rollout when w_air_time != 0 */
+} GqFootReward;
+/* gq_rollout_policy_learn with the foot terms (all four weights 0, or neither rewards nor dones asked for: gq_rollout_policy_learn itself) */
+int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+                                 const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                                 const GqFootReward* feet, void* hip_stream);
+/* gq_reward_eval with the foot terms, lane = row: air_in / air_out device [n][4], the state before / after each row's step (NULL allowed
+ * with air_time off; feet->air_time is not read).  The same routine, the same bits, as inside the rollout. */
+int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act,
+                        const float* act_prev, const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

@@ -1,0 +1,254 @@
+"""CPU tests of the foot terms of the learning rollout's reward (gym_quadruped_amd/csrc/gq_reward_feet.h, gym_quadruped_amd/reward.py
+FootRewardSpec, include/gq.h GqFootReward): the law's definition compiled for the host (tests/foot_reward_host.cpp) against hand-made
+sequences bit for bit, against reward_host with the feet off, against the float64 restatement under a derived bound; the columns per
+legs_order; the spec's validation; the ABI additions."""
+import ctypes
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import foot_reward_ref as F
+import reward_ref as R
+
+ROOT = Path(__file__).resolve().parents[1]
+DT32 = np.float32(F.DT)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+
+
+def _blank(T, S=1):
+    """T steps of S sequences of zero rows, zero torques and actions, no flags"""
+    z12 = np.zeros((T, S, 12), dtype=np.float32)
+    return np.zeros((T, S, F.OBS_DIM), dtype=np.float32), z12, z12.copy(), z12.copy(), np.zeros((T, S), dtype=np.uint8)
+
+
+def _cols(feet, legs=F.LEGS):
+    return feet.columns(F.OBS_NAMES, legs)
+
+
+def _feet_only(feet):
+    return F.with_feet(feet, weights={})
+
+
+@pytest.mark.parametrize('m', [1, 2, 300])
+def test_a_landing_earns_its_air_time_bit_for_bit(m):
+    """foot RL stands, leaves the ground for m steps and lands: that step earns w (t - target), t built by m + 1 float32 additions of dt"""
+    from gym_quadruped_amd.reward import FootRewardSpec
+    w, target = 0.75, 0.2
+    feet = FootRewardSpec(air_time=w, air_time_target=target, min_cmd_speed=0.0)
+    seq = _blank(m + 3)
+    c = _cols(feet)['feet:contact']
+    seq[0][:, 0, list(c)] = 1.0
+    seq[0][1:1 + m, 0, c[2]] = 0.0                     # RL in the air for steps 1 .. m
+    out = F.host_sequence(_feet_only(feet), *seq)
+    t = np.float32(0.0)
+    for _ in range(m):
+        t = np.float32(t + DT32)
+    assert _bits(out['air'][m, 0, 2]) == _bits(t) and (out['air'][m, 0, [0, 1, 3]] == 0).all()
+    tn = np.float32(t + DT32)                           # the landing step adds dt once more before it takes the difference
+    A = np.float32(np.float32(0.0) + np.float32(tn - np.float32(target)))
+    want = np.float32(DT32 * np.float32(np.float32(w) * A))   # fmaf(w, A, 0) = the rounded product; then dt * S
+    assert _bits(out['reward'][m + 1, 0]) == _bits(want)
+    rest = np.delete(out['reward'][:, 0], m + 1)
+    assert (rest == 0).all(), 'standing feet (t = 0) and feet in the air earn nothing'
+    assert (out['air'][m + 1, 0] == 0).all() and (out['air'][-1, 0] == 0).all()
+
+
+def test_the_first_contact_after_a_respawn_and_the_gate():
+    from gym_quadruped_amd.reward import FootRewardSpec
+    feet = FootRewardSpec(air_time=1.0, air_time_target=0.0, min_cmd_speed=0.5)
+    cols = _cols(feet)
+    c, ce, cv = cols['feet:contact'], cols['feet:cmd_err'], cols['feet:cmd_vel']
+    # sequence 0: in the air, re-spawn at step 3 (the state is zeroed), landing at step 4 directly after it: nothing is earned
+    # sequence 1: the same flight without the re-spawn, the command above the gate: the landing earns
+    # sequence 2: the same flight, the command below the gate: the landing earns 0 - and the next flight starts from t = 0 all the same
+    rows, u, a, ap, term = _blank(9, 3)
+    rows[:, :, ce[0]] = 0.25; rows[:, :, cv[0]] = 0.5       # command = err + vel = 0.75 > 0.5
+    rows[:, 2, ce[0]] = -0.25                               # 0.25: below
+    rows[4, :, c[0]] = 1.0                                  # FL lands at step 4 ...
+    rows[7:, :, c[0]] = 1.0                                 # ... flies steps 5, 6 and lands again at 7
+    respawn = np.zeros((9, 3), dtype=np.uint8)
+    respawn[3, 0] = 1
+    out = F.host_sequence(_feet_only(feet), rows, u, a, ap, term, respawn=respawn)
+    assert (out['air'][3, 0] == 0).all(), 'the re-spawn step zeroes the state'
+    assert out['reward'][4, 0] == 0 and out['reward'][4, 1] > 0 and out['reward'][4, 2] == 0
+    assert out['gate'][:, 1].all() and not out['gate'][:, 2].any()
+    t5 = np.float32(0.0)
+    for _ in range(5):
+        t5 = np.float32(t5 + DT32)
+    assert _bits(out['reward'][4, 1]) == _bits(np.float32(DT32 * t5))
+    t3 = np.float32(np.float32(DT32 + DT32) + DT32)
+    assert _bits(out['air'][6, 2, 0]) == _bits(np.float32(DT32 + DT32)), 'with the gate false the state still advances: the next flight starts from 0'
+    for s in (0, 1):
+        assert _bits(out['reward'][7, s]) == _bits(np.float32(DT32 * t3)), s
+    assert out['reward'][7, 2] == 0
+
+
+def test_impact_at_the_limit_and_slip_of_a_foot_in_the_air():
+    from gym_quadruped_amd.reward import FootRewardSpec
+    feet = FootRewardSpec(impact=-2.0, impact_limit=40.0, slip=-1.0)
+    cols = _cols(feet)
+    rows, u, a, ap, term = _blank(3)
+    rows[0, 0, cols['feet:fz'][1]] = 40.0                               # fz == limit: 0
+    rows[1, 0, cols['feet:fz'][1]] = np.nextafter(np.float32(40.0), np.float32(50.0))
+    rows[2, 0, cols['feet:vx'][3]] = 3.0; rows[2, 0, cols['feet:vy'][3]] = 4.0    # a fast foot with c = 0: no slip
+    out = F.host_sequence(_feet_only(feet), rows, u, a, ap, term)
+    assert out['reward'][0, 0] == 0 and not out['impact'][0].any()
+    d = np.float32(np.nextafter(np.float32(40.0), np.float32(50.0)) - np.float32(40.0))
+    assert _bits(out['reward'][1, 0]) == _bits(np.float32(DT32 * np.float32(np.float32(-2.0) * d))) and out['impact'][1, 0, 1]
+    assert out['reward'][2, 0] == 0
+    rows[2, 0, cols['feet:contact'][3]] = 1.0
+    assert F.host_sequence(_feet_only(feet), rows, u, a, ap, term)['reward'][2, 0] == np.float32(DT32 * np.float32(-25.0))
+
+
+def test_all_foot_weights_zero_is_reward_host_bit_for_bit():
+    from gym_quadruped_amd.reward import FootRewardSpec
+    steps = tuple(np.concatenate([e, s]) for e, s in zip(R.edge_steps(), R.random_steps(6000)))
+    for name, spec in R.specs().items():
+        want = R.host_reward(spec, *steps)
+        for feet in (None, FootRewardSpec(), FootRewardSpec(impact_limit=3.0, clearance_target=0.1)):
+            got, air = F.host_rows(F.with_feet(feet, weights=spec.weights), *steps, air=np.full((len(want), 4), 0.3, np.float32), names=R.OBS_NAMES)
+            assert np.array_equal(_bits(got), _bits(want)), name
+            assert (air == np.float32(0.3)).all(), 'air_time off: the state is not touched'
+
+
+@pytest.mark.parametrize('name', ['air_time', 'air_time_ungated', 'slip', 'impact', 'clearance'])
+def test_a_term_that_is_off_does_not_look_at_its_words(name):
+    feet = F.foot_specs()[name]
+    spec = _feet_only(feet)
+    (rows, u, a, ap, term), air = F.random_rows(500, seed=2)
+    want, want_air = F.host_rows(spec, rows, u, a, ap, term, air=air)
+    used = sorted({c for v in spec.columns(F.OBS_NAMES).values() for c in v})
+    poisoned = np.full_like(rows, np.nan)
+    poisoned[:, used] = rows[:, used]
+    nan12 = np.full_like(u, np.nan)
+    got, got_air = F.host_rows(spec, poisoned, nan12, nan12, nan12, term, air=air if 'air_time' in name else np.full_like(air, np.nan))
+    assert np.isfinite(want).all() and np.array_equal(_bits(got), _bits(want))
+    if 'air_time' in name:
+        assert np.array_equal(_bits(got_air), _bits(want_air))
+
+
+@pytest.mark.parametrize('twelve', [False, True])
+@pytest.mark.parametrize('name', list(F.foot_specs()))
+def test_against_the_float64_restatement_with_the_state_carried(name, twelve):
+    """64 sequences of 200 steps; the bound is DERIVED (foot_reward_ref.sequence_reference), the worst measured ratio to it is in
+    profiles/foot_reward_law_error.txt"""
+    feet = F.foot_specs()[name]
+    spec = F.with_feet(feet) if twelve else _feet_only(feet)
+    seq = F.random_sequences(S=64, T=200, seed=0)
+    host = F.host_sequence(spec, *seq)
+    ref, bound, air64 = F.sequence_reference(spec, seq, host)
+    assert np.isfinite(ref).all() and np.isfinite(bound).all()
+    err = np.abs(host['reward'].astype(np.float64) - ref)
+    print(f'{name} twelve={twelve}: worst |f32 - f64| / bound = {(err[bound > 0] / bound[bound > 0]).max():.4f}')
+    assert (err <= bound).all()
+    if feet.air_time != 0.0:
+        landed = (host['air'][:-1] > 0) & (seq[0][1:][:, :, F.contact_columns()] != 0)
+        assert landed.sum() > 500 and host['air'].max() > 30 * F.DT, 'the sequences must contain landings after long flights'
+        assert np.abs(host['air'][-1].astype(np.float64) - air64).max() <= 200 * F.U * 200 * F.DT   # a chain of at most T additions
+        assert host['gate'].any() and not host['gate'].all() or not feet.gated
+    if feet.impact != 0.0:
+        assert host['impact'].any() and not host['impact'].all()
+
+
+def test_columns_point_at_the_same_physical_foot_for_two_legs_orders():
+    from gym_quadruped_amd.cabi import LEG_NAMES
+    from gym_quadruped_amd.reward import FootRewardSpec, RewardSpec
+    feet = F.foot_full()
+    a, b = feet.columns(F.OBS_NAMES, F.LEGS), feet.columns(F.OBS_NAMES, F.LEGS_PERMUTED)
+    start = {'contact_state': 42, 'contact_forces': 46, 'feet_vel': 58, 'feet_pos:base': 70}
+    assert a['feet:contact'] == b['feet:contact'] == (42, 43, 44, 45), 'contact_state is canonical in the row'
+    assert a['feet:vx'] == (58, 61, 64, 67) and a['feet:vy'] == (59, 62, 65, 68) and a['feet:fz'] == (48, 51, 54, 57) and a['feet:zb'] == (72, 75, 78, 81)
+    for i, leg in enumerate(LEG_NAMES):                 # canonical foot i = leg: in the permuted row it sits where legs_order names it
+        slot = F.LEGS_PERMUTED.index(leg)
+        assert b['feet:vx'][i] == start['feet_vel'] + 3 * slot and b['feet:vy'][i] == start['feet_vel'] + 3 * slot + 1
+        assert b['feet:fz'][i] == start['contact_forces'] + 3 * slot + 2 and b['feet:zb'][i] == start['feet_pos:base'] + 3 * slot + 2
+    assert a['feet:cmd_err'] == b['feet:cmd_err'] == (33, 34) and a['feet:cmd_vel'] == (27, 28)
+    # the same physical data laid out in the two orders gives the same bits
+    (rows, u, x, xp, term), air = F.random_rows(300, seed=4)
+    perm = rows.copy()
+    for name in ('contact_forces', 'feet_vel', 'feet_pos:base'):
+        for slot, leg in enumerate(F.LEGS_PERMUTED):
+            i = LEG_NAMES.index(leg)
+            perm[:, start[name] + 3 * slot:start[name] + 3 * slot + 3] = rows[:, start[name] + 3 * i:start[name] + 3 * i + 3]
+    spec = F.with_feet(feet)
+    ra, aa = F.host_rows(spec, rows, u, x, xp, term, air=air)
+    rb, ab = F.host_rows(spec, perm, u, x, xp, term, air=air, legs_order=F.LEGS_PERMUTED)
+    assert np.array_equal(_bits(ra), _bits(rb)) and np.array_equal(_bits(aa), _bits(ab))
+    # RewardSpec with feet: the feet's observables and columns follow the existing ones; without feet nothing changes
+    plain, both = RewardSpec(lin_vel_z=1.0, alive=1.0), RewardSpec(lin_vel_z=1.0, alive=1.0, feet=FootRewardSpec(slip=1.0, air_time=1.0))
+    assert plain.required_obs() == ('base_lin_vel:base',) and plain.columns(F.OBS_NAMES) == {'lin_vel_z': (29,)} and not plain.feet_on
+    assert both.required_obs() == ('base_lin_vel:base', 'contact_state', 'base_lin_vel_err:base', 'feet_vel') and both.feet_on
+    assert list(both.columns(F.OBS_NAMES))[0] == 'lin_vel_z' and both.columns(F.OBS_NAMES)['feet:vx'] == (58, 61, 64, 67)
+    assert FootRewardSpec(air_time=1.0, min_cmd_speed=0.0).required_obs() == ('contact_state',)
+    assert not RewardSpec(alive=1.0, feet=FootRewardSpec()).feet_on and FootRewardSpec().required_obs() == ()
+    with pytest.raises(ValueError, match='contact_forces'):
+        FootRewardSpec(impact=1.0, impact_limit=1.0).columns(R.OBS_NAMES)
+
+
+def test_the_spec_validates_like_the_library():
+    from gym_quadruped_amd.reward import FootRewardSpec, RewardSpec
+    nan, inf = float('nan'), float('inf')
+    for kw, msg in ((dict(slip=nan), 'slip'), (dict(air_time=inf), 'air_time'), (dict(impact=1.0), 'impact_limit'), (dict(impact=1.0, impact_limit=0.0), 'impact_limit'),
+                    (dict(impact=1.0, impact_limit=inf), 'impact_limit'), (dict(air_time=1.0, air_time_target=nan), 'air_time_target'), (dict(min_cmd_speed=-0.1), 'min_cmd_speed'),
+                    (dict(min_cmd_speed=nan), 'min_cmd_speed'), (dict(clearance=1.0), 'clearance_target'), (dict(clearance=1.0, clearance_target=inf), 'clearance_target')):
+        with pytest.raises(ValueError, match=msg):
+            FootRewardSpec(**kw)
+    FootRewardSpec(impact_limit=-1.0, clearance_target=nan)       # parameters of terms that are off are not looked at
+    with pytest.raises(ValueError, match='FootRewardSpec'):
+        RewardSpec(alive=1.0, feet=dict(slip=1.0))
+    with pytest.raises(TypeError):
+        FootRewardSpec(feet_air_time=1.0)
+    assert RewardSpec(alive=1.0).feet is None
+
+
+def test_foot_struct_layout_matches_header_and_the_abi_keeps_its_version():
+    from gym_quadruped_amd import _lib
+    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqFootReward, GqLearn
+    from gym_quadruped_amd.reward import FOOT_TERMS
+    fields = [n for n, _ in GqFootReward._fields_]
+    assert fields[2:6] == ['w_' + t for t in FOOT_TERMS], 'the weights stand in the order the terms continue the sum'
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%d %zu %zu' + ' %zu' * len(fields) + '\\n",GQ_ABI_VERSION,sizeof(GqLearn),sizeof(GqFootReward),'
+           + ','.join(f'offsetof(GqFootReward, {n})' for n in fields) + ');return 0;}')
+    with tempfile.TemporaryDirectory() as d:
+        (Path(d) / 'a.c').write_text(src)
+        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
+        out = [int(v) for v in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
+    assert out[0] == GQ_ABI_VERSION == 660
+    assert out[1] == ctypes.sizeof(GqLearn) == 104, 'GqLearn is what it was: 2 + 12 + 3 + 1 words and 4 pointers'
+    assert out[2] == ctypes.sizeof(GqFootReward)
+    assert out[3:] == [getattr(GqFootReward, n).offset for n in fields]
+    assert 'gq_rollout_policy_learn_feet' in _lib.EXPORTS and 'gq_reward_eval_feet' in _lib.EXPORTS
+    assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
+    L = ctypes.CDLL(str(_lib.LIB_PATH))
+    assert L.gq_version() == 660
+    sizes = (ctypes.c_int32 * 9)(*([-7] * 9))
+    L.gq_struct_sizes(sizes)   # still 8 entries: GqFootReward carries its own size
+    assert all(v > 0 for v in sizes[:8]) and sizes[8] == -7
+    # a stale binding is refused before anything else is looked at (no device is touched: the handle is never reached)
+    L.gq_last_error.restype = ctypes.c_char_p
+    P = ctypes.c_void_p
+    L.gq_reward_eval_feet.argtypes = [P, ctypes.POINTER(GqLearn), ctypes.POINTER(GqFootReward), P, P, P, P, P, P, ctypes.c_int, P, P, P]
+    g = GqLearn(struct_size=ctypes.sizeof(GqLearn))
+    stale = GqFootReward(struct_size=ctypes.sizeof(GqFootReward) - 8)
+    assert L.gq_reward_eval_feet(None, ctypes.byref(g), ctypes.byref(stale), None, None, None, None, None, None, 0, None, None, None) == -1
+    assert b'GqFootReward' in L.gq_last_error() and b'stale binding' in L.gq_last_error()
+    s = F.foot_full()._struct(1234)
+    assert s.struct_size == ctypes.sizeof(GqFootReward) and s.w_clearance == -5.0 and s.impact_limit == 1.0 and s.air_time == 1234
+
+
+def test_the_host_program_is_clean_under_the_sanitizers():
+    """tests/foot_reward_host.cpp built with -fsanitize=address,undefined as a stand-alone program, once over the random and edge inputs: the
+    same bits as the plain build, no report (a report ends the program with a non-zero status)"""
+    spec = F.with_feet(F.foot_full())
+    for (steps, air) in (F.random_rows(2000, seed=9), F.edge_rows()):
+        want, want_air = F.host_rows(spec, *steps, air=air)
+        got, got_air = F.host_rows(spec, *steps, air=air, sanitize=True)
+        assert np.array_equal(_bits(got), _bits(want)) and np.array_equal(_bits(got_air), _bits(want_air))
+    seq = F.random_sequences(S=8, T=50, seed=1)
+    assert np.array_equal(_bits(F.host_sequence(spec, *seq, sanitize=True)['reward']), _bits(F.host_sequence(spec, *seq)['reward']))
