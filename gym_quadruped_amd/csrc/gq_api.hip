@@ -22,8 +22,7 @@
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
-#include "gq_reward.h"
-#include "gq_reward_feet.h"
+#include "gq_learn.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
 #include "gq_host_res.h"
@@ -40,10 +39,8 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
 extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream);
-extern "C" void gq_launch_reward_eval_feet(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
-                                           const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, hipStream_t stream);
-extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
-                                      const uint8_t* terminated, int n, float* out, hipStream_t stream);
+extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                      const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, int feet, hipStream_t stream);
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
@@ -80,7 +77,7 @@ struct Mailbox {
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
-  Buf<int32_t> learn_state;                 /* [N] the window's flags (gq_reward.h LEARN_*) */
+  Buf<int32_t> learn_state;                 /* [N] the window's flags (gq_learn.h LEARN_*) */
   gq::Stream stream; gq::Event fork, join;
   bool ready = false;
 };
@@ -648,6 +645,14 @@ static int obs_column(const GqBatch* b, int canonical) {
     if (b->host.obs_map[c] == canonical) return c;
   return -1;
 }
+/* the column resolver of both laws: the column of an observable, or -1 when nothing that is on reads it; a weighted term whose observable is
+ * absent is refused by name (the first one of a call: ok) */
+static int term_column(const GqBatch* b, const bool needed, const char* term, const int canonical, const char* obs_name, bool& ok, const char* who) {
+  if (!needed) return -1;
+  const int c = obs_column(b, canonical);
+  if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads %s: not in this batch's observation row", who, term, obs_name); ok = false; }
+  return c;
+}
 static int reward_describe(const GqBatch* b, const GqLearn* learn, gq::RewardLaw& R, bool& on, const char* who) {
   static const char* const names[GQ_REWARD_TERMS] = {"track_lin_vel", "track_ang_vel", "lin_vel_z", "ang_vel_xy", "orientation", "base_height", "torques", "joint_vel",
                                                      "power", "action_rate", "alive", "termination"};
@@ -668,13 +673,7 @@ static int reward_describe(const GqBatch* b, const GqLearn* learn, gq::RewardLaw
   R.dt = b->model->host.timestep;
   R.pad_ = 0;
   bool ok = true;
-  /* a column of an observable, or -1 when the term is off; a weighted term whose observable is absent is refused by name */
-  auto col = [&](const int term, const int canonical, const char* obs_name) {
-    if (w[term] == 0.0f) return -1;
-    const int c = obs_column(b, canonical);
-    if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads %s: not in this batch's observation row", who, names[term], obs_name); ok = false; }
-    return c;
-  };
+  auto col = [&](const int term, const int canonical, const char* obs_name) { return term_column(b, w[term] != 0.0f, names[term], canonical, obs_name, ok, who); };
   R.col_lin_err[0] = col(gq::RW_TRACK_LIN_VEL, gq::OB_LIN_VEL_ERR_B + 0, "base_lin_vel_err:base"); R.col_lin_err[1] = col(gq::RW_TRACK_LIN_VEL, gq::OB_LIN_VEL_ERR_B + 1, "base_lin_vel_err:base");
   R.col_ang_err_z = col(gq::RW_TRACK_ANG_VEL, gq::OB_ANG_VEL_ERR_B + 2, "base_ang_vel_err:base");
   R.col_vz = col(gq::RW_LIN_VEL_Z, gq::OB_LIN_VEL_B + 2, "base_lin_vel:base");
@@ -715,12 +714,7 @@ static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw
   F.impact_limit = w[gq::FW_IMPACT] != 0.0f ? feet->impact_limit : 0.0f;
   F.clearance_target = w[gq::FW_CLEARANCE] != 0.0f ? feet->clearance_target : 0.0f;
   bool ok = true;
-  auto col = [&](const bool needed, const int term, const int canonical, const char* obs_name) {
-    if (!needed) return -1;
-    const int c = obs_column(b, canonical);
-    if (c < 0 && ok) { SET_ERR("%s: the reward term %s reads %s: not in this batch's observation row", who, names[term], obs_name); ok = false; }
-    return c;
-  };
+  auto col = [&](const bool needed, const int term, const int canonical, const char* obs_name) { return term_column(b, needed, names[term], canonical, obs_name, ok, who); };
   const bool air = w[gq::FW_AIR_TIME] != 0.0f, slip = w[gq::FW_SLIP] != 0.0f, impact = w[gq::FW_IMPACT] != 0.0f, clear = w[gq::FW_CLEARANCE] != 0.0f;
   const bool gate = gq::foot_needs_cmd(F);
   for (int i = 0; i < 4; i++) {
@@ -781,7 +775,7 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   P.seed_lo = (uint32_t)(mlp->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(mlp->noise_seed >> 32);
   P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
   P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
-  P.learn = learn ? &mb.learn.dev.get()->learn : nullptr;
+  P.learn = learn ? mb.learn.dev.get() : nullptr;
   HIP_TRY(mb.mlp.push(P, stream, true));
   HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
   if (learn) {
@@ -818,49 +812,39 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
   return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
-int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev, const uint8_t* terminated,
-                   int n, float* out, void* hip_stream) {
-  const char* const who = "gq_reward_eval";
+/* gq_reward_eval (feet null) and gq_reward_eval_feet */
+static int reward_eval(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act, const float* act_prev,
+                       const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream, const char* const who) {
   if (!learn) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  if (!learn_fresh(learn, who)) return GQ_EINVAL;
-  if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  DeviceGuard guard(b->model->device);
-  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
-  gq::LearnFeetDev LF = b->mb.learn.shadow;
-  gq::LearnDev& L = LF.learn;
-  bool on = false;
-  if (const int rc = reward_describe(b, learn, L.law, on, who); rc != GQ_OK) return rc;
-  if (gq::reward_needs_u(L.law) && !torques) { SET_ERR("%s: a weighted term reads the torques: torques is null", who); return GQ_EINVAL; }
-  if (gq::reward_needs_a(L.law) && (!act || !act_prev)) { SET_ERR("%s: action_rate reads act and act_prev: null", who); return GQ_EINVAL; }
-  if (n == 0) return GQ_OK;
-  hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(b->mb.learn.push(LF, stream, true));
-  gq_launch_reward_eval(&b->mb.learn.dev.get()->learn, rows, b->host.obs_dim, torques, act, act_prev, terminated, n, out, stream);
-  HIP_TRY(hipGetLastError());
-  return GQ_OK;
-}
-
-int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act, const float* act_prev,
-                        const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream) {
-  const char* const who = "gq_reward_eval_feet";
-  if (!learn || !feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  if (!feet_fresh(feet, who) || !learn_fresh(learn, who)) return GQ_EINVAL;
+  if ((feet && !feet_fresh(feet, who)) || !learn_fresh(learn, who)) return GQ_EINVAL;
   if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
   gq::LearnFeetDev LF = b->mb.learn.shadow;
   bool on = false;
   if (const int rc = reward_describe(b, learn, LF.learn.law, on, who); rc != GQ_OK) return rc;
-  if (const int rc = foot_describe(b, feet, LF.feet, who); rc != GQ_OK) return rc;
+  if (feet) {
+    if (const int rc = foot_describe(b, feet, LF.feet, who); rc != GQ_OK) return rc;
+  }
   if (gq::reward_needs_u(LF.learn.law) && !torques) { SET_ERR("%s: a weighted term reads the torques: torques is null", who); return GQ_EINVAL; }
   if (gq::reward_needs_a(LF.learn.law) && (!act || !act_prev)) { SET_ERR("%s: action_rate reads act and act_prev: null", who); return GQ_EINVAL; }
-  if (LF.feet.w[gq::FW_AIR_TIME] != 0.0f && (!air_in || !air_out)) { SET_ERR("%s: air_time is on: air_in and air_out (the state before and after, device [n][4]) must not be null", who); return GQ_EINVAL; }
+  if (feet && LF.feet.w[gq::FW_AIR_TIME] != 0.0f && (!air_in || !air_out)) { SET_ERR("%s: air_time is on: air_in and air_out (the state before and after, device [n][4]) must not be null", who); return GQ_EINVAL; }
   if (n == 0) return GQ_OK;
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(b->mb.learn.push(LF, stream, true));
-  gq_launch_reward_eval_feet(b->mb.learn.dev.get(), rows, b->host.obs_dim, torques, act, act_prev, terminated, air_in, n, out, air_out, stream);
+  gq_launch_reward_eval(b->mb.learn.dev.get(), rows, b->host.obs_dim, torques, act, act_prev, terminated, air_in, n, out, air_out, feet != nullptr, stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
+}
+int gq_reward_eval(GqBatch* b, const GqLearn* learn, const float* rows, const float* torques, const float* act, const float* act_prev, const uint8_t* terminated,
+                   int n, float* out, void* hip_stream) {
+  return reward_eval(b, learn, nullptr, rows, torques, act, act_prev, terminated, nullptr, n, out, nullptr, hip_stream, "gq_reward_eval");
+}
+int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act, const float* act_prev,
+                        const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream) {
+  const char* const who = "gq_reward_eval_feet";
+  if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return reward_eval(b, learn, feet, rows, torques, act, act_prev, terminated, air_in, n, out, air_out, hip_stream, who);
 }
 
 int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream) {

@@ -11,8 +11,7 @@
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
-#include "gq_reward.h"
-#include "gq_reward_feet.h"
+#include "gq_learn.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -380,18 +379,20 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * as there; the lanes of a pass whose env is ready AND due for a new action are compacted by ballot into tiles of up to 16 rows, which the
  * whole wavefront stages (device-scope loads: every word of the row is another wavefront's store of this launch) and takes through the
  * layers.  An env that re-spawns ignores the torque of that step (next-step auto-reset); its held and last action are kept.
- * LEARN (gq_rollout_policy_learn; false compiles to the kernel as it was): the same seat also records what a learner needs, where the data
- * passes anyway.  At a fresh policy step the row the network is fed and its output before noise and clip are recorded; at the visit for
- * step k >= 1 - the observation after step k - 1 is out, the env waits for this wavefront - the reward of step k - 1 is evaluated
- * (gq_reward.h) from that row, the torques of step k - 1 (still in the env's mailbox), the held action and the one before it, and the
- * batch's `terminated` byte; every one of them a device-scope load.  Three per-env words (acc, wstate, prev: written by the env's lane
- * alone) carry the window; at k % D == 0 the window k / D - 1 is flushed.  Every env gets ONE CLOSING VISIT at k = K, when its last
- * observation is out: it evaluates step K - 1, flushes the last window and pushes nothing - the step side's ticket count is unchanged, and
- * the wait for that observation is the loop's own wait, with its deadline and the abort word.
- * MODE 0: gq_rollout_policy; 1: LEARN; 2: LEARN with the foot terms of gq_reward_feet.h (gq_rollout_policy_learn_feet) - P.learn then points at
- * a LearnFeetDev.  The visit that evaluates step k - 1 also applies the foot law, whose state - the feet's air times, [N][4], read and written
- * by the env's lane alone like acc and wstate - advances whether or not the window is dead (a dead window's tail holds the re-spawn step and
- * the new episode's first steps: they earn nothing, but feet leave the ground in them) and is zeroed at the env's re-spawn step. */
+ * LEARN (MODE != 0, gq_rollout_policy_learn; MODE 0 compiles to the kernel as it was): the same seat also records what a learner needs, where
+ * the data passes anyway.  At a fresh policy step the row the network is fed and its output before noise and clip are recorded.  At every
+ * visit - the observation after step k - 1 is out, the env waits for this wavefront - learn_visit (gq_learn.h, THE definition of the window
+ * law) evaluates the reward of step k - 1 from that row, the torques of step k - 1 (still in the env's mailbox), the held action and the one
+ * before it, and the batch's `terminated` byte, every one of them a device-scope load, and carries the window in per-env words that the
+ * env's lane alone writes.  Every env gets ONE CLOSING VISIT at k = K, when its last observation is out: it pushes nothing - the step side's
+ * ticket count is unchanged, and the wait for that observation is the loop's own wait, with its deadline and the abort word.
+ * MODE 1: learn_visit<false>; 2: learn_visit<true>, the foot terms of gq_reward_feet.h and their state, the air times
+ * (gq_rollout_policy_learn_feet).  With all foot weights 0 mode 2 computes mode 1's bits, but BOTH instantiations are kept: a learning call
+ * without foot terms through mode 2 measured 16.24 - 16.37 M env-steps/s against 16.53 - 16.65 through mode 1 (go2, 4096 envs, K = 96; no
+ * overlap in three alternated turns, profiles/learn_window_refactor.md) - the foot law's block and branches stay in the visit's way even when
+ * nothing of it is on.  Against the kernels before the fold the visit needs fewer VGPRs in both modes (132 / 160 against 180 / 204); mode 2
+ * has 280 SGPR spills (to VGPR lanes, no scratch) against 252: the step's reward now leaves learn_step as a value and is added to acc under
+ * a second `if (earns)` in learn_visit, where it was added inside the branch that evaluated it. */
 template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   constexpr bool LEARN = MODE != 0;
@@ -422,87 +423,9 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
       const bool ready = live && ld_pub(MB.steps_done + e) >= k; /* the observation after step k - 1 is out */
       const bool fresh = ready && k % D == 0 && (!LEARN || k < K); /* ... and the env is due for a new action */
       float a[12];
-      if constexpr (LEARN) {
-        const GQ_MODEL LearnDev& L = *mptr(P.learn);
-        if (L.has_reward && ready) {
-          int ws = ld_pub(L.wstate + e);
-          float acc = ld_pub(L.acc + e);
-          if (k == 0) {
-            if (L.pending && ld_pub_u8(L.pending + e)) ws |= LEARN_RESPAWN; /* the env spends step 0 on its re-spawn */
-          } else {
-            const int term = ld_pub_u8(L.terminated + e);
-            if constexpr (MODE == 2) {
-              const GQ_MODEL LearnFeetDev& LF = *mptr((const LearnFeetDev*)P.learn);
-              const FootLaw F = foot_law_load(LF.feet);
-              const bool air_on = F.w[FW_AIR_TIME] != 0.0f;
-              float* const air = LF.air_time + (size_t)e * 4;
-              float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-              if (!(ws & LEARN_RESPAWN)) {
-                const float* const row = obs + (size_t)e * od;
-                const bool earns = !(ws & LEARN_DEAD);
-                const RewardLaw R = reward_law_load(L.law);
-                /* every load of the visit is issued before the first word is used: the foot columns, the state, then the twelve terms' words */
-                FootIn fin;
-                foot_gather_row(F, [&](const int c) { return ld_pub(row + c); }, fin);
-                if (air_on) {
-#pragma unroll
-                  for (int i = 0; i < 4; i++) t[i] = ld_pub(air + i);
-                }
-                RewardIn in;
-                if (earns) {
-                  reward_gather_row(R, [&](const int c) { return ld_pub(row + c); }, in);
-                  if (reward_needs_u(R)) {
-#pragma unroll
-                    for (int j = 0; j < 12; j++) in.u[j] = ld_pub(MB.act + (size_t)e * 12 + j);
-                  }
-                  if (reward_needs_a(R)) {
-#pragma unroll
-                    for (int j = 0; j < 12; j++) { in.a[j] = ld_pub(P.held + (size_t)e * 12 + j); in.a_prev[j] = ld_pub(L.prev + (size_t)e * 12 + j); }
-                  }
-                }
-                {
-#pragma clang fp contract(off)
-                  if (earns) acc = acc + foot_reward_step(R, F, in, fin, term, t);
-                  else (void)foot_sum(F, fin, R.dt, 0.0f, t); /* a dead window's tail: the state advances, nothing is earned */
-                }
-                if (earns && term) ws |= LEARN_DEAD | LEARN_DONE;
-              }
-              if (air_on) { /* (t is still zero at the env's re-spawn step) */
-#pragma unroll
-                for (int i = 0; i < 4; i++) st_pub(air + i, t[i]);
-              }
-            } else
-            if (!(ws & (LEARN_DEAD | LEARN_RESPAWN))) {
-              const RewardLaw R = reward_law_load(L.law);
-              const float* const row = obs + (size_t)e * od;
-              RewardIn in;
-              reward_gather_row(R, [&](const int c) { return ld_pub(row + c); }, in);
-              if (reward_needs_u(R)) {
-#pragma unroll
-                for (int j = 0; j < 12; j++) in.u[j] = ld_pub(MB.act + (size_t)e * 12 + j);
-              }
-              if (reward_needs_a(R)) {
-#pragma unroll
-                for (int j = 0; j < 12; j++) { in.a[j] = ld_pub(P.held + (size_t)e * 12 + j); in.a_prev[j] = ld_pub(L.prev + (size_t)e * 12 + j); }
-              }
-              {
-#pragma clang fp contract(off)
-                acc = acc + reward_step(R, in, term);
-              }
-              if (term) ws |= LEARN_DEAD | LEARN_DONE;
-            }
-            ws = (ws & ~LEARN_RESPAWN) | (term ? LEARN_RESPAWN : 0);
-            if (k % D == 0) { /* the window k / D - 1 is complete */
-              const size_t at = (size_t)(k / D - 1) * N + e;
-              if (L.rewards) L.rewards[at] = acc;
-              if (L.dones) L.dones[at] = (uint8_t)((ws & LEARN_DONE) != 0);
-              acc = 0.0f;
-              ws &= LEARN_RESPAWN;
-            }
-          }
-          st_pub(L.acc + e, acc);
-          st_pub(L.wstate + e, ws);
-        }
+      if constexpr (LEARN) { /* the visit of the window law (gq_learn.h): step k - 1 is evaluated, the window flushed at k % D == 0 */
+        const GQ_MODEL LearnFeetDev& LF = *mptr(P.learn);
+        if (LF.learn.has_reward && ready) learn_visit<MODE == 2, LearnPub>(LF, obs + (size_t)e * od, MB.act + (size_t)e * 12, P.held + (size_t)e * 12, e, k, D, N);
       }
       /* (the observation words are read AFTER the count has been seen: the ballot below waits for every lane's count) */
       for (uint64_t todo = ballot(fresh); todo != 0;) {
@@ -517,21 +440,23 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         const int er = shfl_idx(e, src < 0 ? 0 : src);
         const float* const row = obs + (size_t)er * od;
         const float* const prev = P.last + (size_t)er * 12;
+        [[maybe_unused]] float* rec_row = nullptr; /* LEARN: the row as the network is fed it, before shift / scale */
         if constexpr (LEARN) {
           const int kr = shfl_idx(k, src < 0 ? 0 : src);
-          float* const rec = mptr(P.learn)->policy_obs;
-          float* const rec_row = rec ? rec + ((size_t)(kr / D) * N + er) * in_dim : nullptr;
-          mlp_tile_stage(net, xt[0], [&](const int, const int c) {
-            if (src < 0 || c >= in_dim) return 0.0f;
-            const float o = ld_pub(c < in_obs ? row + c : prev + (c - in_obs));
-            if (rec_row) rec_row[c] = o; /* the row as the network is fed it, before shift / scale */
-            return c < in_obs ? mlp_obs_in(o, shift, scale, c) : o;
-          });
-        } else
+          float* const rec = mptr(P.learn)->learn.policy_obs;
+          if (rec) rec_row = rec + ((size_t)(kr / D) * N + er) * in_dim;
+        }
         mlp_tile_stage(net, xt[0], [&](const int, const int c) {
           if (src < 0 || c >= in_dim) return 0.0f;
-          if (c < in_obs) return mlp_obs_in(ld_pub(row + c), shift, scale, c);
-          return ld_pub(prev + (c - in_obs));
+          const auto word = [&](const float* const p) { /* a device-scope load, recorded with LEARN */
+            const float o = ld_pub(p);
+            if constexpr (LEARN) {
+              if (rec_row) rec_row[c] = o;
+            }
+            return o;
+          };
+          if (c < in_obs) return mlp_obs_in(word(row + c), shift, scale, c);
+          return word(prev + (c - in_obs));
         });
         const float* const out = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
         if (fresh && ((tile >> lane) & 1)) {
@@ -542,7 +467,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
 #pragma clang fp contract(off)
             float v = out[j * GQ_MLP_ROWS + slot];
             if constexpr (LEARN) {
-              const GQ_MODEL LearnDev& L = *mptr(P.learn);
+              const GQ_MODEL LearnDev& L = mptr(P.learn)->learn;
               if (L.policy_means) L.policy_means[((size_t)(k / D) * N + e) * 12 + j] = v;
             }
             const float sg = P.sigma[j];
@@ -555,7 +480,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
             if (P.clip > 0.0f) v = fminf(fmaxf(v, -P.clip), P.clip);
             a[j] = v;
             if constexpr (LEARN) { /* the action before the held one; a_prev := a in the first window of a call */
-              const GQ_MODEL LearnDev& L = *mptr(P.learn);
+              const GQ_MODEL LearnDev& L = mptr(P.learn)->learn;
               if (L.has_reward) st_pub(L.prev + (size_t)e * 12 + j, k == 0 ? v : ld_pub(P.held + (size_t)e * 12 + j));
             }
             st_pub(P.held + (size_t)e * 12 + j, v);
@@ -633,60 +558,29 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const Pol
   }
 }
 
-/* the reward law alone over rows [n][od] (gq_reward_eval), lane = row: what policy_mlp_eval_* is for the network - the law's bits, to be compared
- * with the host's.  torques / act / act_prev: [n][12], read only by the terms that need them (may be NULL then); terminated: [n] or NULL. */
-__global__ void __launch_bounds__(GQ_WAVE) reward_eval_kernel(const LearnDev* __restrict__ Lp, const float* __restrict__ rows, const int od, const float* __restrict__ torques,
-                                                              const float* __restrict__ act, const float* __restrict__ act_prev, const uint8_t* __restrict__ terminated, const int n,
-                                                              float* __restrict__ out) {
-  const RewardLaw R = reward_law_load(mptr(Lp)->law);
-  const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
-  if (r >= n) return;
-  const float* const row = rows + (size_t)r * od;
-  RewardIn in;
-  reward_gather_row(R, [&](const int c) { return row[c]; }, in);
-  if (reward_needs_u(R)) {
-#pragma unroll
-    for (int j = 0; j < 12; j++) in.u[j] = torques[(size_t)r * 12 + j];
-  }
-  if (reward_needs_a(R)) {
-#pragma unroll
-    for (int j = 0; j < 12; j++) { in.a[j] = act[(size_t)r * 12 + j]; in.a_prev[j] = act_prev[(size_t)r * 12 + j]; }
-  }
-  out[r] = reward_step(R, in, terminated ? (int)terminated[r] : 0);
-}
-
-/* the law with the foot terms over rows (gq_reward_eval_feet), lane = row: air_in / air_out [n][4], the state before and after the row's step
- * (read and written only with air_time on; may be NULL then - and may be the same tensor: a lane reads its row before it writes it) */
-__global__ void __launch_bounds__(GQ_WAVE) reward_eval_feet_kernel(const LearnFeetDev* __restrict__ Lp, const float* __restrict__ rows, const int od, const float* __restrict__ torques,
-                                                                   const float* __restrict__ act, const float* __restrict__ act_prev, const uint8_t* __restrict__ terminated,
-                                                                   const float* air_in, const int n, float* __restrict__ out, float* air_out) {
+/* the step law alone over rows [n][od] (gq_reward_eval, and gq_reward_eval_feet with FEET), lane = row: what policy_mlp_eval_* is for the
+ * network - learn_step's bits, to be compared with the host's.  torques / act / act_prev: [n][12], read only by the terms that need them
+ * (may be NULL then); terminated: [n] or NULL.  FEET: air_in / air_out [n][4], the state before and after the row's step (read and written
+ * only with air_time on; may be NULL then - and may be the same tensor: a lane reads its row before it writes it) */
+template <bool FEET>
+__global__ void __launch_bounds__(GQ_WAVE) reward_eval_kernel(const LearnFeetDev* __restrict__ Lp, const float* __restrict__ rows, const int od, const float* __restrict__ torques,
+                                                              const float* __restrict__ act, const float* __restrict__ act_prev, const uint8_t* __restrict__ terminated,
+                                                              const float* air_in, const int n, float* __restrict__ out, float* air_out) {
   const RewardLaw R = reward_law_load(mptr(Lp)->learn.law);
-  const FootLaw F = foot_law_load(mptr(Lp)->feet);
+  FootLaw F;
+  if constexpr (FEET) F = foot_law_load(mptr(Lp)->feet);
   const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
   if (r >= n) return;
   const float* const row = rows + (size_t)r * od;
-  FootIn fin;
-  foot_gather_row(F, [&](const int c) { return row[c]; }, fin);
   float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  const bool air_on = F.w[FW_AIR_TIME] != 0.0f;
-  if (air_on) {
+  out[r] = learn_step<FEET>(R, F, true, terminated ? (int)terminated[r] : 0, [&](const int c) { return row[c]; }, [&](const int i) { return air_in[(size_t)r * 4 + i]; },
+                            [&](const int j) { return torques[(size_t)r * 12 + j]; }, [&](const int j) { return act[(size_t)r * 12 + j]; },
+                            [&](const int j) { return act_prev[(size_t)r * 12 + j]; }, t);
+  if constexpr (FEET) {
+    if (F.w[FW_AIR_TIME] != 0.0f) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) t[i] = air_in[(size_t)r * 4 + i];
-  }
-  RewardIn in;
-  reward_gather_row(R, [&](const int c) { return row[c]; }, in);
-  if (reward_needs_u(R)) {
-#pragma unroll
-    for (int j = 0; j < 12; j++) in.u[j] = torques[(size_t)r * 12 + j];
-  }
-  if (reward_needs_a(R)) {
-#pragma unroll
-    for (int j = 0; j < 12; j++) { in.a[j] = act[(size_t)r * 12 + j]; in.a_prev[j] = act_prev[(size_t)r * 12 + j]; }
-  }
-  out[r] = foot_reward_step(R, F, in, fin, terminated ? (int)terminated[r] : 0, t);
-  if (air_on) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) air_out[(size_t)r * 4 + i] = t[i];
+      for (int i = 0; i < 4; i++) air_out[(size_t)r * 4 + i] = t[i];
+    }
   }
 }
 
@@ -929,21 +823,19 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
-/* mode 0: gq_rollout_policy, 1: the learning half, 2: the learning half with the foot terms (mlp->learn is a LearnFeetDev) */
+/* mode 0: gq_rollout_policy, 1: the learning half, 2: the learning half with the foot terms */
 extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream) {
   if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<2>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
   else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<1>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
   else hipLaunchKernelGGL(gq::policy_mlp_kernel<0>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
 }
-extern "C" void gq_launch_reward_eval_feet(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
-                                           const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, hipStream_t stream) {
-  hipLaunchKernelGGL(gq::reward_eval_feet_kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, air_in, n, out, air_out);
+/* feet 0: gq_reward_eval (air_in / air_out are not looked at), 1: gq_reward_eval_feet */
+extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
+                                      const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, int feet, hipStream_t stream) {
+  const auto kernel = feet ? gq::reward_eval_kernel<true> : gq::reward_eval_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, air_in, n, out, air_out);
 }
 /* impl 0: mlp_row_forward, a thread per row; 1: mlp_tile_forward, a wavefront per 16 rows */
-extern "C" void gq_launch_reward_eval(const gq::LearnDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
-                                      const uint8_t* terminated, int n, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(gq::reward_eval_kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, n, out);
-}
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
   if (impl == 0) hipLaunchKernelGGL(gq::policy_mlp_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
   else hipLaunchKernelGGL(gq::policy_mlp_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);

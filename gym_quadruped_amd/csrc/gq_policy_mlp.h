@@ -296,7 +296,7 @@ __device__ __forceinline__ void mlp_tile_stage(const MlpNet& net, float* xt0, F 
 #endif /* __HIPCC__ */
 
 /* what a call of gq_rollout_policy hands to policy_mlp_kernel (device pointers), next to the MailboxDev it shares with the step side */
-struct LearnDev;
+struct LearnFeetDev;
 struct PolicyMlpDev {
   MlpNet net;
   int32_t in_obs, feed_last;    /* leading observation columns fed to the net; 1: the env's last action (12) follows them */
@@ -312,6 +312,6 @@ struct PolicyMlpDev {
   float* held;                  /* [N][12] the action the env tracks until its next policy step */
   float* last;                  /* [N][12] the env's previous policy action (feed_last) */
   float* policy_actions;        /* [n_steps / decimation][N][12] record, or NULL */
-  const LearnDev* learn;        /* gq_rollout_policy_learn's block (gq_reward.h): read by policy_mlp_kernel<true> alone */
+  const LearnFeetDev* learn;    /* a learning call's block (gq_learn.h): read by policy_mlp_kernel<1> and <2> alone */
 };
 }  // namespace gq

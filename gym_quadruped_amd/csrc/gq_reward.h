@@ -1,7 +1,7 @@
 /*
  * gq_reward.h - the task reward of the learning rollout (gq_rollout_policy_learn, gq_reward_eval): the law of ONE physics step's reward,
- * the block that carries a call's weights and columns to the device, and the per-env window bookkeeping of policy_mlp_kernel<1> (and <2>,
- * which adds the foot terms of gq_reward_feet.h).
+ * and the block that carries a call's weights and columns to the device.  gq_reward_feet.h continues the sum with the foot terms; the
+ * per-env window bookkeeping of policy_mlp_kernel<1 / 2> is gq_learn.h.
  * Plain C++ for host and device (tests/reward_host.cpp compiles it with g++): contraction off, IEEE +, -, * and fmaf only - the same
  * bits from any compiler.  The ORDER of the operations below is the definition.
  *
@@ -127,25 +127,8 @@ __host__ __device__ inline float reward_finish(const RewardLaw& R, const float S
 }
 __host__ __device__ inline float reward_step(const RewardLaw& R, const RewardIn& in, const int terminated) { return reward_finish(R, reward_sum(R, in), terminated); }
 
-/* what a call of gq_rollout_policy_learn adds to PolicyMlpDev (device pointers), and gq_reward_eval's whole block */
-struct LearnDev {
-  RewardLaw law;
-  int32_t has_reward, pad_;
-  const uint8_t* terminated;    /* [N] the batch's flag: the step side stores it before it publishes the step */
-  const uint8_t* pending;       /* [N] 1: the env re-spawns at its next step (next-step auto-reset), or NULL */
-  float* acc;                   /* [N] the window's reward so far (private to the env's lane) */
-  int32_t* wstate;              /* [N] bit 0: the window is dead, bit 1: it saw a termination, bit 2: the env's next step is its re-spawn */
-  float* prev;                  /* [N][12] the policy action before the held one */
-  float* rewards;               /* [n_steps / decimation][N] or NULL */
-  uint8_t* dones;               /* [n_steps / decimation][N] or NULL */
-  float* policy_obs;            /* [n_steps / decimation][N][in_dim] or NULL */
-  float* policy_means;          /* [n_steps / decimation][N][12] or NULL */
-};
-enum { LEARN_DEAD = 1, LEARN_DONE = 2, LEARN_RESPAWN = 4 };
-
-#if defined(__HIPCC__)
-/* the law out of the device block (constant address space: scalar loads) into registers */
-__device__ __forceinline__ RewardLaw reward_law_load(const GQ_MODEL RewardLaw& s) {
+/* the law out of the device block (constant address space: scalar loads) into registers; a plain copy on the host */
+__host__ __device__ __forceinline__ RewardLaw reward_law_load(const GQ_MODEL RewardLaw& s) {
   RewardLaw r;
 #pragma unroll
   for (int i = 0; i < GQ_REWARD_TERMS; i++) r.w[i] = s.w[i];
@@ -157,7 +140,4 @@ __device__ __forceinline__ RewardLaw reward_law_load(const GQ_MODEL RewardLaw& s
   for (int j = 0; j < 12; j++) r.col_qd[j] = s.col_qd[j];
   return r;
 }
-/* a flag byte that another wavefront stored earlier in this launch: device scope, as ld_pub (the vector L1 may hold the byte's old line) */
-__device__ __forceinline__ int ld_pub_u8(const uint8_t* p) { return (int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 }  // namespace gq

@@ -118,15 +118,8 @@ __host__ __device__ inline float foot_reward_step(const RewardLaw& R, const Foot
   return reward_finish(R, foot_sum(F, fin, R.dt, reward_sum(R, in), t), terminated);
 }
 
-/* gq_rollout_policy_learn_feet's / gq_reward_eval_feet's block: LearnDev (what policy_mlp_kernel<1> reads, at the same offsets) and the feet */
-struct LearnFeetDev {
-  LearnDev learn;
-  FootLaw feet;
-  float* air_time;              /* [N][4] the feet's air times, canonical order: caller-owned, in / out (private to the env's lane) */
-};
-
-#if defined(__HIPCC__)
-__device__ __forceinline__ FootLaw foot_law_load(const GQ_MODEL FootLaw& s) {
+/* as reward_law_load */
+__host__ __device__ __forceinline__ FootLaw foot_law_load(const GQ_MODEL FootLaw& s) {
   FootLaw f;
 #pragma unroll
   for (int i = 0; i < GQ_FOOT_TERMS; i++) f.w[i] = s.w[i];
@@ -136,5 +129,4 @@ __device__ __forceinline__ FootLaw foot_law_load(const GQ_MODEL FootLaw& s) {
   f.col_cmd_err[0] = s.col_cmd_err[0]; f.col_cmd_err[1] = s.col_cmd_err[1]; f.col_cmd_vel[0] = s.col_cmd_vel[0]; f.col_cmd_vel[1] = s.col_cmd_vel[1];
   return f;
 }
-#endif
 }  // namespace gq

@@ -441,7 +441,7 @@ class QuadrupedEnv(AccessorsMixin):
         THE LEARNING HALF (``gq_rollout_policy_learn``; with ``reward=None`` and ``record_transitions=False`` the call and the dict's keys
         are the ones above).  ``reward``: a ``RewardSpec`` - the policy seat evaluates the reward of every physics step from the
         observation row after it, the torques applied in it, the held action and the one before it and the ``terminated`` flag
-        (``csrc/gq_reward.h``), and sums it per decimation window ``s``, the form of ::
+        (``csrc/gq_reward.h``), and sums it per decimation window ``s`` (the window law: ``csrc/gq_learn.h`` is its definition), the form of ::
 
             acc, done, dead = float32(0), 0, False
             for k in range(D * s, D * s + D):
@@ -458,8 +458,8 @@ class QuadrupedEnv(AccessorsMixin):
 
         THE FOOT TERMS (``gq_rollout_policy_learn_feet``; a ``reward`` without ``feet``, or with every foot weight 0, is the call above):
         ``RewardSpec(..., feet=FootRewardSpec(...))`` continues every step's sum with air time, slip, impact and clearance
-        (``csrc/gq_reward_feet.h``).  The air times are ``env.feet_air_time``: they persist across calls, advance at every evaluated step -
-        also in the tail of a window after a fall, which earns nothing - and are zeroed at an env's re-spawn step."""
+        (``csrc/gq_reward_feet.h``).  The air times are ``env.feet_air_time``: they persist across calls, advance at every step but an env's
+        re-spawn step, which zeroes them - also in the tail of a window after a fall, which earns nothing."""
         K, D = int(n_steps), int(decimation)
         if K < 0:
             raise ValueError('n_steps must be >= 0')
@@ -497,18 +497,15 @@ class QuadrupedEnv(AccessorsMixin):
             g.rewards, g.dones = ptr(extra.get('rewards')), ptr(extra.get('dones'))
             g.policy_obs, g.policy_means = ptr(extra.get('policy_obs')), ptr(extra.get('policy_means'))
         self._hm_fresh = False
+        args = (self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
+                self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq))
         if learning and reward is not None and reward.feet_on:
             gf = reward.feet._struct(self._feet_air.data_ptr())
-            _lib.check(self._L.gq_rollout_policy_learn_feet(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out,
-                                                            self._auto_cfg, self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), C.byref(g),
-                                                            C.byref(gf), stream), 'gq_rollout_policy_learn_feet')
+            _lib.check(self._L.gq_rollout_policy_learn_feet(*args, C.byref(g), C.byref(gf), stream), 'gq_rollout_policy_learn_feet')
         elif learning:
-            _lib.check(self._L.gq_rollout_policy_learn(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out,
-                                                       self._auto_cfg, self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), C.byref(g),
-                                                       stream), 'gq_rollout_policy_learn')
+            _lib.check(self._L.gq_rollout_policy_learn(*args, C.byref(g), stream), 'gq_rollout_policy_learn')
         else:
-            _lib.check(self._L.gq_rollout_policy(self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg,
-                                                 self._episode.data_ptr(), self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq), stream), 'gq_rollout_policy')
+            _lib.check(self._L.gq_rollout_policy(*args, stream), 'gq_rollout_policy')
         self._launches += K
         if check:
             self.closed_loop_status()

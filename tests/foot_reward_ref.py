@@ -66,28 +66,38 @@ def foot_columns(spec, names=OBS_NAMES, legs_order=LEGS):
     return four('feet:contact') + four('feet:vx') + four('feet:vy') + four('feet:fz') + four('feet:zb') + list(cols.get('feet:cmd_err', (-1, -1))) + list(cols.get('feet:cmd_vel', (-1, -1)))
 
 
-def host_sequence(spec, rows, torques, a, a_prev, terminated, air=None, respawn=None, dt=DT, names=OBS_NAMES, legs_order=LEGS, sanitize=False):
-    """foot_reward_step (the definition) over T steps of S sequences with the state carried: rows [T, S, od], torques / a / a_prev [T, S, 12],
-    terminated / respawn [T, S], air [S, 4] (None: zeros) -> dict of reward [T, S] f32, air [T, S, 4] f32 (the state after every step),
-    gate [T, S] bool, impact [T, S, 4] bool (the law's threshold decisions)"""
+def host_sequence(spec, rows, torques, a, a_prev, terminated, air=None, D=0, pending=None, dt=DT, names=OBS_NAMES, legs_order=LEGS, sanitize=False):
+    """the host program (tests/foot_reward_host.cpp: learn_step and learn_visit of csrc/gq_learn.h, the definition) over K steps of S
+    sequences with the state carried: rows [K, S, od], torques / a / a_prev [K, S, 12], terminated [K, S], air [S, 4] (None: zeros) -> dict
+    of reward [K, S] f32, air [K, S, 4] f32 (the state after every step), gate [K, S] bool, impact [K, S, 4] bool (the law's threshold
+    decisions).  D = 0: the step law alone, whatever `terminated` says.  D >= 1: the window law with decimation D and pending [S] (None:
+    nobody waits for a re-spawn); the dict gains rewards [K // D, S] f32, dones [K // D, S] bool and air_final [S, 4]."""
     from gym_quadruped_amd.reward import FOOT_TERMS, TERMS, FootRewardSpec
     rows = np.ascontiguousarray(rows, dtype=np.float32)
-    T, S, od = rows.shape
+    K, S, od = rows.shape
     ft = spec.feet if spec.feet is not None else FootRewardSpec()
     head = np.asarray([spec.weights[t] for t in TERMS] + [spec.sigma_lin, spec.sigma_ang, spec.base_height_target, dt] + [ft.weights[t] for t in FOOT_TERMS]
                       + [ft.air_time_target, ft.min_cmd_speed, ft.impact_limit or 0.0, ft.clearance_target or 0.0], dtype=np.float32)
-    ints = np.asarray([S, T, od, *R.law_columns(spec, names), *foot_columns(spec, names, legs_order)], dtype=np.int32)
+    ints = np.asarray([S, K, od, D, *R.law_columns(spec, names), *foot_columns(spec, names, legs_order)], dtype=np.int32)
     air0 = np.zeros((S, 4), dtype=np.float32) if air is None else np.ascontiguousarray(air, dtype=np.float32).reshape(S, 4)
-    flag = lambda v: np.zeros((T, S, 1), dtype=np.float32) if v is None else np.asarray(v).reshape(T, S, 1).astype(np.float32)
-    f12 = lambda v: np.asarray(v, dtype=np.float32).reshape(T, S, 12)
-    body = np.concatenate([rows, f12(torques), f12(a), f12(a_prev), flag(terminated), flag(respawn)], axis=2)
+    pend = np.zeros(S, dtype=np.float32) if pending is None else np.asarray(pending).reshape(S).astype(np.float32)
+    flag = lambda v: np.zeros((K, S, 1), dtype=np.float32) if v is None else np.asarray(v).reshape(K, S, 1).astype(np.float32)
+    f12 = lambda v: np.asarray(v, dtype=np.float32).reshape(K, S, 12)
+    body = np.concatenate([rows, f12(torques), f12(a), f12(a_prev), flag(terminated)], axis=2)
     with tempfile.TemporaryDirectory() as d:
         src, dst = Path(d) / 'in.bin', Path(d) / 'out.bin'
-        np.concatenate([head.view(np.uint32), ints.view(np.uint32), air0.reshape(-1).view(np.uint32), np.ascontiguousarray(body).reshape(-1).view(np.uint32)]).tofile(src)
+        np.concatenate([head.view(np.uint32), ints.view(np.uint32), air0.reshape(-1).view(np.uint32), pend.view(np.uint32),
+                        np.ascontiguousarray(body).reshape(-1).view(np.uint32)]).tofile(src)
         subprocess.run([str(host_program(sanitize)), str(src), str(dst)], check=True)
-        out = np.fromfile(dst, dtype=np.float32).reshape(T, S, 7)
+        raw = np.fromfile(dst, dtype=np.float32)
+    out, tail = raw[:K * S * 7].reshape(K, S, 7), raw[K * S * 7:]
     mask = out[..., 6].astype(np.int64)
-    return dict(reward=out[..., 0].copy(), air=out[..., 1:5].copy(), gate=out[..., 5] != 0, impact=np.stack([(mask >> i) & 1 for i in range(4)], axis=-1).astype(bool))
+    res = dict(reward=out[..., 0].copy(), air=out[..., 1:5].copy(), gate=out[..., 5] != 0, impact=np.stack([(mask >> i) & 1 for i in range(4)], axis=-1).astype(bool))
+    if D > 0:
+        W = K // D
+        assert tail.size == 2 * W * S + 4 * S
+        res.update(rewards=tail[:W * S].reshape(W, S).copy(), dones=tail[W * S:2 * W * S].reshape(W, S) != 0, air_final=tail[2 * W * S:].reshape(S, 4).copy())
+    return res
 
 
 def host_rows(spec, rows, torques, a, a_prev, terminated, air=None, **kw):

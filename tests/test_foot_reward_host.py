@@ -12,13 +12,10 @@ import pytest
 
 import foot_reward_ref as F
 import reward_ref as R
+from learn_windows import _bits, _same, reference_windows
 
 ROOT = Path(__file__).resolve().parents[1]
 DT32 = np.float32(F.DT)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
 
 
 def _blank(T, S=1):
@@ -64,7 +61,8 @@ def test_the_first_contact_after_a_respawn_and_the_gate():
     feet = FootRewardSpec(air_time=1.0, air_time_target=0.0, min_cmd_speed=0.5)
     cols = _cols(feet)
     c, ce, cv = cols['feet:contact'], cols['feet:cmd_err'], cols['feet:cmd_vel']
-    # sequence 0: in the air, re-spawn at step 3 (the state is zeroed), landing at step 4 directly after it: nothing is earned
+    # sequence 0: in the air, falls at step 2 so that step 3 is its re-spawn (the state is zeroed), landing at step 4 directly after it:
+    # nothing is earned (decimation 1: every step is a window of its own, the step after the re-spawn earns again)
     # sequence 1: the same flight without the re-spawn, the command above the gate: the landing earns
     # sequence 2: the same flight, the command below the gate: the landing earns 0 - and the next flight starts from t = 0 all the same
     rows, u, a, ap, term = _blank(9, 3)
@@ -72,9 +70,9 @@ def test_the_first_contact_after_a_respawn_and_the_gate():
     rows[:, 2, ce[0]] = -0.25                               # 0.25: below
     rows[4, :, c[0]] = 1.0                                  # FL lands at step 4 ...
     rows[7:, :, c[0]] = 1.0                                 # ... flies steps 5, 6 and lands again at 7
-    respawn = np.zeros((9, 3), dtype=np.uint8)
-    respawn[3, 0] = 1
-    out = F.host_sequence(_feet_only(feet), rows, u, a, ap, term, respawn=respawn)
+    term[2, 0] = 1
+    out = F.host_sequence(_feet_only(feet), rows, u, a, ap, term, D=1)
+    assert out['dones'][:, 0].tolist() == [k == 2 for k in range(9)] and out['reward'][3, 0] == 0 and out['rewards'][3, 0] == 0
     assert (out['air'][3, 0] == 0).all(), 'the re-spawn step zeroes the state'
     assert out['reward'][4, 0] == 0 and out['reward'][4, 1] > 0 and out['reward'][4, 2] == 0
     assert out['gate'][:, 1].all() and not out['gate'][:, 2].any()
@@ -154,6 +152,48 @@ def test_against_the_float64_restatement_with_the_state_carried(name, twelve):
         assert host['gate'].any() and not host['gate'].all() or not feet.gated
     if feet.impact != 0.0:
         assert host['impact'].any() and not host['impact'].all()
+
+
+def _window_input(D, K, S=64, seed=3):
+    """rows from random_sequences; `terminated` drawn with probability 0.1, `pending` with 0.25"""
+    rng = np.random.default_rng(seed + 3000)
+    rows, u, a, ap, _ = F.random_sequences(S=S, T=K, seed=seed)
+    return (rows, u, a, ap, rng.uniform(size=(K, S)) < 0.1), rng.uniform(size=S) < 0.25
+
+
+WINDOW_SPECS = {'both': lambda: F.with_feet(F.foot_full()), 'twelve': lambda: F.with_feet(None), 'feet': lambda: _feet_only(F.foot_full())}
+
+
+@pytest.mark.parametrize('D,mult', [(D, m) for D in (1, 4) for m in (1, 2, 12)])
+@pytest.mark.parametrize('name', list(WINDOW_SPECS))
+def test_the_window_law_on_the_host_is_the_reference_loop(name, D, mult):
+    """learn_visit (csrc/gq_learn.h) played by the host program for k = 0..K against learn_windows.reference_windows over the program's own
+    per-step rewards: rewards, dones and the final air times, bit for bit.  The air times of the reference are restated here: t + dt in
+    float32, 0 in contact."""
+    spec, K, S = WINDOW_SPECS[name](), D * mult, 64
+    (rows, u, a, ap, term), pending = _window_input(D, K, S)
+    air0 = (np.random.default_rng(7).uniform(0.0, 0.3, (S, 4)) * (np.random.default_rng(8).uniform(size=(S, 4)) > 0.5)).astype(np.float32)
+    out = F.host_sequence(spec, rows, u, a, ap, term, air=air0, D=D, pending=pending)
+    contact = rows[:, :, F.contact_columns()] != 0
+    feet_on = spec.feet is not None
+    step = lambda k, s, t: out['reward'][k] if t is None else (out['reward'][k], np.where(contact[k], np.float32(0.0), t + DT32).astype(np.float32))
+    over = rows[:, :, list(_cols(spec.feet)['feet:fz'])] > np.float32(spec.feet.impact_limit) if feet_on else None
+    want_r, want_d, want_air, seen = reference_windows(step, term, pending, D, air=air0.copy() if feet_on else None, contact=contact, over_limit=over)
+    assert out['rewards'].dtype == np.float32 and want_r.dtype == np.float32 and np.isfinite(want_r).all()
+    assert np.array_equal(out['dones'], want_d)
+    assert _same(out['rewards'], want_r), float(np.abs(out['rewards'] - want_r).max())
+    assert _same(out['air_final'], want_air if feet_on else air0) and _same(out['air'][-1], out['air_final'])
+    # the drawn input contains every case the law distinguishes
+    assert pending.any() and not pending.all(), 'an env that waits for its re-spawn at k = 0, and one that does not'
+    assert seen['last_step_earns'] > 0 and (want_r[-1] != 0).any(), 'the closing visit earns in the last window'
+    if mult == 12:
+        assert (~want_d).any(), 'a window without a termination'
+        assert seen['done_at'][0] > 0 and seen['done_at'][D - 1] > 0 and (D == 1 or sum(seen['done_at'][1:D - 1]) > 0), 'a termination at the first, a middle, the last substep'
+        assert seen['respawn_inside'] > 0 or D == 1
+        if D > 1:
+            assert seen['dead_tail_steps'] > 0, 'a dead-tail step that is not the re-spawn'
+            assert not feet_on or seen['dead_tail_landings'] > 0, 'a landing with t > 0 inside a dead tail'
+        assert not feet_on or ((seen['landings'] > 0).all() and seen['impacts'] > 0)
 
 
 def test_columns_point_at_the_same_physical_foot_for_two_legs_orders():
@@ -252,3 +292,7 @@ def test_the_host_program_is_clean_under_the_sanitizers():
         assert np.array_equal(_bits(got), _bits(want)) and np.array_equal(_bits(got_air), _bits(want_air))
     seq = F.random_sequences(S=8, T=50, seed=1)
     assert np.array_equal(_bits(F.host_sequence(spec, *seq, sanitize=True)['reward']), _bits(F.host_sequence(spec, *seq)['reward']))
+    for D, K in ((1, 12), (4, 48)):   # ... and over the window law's inputs (test_the_window_law_on_the_host_is_the_reference_loop)
+        steps, pending = _window_input(D, K)
+        got, want = (F.host_sequence(spec, *steps, D=D, pending=pending, sanitize=san) for san in (True, False))
+        assert all(np.array_equal(got[k], want[k]) if got[k].dtype == bool else _same(got[k], want[k]) for k in want)

@@ -16,8 +16,8 @@ import torch
 import foot_reward_ref as F
 import policy_mlp_ref as PR
 import reward_ref as R
+from learn_windows import _replay_flags, _same, reference_windows
 from test_gpu_closed_loop import STATE, _env, _twin
-from test_gpu_learn_rollout import _replay_flags, _same
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -78,32 +78,14 @@ def test_the_law_on_the_device(handle, law_rows, name):
         assert _same(handle.reward_eval(spec, *dev), handle.reward_eval(spec, *dev, feet_air=dair)[0])
 
 
-def _reference_windows(env, spec, rows, term, torques, pol, pending, D, air):
-    """the loop of the issue, every env at once: test_gpu_learn_rollout's with the air times carried per step - zeroed at a re-spawn step,
-    advanced by the law at every other step whether or not the window is dead.  Returns rewards, dones, the final state and what the
-    workload contained."""
-    K, n = rows.shape[0], rows.shape[1]
-    cols = spec.feet.columns(OBS, env.legs_order)
-    rewards, dones = torch.zeros(K // D, n, device=DEV), torch.zeros(K // D, n, dtype=torch.bool, device=DEV)
-    air = air.clone()
-    seen = dict(landings=torch.zeros(4, dtype=torch.long, device=DEV), respawn_inside=0, dead_tail_steps=0, impacts=0)
-    for s in range(K // D):
-        acc, done, dead = torch.zeros(n, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV)
-        for k in range(D * s, D * s + D):
-            respawn = term[k - 1] if k > 0 else pending
-            r_k, air_next = env.reward_eval(spec, rows[k], torques[k], pol[s], pol[s - 1] if s > 0 else pol[0], term[k], feet_air=air)
-            contact = rows[k][:, list(cols['feet:contact'])] != 0
-            seen['landings'] += (contact & (air > 0) & ~respawn[:, None]).sum(0)
-            seen['respawn_inside'] += int((respawn & (k % D != 0)).sum())
-            seen['dead_tail_steps'] += int((dead & ~respawn).sum())
-            seen['impacts'] += int(((rows[k][:, list(cols['feet:fz'])] > IMPACT_LIMIT) & ~respawn[:, None]).sum())
-            air = torch.where(respawn[:, None], torch.zeros_like(air), air_next)
-            earn = ~dead & ~respawn
-            acc = torch.where(earn, acc + r_k, acc)
-            done = done | (earn & term[k])
-            dead = dead | (earn & term[k])
-        rewards[s], dones[s] = acc, done
-    return rewards, dones, air, seen
+def _windows(env, spec, rows, term, torques, pol, pending, D, air, names=OBS):
+    """learn_windows.reference_windows with reward_eval(feet_air=) as the step's reward and next state.  Returns rewards, dones, the final
+    state and what the workload contained."""
+    cols = spec.feet.columns(names, env.legs_order)
+    step = lambda k, s, t: env.reward_eval(spec, rows[k], torques[k], pol[s], pol[s - 1] if s > 0 else pol[0], term[k], feet_air=t)
+    contact = rows[:, :, list(cols['feet:contact'])] != 0
+    over = rows[:, :, list(cols['feet:fz'])] > IMPACT_LIMIT if 'feet:fz' in cols else None
+    return reference_windows(step, term, pending, D, air=air.clone(), contact=contact, over_limit=over)
 
 
 @pytest.mark.parametrize('robot,n,K,scene', [('mini_cheetah', 131, 48, 'flat'), ('go2', 256, 24, 'flat'), ('mini_cheetah', 64, 24, 'stairs')])
@@ -120,14 +102,15 @@ def test_the_rollout_is_the_reference_loop(robot, n, K, scene):
         r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, reward=spec)
         code, _, played = b.closed_loop_status()
         assert code == 0 and played == n * K
-        rows, term = _replay_flags(a, b, r, K)
-        want_r, want_d, want_air, seen = _reference_windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D, air)
+        rows, term = _replay_flags(a, b, r, K, STATE)
+        want_r, want_d, want_air, seen = _windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D, air)
         assert torch.equal(r['dones'], want_d)
         assert _same(r['rewards'], want_r), float((r['rewards'] - want_r).abs().max())   # every env, every window
         assert _same(b.feet_air_time, want_air), float((b.feet_air_time - want_air).abs().max())
         assert torch.isfinite(r['rewards']).all()
         for k, v in seen.items():
-            total[k] = total[k] + v
+            if k in total:
+                total[k] = total[k] + v
         print(f'{robot} {scene} n={n} call {call}: windows with done {int(r["dones"].sum())}, pending {int(pending.sum())}, landings per foot {seen["landings"].tolist()}, '
               f're-spawns inside a window {seen["respawn_inside"]}, dead-tail steps {seen["dead_tail_steps"]}, steps with fz over the limit {seen["impacts"]}')
     if robot == 'mini_cheetah' and scene == 'flat':   # the workload is not empty
@@ -201,8 +184,8 @@ def test_edge_sizes_and_the_closing_visit(n, D):
         air = b.feet_air_time.clone()
         r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, reward=spec)
         assert b.closed_loop_status()[2] == n * K
-        rows, term = _replay_flags(a, b, r, K)
-        want_r, want_d, want_air, _ = _reference_windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D, air)
+        rows, term = _replay_flags(a, b, r, K, STATE)
+        want_r, want_d, want_air, _ = _windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D, air)
         assert _same(r['rewards'], want_r) and torch.equal(r['dones'], want_d) and _same(b.feet_air_time, want_air), K
         # step K - 1 alone: the state before it, through the law once, is the state after the call
         cols = spec.feet.columns(OBS)
@@ -281,17 +264,6 @@ def test_refusals_leave_the_batch_usable():
     air = env.feet_air_time.clone()
     r = env.rollout_policy(8, p, KP, KD, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, reward=ok)
     assert env.closed_loop_status()[2] == n * 8
-    rows, term = _replay_flags(a, env, r, 8)
-    K, cols = 8, ok_feet.columns(names)
-    rewards = torch.zeros(K // D, n, device=DEV)
-    for s in range(K // D):   # (the reference loop without the impact column's tallies)
-        acc, dead = torch.zeros(n, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV)
-        for k in range(D * s, D * s + D):
-            respawn = term[k - 1] if k > 0 else pending
-            r_k, air_next = env.reward_eval(ok, rows[k], r['actions'][k], r['policy_actions'][s], r['policy_actions'][s - 1 if s > 0 else 0], term[k], feet_air=air)
-            air = torch.where(respawn[:, None], torch.zeros_like(air), air_next)
-            earn = ~dead & ~respawn
-            acc = torch.where(earn, acc + r_k, acc)
-            dead = dead | (earn & term[k])
-        rewards[s] = acc
-    assert _same(r['rewards'], rewards) and _same(env.feet_air_time, air) and len(cols) > 0
+    rows, term = _replay_flags(a, env, r, 8, STATE)
+    want_r, _, want_air, _ = _windows(env, ok, rows, term, r['actions'], r['policy_actions'], pending, D, air, names=names)
+    assert _same(r['rewards'], want_r) and _same(env.feet_air_time, want_air) and len(ok_feet.columns(names)) > 0

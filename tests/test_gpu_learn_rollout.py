@@ -15,6 +15,7 @@ import torch
 
 import policy_mlp_ref as PR
 import reward_ref as R
+from learn_windows import _replay_flags, _same, reference_windows
 from test_gpu_closed_loop import STATE, _env, _twin
 
 pytestmark = pytest.mark.gpu
@@ -22,14 +23,6 @@ DEV = 'cuda:0'
 KP, KD, SCALE = 25.0, 0.8, 0.25
 OBS = R.OBS_NAMES
 ROW_COUNTS = (1, 63, 64, 65, 131)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 @pytest.fixture(scope='module')
@@ -87,37 +80,10 @@ def test_the_records_are_what_the_network_saw_and_said():
     assert float((pol - means).abs().max()) > 0.05
 
 
-def _replay_flags(a, b, r, K):
-    """the recorded torques through the step loop on the twin: the rows and `terminated` after every step; the states end bit-equal"""
-    rows, term = [], []
-    for k in range(K):
-        a.step(r['actions'][k])
-        rows.append(a._obs_buf.clone())
-        term.append(a._terminated.clone())
-    torch.cuda.synchronize()
-    for f in STATE:
-        assert torch.equal(getattr(a, f), getattr(b, f)), f
-    rows = torch.stack(rows)
-    if r['obs_seq'] is not None:
-        assert torch.equal(rows, r['obs_seq'])
-    return rows, torch.stack(term).bool()
-
-
-def _reference_windows(env, spec, rows, term, torques, pol, pending, D):
-    """the loop of the issue, every env at once: reward_eval per step, float32 adds in k order"""
-    K, n = rows.shape[0], rows.shape[1]
-    rewards, dones = torch.zeros(K // D, n, device=DEV), torch.zeros(K // D, n, dtype=torch.bool, device=DEV)
-    for s in range(K // D):
-        acc, done, dead = torch.zeros(n, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV)
-        for k in range(D * s, D * s + D):
-            respawn = term[k - 1] if k > 0 else pending
-            r_k = env.reward_eval(spec, rows[k], torques[k], pol[s], pol[s - 1] if s > 0 else pol[0], term[k])
-            earn = ~dead & ~respawn
-            acc = torch.where(earn, acc + r_k, acc)
-            done = done | (earn & term[k])
-            dead = dead | (earn & term[k])
-        rewards[s], dones[s] = acc, done
-    return rewards, dones
+def _windows(env, spec, rows, term, torques, pol, pending, D):
+    """learn_windows.reference_windows with reward_eval as the step's reward"""
+    step = lambda k, s, air: env.reward_eval(spec, rows[k], torques[k], pol[s], pol[s - 1] if s > 0 else pol[0], term[k])
+    return reference_windows(step, term, pending, D)[:2]
 
 
 @pytest.mark.parametrize('robot,n,K', [('mini_cheetah', 131, 24), ('go2', 1000, 20)])
@@ -132,8 +98,8 @@ def test_the_reward_is_the_reference_loop(robot, n, K):
         code, _, played = b.closed_loop_status()
         assert code == 0 and played == n * K
         assert r['rewards'].shape == (K // D, n) and r['rewards'].dtype == torch.float32 and r['dones'].shape == (K // D, n) and r['dones'].dtype == torch.bool
-        rows, term = _replay_flags(a, b, r, K)
-        want_r, want_d = _reference_windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D)
+        rows, term = _replay_flags(a, b, r, K, STATE)
+        want_r, want_d = _windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D)
         assert torch.equal(r['dones'], want_d)
         assert _same(r['rewards'], want_r), float((r['rewards'] - want_r).abs().max())   # every env, every window
         assert torch.isfinite(r['rewards']).all() and float(r['rewards'].abs().max()) > 0
@@ -159,8 +125,8 @@ def test_edge_sizes_the_last_step_and_the_first_window(n, step_waves, D):
                                  record_transitions=True)
             code, _, played = b.closed_loop_status()
             assert code == 0 and played == n * K
-            rows, term = _replay_flags(a, b, r, K)
-            want_r, want_d = _reference_windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D)
+            rows, term = _replay_flags(a, b, r, K, STATE)
+            want_r, want_d = _windows(b, spec, rows, term, r['actions'], r['policy_actions'], pending, D)
             assert _same(r['rewards'], want_r) and torch.equal(r['dones'], want_d), (K, float((r['rewards'] - want_r).abs().max()))
             if spec is rate:
                 assert (r['rewards'][0] == 0).all(), 'action_rate is 0 in the first window of a call'
@@ -185,7 +151,7 @@ def test_observing_changes_nothing():
     # the mailbox machinery is as it was: a plain closed-loop rollout on the observed batch still equals the step loop
     r = b.rollout_closed_loop(10, KP, KD, mode='mailbox', record_obs=True, record_actions=True)
     assert b.closed_loop_status()[2] == n * 10
-    _replay_flags(a, b, r, 10)
+    _replay_flags(a, b, r, 10, STATE)
 
 
 def _raw(env, m, g, K=4):
@@ -243,6 +209,6 @@ def test_refusals_leave_the_batch_usable():
     pending = env._terminated.clone().bool()
     r = env.rollout_policy(8, p, KP, KD, record_obs=True, record_actions=True, reward=ok, record_transitions=True)
     assert env.closed_loop_status()[2] == n * 8
-    rows, term = _replay_flags(a, env, r, 8)
-    want_r, want_d = _reference_windows(env, ok, rows, term, r['actions'], r['policy_actions'], pending, 4)
+    rows, term = _replay_flags(a, env, r, 8, STATE)
+    want_r, want_d = _windows(env, ok, rows, term, r['actions'], r['policy_actions'], pending, 4)
     assert _same(r['rewards'], want_r) and torch.equal(r['dones'], want_d)
