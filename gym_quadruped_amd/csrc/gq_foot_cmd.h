@@ -78,7 +78,8 @@ __device__ __forceinline__ void foot_cmd_chain(const float* o0, const float* o1,
   for (int i = 0; i < 3; i++) tau[i] = dot(J[i], F) + c.tau_ff[i];
 }
 /* The two halves put together over plain arguments: the entry of the host test (tests/test_foot_cmd_host.py).  The kernel calls the halves
- * itself, with LDS in between (foot_cmd_inline, gq_kernels.hip); that hand-over is covered by the GPU law-value test, not by the host run. */
+ * itself, with LDS in between (foot_cmd_inline, gq_step_driver.h); that hand-over is covered by the GPU law-value test and, under the host
+ * emulator, by tests/test_window_emulated.py - not by that host run. */
 __device__ __forceinline__ void foot_cmd_law(const GqDevLinkRec& L0, const GqDevLinkRec& L1, const GqDevLinkRec& L2, const float* foot /* [3] calf frame */,
                                              const float* q /* [3] */, const float* qd /* [3] */, const float* qb /* [4] */, const FootCmd& c, const int frame,
                                              float* tau /* [3] out */) {

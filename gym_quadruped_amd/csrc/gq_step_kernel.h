@@ -84,6 +84,9 @@ constexpr bool scene_boxes(Scene s) { return s == SCENE_WORLD_HULL || s == SCENE
 constexpr bool scene_self(Scene s) { return s != SCENE_FLAT; }
 constexpr bool scene_prim(Scene s) { return s != SCENE_WORLD_HULL && s != SCENE_FLAT_SELF_HULL; }
 constexpr bool scene_cvx(Scene s) { return s != SCENE_FLAT_SELF_PRIM && s != SCENE_FLAT; }
+/* the CVX template argument of a scene's kernels: false for a self stage without the convex block (the _prim kernels); SCENE_FLAT has no
+ * self stage at all and keeps the default */
+constexpr bool kernel_cvx(Scene s) { return scene_cvx(s) || !scene_self(s); }
 /* A step-kernel variant is a Key: solver (0 PGS, 1 Newton), mode (0 production; 1 debug record + stage timers; 2 stage cut,
  * gq_debug_stop_stage - its early returns cost the production kernel ~8 % when merely compiled in), cone (1 elliptic, Newton only:
  * gq_model_create rejects it with PGS), scene, and mailbox (1: the closed-loop rollout's mailbox_step_kernel, production Newton only; 0:

@@ -85,20 +85,22 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def emu_step(mm, ctrl, qpos, qvel, warm=None, applied=None, time=None, friction=None, cmd=None, obs_names=ALL_OBS,
-             legs_order=(0, 1, 2, 3), mask=None, debug_envs=0, auto_reset=None, episode=None, first_pass=0, imu=None,
-             imu_bias=None, step_num=None, pending=None, lift_pending=None, friction_next=None, lift_failed=None):
-    """Run the kernel body under the emulator. Arrays are updated in place like the device tensors would be."""
-    L = emu_lib()
+def _emu_launch_args(mm, ctrl, ctrl_shape, qpos, qvel, warm=None, applied=None, time=None, friction=None, cmd=None, obs_names=ALL_OBS,
+                     legs_order=(0, 1, 2, 3), mask=None, debug_envs=0, auto_reset=None, episode=None, first_pass=0, imu=None,
+                     imu_bias=None, step_num=None, pending=None, lift_pending=None, friction_next=None, lift_failed=None, obs=None):
+    """The host tensors of an emulated step launch and the two runs of arguments both step entries of the emulator take
+    (tests/simt_emu/emu_step.cpp): (st, model ... step_num, auto_reset ... lift_pending).  ctrl None: zeros of ctrl_shape, or no tensor
+    at all where ctrl_shape is None.  obs: the observation rows an earlier launch left (the inline PD policy reads them)."""
     n = qpos.shape[0]
     ids = np.asarray(obs_ids_from_names(obs_names), dtype=np.int32)
     od = int(sum(OBS_DIMS[i] for i in ids))
     f32 = lambda a, shape: np.zeros(shape, np.float32) if a is None else np.ascontiguousarray(a, dtype=np.float32)
     st = dict(
-        ctrl=f32(ctrl, (n, 12)), qpos=np.ascontiguousarray(qpos, dtype=np.float64), qvel=f32(qvel, (n, 18)),
+        ctrl=None if ctrl is None and ctrl_shape is None else f32(ctrl, ctrl_shape),
+        qpos=np.ascontiguousarray(qpos, dtype=np.float64), qvel=f32(qvel, (n, 18)),
         qacc=np.zeros((n, 18), np.float32), warm=f32(warm, (n, 18)), applied=f32(applied, (n, 18)),
         time=f32(time, (n,)), friction=np.full(n, -1, np.float32) if friction is None else f32(friction, (n,)),
-        cmd=f32(cmd, (n, 4)), obs=np.zeros((n, od), np.float32), reward=np.zeros(n, np.float32),
+        cmd=f32(cmd, (n, 4)), obs=f32(obs, (n, od)), reward=np.zeros(n, np.float32),
         terminated=np.zeros(n, np.uint8), truncated=np.zeros(n, np.uint8), invalid=np.zeros(n, np.uint8),
         step_num=np.zeros(n, np.int32) if step_num is None else np.ascontiguousarray(step_num, dtype=np.int32), debug=np.zeros((max(debug_envs, 1), DBG_SIZE), np.float32),
         episode=np.zeros(n, np.int32) if episode is None else np.ascontiguousarray(episode, dtype=np.int32),
@@ -107,18 +109,64 @@ def emu_step(mm, ctrl, qpos, qvel, warm=None, applied=None, time=None, friction=
         lift_pending=np.zeros(n, np.uint8) if lift_pending is None else np.ascontiguousarray(lift_pending, dtype=np.uint8),
         pending=np.zeros(n, np.uint8) if pending is None else np.ascontiguousarray(pending, dtype=np.uint8),
         imu_bias=np.zeros((n, 6), np.float32) if imu_bias is None else np.ascontiguousarray(imu_bias, dtype=np.float32))
-    lo = np.asarray(legs_order, dtype=np.int32)
+    st['obs_names'] = list(obs_names)
+    # (the arrays the calls only read are kept alive by the dict)
+    st['_ids'], st['_legs'], st['_mask'] = ids, np.asarray(legs_order, dtype=np.int32), None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    head = [C.byref(mm.desc), n, _p(ids), len(ids), _p(st['_legs']), _p(st['ctrl']), _p(st['_mask']), _p(st['qpos']), _p(st['qvel']),
+            _p(st['qacc']), _p(st['warm']), _p(st['applied']), _p(st['time']), _p(st['friction']), _p(st['cmd']),
+            _p(st['obs']), _p(st['reward']), _p(st['terminated']), _p(st['truncated']), _p(st['invalid']), _p(st['step_num'])]
+    tail = [None if auto_reset is None else C.byref(auto_reset), _p(st['episode']), _p(st['lift_failed']), _p(st['friction_next']), int(first_pass),
+            None if imu is None else C.byref(imu), _p(st['imu_bias']), _p(st['pending']), _p(st['lift_pending'])]
+    return st, head, tail
+
+
+def emu_step(mm, ctrl, qpos, qvel, debug_envs=0, **kw):
+    """Run the instrumented step kernel (mode 1) under the emulator. Arrays are updated in place like the device tensors would be."""
+    st, head, tail = _emu_launch_args(mm, ctrl, (qpos.shape[0], 12), qpos, qvel, debug_envs=debug_envs, **kw)
     err = C.create_string_buffer(512)
-    m8 = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    rc = L.emu_step(C.byref(mm.desc), n, _p(ids), len(ids), _p(lo), _p(st['ctrl']), _p(m8), _p(st['qpos']), _p(st['qvel']),
-                    _p(st['qacc']), _p(st['warm']), _p(st['applied']), _p(st['time']), _p(st['friction']), _p(st['cmd']),
-                    _p(st['obs']), _p(st['reward']), _p(st['terminated']), _p(st['truncated']), _p(st['invalid']),
-                    _p(st['step_num']), _p(st['debug']), debug_envs, None if auto_reset is None else C.byref(auto_reset),
-                    _p(st['episode']), _p(st['lift_failed']), _p(st['friction_next']), int(first_pass),
-                    None if imu is None else C.byref(imu), _p(st['imu_bias']), _p(st['pending']), _p(st['lift_pending']), err, 512)
+    rc = emu_lib().emu_step(*head, _p(st['debug']), debug_envs, *tail, err, 512)
     if rc < 0:
         raise RuntimeError(err.value.decode())
-    st['obs_names'] = list(obs_names)
+    return st
+
+
+class PolicyPdDev(C.Structure):   # csrc/gq_step_kernel.h
+    _fields_ = [('kp', C.c_float * 12), ('kd', C.c_float * 12), ('qdes', C.c_float * 12), ('col_q', C.c_int32 * 12), ('col_qd', C.c_int32 * 12),
+                ('sigma', C.c_float), ('seed_lo', C.c_uint32), ('seed_hi', C.c_uint32), ('step0', C.c_int32), ('env_id_offset', C.c_int32)]
+
+
+class JointCmdDev(C.Structure):   # csrc/gq_joint_cmd.h
+    _fields_ = [('q_des', C.c_void_p), ('qd_des', C.c_void_p), ('tau_ff', C.c_void_p), ('kp', C.c_void_p), ('kd', C.c_void_p),
+                ('tau_out', C.c_void_p), ('term_any', C.c_void_p), ('gain_stride', C.c_int32), ('pad_', C.c_int32)]
+
+
+class FootCmdDev(C.Structure):   # csrc/gq_foot_cmd.h
+    _fields_ = [('p_des', C.c_void_p), ('v_des', C.c_void_p), ('f_ff', C.c_void_p), ('tau_ff', C.c_void_p), ('kp', C.c_void_p), ('kd', C.c_void_p),
+                ('tau_out', C.c_void_p), ('term_any', C.c_void_p), ('gain_stride', C.c_int32), ('frame', C.c_int32)]
+
+
+_POLICY_KINDS = (PolicyPdDev, JointCmdDev, FootCmdDev)   # emu_step_window's policy_kind
+
+
+def emu_window(mm, ctrl_seq, qpos, qvel, n_steps=1, policy=None, obs_seq=False, act_seq=False, **kw):
+    """Run the production step kernels (mode 0) under the emulator, as the library launches them: the single-step kernel, or - with
+    n_steps > 1 or a policy - the persistent window of n_steps steps per env in one launch.  ctrl_seq [n_steps][N][12] or None (an inline
+    policy, or zero control); policy: a PolicyPdDev, JointCmdDev or FootCmdDev whose pointers name arrays the caller keeps alive; obs_seq /
+    act_seq: record every step's observation rows / actions into st['obs_seq'] [n_steps][N][obs_dim] / st['act_seq'] [n_steps][N][12].
+    Arrays are updated in place like emu_step's."""
+    L = emu_lib()
+    sizes = (C.c_int * 3)()
+    L.emu_policy_sizes(sizes)
+    assert list(sizes) == [C.sizeof(t) for t in _POLICY_KINDS], 'the policy blocks of helpers.py do not mirror the library\'s'
+    n = qpos.shape[0]
+    st, head, tail = _emu_launch_args(mm, ctrl_seq, None if ctrl_seq is None else (n_steps, n, 12), qpos, qvel, **kw)
+    st['obs_seq'] = np.zeros((n_steps, n, st['obs'].shape[1]), np.float32) if obs_seq else None
+    st['act_seq'] = np.zeros((n_steps, n, 12), np.float32) if act_seq else None
+    kind = 0 if policy is None else _POLICY_KINDS.index(type(policy))
+    err = C.create_string_buffer(512)
+    rc = L.emu_step_window(*head, *tail, n * 12, int(n_steps), _p(st['obs_seq']), _p(st['act_seq']), kind, None if policy is None else C.byref(policy), err, 512)
+    if rc < 0:
+        raise RuntimeError(err.value.decode())
     return st
 
 

@@ -1,13 +1,16 @@
-/* TEST INFRASTRUCTURE - runs the unmodified step kernel body (csrc/gq_step_body.h) under the host SIMT emulator.
- * Exposes a C entry point with the same tensors as gq_step, operating on host memory.  The argument blocks are filled by the library's
- * gq_step_call.h and the instantiation is picked by its step_key / for_variant (gq_step_kernel.h).  The re-spawn loop around step_wave is
- * still written out here: shared with gq::step_kernel as a function it changed the instruction streams of that kernel's variants. */
+/* TEST INFRASTRUCTURE - runs the unmodified step kernels under the host SIMT emulator: their driver gq::step_kernel_body
+ * (csrc/gq_step_driver.h: the persistent step loop, the re-spawn loop, the inline policies) around the step itself (csrc/gq_step_body.h), one
+ * wavefront after the other.  Two C entry points over host memory: emu_step, the instrumented kernel (mode 1) with the tensors of gq_step,
+ * and emu_step_window, the production kernels (mode 0) as launch_variant (csrc/gq_kernels.hip) picks them - single step, persistent window,
+ * foot-space window.  The argument blocks are filled by the library's gq_step_call.h; the instantiation comes from its step_key /
+ * for_variant / kernel_cvx (gq_step_kernel.h).  Not here: the mailbox side and the policy kernels, whose protocol needs concurrent wavefronts. */
 #include <functional>
 #include <vector>
 #include <cstdio>
 
 #include "gq_device.h"          /* the emulator shim (this directory comes first on the include path) */
 #include "gq_step_call.h"
+#include "gq_step_driver.h"
 #include "emu_model.h"
 #include "hfield_probe.h"
 #include <cstring>
@@ -28,18 +31,17 @@ static gq::BatchPtrs emu_ptrs(EmuModel& m, GqDevBatch* B, float* friction_next, 
   return p;
 }
 
-extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order,
-                        const float* ctrl, const uint8_t* mask, double* qpos, float* qvel, float* qacc, float* warm,
-                        float* applied, float* time, float* friction, float* cmd, float* obs,
-                        float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* invalid_contact,
-                        int32_t* step_num, float* debug, int debug_envs, const GqResetCfg* auto_reset, int32_t* episode,
-                        uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
-                        uint8_t* pending, uint8_t* lift_pending, char* err, int errlen) {
+/* What the two step entries share: the model, the batch (both kept across calls, with the batch's own memory) and the argument block of a
+ * launch over the caller's host tensors.  Returns the model, NULL on error; *obs_dim: floats per observation row. */
+static const GqDevModel* emu_bind(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order, int debug_envs,
+                                  const GqState& st, const GqObsOut& out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed,
+                                  float* friction_next, const GqImuCfg* imu, float* imu_bias, uint8_t* pending, uint8_t* lift_pending,
+                                  gq::FusedArgs* f, int* obs_dim, char* err, int errlen) {
   static EmuModel m;
   static GqDevBatch B;
-  if (emu_build_model(desc, m, err, errlen)) return -1;
+  if (emu_build_model(desc, m, err, errlen)) return nullptr;
   const GqDevModel& M = m.M;
-  if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &B, err, (size_t)errlen)) return -1;
+  if (gq_build_dev_batch(n_envs, obs_ids, n_obs, legs_order, &B, err, (size_t)errlen)) return nullptr;
   B.debug_envs = debug_envs;
   if (imu) gq_fill_imu(&B, imu);
   static std::vector<int32_t> xq;
@@ -54,46 +56,99 @@ extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_
     B.xq = xq.data(); B.xq_slots = slots;
   }
   const gq::BatchPtrs p = emu_ptrs(m, &B, friction_next, pending, lift_pending, imu ? imu_bias : nullptr);
-  const GqState st{qpos, qvel, qacc, warm, applied, time, friction, cmd};
-  const GqObsOut out{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr};
-  gq::FusedArgs f{};
-  gq::fill_step_args(&f.s, p, M, n_envs, st, out, episode, lift_failed);
-  if (auto_reset) gq::fill_reset_args(&f.r, p, B.rs_cmd_reset, auto_reset, st, out, episode, lift_failed);
+  *f = gq::FusedArgs{};
+  gq::fill_step_args(&f->s, p, M, n_envs, st, out, episode, lift_failed);
+  if (auto_reset) gq::fill_reset_args(&f->r, p, B.rs_cmd_reset, auto_reset, st, out, episode, lift_failed);
+  *obs_dim = B.obs_dim;
+  return &M;
+}
+/* a launch with grid = n_envs: the wavefronts one after the other (a masked env's returns at once, as on the device) */
+template <class Kernel>
+static void emu_launch(int n_envs, Kernel&& kernel) {
+  for (int e = 0; e < n_envs; e++) emu_run_wave((unsigned)e, (unsigned)n_envs, kernel);
+}
+
+/* gq_step with the inspection record: the instrumented variant of the model's key (mode 1), whether or not a record is asked for */
+extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order,
+                        const float* ctrl, const uint8_t* mask, double* qpos, float* qvel, float* qacc, float* warm,
+                        float* applied, float* time, float* friction, float* cmd, float* obs,
+                        float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* invalid_contact,
+                        int32_t* step_num, float* debug, int debug_envs, const GqResetCfg* auto_reset, int32_t* episode,
+                        uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
+                        uint8_t* pending, uint8_t* lift_pending, char* err, int errlen) {
+  gq::FusedArgs f;
+  int obs_dim = 0;
+  const GqDevModel* const M = emu_bind(desc, n_envs, obs_ids, n_obs, legs_order, debug_envs, GqState{qpos, qvel, qacc, warm, applied, time, friction, cmd},
+                                       GqObsOut{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr}, auto_reset, episode, lift_failed,
+                                       friction_next, imu, imu_bias, pending, lift_pending, &f, &obs_dim, err, errlen);
+  if (!M) return -1;
   gq::StepCall call{};
   call.ctrl = ctrl; call.mask = mask; call.debug = debug; call.auto_reset = gq::auto_reset_mode(auto_reset); call.first_pass = first_pass;
-  /* the instrumented variant of the model's key (mode 1: the one with the debug record), whether or not a record is asked for */
-  const bool known = gq::for_variant(gq::step_key(M.solver, M.cone, gq::model_scene(M), true, 0, 0), [&](auto S, auto MODE, auto CONE, auto SC, auto MB) {
+  const bool known = gq::for_variant(gq::step_key(M->solver, M->cone, gq::model_scene(*M), true, 0, 0), [&](auto S, auto MODE, auto CONE, auto SC, auto MB) {
     if constexpr (MODE != 1 || MB != 0) return false;
     else {
       constexpr gq::Scene sc = gq::Scene(int(SC));
-      for (int e = 0; e < n_envs; e++) {
-        if (mask && !mask[e]) continue;
-        emu_run_wave((unsigned)e, (unsigned)n_envs, [&]() { /* the loop of gq::step_kernel (csrc/gq_kernels.hip), kept in step with it by hand */
-          constexpr bool BOXES = gq::scene_boxes(sc), SELF = gq::scene_self(sc), PRIM = gq::scene_prim(sc);
-          __shared__ gq::WaveMem W;
-          gq::WaveCtx C;
-          int pass = call.first_pass;
-          int hint = gq::load_rows<S>(f.s, call, W, e, pass == 0, C);
-          bool respawn = call.auto_reset == 2 && C.pend;
-          for (;;) {
-            if (respawn) {
-              gq::wave_barrier();
-              gq::reset_wave<BOXES, PRIM>(f.r, W);
-              pass = call.auto_reset;
-              hint = gq::load_rows<S>(f.s, call, W, e, false, C, true);
-            }
-            const int term = gq::step_wave<S, 1, CONE != 0, BOXES, SELF, PRIM>(f.s, call, W, pass, hint, C);
-            if (pass != 0 || call.auto_reset != 1 || !term) break;
-            respawn = true;
-          }
-        });
-      }
+      emu_launch(n_envs, [&]() { gq::step_kernel_body<S, 1, CONE != 0, gq::scene_boxes(sc), gq::scene_self(sc), gq::scene_prim(sc), false, gq::kernel_cvx(sc)>(&f, call); });
       return true;
     }
   });
-  if (!known) { std::snprintf(err, (size_t)errlen, "emu_step: no step-kernel variant for solver %d cone %d", M.solver, M.cone); return -1; }
-  return B.obs_dim;
+  if (!known) { std::snprintf(err, (size_t)errlen, "emu_step: no step-kernel variant for solver %d cone %d", M->solver, M->cone); return -1; }
+  return obs_dim;
 }
+
+/* The production launches (mode 0), as launch_variant (csrc/gq_kernels.hip) makes them: with n_steps > 1 or a policy the PERSIST variant - for
+ * a foot-space policy the FOOT variant - otherwise the single-step kernel with n_steps = 1.  Takes what a StepCall of gq_step, gq_rollout,
+ * gq_rollout_closed (inline mode), gq_step_joint_cmd and gq_step_foot_cmd carries: ctrl [n_steps][n_envs][12] rows ctrl_stride floats apart (or
+ * NULL), obs_seq, act_seq, and policy: NULL, or a block of the kind policy_kind names - 0 PolicyPdDev, 1 JointCmdDev, 2 FootCmdDev - which is
+ * tagged here with the library's policy_tag_*; a JointCmdDev or FootCmdDev needs the Newton solver, as in the library (persistent_ok).
+ * Every key's variants are built in: the emulator's build takes 80 s with them against 45 s without (profiles/step_driver_move.md). */
+extern "C" int emu_step_window(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order,
+                               const float* ctrl, const uint8_t* mask, double* qpos, float* qvel, float* qacc, float* warm,
+                               float* applied, float* time, float* friction, float* cmd, float* obs,
+                               float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* invalid_contact,
+                               int32_t* step_num, const GqResetCfg* auto_reset, int32_t* episode,
+                               uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
+                               uint8_t* pending, uint8_t* lift_pending, int ctrl_stride, int n_steps, float* obs_seq, float* act_seq,
+                               int policy_kind, const void* policy, char* err, int errlen) {
+  gq::FusedArgs f;
+  int obs_dim = 0;
+  const GqDevModel* const M = emu_bind(desc, n_envs, obs_ids, n_obs, legs_order, 0, GqState{qpos, qvel, qacc, warm, applied, time, friction, cmd},
+                                       GqObsOut{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr}, auto_reset, episode, lift_failed,
+                                       friction_next, imu, imu_bias, pending, lift_pending, &f, &obs_dim, err, errlen);
+  if (!M) return -1;
+  gq::StepCall call{};
+  call.ctrl = ctrl; call.mask = mask; call.auto_reset = gq::auto_reset_mode(auto_reset); call.first_pass = first_pass;
+  call.ctrl_stride = ctrl_stride; call.n_steps = n_steps; call.obs_seq = obs_seq; call.act_seq = act_seq;
+  if (policy) {
+    if (policy_kind == 0) call.policy = static_cast<const gq::PolicyPdDev*>(policy);
+    else if (policy_kind == 1) call.policy = gq::policy_tag_joint_cmd(static_cast<const gq::JointCmdDev*>(policy));
+    else if (policy_kind == 2) call.policy = gq::policy_tag_foot_cmd(static_cast<const gq::FootCmdDev*>(policy));
+    else { std::snprintf(err, (size_t)errlen, "emu_step_window: policy_kind %d", policy_kind); return -1; }
+    if (policy_kind != 0 && M->solver != 1) { std::snprintf(err, (size_t)errlen, "emu_step_window: policy_kind %d needs the Newton solver", policy_kind); return -1; }
+  }
+  const bool known = gq::for_variant(gq::step_key(M->solver, M->cone, gq::model_scene(*M), false, 0, 0), [&](auto S, auto MODE, auto CONE, auto SC, auto MB) {
+    if constexpr (MODE != 0 || MB != 0) return false;
+    else {
+      constexpr gq::Scene sc = gq::Scene(int(SC));
+      constexpr bool C = CONE != 0, B = gq::scene_boxes(sc), SF = gq::scene_self(sc), P = gq::scene_prim(sc), CVX = gq::kernel_cvx(sc);
+      if (call.n_steps > 1 || call.policy) {
+        if constexpr (S == 1) if (gq::policy_is_foot_cmd(call.policy)) {
+          emu_launch(n_envs, [&]() { gq::step_kernel_body<1, 0, C, B, SF, P, true, CVX, true>(&f, call); });
+          return true;
+        }
+        emu_launch(n_envs, [&]() { gq::step_kernel_body<S, 0, C, B, SF, P, true, CVX>(&f, call); });
+        return true;
+      }
+      call.n_steps = 1;
+      emu_launch(n_envs, [&]() { gq::step_kernel_body<S, 0, C, B, SF, P, false, CVX>(&f, call); });
+      return true;
+    }
+  });
+  if (!known) { std::snprintf(err, (size_t)errlen, "emu_step_window: no step-kernel variant for solver %d cone %d", M->solver, M->cone); return -1; }
+  return obs_dim;
+}
+/* sizes of the policy blocks, for the ctypes mirrors of tests/helpers.py: PolicyPdDev, JointCmdDev, FootCmdDev */
+extern "C" void emu_policy_sizes(int* out) { out[0] = (int)sizeof(gq::PolicyPdDev); out[1] = (int)sizeof(gq::JointCmdDev); out[2] = (int)sizeof(gq::FootCmdDev); }
 
 extern "C" int emu_reset(const GqModelDesc* desc, int n_envs, const uint8_t* mask, const double* qpos_new, const float* qvel_new,
                          const GqResetCfg* cfg, double* qpos, float* qvel, float* qacc, float* warm, float* applied,

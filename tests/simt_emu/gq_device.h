@@ -86,6 +86,7 @@ static inline void wave_priority(int) {}
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
 #define __builtin_amdgcn_s_getreg(x) 0
+#define __builtin_amdgcn_fence(...) ((void)0) /* a wavefront's lanes run on one thread, its stores are in order */
 #define __builtin_amdgcn_exp2f(x) exp2f(x)   /* v_exp_f32 / v_log_f32 (gq_camera.h cam_pow) */
 #define __builtin_amdgcn_logf(x) log2f(x)
 static inline float fast_rcp(float x) { return 1.0f / x; }

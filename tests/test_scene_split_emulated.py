@@ -4,12 +4,9 @@ arguments of step_wave - and through a second build of the same sources with -DG
 both pair routines, as before the split.  The two must agree to the bit.
 
 What this reaches: for mini_cheetah and hyqreal1 (SCENE_FLAT_SELF_HULL) the body without the exact box routines, PRIM = false - one point per
-pair and the ballot form of the append - against the body with them.  For go2 and aliengo (SCENE_FLAT_SELF_PRIM) the emulator's driver
-(tests/simt_emu/emu_step.cpp) instantiates step_wave<SOLVER, MODE, CONE, BOXES, SELF, PRIM> and leaves CVX at its default, true: the flag that
-drops the convex block is set by the kernels (step_kernel_prim), where the variant is launched, and cannot be derived from those six
-arguments, which are the same for SCENE_FLAT_SELF and SCENE_FLAT_SELF_PRIM.  For these two robots both builds therefore run the same body, and
-the test holds the scene choice and the unchanged result; the body without the convex block is held by the digests of
-tests/test_gpu_scene_split.py on the device."""
+pair and the ballot form of the append - against the body with them.  For go2 and aliengo (SCENE_FLAT_SELF_PRIM) the body without the convex
+block and the pair exchange, CVX = false - the emulator runs the kernels' own driver (csrc/gq_step_driver.h) with CVX from the rule the
+launches use (gq_step_kernel.h kernel_cvx), so it instantiates what step_kernel_prim does - against the body with them."""
 import numpy as np
 import pytest
 
