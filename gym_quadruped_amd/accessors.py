@@ -113,7 +113,8 @@ class AccessorsMixin:
         """mjData.contact of the last forward pass as tensors (needs accessors=True): dict with 'ncon' [N] and, per contact
         slot k < 12 (MuJoCo's order; slots >= ncon are zero), 'geom1' (-1: a world geom), 'geom2', 'dist', 'pos' (x / y relative
         to the pre-step base x / y), 'frame' [N, 12, 3, 3] (rows: normal, tangent 1, tangent 2), 'dim', 'force' [N, 12, 6]
-        (mj_contactForce: contact-frame force and torque), 'mu'."""
+        (mj_contactForce: contact-frame force and torque), 'mu' (mjContact.friction[0], the sliding coefficient - not the regularised
+        mjContact.mu, which is this divided by sqrt(impratio))."""
         if getattr(self, '_contacts', None) is None:
             raise _lib.GqError('contacts() needs an env built with accessors=True')
         from .cabi import GQ_CON_MAX, GQ_CON_REC

@@ -82,6 +82,15 @@ int gq_build_dev_model(const GqModelDesc* d, GqDevModel* out, std::vector<float>
   if (d->cone != 0 && d->cone != 1) FAIL("cone must be 0 (pyramidal) or 1 (elliptic)");
   if (d->cone == 1 && d->solver != 1) FAIL("elliptic friction cones need the Newton solver (solver = 1): the PGS path has no per-contact cone projection");
   if (d->solver != 0 && d->solver != 1) FAIL("solver must be 0 (PGS) or 1 (Newton)");
+  if (d->cone == 0) { /* pyramidal cones: the step builds, and the contact row decodes (mju_decodePyramid), the one row of condim 1 and the four of condim 3 */
+    int worst = d->floor_condim;
+    for (int g = 0; g < d->ngeom; g++)
+      if (d->geom_cloudid[g] >= 0 && d->geom_bodyid[g] != 0 && d->geom_condim[g] > worst) worst = d->geom_condim[g];
+    for (int b = 0; b < d->nbox; b++)
+      if (d->box_condim[b] > worst) worst = d->box_condim[b];
+    if (d->hfield_nrow > 0 && d->hfield_condim > worst) worst = d->hfield_condim;
+    if (worst > 3) FAIL("pyramidal friction cones (cone = 0) with a geom of condim %d: only condim 1 and 3 have pyramid rows here (torsional / rolling friction needs the elliptic cone, cone = 1)", worst);
+  }
   if (d->gravity[0] != 0 || d->gravity[1] != 0) FAIL("gravity must be along z");
   M.timestep = (float)d->timestep; M.gravity_z = (float)d->gravity[2]; M.impratio = (float)d->impratio;
   M.meaninertia = (float)d->meaninertia; M.tolerance = (float)d->tolerance; M.noise_floor = (float)d->noise_floor; M.iterations = d->iterations; M.cone = d->cone; M.solver = d->solver;

@@ -1660,7 +1660,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
       else if constexpr (CONE) {
 #pragma unroll
         for (int q = 0; q < 6; q++) f6[q] = q < dimc ? W.force[r0 + q < 63 ? r0 + q : 63] : 0.0f;
-      } else { /* mju_decodePyramid */
+      } else { /* mju_decodePyramid of condim 3: no robot model combines pyramidal cones with condim 4 or 6, and gq_build_dev_model refuses one that does */
         const float f0 = W.force[r0], f1 = W.force[r0 + 1], f2 = W.force[r0 + 2], f3 = W.force[r0 + 3], mu = W.con_mu[c];
         f6[0] = f0 + f1 + f2 + f3; f6[1] = mu * (f0 - f1); f6[2] = mu * (f2 - f3);
       }

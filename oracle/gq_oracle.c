@@ -30,6 +30,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <stdint.h>
 #include <string.h>
 
 #include "gq.h"
@@ -56,6 +57,7 @@ typedef struct {
   double tiegap; /* depth gap to the second deepest vertex of the geom's cloud (test diagnostics) */
   int geom, body, dim, efc_address;
   int geom1, body1; /* the other geom: -1 / 0 for a world geom (floor, box, height field), else a robot geom and its body */
+  int cvx, wgeom;   /* test diagnostics: 1 = made by the general convex routine; the world geom of a world contact (-1 floor, box index, nbox = height field), -2 for a robot pair */
 } Contact;
 
 typedef struct GqOracle {
@@ -86,6 +88,10 @@ typedef struct GqOracle {
   double imu_pos[3], imu_quat[4], imu_acc[3], imu_gyro[3];
   int warning; /* bad qpos/qvel/qacc seen (mj_checkPos/Vel/Acc) */
   double cloud_aabb[64][6]; int cloud_aabb_ok[64]; /* geom-frame box of every cloud (centre, half extents): mid phase of the convex pairs */
+  /* contact-point override (gqo_set_contact_pos, test infrastructure): world points that replace contact[i].pos after collision detection */
+  double pose_noise; uint32_t pose_noise_seed; /* gqo_set_pose_noise (test infrastructure): how far one fp32 rounding of the geom poses moves the contacts */
+  int npos_override, pos_override_idx[NCON], nrm_override_on[NCON];
+  double pos_override[NCON][3], nrm_override[NCON][3];
 } GqOracle;
 
 /* ------------------------------------------------------------------ small vector helpers */
@@ -262,6 +268,16 @@ static void gqo_kinematics(GqOracle* o) {
     quat_mul(q, o->xquat[b], m->geom_quat + 4 * g);
     quat2mat(o->geom_xmat[g], q);
   }
+  if (o->pose_noise > 0) { /* gqo_set_pose_noise: every entry of the geom poses (x / y: relative to the base) moves by the relative amount, signs from a fixed sequence */
+    uint32_t z = o->pose_noise_seed;
+    for (int g = 0; g < m->ngeom; g++)
+      for (int k = 0; k < 12; k++) {
+        z = z * 1664525u + 1013904223u;
+        const double f = (z >> 16) & 1 ? o->pose_noise : -o->pose_noise;
+        if (k < 3) o->geom_xpos[g][k] += f * (o->geom_xpos[g][k] - (k < 2 ? o->xpos[1][k] : 0.0)); /* x / y relative to the base, as the kernel carries them */
+        else o->geom_xmat[g][k - 3] *= 1.0 + f;
+      }
+  }
 }
 
 /* ------------------------------------------------------------------ mj_comPos */
@@ -431,6 +447,7 @@ static void contact_param(const GqOracle* o, int w, int g, Contact* c) {
   const GqModelDesc* m = &o->d;
   double f1[3], f2[3];
   const int hf = w >= m->nbox; /* the height field comes after the boxes */
+  c->wgeom = w;
   memcpy(f1, w < 0 ? m->floor_friction : (hf ? m->hfield_friction : m->box_friction + 3 * w), sizeof f1);
   memcpy(f2, m->geom_friction + 3 * g, sizeof f2);
   if (o->friction >= 0) { /* _set_ground_friction (quadruped_env.py:1277-1298): geoms named ground/floor/hfield/terrain and the
@@ -480,6 +497,7 @@ static void contact_param(const GqOracle* o, int w, int g, Contact* c) {
 static void contact_param_pair(const GqOracle* o, int g1, int g2, Contact* c) {
   const GqModelDesc* m = &o->d;
   double f1[3], f2[3], fri[3];
+  c->wgeom = -2;
   memcpy(f1, m->geom_friction + 3 * g1, sizeof f1); memcpy(f2, m->geom_friction + 3 * g2, sizeof f2);
   if (o->friction >= 0) { /* _set_ground_friction rewrites the feet geoms (quadruped_env.py:1277-1298) */
     if (is_foot(m, g1)) { f1[0] = o->friction; f1[1] = 0.005; f1[2] = 0.0; }
@@ -990,6 +1008,7 @@ static void prim_of_geom(const GqOracle* o, int g, Prim* P) {
 static void gqo_collision(GqOracle* o) {
   const GqModelDesc* m = &o->d;
   o->ncon = 0;
+  for (int i = 0; i < NCON; i++) o->contact[i].cvx = 0;
   const double normal[3] = {0, 0, 1};
   for (int g = 0; g < m->ngeom && o->ncon < NCON; g++) {
     int cl = m->geom_cloudid[g];
@@ -1153,7 +1172,7 @@ static void gqo_collision(GqOracle* o) {
         }
         if (!cvx_pair_counted(&A, &B, margin, &dist, nrm, pos, 0, hint)) continue;
         Contact* c = &o->contact[o->ncon++];
-        c->geom = g; c->body = m->geom_bodyid[g]; c->geom1 = -1; c->body1 = 0; c->dist = dist; c->tiegap = g_cvx_capped ? 0.0 : (cvx_point_tie(&A, &B, nrm) > 0 ? 1.0 : -1.0); /* -1: depth and normal are determined, the contact POINT is not */
+        c->geom = g; c->body = m->geom_bodyid[g]; c->geom1 = -1; c->body1 = 0; c->dist = dist; c->cvx = 1; c->tiegap = g_cvx_capped ? 0.0 : (cvx_point_tie(&A, &B, nrm) > 0 ? 1.0 : -1.0); /* -1: depth and normal are determined, the contact POINT is not */
         memcpy(c->pos, pos, sizeof c->pos);
         set_frame(c, nrm, NULL);
         contact_param(o, w, g, c);
@@ -1281,7 +1300,7 @@ static void gqo_collision(GqOracle* o) {
         if (full_before) g_cvx_stat[10] += g_cvx_last_queries; /* census: support queries spent on pairs behind the kernel's 12-contact capacity */
         if (!hit_) continue;
         Contact* c = &o->contact[o->ncon++];
-        c->geom = g2; c->body = b2; c->geom1 = g1; c->body1 = b1; c->dist = dist; c->tiegap = g_cvx_capped ? 0.0 : (cvx_point_tie(&A, &B, nrm) > 0 ? 1.0 : -1.0); /* -1: depth and normal are determined, the contact POINT is not */
+        c->geom = g2; c->body = b2; c->geom1 = g1; c->body1 = b1; c->dist = dist; c->cvx = 1; c->tiegap = g_cvx_capped ? 0.0 : (cvx_point_tie(&A, &B, nrm) > 0 ? 1.0 : -1.0); /* -1: depth and normal are determined, the contact POINT is not */
         memcpy(c->pos, pos, sizeof c->pos);
         set_frame(c, nrm, NULL);
         contact_param_pair(o, g1, g2, c);
@@ -1492,13 +1511,25 @@ static void gqo_rne(GqOracle* o, double* res) {
   }
 }
 
-static void gqo_fwd_position(GqOracle* o) {
+static int gqo_fwd_position(GqOracle* o) {
   gqo_kinematics(o);
   gqo_com_pos(o);
   gqo_crb(o);
   gqo_factor_m(o);
   gqo_collision(o);
+  /* the contact-point override: the point alone (dist, frame, parameters and the list itself stay the collision routines') - and the normal where
+   * the caller hands one in - before the rows are built */
+  for (int k = 0; k < o->npos_override; k++) {
+    const int i = o->pos_override_idx[k];
+    if (i < 0 || i >= o->ncon) {
+      snprintf(g_err, sizeof g_err, "contact-point override of contact %d: the list has %d contacts", i, o->ncon);
+      return GQ_EINVAL;
+    }
+    memcpy(o->contact[i].pos, o->pos_override[k], sizeof o->pos_override[k]);
+    if (o->nrm_override_on[k]) set_frame(&o->contact[i], o->nrm_override[k], NULL); /* an equally deep minimum translation: the frame follows as at the convex routine's call sites */
+  }
   gqo_make_constraint(o);
+  return GQ_OK;
 }
 
 static void gqo_fwd_velocity(GqOracle* o) {
@@ -1980,7 +2011,7 @@ static int bad(const double* x, int n, double lim) {
 /* mj_forward; stage 1 = position + velocity only (what mj_step1 evaluates, quadruped_env.py:376) */
 int gqo_forward(GqOracle* o, const double* ctrl, int stage) {
   if (ctrl) memcpy(o->ctrl, ctrl, sizeof(double) * o->d.nu);
-  gqo_fwd_position(o);
+  if (gqo_fwd_position(o) != GQ_OK) return GQ_EINVAL;
   gqo_fwd_velocity(o);
   if (stage == 1) return GQ_OK;
   gqo_fwd_actuation(o);
@@ -2012,7 +2043,7 @@ int gqo_set_imu(GqOracle* o, const double* pos, const double* quat) {
 
 int gqo_step(GqOracle* o, const double* ctrl) {
   o->warning = bad(o->qpos, NQ, 1e10) | bad(o->qvel, NV, 1e10);
-  gqo_forward(o, ctrl, 0);
+  if (gqo_forward(o, ctrl, 0) != GQ_OK) return GQ_EINVAL; /* (a contact-point override past the list: the state is left where it was) */
   o->warning |= bad(o->qacc, NV, 1e10);
   gqo_euler(o);
   return GQ_OK;
@@ -2026,8 +2057,31 @@ int gqo_set_state(GqOracle* o, const double* qpos, const double* qvel, const dou
   if (qfrc_applied) memcpy(o->qfrc_applied, qfrc_applied, sizeof o->qfrc_applied);
   o->time = time;
   o->friction = friction;
+  o->npos_override = 0;
   return GQ_OK;
 }
+
+/* Test infrastructure: from the next gqo_forward / gqo_step on, contact[idx[k]].pos = pos[k] (world coordinates) once collision detection has
+ * run and before the constraint rows are built - nothing else of the contact changes.  For the contacts whose point is not determined
+ * (Contact.tiegap): with the kernel's point substituted, the rest of the step can be compared value by value.  nrm (NULL, or [n][3] with NaN
+ * rows for "keep"): the contact's normal as well, its tangents made from it - for a convex pair whose minimum translation has two directions of
+ * equal depth.  Cleared by gqo_set_state. */
+int gqo_set_contact_pos(GqOracle* o, int n, const int* idx, const double* pos, const double* nrm) {
+  if (n < 0 || n > NCON) { snprintf(g_err, sizeof g_err, "gqo_set_contact_pos: %d entries (0..%d)", n, NCON); return GQ_EINVAL; }
+  o->npos_override = n;
+  for (int k = 0; k < n; k++) {
+    o->pos_override_idx[k] = idx[k]; memcpy(o->pos_override[k], pos + 3 * k, sizeof o->pos_override[k]);
+    o->nrm_override_on[k] = nrm && nrm[3 * k] == nrm[3 * k];
+    if (o->nrm_override_on[k]) memcpy(o->nrm_override[k], nrm + 3 * k, sizeof o->nrm_override[k]);
+  }
+  return GQ_OK;
+}
+
+/* Test infrastructure: from the next forward pass on, every entry of geom_xpos (x / y taken relative to the base body, as the kernel carries
+ * them) and geom_xmat is multiplied by 1 +- rel after the kinematics (rel = 2^-23: one fp32 rounding), so that the movement of the oracle's
+ * own dist / normal / point under the perturbation can be recorded (profiles/contact_list_parity.md).  rel = 0 switches it off;
+ * gqo_set_state leaves it as it is. */
+int gqo_set_pose_noise(GqOracle* o, double rel, unsigned seed) { o->pose_noise = rel; o->pose_noise_seed = seed; return GQ_OK; }
 
 /* value of the primal objective mj_solNewton minimises, at an arbitrary qacc (after gqo_forward built the rows) */
 double gqo_primal_cost(GqOracle* o, const double* qacc) { return primal_cost(o, qacc, NULL); }
@@ -2088,6 +2142,8 @@ int gqo_get(const GqOracle* o, const char* name, double* out, int max_n) {
   if (!strcmp(name, "contact_mu")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].mu; return n; }
   if (!strcmp(name, "contact_efc_address")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].efc_address; return n; }
   if (!strcmp(name, "contact_friction")) { int n = 5 * o->ncon < max_n ? 5 * o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i / 5].friction[i % 5]; return n; }
+  if (!strcmp(name, "contact_cvx")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].cvx; return n; }
+  if (!strcmp(name, "contact_wgeom")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].wgeom; return n; }
   if (!strcmp(name, "contact_body1")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].body1; return n; }
   if (!strcmp(name, "contact_geom1")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].geom1; return n; }
   if (!strcmp(name, "contact_body")) { int n = o->ncon < max_n ? o->ncon : max_n; for (int i = 0; i < n; i++) out[i] = o->contact[i].body; return n; }

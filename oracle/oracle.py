@@ -42,6 +42,8 @@ def lib():
         L.gqo_get_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gqo_rollout.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.gqo_set_imu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gqo_set_pose_noise.argtypes = [C.c_void_p, C.c_double, C.c_uint]
+        L.gqo_set_contact_pos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gqo_primal_cost.argtypes = [C.c_void_p, C.c_void_p]
         L.gqo_primal_cost.restype = C.c_double
         L.gqo_last_error.restype = C.c_char_p
@@ -88,11 +90,29 @@ class Oracle:
 
     def forward(self, ctrl=None, stage=0):
         c = None if ctrl is None else np.ascontiguousarray(ctrl, dtype=np.float64)
-        self.L.gqo_forward(self.h, _p(c), stage)
+        if self.L.gqo_forward(self.h, _p(c), stage) != 0:
+            raise RuntimeError(self.L.gqo_last_error().decode())
 
     def step(self, ctrl):
         c = np.ascontiguousarray(ctrl, dtype=np.float64)
-        self.L.gqo_step(self.h, _p(c))
+        if self.L.gqo_step(self.h, _p(c)) != 0:
+            raise RuntimeError(self.L.gqo_last_error().decode())
+
+    def set_pose_noise(self, rel=0.0, seed=1):
+        """Every entry of the geom poses is multiplied by 1 +- rel after the kinematics of each later forward pass (rel 0: off)."""
+        self.L.gqo_set_pose_noise(self.h, float(rel), int(seed))
+
+    def set_contact_pos(self, index, pos, normal=None):
+        """Contact-point override: from the next forward() / step() on, contact[index[k]].pos = pos[k] (world coordinates) after collision
+        detection and before the constraint rows are built; nothing else of the contact changes.  normal [k][3] (NaN rows: keep): the
+        contact's normal as well, its tangents made from it.  An index past the list makes that forward() / step() raise.  Cleared by
+        set_state()."""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        p = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        nr = None if normal is None else np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+        assert len(idx) == len(p) and (nr is None or len(nr) == len(p))
+        if self.L.gqo_set_contact_pos(self.h, len(idx), _p(idx), _p(p), _p(nr)) != 0:
+            raise RuntimeError(self.L.gqo_last_error().decode())
 
     def get(self, name, n=None):
         buf = np.zeros(n if n is not None else 1024 * 18, dtype=np.float64)

@@ -13,7 +13,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from gym_quadruped_amd.cabi import ALL_OBS, IMU_OBS, OBS_DIMS, OBS_NAMES, GqImuCfg, GqModelDesc, MarshalledModel, obs_ids_from_names  # noqa: E402
+from gym_quadruped_amd.cabi import GQ_CON_STRIDE, GQ_DYN, ALL_OBS, IMU_OBS, OBS_DIMS, OBS_NAMES, GqImuCfg, GqModelDesc, MarshalledModel, obs_ids_from_names  # noqa: E402
 from gym_quadruped_amd.mjcf import load_compiled  # noqa: E402
 from gym_quadruped_amd.robot_cfgs import get_robot_config  # noqa: E402
 
@@ -87,9 +87,9 @@ def _p(a):
 
 def _emu_launch_args(mm, ctrl, ctrl_shape, qpos, qvel, warm=None, applied=None, time=None, friction=None, cmd=None, obs_names=ALL_OBS,
                      legs_order=(0, 1, 2, 3), mask=None, debug_envs=0, auto_reset=None, episode=None, first_pass=0, imu=None,
-                     imu_bias=None, step_num=None, pending=None, lift_pending=None, friction_next=None, lift_failed=None, obs=None):
+                     imu_bias=None, step_num=None, pending=None, lift_pending=None, friction_next=None, lift_failed=None, obs=None, rows=False):
     """The host tensors of an emulated step launch and the two runs of arguments both step entries of the emulator take
-    (tests/simt_emu/emu_step.cpp): (st, model ... step_num, auto_reset ... lift_pending).  ctrl None: zeros of ctrl_shape, or no tensor
+    (tests/simt_emu/emu_step.cpp): (st, model ... step_num, auto_reset ... lift_pending); st['dyn'] / st['contacts'] go last in both.  ctrl None: zeros of ctrl_shape, or no tensor
     at all where ctrl_shape is None.  obs: the observation rows an earlier launch left (the inline PD policy reads them)."""
     n = qpos.shape[0]
     ids = np.asarray(obs_ids_from_names(obs_names), dtype=np.int32)
@@ -108,7 +108,10 @@ def _emu_launch_args(mm, ctrl, ctrl_shape, qpos, qvel, warm=None, applied=None, 
         friction_next=np.zeros(n, np.float32) if friction_next is None else np.ascontiguousarray(friction_next, dtype=np.float32),
         lift_pending=np.zeros(n, np.uint8) if lift_pending is None else np.ascontiguousarray(lift_pending, dtype=np.uint8),
         pending=np.zeros(n, np.uint8) if pending is None else np.ascontiguousarray(pending, dtype=np.uint8),
-        imu_bias=np.zeros((n, 6), np.float32) if imu_bias is None else np.ascontiguousarray(imu_bias, dtype=np.float32))
+        imu_bias=np.zeros((n, 6), np.float32) if imu_bias is None else np.ascontiguousarray(imu_bias, dtype=np.float32),
+        # rows=True: the rows of gq_batch_set_outputs (accessors=True) - the kernel's own dynamics and contact rows, NaN where it wrote nothing;
+        # otherwise none, as in a launch of the benchmark
+        dyn=np.full((n, GQ_DYN['STRIDE']), np.nan, np.float32) if rows else None, contacts=np.full((n, GQ_CON_STRIDE), np.nan, np.float32) if rows else None)
     st['obs_names'] = list(obs_names)
     # (the arrays the calls only read are kept alive by the dict)
     st['_ids'], st['_legs'], st['_mask'] = ids, np.asarray(legs_order, dtype=np.int32), None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
@@ -124,7 +127,7 @@ def emu_step(mm, ctrl, qpos, qvel, debug_envs=0, **kw):
     """Run the instrumented step kernel (mode 1) under the emulator. Arrays are updated in place like the device tensors would be."""
     st, head, tail = _emu_launch_args(mm, ctrl, (qpos.shape[0], 12), qpos, qvel, debug_envs=debug_envs, **kw)
     err = C.create_string_buffer(512)
-    rc = emu_lib().emu_step(*head, _p(st['debug']), debug_envs, *tail, err, 512)
+    rc = emu_lib().emu_step(*head, _p(st['debug']), debug_envs, *tail, err, 512, _p(st['dyn']), _p(st['contacts']))
     if rc < 0:
         raise RuntimeError(err.value.decode())
     return st
@@ -164,7 +167,8 @@ def emu_window(mm, ctrl_seq, qpos, qvel, n_steps=1, policy=None, obs_seq=False, 
     st['act_seq'] = np.zeros((n_steps, n, 12), np.float32) if act_seq else None
     kind = 0 if policy is None else _POLICY_KINDS.index(type(policy))
     err = C.create_string_buffer(512)
-    rc = L.emu_step_window(*head, *tail, n * 12, int(n_steps), _p(st['obs_seq']), _p(st['act_seq']), kind, None if policy is None else C.byref(policy), err, 512)
+    rc = L.emu_step_window(*head, *tail, n * 12, int(n_steps), _p(st['obs_seq']), _p(st['act_seq']), kind, None if policy is None else C.byref(policy), err, 512,
+                           _p(st['dyn']), _p(st['contacts']))
     if rc < 0:
         raise RuntimeError(err.value.decode())
     return st

@@ -2,7 +2,8 @@
  * (csrc/gq_step_driver.h: the persistent step loop, the re-spawn loop, the inline policies) around the step itself (csrc/gq_step_body.h), one
  * wavefront after the other.  Two C entry points over host memory: emu_step, the instrumented kernel (mode 1) with the tensors of gq_step,
  * and emu_step_window, the production kernels (mode 0) as launch_variant (csrc/gq_kernels.hip) picks them - single step, persistent window,
- * foot-space window.  The argument blocks are filled by the library's gq_step_call.h; the instantiation comes from its step_key /
+ * foot-space window.  Both take the caller's dynamics and contact rows (gq_batch_set_outputs) as two trailing arrays, so the kernels' own
+ * row-writing code runs emulated in either variant.  The argument blocks are filled by the library's gq_step_call.h; the instantiation comes from its step_key /
  * for_variant / kernel_cvx (gq_step_kernel.h).  Not here: the mailbox side and the policy kernels, whose protocol needs concurrent wavefronts. */
 #include <functional>
 #include <vector>
@@ -23,11 +24,14 @@ static int g_emu_xq_on = 0;
 extern "C" void emu_set_exchange(int on) { g_emu_xq_on = on; }
 extern "C" void emu_exchange_stats(int* out) { out[0] = gq::g_emu_cas_ok; out[1] = out[2] = out[3] = 0; }
 
-/* the emulator's batch has neither resampling, a step-time height map nor dyn / contact rows, and no solver-load hint */
-static gq::BatchPtrs emu_ptrs(EmuModel& m, GqDevBatch* B, float* friction_next, uint8_t* pending, uint8_t* lift_pending, float* imu_bias) {
+/* the emulator's batch has neither resampling nor a step-time height map, and no solver-load hint; dyn / contacts: the caller's rows of
+ * gq_batch_set_outputs ([N][GQ_DYN_STRIDE] / [N][GQ_CON_STRIDE] floats), or NULL */
+static gq::BatchPtrs emu_ptrs(EmuModel& m, GqDevBatch* B, float* friction_next, uint8_t* pending, uint8_t* lift_pending, float* imu_bias,
+                              float* dyn = nullptr, float* contacts = nullptr) {
   gq::BatchPtrs p{};
   p.model = &m.M; p.batch = B; p.vx = m.vx.data(); p.vy = m.vy.data(); p.vz = m.vz.data();
   p.friction_next = friction_next; p.pending = pending; p.lift_pending = lift_pending; p.imu_bias = imu_bias;
+  p.dyn = dyn; p.contacts = contacts;
   return p;
 }
 
@@ -36,7 +40,7 @@ static gq::BatchPtrs emu_ptrs(EmuModel& m, GqDevBatch* B, float* friction_next, 
 static const GqDevModel* emu_bind(const GqModelDesc* desc, int n_envs, const int32_t* obs_ids, int n_obs, const int32_t* legs_order, int debug_envs,
                                   const GqState& st, const GqObsOut& out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed,
                                   float* friction_next, const GqImuCfg* imu, float* imu_bias, uint8_t* pending, uint8_t* lift_pending,
-                                  gq::FusedArgs* f, int* obs_dim, char* err, int errlen) {
+                                  float* dyn, float* contacts, gq::FusedArgs* f, int* obs_dim, char* err, int errlen) {
   static EmuModel m;
   static GqDevBatch B;
   if (emu_build_model(desc, m, err, errlen)) return nullptr;
@@ -55,7 +59,7 @@ static const GqDevModel* emu_bind(const GqModelDesc* desc, int n_envs, const int
     if (xq.empty()) xq.assign((size_t)slots * (1 + GQ_XQ_ITEM), 0);
     B.xq = xq.data(); B.xq_slots = slots;
   }
-  const gq::BatchPtrs p = emu_ptrs(m, &B, friction_next, pending, lift_pending, imu ? imu_bias : nullptr);
+  const gq::BatchPtrs p = emu_ptrs(m, &B, friction_next, pending, lift_pending, imu ? imu_bias : nullptr, dyn, contacts);
   *f = gq::FusedArgs{};
   gq::fill_step_args(&f->s, p, M, n_envs, st, out, episode, lift_failed);
   if (auto_reset) gq::fill_reset_args(&f->r, p, B.rs_cmd_reset, auto_reset, st, out, episode, lift_failed);
@@ -75,12 +79,12 @@ extern "C" int emu_step(const GqModelDesc* desc, int n_envs, const int32_t* obs_
                         float* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* invalid_contact,
                         int32_t* step_num, float* debug, int debug_envs, const GqResetCfg* auto_reset, int32_t* episode,
                         uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
-                        uint8_t* pending, uint8_t* lift_pending, char* err, int errlen) {
+                        uint8_t* pending, uint8_t* lift_pending, char* err, int errlen, float* dyn, float* contacts) {
   gq::FusedArgs f;
   int obs_dim = 0;
   const GqDevModel* const M = emu_bind(desc, n_envs, obs_ids, n_obs, legs_order, debug_envs, GqState{qpos, qvel, qacc, warm, applied, time, friction, cmd},
                                        GqObsOut{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr}, auto_reset, episode, lift_failed,
-                                       friction_next, imu, imu_bias, pending, lift_pending, &f, &obs_dim, err, errlen);
+                                       friction_next, imu, imu_bias, pending, lift_pending, dyn, contacts, &f, &obs_dim, err, errlen);
   if (!M) return -1;
   gq::StepCall call{};
   call.ctrl = ctrl; call.mask = mask; call.debug = debug; call.auto_reset = gq::auto_reset_mode(auto_reset); call.first_pass = first_pass;
@@ -109,12 +113,12 @@ extern "C" int emu_step_window(const GqModelDesc* desc, int n_envs, const int32_
                                int32_t* step_num, const GqResetCfg* auto_reset, int32_t* episode,
                                uint8_t* lift_failed, float* friction_next, int first_pass, const GqImuCfg* imu, float* imu_bias,
                                uint8_t* pending, uint8_t* lift_pending, int ctrl_stride, int n_steps, float* obs_seq, float* act_seq,
-                               int policy_kind, const void* policy, char* err, int errlen) {
+                               int policy_kind, const void* policy, char* err, int errlen, float* dyn, float* contacts) {
   gq::FusedArgs f;
   int obs_dim = 0;
   const GqDevModel* const M = emu_bind(desc, n_envs, obs_ids, n_obs, legs_order, 0, GqState{qpos, qvel, qacc, warm, applied, time, friction, cmd},
                                        GqObsOut{obs, reward, terminated, truncated, invalid_contact, step_num, nullptr, nullptr}, auto_reset, episode, lift_failed,
-                                       friction_next, imu, imu_bias, pending, lift_pending, &f, &obs_dim, err, errlen);
+                                       friction_next, imu, imu_bias, pending, lift_pending, dyn, contacts, &f, &obs_dim, err, errlen);
   if (!M) return -1;
   gq::StepCall call{};
   call.ctrl = ctrl; call.mask = mask; call.auto_reset = gq::auto_reset_mode(auto_reset); call.first_pass = first_pass;

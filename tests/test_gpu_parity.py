@@ -12,6 +12,7 @@ import torch
 from helpers import ROOT, budgeted_states, oracle_fits_row_budget, ALL_OBS, marshalled, random_states, self_contact_states, split_obs, tally_note
 import newton_first_step as nfs
 import step_parity as sp
+from contact_list import Shapes
 from step_parity import ParityTally, gpu_records
 
 pytestmark = pytest.mark.gpu
@@ -907,7 +908,7 @@ def test_robot_self_collision_step_parity(robot):
     half of them between two different legs (dense Newton step), mixed with floor contacts."""
     from oracle.oracle import Oracle
     n = 160
-    env = _make_env(n, iters=100, tol=1e-8, solver='newton', robot=robot)
+    env = _make_env(n, iters=100, tol=1e-8, solver='newton', robot=robot, accessors=True)   # (accessors=True: the contact row, read through env.contacts())
     o = Oracle(marshalled(robot, solver=1, iterations=100, tolerance=1e-12))
     hip = env.robot_cfg.hip_height
     rng = np.random.default_rng(5)
@@ -920,18 +921,21 @@ def test_robot_self_collision_step_parity(robot):
     cmd = np.tile(np.array([0.4, -0.2, 0.0, 0.1], np.float32), (n, 1))
     env._qpos.copy_(torch.as_tensor(qpos)); env._qvel.copy_(torch.as_tensor(qvel)); env._warm.copy_(torch.as_tensor(warm))
     env._cmd.copy_(torch.as_tensor(cmd)); env._friction.fill_(0.8)
-    env.enable_debug(n)
+    env.enable_debug(n)   # (the instrumented variant writes the contact row too: one env, one launch, both records)
     obs, rew, term, trunc, info = env.step(torch.as_tensor(ctrl))
     kern = gpu_records(env, n, ['qacc', 'niter', 'nefc', 'ncon', 'efc_J', 'efc_R', 'efc_aref'])
-    tally = ParityTally(cone, 3e-7)
+    assert all('contacts' in k for k in kern)
+    tally = ParityTally(cone, 3e-7, shapes=Shapes(env._mm))
     nself = ncross = 0
     leg = lambda b: (b - 2) // 3 if b >= 2 else -1
     ea, ev = [], []
     for e in range(n):
         # (over the budget: held to the prefix rule like everywhere else, and reported to the caller; the observables of SELF_STEP_GPU: robot-robot
-        # contacts set no foot contact state and no termination)
+        # contacts set no foot contact state and no termination.  An env whose contact POINTS alone are undecided - two flat faces of CAD hulls, a
+        # cylinder rim on a box: up to 60 % on b2 / hyqreal1 - has its list held contact by contact and is compared like an 'ok' env against the
+        # oracle that took the kernel's points: ParityTally.step_env_with_list)
         k = kern[e]
-        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8), ctrl[e], k, sp.SELF_STEP_GPU, prefix=True, cmd=cmd[e]) != 'ok':
+        if tally.step_env(e, o, (qpos[e], qvel[e], warm[e], np.zeros(18), 0.0, 0.8), ctrl[e], k, sp.SELF_STEP_GPU, prefix=True, cmd=cmd[e]) not in sp.COMPARED:
             continue
         b1, b2 = o.get('contact_body1').astype(int), o.get('contact_body').astype(int)
         nself += int((b1 > 0).any()); ncross += int(any(x > 0 and leg(x) >= 0 and leg(x) != leg(y) for x, y in zip(b1, b2)))
@@ -942,10 +946,12 @@ def test_robot_self_collision_step_parity(robot):
     p99 = lambda x: float(np.percentile(x, 99))
     assert p99(ea) < (1e-4 if cone else 2e-5) * 5 and max(ea) < 2e-3, (p99(ea), max(ea))
     assert p99(ev) < (7e-4 if cone else 5e-5) * 5 and max(ev) < 5e-3, (p99(ev), max(ev))
-    tally.finish(f'self-collision one-step parity {robot}', min_checked=0.75, max_tie=0.15, max_budget=0.1)
-    assert tally.checked >= 50   # (of 160: where two flat faces of CAD hulls or a cylinder rim and a box meet, the contact POINT is not determined - those envs, up to 60 % on
-                                 #  b2 / hyqreal1, are held to the oracle's row count only, see ParityTally.classify)
-    assert nself >= 0.9 * tally.checked and ncross >= 0.25 * tally.checked, (nself, ncross, tally.checked)
+    # at least 0.9 n envs compared by value ('ok' ones and the ones held by substitution; the oracle alone classes 0.93 - 0.98 of these draws so), at
+    # most 0.03 n left out for a capped convex pair or a vertex tie that changed a manifold (the oracle alone: at most 2 of 160), no mismatch
+    tally.finish_held(f'self-collision one-step parity {robot}', min_checked=0.75, max_uncompared=0.03, max_budget=0.1, min_compared=0.9,
+                      max_normal_tie=sp.GO1_NORMAL_TIES if robot == 'go1' else 0.0)
+    compared = tally.checked + tally.point_held + tally.tie_held
+    assert nself >= 0.9 * compared and ncross >= 0.25 * compared, (nself, ncross, compared)
 
 
 @pytest.mark.parametrize('robot', ['go1', 'spot', 'b2'])
@@ -973,8 +979,8 @@ def test_step_parity_on_benchmark_rollout_states(robot, scene):
     the fp64 oracle from the same (qpos, qvel, friction, ctrl); contact sets must agree (0 mismatches), qacc within the
     one-step tolerances of the report."""
     n, nsample = 1024, 160
-    env = _make_env(n, solver='newton', iters=100, tol=1e-8, robot=robot, scene=scene, auto_reset='next_step')
-    env.reset(random=True)
+    env = _make_env(n, solver='newton', iters=100, tol=1e-8, robot=robot, scene=scene, auto_reset='next_step', accessors=True)   # (the contact row: extra outputs,
+    env.reset(random=True)                                                                                                         #  every contact still played - 'dropped' below)
     g = torch.Generator(device='cuda').manual_seed(3)
     for _ in range(120):
         env.step(torch.randn(n, 12, generator=g, device='cuda') * 50)
@@ -989,13 +995,14 @@ def test_step_parity_on_benchmark_rollout_states(robot, scene):
     d = gpu_records(env, int(idx.max()) + 1, ['qacc', 'nefc', 'ncon', 'niter', 'efc_J', 'efc_R', 'efc_aref'])
     o = _oracle(env)
     cone = env.mjModel.cone == 1
-    tally = ParityTally(cone, 3e-7 if scene == 'flat' else 3e-6)
+    assert all('contacts' in d[e] for e in idx)
+    tally = ParityTally(cone, 3e-7 if scene == 'flat' else 3e-6, shapes=Shapes(env._mm))
     ea, ev, nit = [], [], []
     for e in idx:
         cls = tally.step_env(e, o, (qpos[e], qvel[e], warm[e], app[e], 0.0, float(fr[e])), ctrl[e], d[e], sp.CONTACT_COUNT)
         if cls == 'budget':
             tally.check_budget_prefix(e, o, d[e])
-        if cls != 'ok':
+        if cls not in sp.COMPARED:
             continue
         assert d[e]['dropped'] == 0   # the benchmark's states are played with every contact
         ea.append(np.abs(d[e]['qacc'] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
@@ -1008,7 +1015,7 @@ def test_step_parity_on_benchmark_rollout_states(robot, scene):
     assert p99(ev) < (7e-4 if cone else 5e-5) and max(ev) < 5e-3, (p99(ev), max(ev))
     # measured on MI355X (profiles/r03_parity_tallies.txt): 0 of 160 over the row budget for every robot on flat; ties only on
     # hull robots.  A regression that drops contacts shows up as budget / mismatch counts far above these bounds.
-    tally.finish(f'benchmark-state one-step parity {robot} {scene}', min_checked=0.85, max_tie=0.12, max_budget=0.03)
+    tally.finish_held(f'benchmark-state one-step parity {robot} {scene}', min_checked=0.85, max_uncompared=0.12, max_budget=0.03, min_compared=0.85)
 
 
 @pytest.mark.parametrize('mode', ['step', 'rollout', 'spot_boxes', 'sharded'])

@@ -874,3 +874,139 @@ def test_closest_on_triangle_routine_against_projection_reference():
     import hfield_cases as hc
     e, i = hc.check_triangles(*hc.oracle_triangles(), hc.ORACLE_TOL)
     print(f'closest_on_triangle: {dict(zip(hc._FEATURES, hc.triangle_cases()["counts"]))}, max point error {e:.3g} (case {i})')
+
+
+def _self_contact_oracle(robot, n, seed, want_point=False):
+    """(mm, oracle, states): n states with a robot-robot contact; want_point: each with a convex contact whose point is not determined"""
+    from helpers import self_contact_states
+    mm = marshalled(robot, solver=1, iterations=100, tolerance=1e-12)
+    o = Oracle(mm)
+    rng = np.random.default_rng(seed)
+    keep = []
+    for _ in range(40):
+        for q, v in zip(*self_contact_states(mm.md, n, rng, o)):
+            o.set_state(q, v, np.zeros(18), np.zeros(18), 0.0, 0.7); o.forward(np.zeros(12), stage=1)
+            if not want_point or (o.get('contact_tiegap') == -1.0).any():
+                keep.append((q, v))
+        if len(keep) >= n:
+            break
+    assert len(keep) >= n
+    return mm, o, keep[:n]
+
+
+_STEP_OUTPUTS = ('qpos', 'qvel', 'qacc', 'efc_J', 'efc_R', 'efc_aref', 'efc_force', 'contact_pos', 'contact_frame', 'contact_dist', 'contact_force')
+
+
+@pytest.mark.parametrize('robot', ['b2', 'go2'])
+def test_contact_point_override_changes_the_point_alone(robot):
+    """Oracle.set_contact_pos: an override equal to the oracle's own points - and, for convex contacts, normals - changes no output bit; a moved
+    point moves the rows and nothing of the list; a NaN normal keeps the normal; set_state clears the override; an index past the list is an error."""
+    mm, o, states = _self_contact_oracle(robot, 4, 3)
+    ctrl = np.random.default_rng(0).normal(0, 10, 12)
+    with_normal = 0
+    for q, v in states:
+        state = (q, v, np.zeros(18), np.zeros(18), 0.0, 0.7)
+        o.set_state(*state); o.step(ctrl)
+        ref = {k: getattr(o, k).copy() for k in _STEP_OUTPUTS}
+        ncon, nefc = o.ncon, o.nefc
+        o.set_state(*state); o.set_contact_pos(np.arange(ncon), ref['contact_pos']); o.step(ctrl)
+        for k in _STEP_OUTPUTS:
+            assert np.array_equal(getattr(o, k), ref[k]), k
+        o.set_state(*state); o.set_contact_pos([ncon - 1], ref['contact_pos'][ncon - 1] + [0.0, 0.01, 0.0]); o.step(ctrl)
+        assert (o.ncon, o.nefc) == (ncon, nefc)
+        assert np.array_equal(o.contact_pos[:ncon - 1], ref['contact_pos'][:ncon - 1]) and np.array_equal(o.contact_pos[ncon - 1], ref['contact_pos'][ncon - 1] + [0.0, 0.01, 0.0])
+        for k in ('contact_frame', 'contact_dist', 'efc_R'):
+            assert np.array_equal(getattr(o, k), ref[k]), k
+        assert not np.array_equal(o.efc_J, ref['efc_J'])
+        # the normal that goes with a point (a second minimum translation of a convex pair): the oracle's own normal changes no output bit, a NaN
+        # row keeps the normal, another normal turns the frame of that contact alone and leaves its point, its depth and the list
+        cvx = np.where(o.get('contact_cvx')[:ncon] == 1.0)[0]
+        if len(cvx):
+            with_normal += 1
+            own = np.full((ncon, 3), np.nan); own[cvx] = ref['contact_frame'][cvx, 0]
+            o.set_state(*state); o.set_contact_pos(np.arange(ncon), ref['contact_pos'], own); o.step(ctrl)
+            for k in _STEP_OUTPUTS:
+                assert np.array_equal(getattr(o, k), ref[k]), k
+            c, turned = cvx[0], np.full((ncon, 3), np.nan)
+            turned[c] = ref['contact_frame'][c, 0] + 0.1 * ref['contact_frame'][c, 1]
+            o.set_state(*state); o.set_contact_pos(np.arange(ncon), ref['contact_pos'], turned); o.step(ctrl)
+            assert (o.ncon, o.nefc) == (ncon, nefc)
+            others = np.arange(ncon) != c
+            assert np.array_equal(o.contact_frame[others], ref['contact_frame'][others]) and np.array_equal(o.contact_pos, ref['contact_pos'])
+            assert np.array_equal(o.contact_dist, ref['contact_dist'])
+            np.testing.assert_allclose(o.contact_frame[c][0], turned[c] / np.linalg.norm(turned[c]), atol=1e-15)
+            assert np.abs(o.contact_frame[c] @ o.contact_frame[c].T - np.eye(3)).max() < 1e-14
+        o.set_state(*state); o.step(ctrl)            # cleared by set_state
+        for k in _STEP_OUTPUTS:
+            assert np.array_equal(getattr(o, k), ref[k]), k
+        o.set_state(*state); o.set_contact_pos([ncon], [np.zeros(3)])
+        with pytest.raises(RuntimeError, match='override'):
+            o.step(ctrl)
+        with pytest.raises(RuntimeError, match='override'):
+            o.forward(ctrl, stage=1)
+        o.set_state(*state)
+    assert with_normal >= 2 or robot != 'b2', with_normal   # (b2: hull against hull; go2 has primitives only)
+
+
+@pytest.mark.parametrize('robot', ['b2', 'hyqreal1', 'go1'])
+def test_contact_feature_distances_on_the_oracles_own_points(robot):
+    """contact_list.Shapes, the signed distances that decide whether the point of a convex contact lies on the contact feature, with neither
+    GPU nor emulator: the oracle's own points - determined or not - lie within half the depth of both shapes; from such a point along
+    a tangent a shape is left within the geom's extent, and 1 mm past the last point that still holds the condition fails; along the normal
+    1 mm fails at once."""
+    from contact_cases import CVX_TOL
+    from contact_list import Shapes
+    mm, o, states = _self_contact_oracle(robot, 6, 5, want_point=True)
+    sh = Shapes(mm)
+    ncvx = nund = 0
+    for q, v in states:
+        o.set_state(q, v, np.zeros(18), np.zeros(18), 0.0, 0.7); o.forward(np.zeros(12), stage=1)
+        gap, cvx, dist, pos, frame = o.get('contact_tiegap'), o.get('contact_cvx'), o.get('contact_dist'), o.contact_pos, o.contact_frame
+        for c in range(o.ncon):
+            if not cvx[c] or gap[c] == 0.0:
+                continue
+            ncvx += 1; nund += gap[c] == -1.0
+            ok, sd = sh.on_feature(o, c, pos[c], dist[c])
+            assert ok, (c, sd, dist[c])
+            assert abs(sh.depth_along(o, c, frame[c][0]) - dist[c]) < CVX_TOL['dist'], (c, sh.depth_along(o, c, frame[c][0]), dist[c])   # the normal is a direction of minimum depth
+            if abs(dist[c]) < 0.9e-3:
+                assert not sh.on_feature(o, c, pos[c] + 1e-3 * frame[c][0], dist[c])[0] and not sh.on_feature(o, c, pos[c] - 1e-3 * frame[c][0], dist[c])[0]
+            rb = [float(mm.md.geom_rbound[int(o.get(k)[c])]) for k in ('contact_geom1', 'contact_geom')]
+            reach = 2.0 * min(rb) + 0.01   # the overlap lies inside both shapes: past the smaller one's diameter the point has left it
+            for t in (frame[c][1], -frame[c][1], frame[c][2], -frame[c][2]):
+                holds = lambda x: sh.on_feature(o, c, pos[c] + x * t, dist[c])[0]
+                assert not holds(reach), (c, 'the point never leaves the shapes', reach)
+                hi = reach   # (the condition holds on an interval of the line: both distances are convex)
+                s = 0.0
+                while hi - s > 2.5e-4:
+                    mid = 0.5 * (s + hi)
+                    s, hi = (mid, hi) if holds(mid) else (s, mid)
+                assert not sh.on_feature(o, c, pos[c] + (s + 1e-3) * t, dist[c])[0], (c, s)
+    assert ncvx >= 12 and nund >= 6, (ncvx, nund)
+
+
+def test_convex_routine_point_deep_inside_a_prism():
+    """The reference side of an open finding (profiles/contact_list_parity.md): a sphere's centre centimetres inside b2's 32-vertex cylinder
+    prism - a foot inside a hip cylinder in the self-collision test's random poses.  The depth is the distance to the nearest face plane of the
+    prism, the normal that face's; the oracle's convex routine gives both in every case.  (The kernel's fp32 routine, called alone on these
+    cases, ends GJK on a sub-simplex and reports the cores as apart in 27 of 2000 under the host emulator and 29 of 2000 on the device; when it is mended, its comparison
+    with the oracle belongs in contact_cases.convex_cases, which stops at 30 mm of overlap.)"""
+    from scipy.spatial import ConvexHull
+    from scipy.spatial.transform import Rotation as Rot
+    md = marshalled('b2', solver=1).md
+    cl = next(c for c in range(len(md.cloud_vertnum)) if md.cloud_vertnum[c] == 32)
+    V = np.asarray(md.vert_pos[md.cloud_vertadr[cl]:md.cloud_vertadr[cl] + 32], np.float32).astype(np.float64)
+    eq = ConvexHull(V).equations
+    R, H = V[:, :2].max(), V[:, 2].max()
+    rng = np.random.default_rng(0)
+    n = 0
+    while n < 300:
+        q = rng.uniform(-1, 1, 3) * [0.9 * R, 0.9 * R, 0.95 * H]
+        s = eq[:, :3] @ q + eq[:, 3]
+        if np.hypot(q[0], q[1]) > 0.95 * R or np.sort(s)[-1] - np.sort(s[np.abs(eq[:, :3] @ eq[s.argmax(), :3]) < 0.999])[-1] < 1e-6:
+            continue   # (outside the rim, or two faces of different direction equally near)
+        RA = Rot.random(random_state=int(rng.integers(1 << 30))).as_matrix()
+        rc, dist, pos, nrm, git, eit = convex_oracle(V, None, RA, np.zeros(3), 0.0, np.zeros((1, 3)), None, np.eye(3), RA @ q, 0.032, 0.0)
+        assert rc == 1 and abs(dist - (s.max() - 0.032)) < 1e-12, (q, dist, s.max() - 0.032)
+        assert np.abs(nrm - RA @ eq[s.argmax(), :3]).max() < 1e-9, (q, nrm)
+        n += 1
