@@ -51,6 +51,22 @@ static thread_local char g_err[512] = "";
     hipError_t e_ = (expr);                                                             \
     if (e_ != hipSuccess) { SET_ERR("%s: %s", #expr, hipGetErrorString(e_)); return GQ_EDEVICE; } \
   } while (0)
+/* every block that carries its own size (include/gq.h: struct_size) must be there, and a binding written against another header is refused by name */
+template <class T>
+static bool fresh(const T* blk, const char* type, const char* who) {
+  if (!blk) { SET_ERR("%s: bad argument", who); return false; }
+  if (blk->struct_size == (int32_t)sizeof(T)) return true;
+  SET_ERR("%s: %s.struct_size is %d, this library's struct has %d bytes: stale binding", who, type, blk->struct_size, (int)sizeof(T));
+  return false;
+}
+/* the head gq_step_joint_cmd and gq_step_foot_cmd share: the command block is there and this library's, the batch is there, the window has a step */
+template <class Cmd>
+static bool cmd_window_args(const GqBatch* b, const Cmd* cmd, const char* type, int decimation, const char* who) {
+  if (!fresh(cmd, type, who)) return false;
+  if (!b) { SET_ERR("%s: bad argument", who); return false; }
+  if (decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, decimation); return false; }
+  return true;
+}
 
 using gq::Buf;
 /* every device / pinned block, stream and event below is owned by its holder (gq_host_res.h): deleting the handle frees it */
@@ -610,11 +626,6 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   return mailbox_steps(b, auto_reset, step_waves, pd != nullptr, stream, who);
 }
 
-static bool mlp_fresh(const GqPolicyMlp* mlp, const char* who) {
-  if (!mlp) { SET_ERR("%s: bad argument", who); return false; }
-  if (mlp->struct_size != (int32_t)sizeof(GqPolicyMlp)) { SET_ERR("%s: GqPolicyMlp.struct_size is %d, this library's struct has %d bytes: stale binding", who, mlp->struct_size, (int)sizeof(GqPolicyMlp)); return false; }
-  return true;
-}
 /* the shape of the network and what the law needs, checked and copied into the device block's form */
 static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who) {
   if (mlp->n_layers < 1 || mlp->n_layers > GQ_MLP_MAXL) { SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, GQ_MLP_MAXL); return GQ_EINVAL; }
@@ -636,10 +647,6 @@ static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char*
 }
 
 /* ---- the reward law's block (gq_reward.h) from the C block: weights checked, columns resolved by observable in this batch's row ---- */
-static bool learn_fresh(const GqLearn* learn, const char* who) {
-  if (learn->struct_size != (int32_t)sizeof(GqLearn)) { SET_ERR("%s: GqLearn.struct_size is %d, this library's struct has %d bytes: stale binding", who, learn->struct_size, (int)sizeof(GqLearn)); return false; }
-  return true;
-}
 static int obs_column(const GqBatch* b, int canonical) {
   for (int c = 0; c < b->host.obs_dim; c++)
     if (b->host.obs_map[c] == canonical) return c;
@@ -694,10 +701,6 @@ static int reward_describe(const GqBatch* b, const GqLearn* learn, gq::RewardLaw
 
 /* ---- the foot terms' block (gq_reward_feet.h) from the C block: parameters checked, columns resolved per CANONICAL foot (obs_map holds the
  * canonical index of every column, so legs_order is already undone) ---- */
-static bool feet_fresh(const GqFootReward* feet, const char* who) {
-  if (feet->struct_size != (int32_t)sizeof(GqFootReward)) { SET_ERR("%s: GqFootReward.struct_size is %d, this library's struct has %d bytes: stale binding", who, feet->struct_size, (int)sizeof(GqFootReward)); return false; }
-  return true;
-}
 static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw& F, const char* who) {
   static const char* const names[GQ_FOOT_TERMS] = {"air_time", "slip", "impact", "clearance"};
   const float w[GQ_FOOT_TERMS] = {feet->w_air_time, feet->w_slip, feet->w_impact, feet->w_clearance};
@@ -734,9 +737,9 @@ static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw
 static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                           const GqFootReward* feet, void* hip_stream, const char* const who) {
-  if (feet && !feet_fresh(feet, who)) return GQ_EINVAL;
-  if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
-  if (learn && !learn_fresh(learn, who)) return GQ_EINVAL;
+  if (feet && !fresh(feet, "GqFootReward", who)) return GQ_EINVAL;
+  if (!fresh(mlp, "GqPolicyMlp", who)) return GQ_EINVAL;
+  if (learn && !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
@@ -816,7 +819,7 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
 static int reward_eval(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act, const float* act_prev,
                        const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream, const char* const who) {
   if (!learn) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  if ((feet && !feet_fresh(feet, who)) || !learn_fresh(learn, who)) return GQ_EINVAL;
+  if ((feet && !fresh(feet, "GqFootReward", who)) || !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (!b || !rows || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
@@ -849,7 +852,7 @@ int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* fe
 
 int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, int n_rows, int impl, float* out, void* hip_stream) {
   const char* const who = "gq_policy_mlp_eval";
-  if (!mlp_fresh(mlp, who)) return GQ_EINVAL;
+  if (!fresh(mlp, "GqPolicyMlp", who)) return GQ_EINVAL;
   if (!b || !rows || !out || n_rows < 0 || (impl != 0 && impl != 1)) { SET_ERR("gq_policy_mlp_eval: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
@@ -863,52 +866,54 @@ int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, in
   return GQ_OK;
 }
 
+/* gq_step_joint_cmd / gq_step_foot_cmd: what both check (cmd_window_args above, before each one's own fields, and the gain layout) */
+static bool cmd_gain_stride_ok(int gain_stride, const char* who) {
+  if (gain_stride != 0 && gain_stride != 12) { SET_ERR("%s: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", who, gain_stride); return false; }
+  return true;
+}
+/* ... and the tail: `decimation` substeps in the persistent step kernel, the law selected by the tagged pointer to its device block */
+static int cmd_window_launch(GqBatch* b, int decimation, const gq::PolicyPdDev* policy, const GqResetCfg* auto_reset, float* obs_seq, float* act_seq, hipStream_t stream) {
+  gq::StepCall c{};
+  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = policy;
+  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
+  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
+  return GQ_OK;
+}
+
 int gq_step_joint_cmd(GqBatch* b, const GqJointCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
                       int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  if (!cmd) { SET_ERR("gq_step_joint_cmd: bad argument"); return GQ_EINVAL; }
-  if (cmd->struct_size != (int32_t)sizeof(GqJointCmd)) { SET_ERR("gq_step_joint_cmd: GqJointCmd.struct_size is %d, this library's struct has %d bytes: stale binding", cmd->struct_size, (int)sizeof(GqJointCmd)); return GQ_EINVAL; }
-  if (!b) { SET_ERR("gq_step_joint_cmd: bad argument"); return GQ_EINVAL; }
-  if (decimation < 1) { SET_ERR("gq_step_joint_cmd: decimation must be >= 1 (got %d)", decimation); return GQ_EINVAL; }
-  if (!cmd->q_des || !cmd->kp || !cmd->kd) { SET_ERR("gq_step_joint_cmd: q_des, kp and kd must be given"); return GQ_EINVAL; }
-  if (cmd->gain_stride != 0 && cmd->gain_stride != 12) { SET_ERR("gq_step_joint_cmd: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", cmd->gain_stride); return GQ_EINVAL; }
-  if (!persistent_ok(b, auto_reset, "gq_step_joint_cmd")) return GQ_EINVAL;
+  const char* const who = "gq_step_joint_cmd";
+  if (!cmd_window_args(b, cmd, "GqJointCmd", decimation, who)) return GQ_EINVAL;
+  if (!cmd->q_des || !cmd->kp || !cmd->kd) { SET_ERR("%s: q_des, kp and kd must be given", who); return GQ_EINVAL; }
+  if (!cmd_gain_stride_ok(cmd->gain_stride, who)) return GQ_EINVAL;
+  if (!persistent_ok(b, auto_reset, who)) return GQ_EINVAL;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_step_joint_cmd"); rc != GQ_OK) return rc;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
   DeviceGuard guard(b->model->device);
   /* the command pointers travel in a device block of their own: uploaded, stream-ordered, only when one of them changed */
   gq::JointCmdDev J = b->jc.shadow; /* a copy of the shadow, then the fields: see Staged */
   J.q_des = cmd->q_des; J.qd_des = cmd->qd_des; J.tau_ff = cmd->tau_ff; J.kp = cmd->kp; J.kd = cmd->kd;
   J.tau_out = cmd->tau_out; J.term_any = cmd->terminated_any; J.gain_stride = cmd->gain_stride; J.pad_ = 0;
   HIP_TRY(b->jc.push(J, stream, false));
-  gq::StepCall c{};
-  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_joint_cmd(b->jc.dev.get());
-  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
-  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
-  return GQ_OK;
+  return cmd_window_launch(b, decimation, gq::policy_tag_joint_cmd(b->jc.dev.get()), auto_reset, obs_seq, act_seq, stream);
 }
 
 int gq_step_foot_cmd(GqBatch* b, const GqFootCmd* cmd, int decimation, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
                      int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  if (!cmd) { SET_ERR("gq_step_foot_cmd: bad argument"); return GQ_EINVAL; }
-  if (cmd->struct_size != (int32_t)sizeof(GqFootCmd)) { SET_ERR("gq_step_foot_cmd: GqFootCmd.struct_size is %d, this library's struct has %d bytes: stale binding", cmd->struct_size, (int)sizeof(GqFootCmd)); return GQ_EINVAL; }
-  if (!b) { SET_ERR("gq_step_foot_cmd: bad argument"); return GQ_EINVAL; }
-  if (decimation < 1) { SET_ERR("gq_step_foot_cmd: decimation must be >= 1 (got %d)", decimation); return GQ_EINVAL; }
-  if (!cmd->p_des || !cmd->kp || !cmd->kd) { SET_ERR("gq_step_foot_cmd: p_des, kp and kd must be given"); return GQ_EINVAL; }
-  if (cmd->gain_stride != 0 && cmd->gain_stride != 12) { SET_ERR("gq_step_foot_cmd: gain_stride must be 0 (one row of 12) or 12 ([N][12]), got %d", cmd->gain_stride); return GQ_EINVAL; }
-  if (cmd->frame != 0 && cmd->frame != 1) { SET_ERR("gq_step_foot_cmd: frame must be 0 (base) or 1 (world axes), got %d", cmd->frame); return GQ_EINVAL; }
-  if (!persistent_ok(b, auto_reset, "gq_step_foot_cmd")) return GQ_EINVAL;
+  const char* const who = "gq_step_foot_cmd";
+  if (!cmd_window_args(b, cmd, "GqFootCmd", decimation, who)) return GQ_EINVAL;
+  if (!cmd->p_des || !cmd->kp || !cmd->kd) { SET_ERR("%s: p_des, kp and kd must be given", who); return GQ_EINVAL; }
+  if (!cmd_gain_stride_ok(cmd->gain_stride, who)) return GQ_EINVAL;
+  if (cmd->frame != 0 && cmd->frame != 1) { SET_ERR("%s: frame must be 0 (base) or 1 (world axes), got %d", who, cmd->frame); return GQ_EINVAL; }
+  if (!persistent_ok(b, auto_reset, who)) return GQ_EINVAL;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, "gq_step_foot_cmd"); rc != GQ_OK) return rc;
+  if (const int rc = bind(b, st, out, auto_reset, episode, lift_failed, stream, who); rc != GQ_OK) return rc;
   DeviceGuard guard(b->model->device);
   gq::FootCmdDev F = b->fc.shadow; /* a copy of the shadow, then the fields: see Staged */
   F.p_des = cmd->p_des; F.v_des = cmd->v_des; F.f_ff = cmd->f_ff; F.tau_ff = cmd->tau_ff; F.kp = cmd->kp; F.kd = cmd->kd;
   F.tau_out = cmd->tau_out; F.term_any = cmd->terminated_any; F.gain_stride = cmd->gain_stride; F.frame = cmd->frame;
   HIP_TRY(b->fc.push(F, stream, false));
-  gq::StepCall c{};
-  c.n_steps = decimation; c.obs_seq = obs_seq; c.act_seq = act_seq; c.policy = gq::policy_tag_foot_cmd(b->fc.dev.get());
-  c.auto_reset = gq::auto_reset_mode(auto_reset); c.stop_stage = 0;
-  HIP_TRY(launch_step_kernel(b, &c, b->host.n_envs, stream));
-  return GQ_OK;
+  return cmd_window_launch(b, decimation, gq::policy_tag_foot_cmd(b->fc.dev.get()), auto_reset, obs_seq, act_seq, stream);
 }
 
 int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream) {
@@ -1004,7 +1009,7 @@ static bool cam_unit_range(const float* v, int n) {
 static int camera_shade(const GqCamShade* in, gq::CamShade& s) {
   const char* fn = "gq_camera_shaded";
   if (!in) { SET_ERR("%s: null shade", fn); return GQ_EINVAL; }
-  if (in->struct_size != (int32_t)sizeof(GqCamShade)) { SET_ERR("%s: GqCamShade.struct_size %d != %d (header mismatch)", fn, in->struct_size, (int)sizeof(GqCamShade)); return GQ_EINVAL; }
+  if (!fresh(in, "GqCamShade", fn)) return GQ_EINVAL;
   if (!in->geom_mat) { SET_ERR("%s: null geom_mat", fn); return GQ_EINVAL; }
   if (in->nlight < 0 || in->nlight > GQ_CAM_MAXLIGHT) { SET_ERR("%s: nlight %d is not in [0, %d]", fn, in->nlight, GQ_CAM_MAXLIGHT); return GQ_EINVAL; }
   if (in->head_active != 0 && in->head_active != 1) { SET_ERR("%s: head_active %d is not 0 / 1", fn, in->head_active); return GQ_EINVAL; }
@@ -1065,9 +1070,7 @@ static int camera_run(const char* fn, const int mode, GqBatch* b, const double* 
                       void* hip_stream) {
   if (mode >= 2) {
     if (!layers) { SET_ERR("%s: null layers", fn); return GQ_EINVAL; }
-    if (layers->struct_size != (int32_t)sizeof(GqCamLayers)) {
-      SET_ERR("%s: GqCamLayers.struct_size %d != %d (header mismatch)", fn, layers->struct_size, (int)sizeof(GqCamLayers)); return GQ_EINVAL;
-    }
+    if (!fresh(layers, "GqCamLayers", fn)) return GQ_EINVAL;
     if (layers->n_ghost < 0 || layers->n_ghost > GQ_CAM_MAXGHOST) { SET_ERR("%s: n_ghost %d is not in [0, %d]", fn, layers->n_ghost, GQ_CAM_MAXGHOST); return GQ_EINVAL; }
     if (layers->n_marker < 0 || layers->n_marker > GQ_CAM_MAXMARKER) { SET_ERR("%s: n_marker %d is not in [0, %d]", fn, layers->n_marker, GQ_CAM_MAXMARKER); return GQ_EINVAL; }
     if (layers->n_ghost > 0 && (!layers->ghost_qpos || !layers->ghost_alpha)) { SET_ERR("%s: n_ghost > 0 with a null ghost_qpos or ghost_alpha", fn); return GQ_EINVAL; }

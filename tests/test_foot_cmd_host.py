@@ -175,20 +175,8 @@ def test_law_reduces_exactly(law, robot):
 
 def test_abi_of_the_foot_command_entry_point():
     from gym_quadruped_amd import _lib
-    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqFootCmd, GqObsOut, GqResetCfg, GqState
-    fields = [f[0] for f in GqFootCmd._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%zu", sizeof(GqFootCmd));'
-           + ''.join(f'printf(" %zu", offsetof(GqFootCmd, {f}));' for f in fields) + 'printf("\\n");return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = [int(x) for x in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
-    assert out == [ctypes.sizeof(GqFootCmd)] + [getattr(GqFootCmd, f).offset for f in fields]
-    assert 'gq_step_foot_cmd' in _lib.EXPORTS
-    assert GQ_ABI_VERSION == 660
-    assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
-    syms = subprocess.run(['nm', '-D', '--defined-only', str(_lib.LIB_PATH)], check=True, capture_output=True, text=True).stdout
-    assert ' T gq_step_foot_cmd\n' in syms
+    from gym_quadruped_amd.cabi import GqFootCmd, GqObsOut, GqResetCfg, GqState
+    assert 'gq_step_foot_cmd' in _lib.EXPORTS                  # layout and export: tests/test_host_and_abi.py, for every struct and symbol
     L = _lib.lib()
     assert L.gq_version() == 660                               # the entry point is additive: the ABI number and the eight pinned sizes stay
     C = ctypes

@@ -3,9 +3,6 @@ FootRewardSpec, include/gq.h GqFootReward): the law's definition compiled for th
 sequences bit for bit, against reward_host with the feet off, against the float64 restatement under a derived bound; the columns per
 legs_order; the spec's validation; the ABI additions."""
 import ctypes
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -14,7 +11,6 @@ import foot_reward_ref as F
 import reward_ref as R
 from learn_windows import _bits, _same, reference_windows
 
-ROOT = Path(__file__).resolve().parents[1]
 DT32 = np.float32(F.DT)
 
 
@@ -249,31 +245,23 @@ def test_the_spec_validates_like_the_library():
 
 def test_foot_struct_layout_matches_header_and_the_abi_keeps_its_version():
     from gym_quadruped_amd import _lib
-    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqFootReward, GqLearn
+    from gym_quadruped_amd.cabi import GqFootReward, GqLearn
     from gym_quadruped_amd.reward import FOOT_TERMS
     fields = [n for n, _ in GqFootReward._fields_]
     assert fields[2:6] == ['w_' + t for t in FOOT_TERMS], 'the weights stand in the order the terms continue the sum'
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%d %zu %zu' + ' %zu' * len(fields) + '\\n",GQ_ABI_VERSION,sizeof(GqLearn),sizeof(GqFootReward),'
-           + ','.join(f'offsetof(GqFootReward, {n})' for n in fields) + ');return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = [int(v) for v in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == GQ_ABI_VERSION == 660
-    assert out[1] == ctypes.sizeof(GqLearn) == 104, 'GqLearn is what it was: 2 + 12 + 3 + 1 words and 4 pointers'
-    assert out[2] == ctypes.sizeof(GqFootReward)
-    assert out[3:] == [getattr(GqFootReward, n).offset for n in fields]
+    # (layout and export: tests/test_host_and_abi.py, for every struct and symbol)
+    assert ctypes.sizeof(GqLearn) == 104, 'GqLearn is what it was: 2 + 12 + 3 + 1 words and 4 pointers'
     assert 'gq_rollout_policy_learn_feet' in _lib.EXPORTS and 'gq_reward_eval_feet' in _lib.EXPORTS
     assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
     L = ctypes.CDLL(str(_lib.LIB_PATH))
     assert L.gq_version() == 660
-    sizes = (ctypes.c_int32 * 9)(*([-7] * 9))
-    L.gq_struct_sizes(sizes)   # still 8 entries: GqFootReward carries its own size
-    assert all(v > 0 for v in sizes[:8]) and sizes[8] == -7
+    n = len(_lib.SIZED_STRUCTS)
+    sizes = (ctypes.c_int32 * (n + 1))(*([-7] * (n + 1)))
+    L.gq_struct_sizes(sizes)   # GqFootReward carries its own size: the library reports the pinned structs and not one word more
+    assert all(v > 0 for v in sizes[:n]) and sizes[n] == -7
     # a stale binding is refused before anything else is looked at (no device is touched: the handle is never reached)
     L.gq_last_error.restype = ctypes.c_char_p
-    P = ctypes.c_void_p
-    L.gq_reward_eval_feet.argtypes = [P, ctypes.POINTER(GqLearn), ctypes.POINTER(GqFootReward), P, P, P, P, P, P, ctypes.c_int, P, P, P]
+    L.gq_reward_eval_feet.argtypes = _lib.ABI['gq_reward_eval_feet'][1]
     g = GqLearn(struct_size=ctypes.sizeof(GqLearn))
     stale = GqFootReward(struct_size=ctypes.sizeof(GqFootReward) - 8)
     assert L.gq_reward_eval_feet(None, ctypes.byref(g), ctypes.byref(stale), None, None, None, None, None, None, 0, None, None, None) == -1

@@ -8,7 +8,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import abi_layout
+from gym_quadruped_amd import cabi
+
 ROOT = Path(__file__).resolve().parents[1]
+MIRRORS = abi_layout.mirrors(cabi)   # every ctypes.Structure of the binding, discovered: a new mirror is held to the header the day it is added
 REF_XML = Path('/root/reference/gym_quadruped/robot_model')
 
 
@@ -71,36 +75,58 @@ def test_mjcf_defaults_childclass_and_fromto(tmp_path):
 
 
 def test_cabi_library_exports_every_declared_symbol():
+    """include/gq.h, _lib.py's table and the built library name the same functions; every entry has as many argument types as its prototype parameters"""
     from gym_quadruped_amd import _lib
     assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
-    header = (ROOT / 'include' / 'gq.h').read_text()
-    declared = set(re.findall(r'\b(gq_[a-z_]+)\s*\(', header))
+    declared = set(re.findall(r'\b(gq_[a-z_]+)\s*\(', abi_layout.header_text()))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    assert _lib.EXPORTS == list(_lib.ABI)
     syms = subprocess.run(['nm', '-D', '--defined-only', str(_lib.LIB_PATH)], check=True, capture_output=True, text=True).stdout
     for s in declared:
         assert f' T {s}\n' in syms, f'{s} not exported'
+    protos = abi_layout.header_prototypes()
+    assert set(protos) == declared, set(protos) ^ declared   # the parameter parse saw every prototype
+    for name, (restype, argtypes) in _lib.ABI.items():
+        assert len(argtypes) == protos[name], f'{name}: include/gq.h declares {protos[name]} parameters, _lib.ABI has {len(argtypes)} argument types'
+
+
+@pytest.mark.parametrize('mirror', MIRRORS, ids=lambda t: t.__name__)
+def test_ctypes_mirror_layout_matches_header(mirror):
+    """every ctypes.Structure of cabi.py against its struct in include/gq.h as the C compiler lays it out: the size and the offset of EVERY field"""
+    size, offsets = abi_layout.c_layout(tuple(MIRRORS))[mirror.__name__]
+    for f, *_ in mirror._fields_:
+        assert getattr(mirror, f).offset == offsets[f], f'{mirror.__name__}.{f}: cabi.py has it at byte {getattr(mirror, f).offset}, include/gq.h at {offsets[f]}'
+    assert ctypes.sizeof(mirror) == size, f'{mirror.__name__}: cabi.py makes it {ctypes.sizeof(mirror)} bytes, include/gq.h {size}'
 
 
 def test_ctypes_struct_layout_matches_header():
-    """sizeof of the ctypes mirrors must equal what the C compiler sees (guards against field drift) - every struct that
-    crosses the boundary, in the order of gq_struct_sizes."""
-    from gym_quadruped_amd.cabi import GqImuCfg, GqMailboxView, GqModelDesc, GqObsOut, GqPolicyPd, GqResampleCfg, GqResetCfg, GqState
-    names = ['GqModelDesc', 'GqState', 'GqObsOut', 'GqResetCfg', 'GqResampleCfg', 'GqImuCfg', 'GqPolicyPd', 'GqMailboxView']
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("' + '%zu ' * len(names) + '%zu\\n",' + ','.join(f'sizeof({n})' for n in names)
-           + ',offsetof(GqPolicyPd, noise_seed));return 0;}')
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()
-    mirror = [GqModelDesc, GqState, GqObsOut, GqResetCfg, GqResampleCfg, GqImuCfg, GqPolicyPd, GqMailboxView]
-    assert [int(x) for x in out[:-1]] == [ctypes.sizeof(t) for t in mirror]
-    assert int(out[-1]) == GqPolicyPd.noise_seed.offset   # the 8-byte-aligned word after 37 floats
-    # ... and the built library reports the same eight numbers (what _lib.lib() refuses a stale build with)
+    """gq_struct_sizes of the built library == the mirrors of _lib.SIZED_STRUCTS (what _lib.lib() refuses a stale build with) == the header's sizes"""
     from gym_quadruped_amd import _lib
+    assert set(_lib.SIZED_STRUCTS) <= set(MIRRORS) and len(_lib.SIZED_STRUCTS) == 8
+    mirror = [ctypes.sizeof(t) for t in _lib.SIZED_STRUCTS]
+    layout = abi_layout.c_layout(tuple(MIRRORS))
+    assert [layout[t.__name__][0] for t in _lib.SIZED_STRUCTS] == mirror
     L = ctypes.CDLL(str(_lib.LIB_PATH))
-    sizes = (ctypes.c_int32 * 8)()
-    assert L.gq_struct_sizes(sizes) == 0 and list(sizes) == [ctypes.sizeof(t) for t in mirror]
+    sizes = (ctypes.c_int32 * len(mirror))()
+    assert L.gq_struct_sizes(sizes) == 0 and list(sizes) == mirror
+
+
+def test_cabi_constants_match_header():
+    """every constant cabi.py mirrors against include/gq.h's #define: its GQ_* integers by name, its GQ_* dicts by entry (GQ_DYN['MB']: GQ_DYN_MB), SUPPORT_GRID"""
+    from gym_quadruped_amd import cabi
+    header = abi_layout.header_constants()
+    mirrored = {'GQ_SUPPORT_GRID': cabi.SUPPORT_GRID}
+    for name, v in vars(cabi).items():
+        if name.startswith('GQ_') and isinstance(v, int):
+            mirrored[name] = v
+        elif name.startswith('GQ_') and isinstance(v, dict):
+            mirrored.update({f'{name}_{k.upper()}': x for k, x in v.items()})
+    assert {'GQ_ABI_VERSION', 'GQ_NLEG', 'GQ_DYN_STRIDE', 'GQ_CON_MAX', 'GQ_CON_REC', 'GQ_CON_STRIDE', 'GQ_CAM_ROBOT', 'GQ_CAM_SCENE', 'GQ_CAM_TRACK', 'GQ_CAM_MAXLIGHT',
+            'GQ_CAM_MAXGHOST', 'GQ_CAM_MAXMARKER', 'GQ_CAM_MAXLAYER', 'GQ_ACT_TANH'} <= set(mirrored)
+    for name, v in mirrored.items():
+        assert name in header, f'cabi.py mirrors {name}: include/gq.h has no such #define'
+        assert v == header[name], f'{name}: cabi.py has {v}, include/gq.h {header[name]}'
+    assert header['GQ_ABI_VERSION'] == 660
 
 
 def integration_stub_text():

@@ -2,7 +2,6 @@
 emulator's shim and compared bit for bit with the elementwise float32 expression, and the C ABI of the new entry point."""
 import ctypes
 import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -118,18 +117,8 @@ def test_law_without_velocity_target_and_feed_forward_is_the_pd_law(law):
 
 def test_abi_of_the_joint_command_entry_point():
     from gym_quadruped_amd import _lib
-    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqJointCmd, GqObsOut, GqResetCfg, GqState
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(GqJointCmd), offsetof(GqJointCmd, q_des), offsetof(GqJointCmd, terminated_any));return 0;}'
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = [int(x) for x in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
-    assert out == [ctypes.sizeof(GqJointCmd), GqJointCmd.q_des.offset, GqJointCmd.terminated_any.offset]
-    assert 'gq_step_joint_cmd' in _lib.EXPORTS
-    assert GQ_ABI_VERSION == 660
-    assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
-    syms = subprocess.run(['nm', '-D', '--defined-only', str(_lib.LIB_PATH)], check=True, capture_output=True, text=True).stdout
-    assert ' T gq_step_joint_cmd\n' in syms
+    from gym_quadruped_amd.cabi import GqJointCmd, GqObsOut, GqResetCfg, GqState
+    assert 'gq_step_joint_cmd' in _lib.EXPORTS                 # layout and export: tests/test_host_and_abi.py, for every struct and symbol
     L = _lib.lib()
     assert L.gq_version() == 660                               # the entry point is additive: the ABI number and the eight pinned sizes stay
     C = ctypes

@@ -2,16 +2,12 @@
 law's definition (mlp_row_forward in tests/policy_mlp_host.cpp, a stand-alone g++ program) against a float64 evaluation layer by layer,
 the header's activations and noise, the torch import, and the new struct and entry points of the ABI."""
 import ctypes
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import policy_mlp_ref as R
 
-ROOT = Path(__file__).resolve().parents[1]
 CASES = [(shape, act, out) for shape in ('odd', 'wide', 'single') for act, out in (('relu', None), ('elu', 'tanh'), ('tanh', None))]
 
 
@@ -100,17 +96,8 @@ def test_from_torch_round_trips_and_refuses_what_it_does_not_know():
 
 def test_policy_mlp_struct_layout_matches_header_and_the_abi_keeps_its_version():
     from gym_quadruped_amd import _lib
-    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqPolicyMlp
-    fields = [n for n, _ in GqPolicyMlp._fields_]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%d %zu' + ' %zu' * len(fields) + '\\n",GQ_ABI_VERSION,sizeof(GqPolicyMlp),'
-           + ','.join(f'offsetof(GqPolicyMlp, {n})' for n in fields) + ');return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = [int(v) for v in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == GQ_ABI_VERSION == 660
-    assert out[1] == ctypes.sizeof(GqPolicyMlp)
-    assert out[2:] == [getattr(GqPolicyMlp, n).offset for n in fields]
+    from gym_quadruped_amd.cabi import GqPolicyMlp
+    # (layout and export: tests/test_host_and_abi.py, for every struct and symbol)
     assert 'gq_rollout_policy' in _lib.EXPORTS and 'gq_policy_mlp_eval' in _lib.EXPORTS
     assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
     L = ctypes.CDLL(str(_lib.LIB_PATH))
@@ -119,5 +106,5 @@ def test_policy_mlp_struct_layout_matches_header_and_the_abi_keeps_its_version()
     # a stale binding is refused before anything else is looked at (no device is touched: the handle is never reached)
     L.gq_last_error.restype = ctypes.c_char_p
     m = GqPolicyMlp(struct_size=ctypes.sizeof(GqPolicyMlp) - 8, n_layers=1)
-    L.gq_policy_mlp_eval.argtypes = [ctypes.c_void_p, ctypes.POINTER(GqPolicyMlp), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.gq_policy_mlp_eval.argtypes = _lib.ABI['gq_policy_mlp_eval'][1]
     assert L.gq_policy_mlp_eval(None, ctypes.byref(m), None, 0, 0, None, None) == -1 and b'stale binding' in L.gq_last_error()

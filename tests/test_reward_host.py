@@ -2,16 +2,12 @@
 definition (reward_step in tests/reward_host.cpp, a stand-alone g++ program) against the float64 evaluation, RewardSpec's validation and
 column resolution, and the new struct and entry points of the ABI."""
 import ctypes
-import subprocess
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import reward_ref as R
 
-ROOT = Path(__file__).resolve().parents[1]
 SPECS = R.specs()
 
 
@@ -122,33 +118,20 @@ def test_reference_is_the_formula():
 
 def test_learn_struct_layout_matches_header_and_the_abi_keeps_its_version():
     from gym_quadruped_amd import _lib
-    from gym_quadruped_amd.cabi import GQ_ABI_VERSION, GqLearn
+    from gym_quadruped_amd.cabi import GqLearn
     from gym_quadruped_amd.reward import TERMS
     fields = [n for n, _ in GqLearn._fields_]
     assert fields[2:14] == ['w_' + t for t in TERMS], 'the weights stand in the order of the law\'s sum'
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "gq.h"\nint main(){printf("%d %zu' + ' %zu' * len(fields) + '\\n",GQ_ABI_VERSION,sizeof(GqLearn),'
-           + ','.join(f'offsetof(GqLearn, {n})' for n in fields) + ');return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        (Path(d) / 'a.c').write_text(src)
-        subprocess.run(['gcc', '-I', str(ROOT / 'include'), str(Path(d) / 'a.c'), '-o', str(Path(d) / 'a')], check=True)
-        out = [int(v) for v in subprocess.run([str(Path(d) / 'a')], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == GQ_ABI_VERSION == 660
-    assert out[1] == ctypes.sizeof(GqLearn)
-    assert out[2:] == [getattr(GqLearn, n).offset for n in fields]
-    assert 'gq_rollout_policy_learn' in _lib.EXPORTS and 'gq_reward_eval' in _lib.EXPORTS
-    table = (ROOT / 'gym_quadruped_amd' / '_lib.py').read_text()
-    assert 'L.gq_rollout_policy_learn.argtypes' in table and 'L.gq_reward_eval.argtypes' in table
+    # (layout and export: tests/test_host_and_abi.py, for every struct and symbol) both entry points are in the binding's table, with arguments
+    assert _lib.ABI['gq_rollout_policy_learn'][1] and _lib.ABI['gq_reward_eval'][1]
     assert _lib.LIB_PATH.exists(), 'build the HIP extension first (__graft_entry__.build())'
     L = ctypes.CDLL(str(_lib.LIB_PATH))
     assert L.gq_version() == 660
-    sizes = (ctypes.c_int32 * 8)()
-    L.gq_struct_sizes(sizes)   # still 8 entries: GqLearn carries its own size
     assert L.gq_rollout_policy_learn and L.gq_reward_eval
     # a stale binding is refused before anything else is looked at (no device is touched: the handle is never reached)
     L.gq_last_error.restype = ctypes.c_char_p
     g = GqLearn(struct_size=ctypes.sizeof(GqLearn) - 8)
-    L.gq_reward_eval.argtypes = [ctypes.c_void_p, ctypes.POINTER(GqLearn), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                 ctypes.c_void_p, ctypes.c_void_p]
+    L.gq_reward_eval.argtypes = _lib.ABI['gq_reward_eval'][1]
     assert L.gq_reward_eval(None, ctypes.byref(g), None, None, None, None, None, 0, None, None) == -1 and b'stale binding' in L.gq_last_error()
     spec_struct = SPECS['all']._struct()
     assert spec_struct.struct_size == ctypes.sizeof(GqLearn) and spec_struct.w_termination == -2.0 and abs(spec_struct.base_height_target - 0.3) < 1e-7
