@@ -38,6 +38,21 @@ BASE_OBS_BASE_FRAME = _ALL_OBS[10:15]
 GEN_COORDS_OBS = _ALL_OBS[15:22]
 FEET_OBS = _ALL_OBS[22:31]
 
+# Lowest ground friction the pyramidal-cone Newton kernel is held to the fp64 oracle at (tests/row_edge_cases.py, DESIGN.md "Known
+# deviations"): R of a pyramid edge row goes with mu^2, and below this the primal Hessian M + J^T D J is out of fp32's reach
+PYRAMIDAL_NEWTON_MIN_FRICTION = 0.05
+
+
+def check_ground_friction(cone: int, solver: str, lowest: float, robot: str = ''):
+    """Refuse a ground friction the solver gives a silently wrong answer at: ``ValueError`` for a pyramidal-cone model (``cone`` 0) under
+    ``solver='newton'`` when ``lowest`` - the lower end of ``ground_friction_coeff``, or a friction set later - is below the floor."""
+    if int(cone) == 0 and solver == 'newton' and float(lowest) < PYRAMIDAL_NEWTON_MIN_FRICTION:
+        raise ValueError(
+            f"ground friction {float(lowest):g} is below the floor {PYRAMIDAL_NEWTON_MIN_FRICTION:g} of solver='newton' on a pyramidal-cone model"
+            f"{' (' + robot + ')' if robot else ''}: the regularisation of a pyramid edge row goes with the square of the friction coefficient, so the "
+            "fp32 Newton Hessian loses the contact and the step returns a wrong acceleration without a flag.  solver='pgs' and the "
+            'elliptic-cone robots have no such floor.')
+
 
 def _make_info(env):
     """``info`` dict of ``step``: 'time', 'step_num' (value before this step's increment, as the reference reports
@@ -93,7 +108,7 @@ class QuadrupedEnv(AccessorsMixin):
         self.base_vel_command_type = base_vel_command_type
         self.base_lin_vel_range = _process_range(ref_base_lin_vel)
         self.base_ang_vel_range = _process_range(ref_base_ang_vel)
-        self.ground_friction_coeff_range = _process_range(ground_friction_coeff)
+        self._ground_friction_coeff_range = _process_range(ground_friction_coeff)   # (checked against the solver's floor once the model is known)
         self.legs_order = tuple(legs_order)
         self.num_envs = int(num_envs)
         # False | True / 'same_step' (terminated envs are re-spawned inside the same step call; obs = first of the new
@@ -121,6 +136,8 @@ class QuadrupedEnv(AccessorsMixin):
                                    floor=self.scene_desc.get('floor'), boxes=self.scene_desc.get('boxes'),
                                    hfield=self.scene_desc.get('hfield'), self_collision=self_collision)
         self._sim_dt = float(sim_dt)
+        self._solver = solver
+        check_ground_friction(self.mjModel.cone, solver, self.ground_friction_coeff_range[0], robot)
 
         # leg index maps (reference :189-212)
         self.joint_info = extract_mj_joint_info(self.mjModel)
@@ -929,6 +946,20 @@ class QuadrupedEnv(AccessorsMixin):
     def feet_air_time(self, value):
         self._feet_air.copy_(torch.as_tensor(value, dtype=torch.float32, device=self.device).reshape(self.num_envs, 4))
 
+    @property
+    def ground_friction_coeff_range(self):
+        """``(low, high)`` of the ground friction the resets draw from.  Assigning a scalar or a pair applies from the next reset (the
+        auto-resets inside ``step`` included); a range whose lower end is under the solver's floor is refused (``check_ground_friction``)."""
+        return self._ground_friction_coeff_range
+
+    @ground_friction_coeff_range.setter
+    def ground_friction_coeff_range(self, value):
+        rng = _process_range(value)
+        check_ground_friction(self.mjModel.cone, self._solver, rng[0], self.robot_name)
+        self._ground_friction_coeff_range = rng
+        for cfg in (self._reset_cfg, self._auto_cfg_struct):
+            cfg.friction_range = (C.c_float * 2)(*map(float, rng))
+
     def target_base_vel(self):
         """Reference command in the heading frame ``[N,3]`` and yaw rate ``[N]`` (reference :488-499 inputs)."""
         return self._cmd[:, 0:3], self._cmd[:, 3]
@@ -948,6 +979,11 @@ class QuadrupedEnv(AccessorsMixin):
 
     def load_state_dict(self, d):
         self._hm_fresh = False
+        if '_friction' in d:   # a checkpoint's per-env ground friction (< 0: the XML's, until the first reset) is held to the solver's floor too
+            set_mu = torch.as_tensor(d['_friction'])
+            set_mu = set_mu[set_mu >= 0]
+            if set_mu.numel():
+                check_ground_friction(self.mjModel.cone, self._solver, float(set_mu.min()), self.robot_name)
         for k, v in d.items():
             if k in self._LEGACY_H9:  # checkpoints written before the resampling counters moved into one [N, 6] tensor
                 self._h9[:, self._LEGACY_H9[k]].copy_(torch.as_tensor(v, device=self.device).to(torch.int32))
