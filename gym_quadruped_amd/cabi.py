@@ -133,6 +133,8 @@ class GqFootCmd(C.Structure):
 
 
 GQ_ACT = dict(none=0, relu=1, elu=2, tanh=3)   # GQ_ACT_*
+# gq_rollout_closed_status's abort codes, GQ_CLOSED_ABORT_* (0: the rollout ran to its end)
+GQ_CLOSED_ABORT = dict(step_deadline=1, policy_deadline=2, policy_absent=3, xcd_no_policy=4)
 
 
 class GqPolicyMlp(C.Structure):

@@ -32,6 +32,9 @@ extern "C" void gq_launch_reset(const gq::ResetArgs* a, int n_envs, gq::Scene sc
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream);
 extern "C" void gq_launch_camera(const GqDevModel* model, const gq::CamCall* c, const gq::CamShade* s, const gq::CamLayers* l, int n_envs, hipStream_t stream);
 static_assert(GQ_CAM_NLAYER == GQ_CAM_MAXLAYER, "the pixel pass composites GQ_CAM_MAXLAYER layers");
+static_assert(GQ_CLOSED_ABORT_STEP_DEADLINE == gq::MB_ABORT_STEP_DEADLINE && GQ_CLOSED_ABORT_POLICY_DEADLINE == gq::MB_ABORT_POLICY_DEADLINE &&
+              GQ_CLOSED_ABORT_POLICY_ABSENT == gq::MB_ABORT_POLICY_ABSENT && GQ_CLOSED_ABORT_XCD_NO_POLICY == gq::MB_ABORT_XCD_NO_POLICY,
+              "include/gq.h names the abort codes of gq_mailbox.h");
 extern "C" void gq_launch_ray(const GqDevModel* model, const double* origin, const float* dir, int total, float* dist, int32_t* geom, hipStream_t stream);
 extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* center, int center_stride, const float* yaw, int yaw_stride, int n_envs, int rows, int cols,
                                     float dist_x, float dist_y, float* out, hipStream_t stream);
@@ -460,7 +463,7 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.steps_done.ensure(N, false));
   HIP_TRY(t.issued.ensure(N, false));
   HIP_TRY(t.q_items.ensure((size_t)nq * qcap, false));
-  HIP_TRY(t.q_ctr.ensure((size_t)nq * 3 * GQ_MB_QSTRIDE, false));
+  HIP_TRY(t.q_ctr.ensure(gq::mb_ctr_words(nq), false));
   HIP_TRY(t.status.ensure(8, true));
   HIP_TRY(t.dev.ensure(1, false));
   HIP_TRY(t.policy.create());
@@ -505,8 +508,8 @@ static int closed_begin(GqBatch* b, int n_steps, const GqState& st, const GqObsO
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
   const int N = b->host.n_envs;
   const gq::MailboxDev& h = b->mb.host;
-  /* queue tickets are 32-bit: the env-steps that pass through one queue must stay below 2^31 (items carry env + 1 in 24 bits) */
-  if (N >= (1 << 24) || (int64_t)((N + h.nq - 1) / h.nq) * (int64_t)n_steps >= ((int64_t)1 << 31) - 65536) {
+  /* items carry env + 1 in 24 bits, and queue tickets are 32-bit: the env-steps that pass through queue 0, which holds the most envs */
+  if (!gq::mb_rollout_fits(N, h.nq, n_steps)) { /* (mb_queue_tickets against the bound) */
     SET_ERR("%s: %d envs x %d steps over %d queues overflows the 32-bit ticket counters: split the rollout", who, N, n_steps, h.nq); return GQ_EINVAL;
   }
   return GQ_OK;
@@ -530,16 +533,13 @@ static int mailbox_start(GqBatch* b, int n_steps, int& step_waves, double timeou
   Mailbox& mb = b->mb;
   gq::MailboxDev& h = mb.host;
   const int N = b->host.n_envs;
-  if (step_waves <= 0) step_waves = N; /* more workgroups than free slots (or than envs) is harmless: pop tickets that run ahead of the pushes
-                                        * wait on lap-tagged slots, the late ones find the queues drained */
-  if (step_waves < 4 * h.nq) step_waves = 4 * h.nq; /* a wavefront pops from ITS XCD's queue only: every XCD needs stepping wavefronts, also for a batch of
-                                                      * one env (workgroups are dealt round-robin over the XCDs; the surplus finds its queue empty and leaves) */
+  step_waves = gq::mb_step_waves(step_waves, N, h.nq);
   h.n_steps = n_steps; h.obs_seq = obs_seq; h.act_seq = act_seq;
   h.timeout_ticks = (int64_t)((timeout_s > 0.0 ? timeout_s : 5.0) * 1e8);
   HIP_TRY(hipMemsetAsync(h.steps_done, 0, sizeof(int32_t) * (size_t)N, stream));
   HIP_TRY(hipMemsetAsync(h.issued, 0, sizeof(int32_t) * (size_t)N, stream));
   HIP_TRY(hipMemsetAsync(h.q_items, 0, sizeof(int32_t) * (size_t)h.nq * h.qcap, stream));
-  HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * (size_t)h.nq * 3 * GQ_MB_QSTRIDE, stream));
+  HIP_TRY(hipMemsetAsync(h.q_ctr, 0, sizeof(int32_t) * gq::mb_ctr_words(h.nq), stream));
   HIP_TRY(hipMemsetAsync(h.status, 0, sizeof(int32_t) * 8, stream));
   HIP_TRY(hipStreamSynchronize(stream)); /* the pinned staging block below is reused per call; a rollout is thousands of launches' worth of work */
   std::memcpy(mb.staging.get(), &h, sizeof h);
@@ -563,7 +563,7 @@ static int policy_resident(Mailbox& mb, int policy_waves, hipStream_t stream, co
     std::this_thread::yield();
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
       /* it cannot start: tell it to leave as soon as it does, and report */
-      mb.status_host.get()[0] = 3; /* pinned: the source of an asynchronous copy must outlive this frame */
+      mb.status_host.get()[0] = gq::MB_ABORT_POLICY_ABSENT; /* pinned: the source of an asynchronous copy must outlive this frame */
       (void)hipMemcpyAsync(mb.host.status, mb.status_host.get(), sizeof(int32_t), hipMemcpyHostToDevice, stream);
       (void)hipStreamSynchronize(stream);
       (void)hipStreamSynchronize(mb.stream.get()); /* the policy kernel has left (or never ran): nothing of this call touches `alive` later */
@@ -601,9 +601,7 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   if (pd) {
     if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "PD"); rc != GQ_OK) return rc;
     for (int j = 0; j < 12; j++) { P.kp[j] = pd->kp[j]; P.kd[j] = pd->kd[j]; P.qdes[j] = pd->q_des[j]; }
-    if (policy_waves <= 0) policy_waves = 64; /* lane = env: 4096 envs get a lane each */
-    if (policy_waves > 256) policy_waves = 256;
-    if (policy_waves < 2 * h.nq) policy_waves = 2 * h.nq; /* every XCD needs policy wavefronts of its own (dispatch is round-robin over the XCDs) */
+    policy_waves = gq::mb_policy_waves(policy_waves, 64, 256, h.nq); /* lane = env: by default 4096 envs get a lane each */
     P.sigma = pd->noise_sigma; P.seed_lo = (uint32_t)(pd->noise_seed & 0xffffffffu); P.seed_hi = (uint32_t)(pd->noise_seed >> 32);
     P.step0 = pd->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
     HIP_TRY(mb.policy.push(P, stream, true)); /* sent with every call, as ever */
@@ -768,9 +766,7 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   const int N = b->host.n_envs, od = b->host.obs_dim;
   Mailbox& mb = b->mb;
   gq::MailboxDev& h = mb.host;
-  if (policy_waves <= 0) policy_waves = 128; /* a wavefront takes its ready envs through the network 16 at a time */
-  if (policy_waves > 1024) policy_waves = 1024;
-  if (policy_waves < 2 * h.nq) policy_waves = 2 * h.nq; /* every XCD needs policy wavefronts of its own (dispatch is round-robin over the XCDs) */
+  policy_waves = gq::mb_policy_waves(policy_waves, 128, 1024, h.nq); /* a wavefront takes its ready envs through the network 16 at a time */
   for (int j = 0; j < 12; j++) {
     P.kp[j] = mlp->kp[j]; P.kd[j] = mlp->kd[j]; P.q_default[j] = mlp->q_default[j]; P.action_scale[j] = mlp->action_scale[j]; P.sigma[j] = mlp->noise_sigma[j];
   }
@@ -923,8 +919,17 @@ int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream) {
   HIP_TRY(hipMemcpyAsync(b->mb.status_host.get(), b->mb.host.status, sizeof(int32_t) * 8, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
   for (int i = 0; i < 4; i++) out[i] = b->mb.status_host.get()[i];
-  if (out[0] != 0) { SET_ERR("closed-loop rollout aborted: code %d (1: a step wavefront waited past the deadline for ticket %d; 2: policy lane %d waited past the deadline; 3: policy not resident; 4: no policy wavefront on XCD queue %d), %d env-steps were played", out[0], out[1], out[1], out[1], out[2]); return GQ_EDEVICE; }
-  return GQ_OK;
+  if (out[0] == 0) return GQ_OK;
+  char why[96];
+  switch (out[0]) { /* gq_mailbox.h: the codes, and who stands in out[1] for each */
+    case gq::MB_ABORT_STEP_DEADLINE: std::snprintf(why, sizeof why, "a step wavefront waited past the deadline for ticket %d", out[1]); break;
+    case gq::MB_ABORT_POLICY_DEADLINE: std::snprintf(why, sizeof why, "policy lane %d waited past the deadline", out[1]); break;
+    case gq::MB_ABORT_POLICY_ABSENT: std::snprintf(why, sizeof why, "policy not resident"); break;
+    case gq::MB_ABORT_XCD_NO_POLICY: std::snprintf(why, sizeof why, "no policy wavefront on XCD queue %d", out[1]); break;
+    default: std::snprintf(why, sizeof why, "unknown code, detail %d", out[1]); break;
+  }
+  SET_ERR("closed-loop rollout aborted: code %d (%s), %d env-steps were played", out[0], why, out[2]);
+  return GQ_EDEVICE;
 }
 
 int gq_batch_bind(GqBatch* b, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, void* hip_stream) {

@@ -176,6 +176,7 @@ template <bool PUB, class T> __device__ __forceinline__ T ldv(const T* p) {
   else return *(const GQ_GLOBAL T*)p;
 }
 __device__ __forceinline__ int add_pub(int32_t* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int add_sys(int32_t* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } /* a word the host reads */
 __device__ __forceinline__ bool cas_pub(int32_t* p, int expect, int v) { return __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void publish_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); /* compiler: no store sinks below */

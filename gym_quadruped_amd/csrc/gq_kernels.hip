@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) step_kernel_prim(const FusedArgs* 
   step_kernel_body<SOLVER, MODE, CONE, false, true, true, PERSIST, false>(A, c);
 }
 
-/* Closed-loop persistent rollout, the stepping side (protocol: gq_step_kernel.h MailboxDev).  grid = any number of one-wave workgroups:
+/* Closed-loop persistent rollout, the stepping side (protocol: gq_mailbox.h).  grid = any number of one-wave workgroups:
  * each pops tickets of ITS XCD's ready queue until every env-step of the rollout has been claimed.  Production Newton variants only. */
 template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM, bool CVX>
 __device__ __forceinline__ void mailbox_step_body(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
@@ -63,34 +63,17 @@ __device__ __forceinline__ void mailbox_step_body(const FusedArgs* __restrict__ 
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
   const int q = MB.xcc_queue[xcc_id()];
   const int N = MB.n_envs, nq = MB.nq, qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
-  const int total = ((N - q + nq - 1) / nq) * MB.n_steps; /* env-steps that will ever pass through this queue (< 2^31: checked by gq_rollout_closed) */
-  int32_t* const head = MB.q_ctr + (size_t)(3 * q) * GQ_MB_QSTRIDE;
+  const int total = mb_queue_envs(N, q, nq) * MB.n_steps; /* mb_queue_tickets of this queue: it fits 32 bits (mb_rollout_fits, checked by the host) */
+  int32_t* const head = mb_ctr(MB.q_ctr, q, MB_CTR_POP);
   int32_t* const items = MB.q_items + (size_t)q * MB.qcap;
   int played = 0;
   for (;;) {
     int ticket = 0;
     if (lane_id() == 0) ticket = add_pub(head, 1);
-    ticket = __builtin_amdgcn_readfirstlane(ticket);
+    ticket = uniform(ticket);
     if (ticket >= total) break;
-    int32_t* const slot = items + (ticket & qmask);
-    /* an item carries the LAP of its push ticket (bits 24..30 = (s / qcap) mod 128): tickets may run ahead of the pushes by the number
-     * of resident step wavefronts, which can exceed qcap for a small batch - ticket t and ticket t + qcap then wait on the same slot,
-     * and each must take the item of ITS lap only (an env stepped by two wavefronts at once otherwise).  Nothing is cleared: the
-     * slot is simply overwritten one lap later, and a lap's item is at most one lap old when its ticket reads it. */
-    const int want = (ticket >> qshift) & 0x7f;
-    int item;
-    const long long t0 = wall_clock64();
-    for (int spin = 0;; spin++) { /* the ticket's env is pushed as soon as the policy has its action */
-      item = __builtin_amdgcn_readfirstlane(ld_pub(slot));
-      if ((item & 0xffffff) != 0 && (item >> 24) == want) break;
-      nap();
-      if ((spin & 31) == 31) {
-        bool leave = ld_pub(MB.status) != 0;
-        if (!leave && wall_clock64() - t0 > MB.timeout_ticks) { if (lane_id() == 0) { st_pub(MB.status + 1, ticket); st_pub(MB.status, 1); } leave = true; }
-        if (leave) { if (lane_id() == 0 && played) add_pub(MB.status + 2, played); return; }
-      }
-    }
-    const int env = (item & 0xffffff) - 1;
+    /* the item of the ticket's own lap; an aborted rollout is left here, with what this wavefront has played */
+    GQ_MB_WAIT_ITEM(env, { if (lane_id() == 0 && played) mb_add_played(MB.status, played); return; })
     adopt_fence();
     /* the env's step index is only needed to place the row in obs_seq: otherwise that round trip is not taken */
     const int k = MB.obs_seq ? __builtin_amdgcn_readfirstlane(ld_pub(MB.steps_done + env)) : 0;
@@ -116,7 +99,7 @@ __device__ __forceinline__ void mailbox_step_body(const FusedArgs* __restrict__ 
     wave_barrier();
     played++;
   }
-  if (lane_id() == 0 && played) add_pub(MB.status + 2, played);
+  if (lane_id() == 0 && played) mb_add_played(MB.status, played);
 }
 template <int SOLVER, bool CONE, bool BOXES, bool SELF, bool PRIM>
 __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel(const FusedArgs* __restrict__ A, const StepCall c0, const MailboxDev* __restrict__ MBp) {
@@ -128,30 +111,6 @@ __global__ void __launch_bounds__(GQ_WAVE, 4) mailbox_step_kernel_prim(const Fus
 }
 
 #if GQ_IN_MISC
-/* The head of a policy kernel, shared as TEXT (policy_pd_kernel keeps the code it had when the statements stood in its body: a function
- * around them changed its register allocation): the wavefront says on which XCD it runs and waits until every policy wavefront of the launch
- * has - rank = its number among those of its XCD's queue q, mine = how many there are (the stride over the queue's envs); it RETURNS from
- * the kernel when the abort word is up, the deadline passes or an XCD got no policy wavefront.  Needs MB, lane, nq, q in scope. */
-#define GQ_POLICY_REGISTER()                                                                                                                      \
-  const int P_all = (int)gridDim.x;                                                                                                               \
-  int rank = 0;                                                                                                                                   \
-  if (lane == 0) rank = add_pub(MB.q_ctr + (size_t)(3 * q + 2) * GQ_MB_QSTRIDE, 1);                                                               \
-  rank = __builtin_amdgcn_readfirstlane(rank);                                                                                                    \
-  if (lane == 0) __hip_atomic_fetch_add(MB.alive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);                                                \
-  long long t_last = wall_clock64();                                                                                                              \
-  int mine = 0;                                                                                                                                   \
-  for (;;) { /* every policy wavefront has said where it runs: the stride of this XCD is known */                                                 \
-    int sum = 0;                                                                                                                                  \
-    for (int x = 0; x < nq; x++) { const int c = ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE); sum += c; if (x == q) mine = c; }        \
-    if (sum >= P_all) {                                                                                                                           \
-      for (int x = 0; x < nq; x++)                                                                                                                \
-        if (ld_pub(MB.q_ctr + (size_t)(3 * x + 2) * GQ_MB_QSTRIDE) == 0) { if (lane == 0) { st_pub(MB.status + 1, x); st_pub(MB.status, 4); } return; } /* an XCD without policy */ \
-      break;                                                                                                                                      \
-    }                                                                                                                                             \
-    nap();                                                                                                                                        \
-    if (ld_pub(MB.status) != 0) return;                                                                                                           \
-    if (wall_clock64() - t_last > MB.timeout_ticks) { if (lane == 0) { st_pub(MB.status + 1, -1 - rank); st_pub(MB.status, 2); } return; }        \
-  }
 /* the built-in policy of the closed-loop rollout.  A policy wavefront serves envs of ITS XCD's queue only (lane = env, strided over the
  * policy wavefronts that landed on the XCD): observation row, action row, count and queue slot of an env are written and read
  * through one L2, like the env's state rows - no hand-off of the rollout depends on coherence between two XCDs' L2s, and none
@@ -161,10 +120,10 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
   const GQ_MODEL PolicyPdDev& P = *mptr(Pp);
   const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
   const int N = MB.n_envs, K = MB.n_steps;
-  GQ_POLICY_REGISTER()
-  const int nmine = (N - q + nq - 1) / nq;           /* envs of this queue: e = q + nq * i */
+  GQ_MB_POLICY_REGISTER() /* rank, mine, t_last (gq_mailbox.h) */
+  const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int g = rank * GQ_WAVE + lane, G = mine * GQ_WAVE;
-  int32_t* const tail = MB.q_ctr + (size_t)(3 * q + 1) * GQ_MB_QSTRIDE;
+  int32_t* const tail = mb_ctr(MB.q_ctr, q, MB_CTR_PUSH);
   int32_t* const items = MB.q_items + (size_t)q * MB.qcap;
   t_last = wall_clock64();
   for (;;) {
@@ -181,23 +140,20 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
 #pragma unroll
       for (int j = 0; j < 12; j++) { qj[j] = ld_pub(row + P.col_q[j]); qd[j] = ld_pub(row + P.col_qd[j]); }
       /* the action row and the push ticket travel together */
-      const int s = add_pub(tail, 1);
+      const int s = mb_push_ticket(tail);
 #pragma unroll
       for (int j = 0; j < 12; j++) {
         const float a = pd_action(P, j, qj[j], qd[j], k, (uint32_t)(e + P.env_id_offset));
         st_pub(MB.act + (size_t)e * 12 + j, a);
         if (MB.act_seq) MB.act_seq[((size_t)k * N + e) * 12 + j] = a;
       }
-      publish_fence();
-      st_pub(items + (s & qmask), (((s >> qshift) & 0x7f) << 24) | (e + 1)); /* the item (lap of its ticket | env + 1) - after the action is in place */
+      mb_push_item(items, qmask, qshift, s, e); /* after the action is in place */
       MB.issued[e] = k + 1;
       progress = true;
     }
     if (all_done) break;
     if (progress) { t_last = wall_clock64(); continue; }
-    nap();
-    if (ld_pub(MB.status) != 0) break;
-    if (wall_clock64() - t_last > MB.timeout_ticks) { st_pub(MB.status + 1, g); st_pub(MB.status, 2); break; }
+    GQ_MB_POLICY_IDLE(true, g) /* every lane looks, and speaks, for itself */
   }
 }
 
@@ -229,14 +185,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
   const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
   const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
   const int N = MB.n_envs, K = MB.n_steps, D = P.decimation;
-  GQ_POLICY_REGISTER()
+  GQ_MB_POLICY_REGISTER() /* rank, mine, t_last (gq_mailbox.h) */
   const MlpNet net = mlp_net_load(P.net);
   const int in_obs = P.in_obs, in_dim = net.in_dim;
   const float* const shift = P.shift;
   const float* const scale = P.scale;
-  const int nmine = (N - q + nq - 1) / nq;           /* envs of this queue: e = q + nq * i */
+  const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int G = mine * GQ_WAVE;
-  int32_t* const tail = MB.q_ctr + (size_t)(3 * q + 1) * GQ_MB_QSTRIDE;
+  int32_t* const tail = mb_ctr(MB.q_ctr, q, MB_CTR_PUSH);
   int32_t* const items = MB.q_items + (size_t)q * MB.qcap;
   t_last = wall_clock64();
   for (;;) {
@@ -329,7 +285,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         if (!fresh) a[j] = ld_pub(P.held + (size_t)e * 12 + j);
       }
       /* the action row and the push ticket travel together */
-      const int s = add_pub(tail, 1);
+      const int s = mb_push_ticket(tail);
 #pragma unroll
       for (int j = 0; j < 12; j++) {
 #pragma clang fp contract(off)
@@ -339,8 +295,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         st_pub(MB.act + (size_t)e * 12 + j, u);
         if (MB.act_seq) MB.act_seq[((size_t)k * N + e) * 12 + j] = u;
       }
-      publish_fence();
-      st_pub(items + (s & qmask), (((s >> qshift) & 0x7f) << 24) | (e + 1)); /* the item (lap of its ticket | env + 1) - after the action is in place */
+      mb_push_item(items, qmask, qshift, s, e); /* after the action is in place */
       P.issued[e] = k + 1;
       progress = true;
     }
@@ -349,9 +304,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
     const bool any_live = ballot(!all_done) != 0, any_progress = ballot(progress) != 0;
     if (!any_live) break;
     if (any_progress) { t_last = wall_clock64(); continue; }
-    nap();
-    if (ld_pub(MB.status) != 0) break;
-    if (wall_clock64() - t_last > MB.timeout_ticks) { if (lane == 0) { st_pub(MB.status + 1, rank * GQ_WAVE); st_pub(MB.status, 2); } break; }
+    GQ_MB_POLICY_IDLE(lane == 0, rank * GQ_WAVE)
   }
 }
 

@@ -28,6 +28,7 @@
 #include <gq_device.h> /* angle brackets: the include path decides (csrc/ for the product, tests/simt_emu/ for the emulator) */
 #include "gq_model_dev.h"
 #include "gq_joint_cmd.h"
+#include "gq_mailbox.h"
 #include <cstddef>
 #include <type_traits>
 
@@ -145,30 +146,8 @@ struct StepCall {
   int32_t stop_stage;   /* profiling aid (env GQ_STOP_STAGE, tools/stage_insts.sh): return after stage marker i; 0 = run everything */
 };
 
-/* ---- closed-loop persistent rollout (gq_rollout_closed): env-steps are TASKS.  A policy - a kernel of its own on a second stream,
- * or anything else that follows the protocol - turns the observation an env published after step k - 1 into the action of step k,
- * writes it into the env's action mailbox and pushes the env onto a ready queue; the wavefronts of ONE persistent step launch pop
- * ready envs, play one step each (QuadrupedEnv.step() semantics per env, next-step auto-reset included), publish the observation
- * row and the env's step count, and pop again.  No env waits for another env's Newton tail or for a launch boundary, any number of
- * envs works with any number of resident wavefronts, and nothing can deadlock: every wait has a deadline that raises the abort word.
- * One queue per XCD: an env is always stepped by wavefronts of the same XCD, so its state rows stay coherent in that XCD's L2 and
- * only the mailbox words (actions, observation rows, sequence numbers, queue slots) travel with device-coherent accesses. */
-#define GQ_MB_QSTRIDE 32  /* int32 words between two queue counters: a 128-byte line each */
-struct MailboxDev {
-  float* act;             /* [N][12] action mailbox: written by the policy, read by the wavefront that plays the env's next step */
-  int32_t* steps_done;    /* [N] steps the env has completed in this rollout: published AFTER its observation row */
-  int32_t* issued;        /* [N] actions the built-in policy has issued per env (its private scratch) */
-  int32_t* q_items;       /* [nq][qcap] ring of env + 1 (0: empty slot); qcap is a power of two >= N, an env is queued at most once */
-  int32_t* q_ctr;         /* [nq][3][GQ_MB_QSTRIDE]: pop tickets, push tickets, policy wavefronts registered on the queue's XCD */
-  int32_t* status;        /* [8] word 0: abort code (0 running / fine, 1 a step wavefront waited past the deadline, 2 the policy did),
-                           * word 1: the ticket / policy lane that gave up, word 2: env-steps played */
-  int32_t* alive;         /* pinned host word: policy workgroups that are resident (the host waits for it before the step launch) */
-  float* act_seq;         /* [K][N][12] every action taken, or NULL */
-  float* obs_seq;         /* [K][N][obs_dim] every observation row, or NULL */
-  int32_t n_envs, n_steps, qcap, nq;
-  int32_t xcc_queue[16];  /* HW_REG_XCC_ID -> queue */
-  int64_t timeout_ticks;  /* deadline of every wait, 100 MHz ticks */
-};
+/* the closed-loop persistent rollout's mailbox protocol - GQ_MB_QSTRIDE, MailboxDev, the item word, the abort codes - is gq_mailbox.h (included
+ * above: every includer of this header sees it) */
 /* built-in policy: joint-space PD towards a posture, torque_j = kp_j (q_des_j - q_j) - kd_j qd_j (rounded after every operation,
  * like the elementwise torch expression); col_*: columns of the joint angles / velocities in the observation row */
 struct PolicyPdDev {

@@ -779,8 +779,11 @@ class QuadrupedEnv(AccessorsMixin):
         return self._window_done(D, obs_seq, act_seq)
 
     def closed_loop_status(self):
-        """Wait for the last ``rollout_closed_loop`` and return (abort code, detail, env-steps played); raises ``GqError`` if it
-        was aborted (a wait passed its deadline: missing / stuck policy, or the policy kernel could not become resident)."""
+        """Wait for the last ``rollout_closed_loop`` / ``rollout_policy`` and return (abort code, detail, env-steps played); the code
+        is 0 for a rollout that ran to its end.  Raises ``GqError`` if it was aborted, with the code in the message - the values of
+        ``cabi.GQ_CLOSED_ABORT``: ``step_deadline`` (a step wavefront waited past the deadline for an action; detail = its ticket),
+        ``policy_deadline`` (a policy wait passed the deadline: missing / stuck policy; detail = the policy lane), ``policy_absent``
+        (the policy kernel could not become resident), ``xcd_no_policy`` (an XCD got no policy wavefront; detail = its queue)."""
         st = (C.c_int32 * 4)()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._L.gq_rollout_closed_status(self._hbatch, st, stream), 'gq_rollout_closed')

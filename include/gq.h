@@ -429,9 +429,10 @@ int gq_rollout(GqBatch* b, const float* ctrl_seq, int n_steps, int shards, GqSta
  *                 env each (mj_step, observation / termination epilogue, next-step auto-reset exactly as gq_step), publish the
  *                 observation row and steps_done[e] = k + 1, and pop again until all N * n_steps env-steps are claimed.
  * Any number of envs works with any number of resident wavefronts (an env is not bound to a wavefront), and every wait has a
- * deadline: when it passes, status[0] becomes non-zero, every participant leaves, and gq_rollout_closed_status reports it - a
- * missing or stuck policy is an error, not a hang.  The final state and flags are those of n_steps gq_step calls with the same
- * actions, bit for bit.
+ * deadline: when it passes, status[0] becomes one of GQ_CLOSED_ABORT_* (a caller's policy raises GQ_CLOSED_ABORT_POLICY_DEADLINE the
+ * same way: status[1] = who, then status[0]), every participant leaves, and gq_rollout_closed_status reports it - a missing or stuck
+ * policy is an error, not a hang.  csrc/gq_mailbox.h is the definition of all of this, delivery assumption included.  The final
+ * state and flags are those of n_steps gq_step calls with the same actions, bit for bit.
  * pd != NULL: the library runs its built-in policy kernel (joint-space PD: torque_j = kp_j (q_des_j - q_j) - kd_j qd_j on the
  * qpos_js / qvel_js - or qpos / qvel - columns of the observation row, every operation rounded like the elementwise expression)
  * on a stream of its own, `policy_waves` wavefronts (0: default), launched BEFORE the step kernel and awaited until resident.
@@ -461,7 +462,7 @@ typedef struct GqMailboxView {
   int32_t* steps_done;      /* device [N] */
   int32_t* queue_items;     /* device [n_queues][queue_capacity] */
   int32_t* queue_counters;  /* device [n_queues][3][counter_stride]: pop tickets, push tickets, (built-in policy's registration count) */
-  int32_t* status;          /* device [8]: word 0 abort code */
+  int32_t* status;          /* device [8]: word 0 abort code (GQ_CLOSED_ABORT_*), word 1 who raised it, word 2 env-steps played */
   int32_t n_queues, queue_capacity, counter_stride;
   int32_t xcc_queue[16];    /* HW_REG_XCC_ID -> queue: queue q's envs are stepped by wavefronts of that XCD only */
 } GqMailboxView;
@@ -469,9 +470,14 @@ typedef struct GqMailboxView {
 #define GQ_CLOSED_INLINE 1  /* the stepping wavefront evaluates the built-in policy itself: no mailbox traffic, no policy kernel */
 int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream);
-/* waits for hip_stream, then out[0] = abort code (0 = the rollout ran to its end), out[1] = who gave up, out[2] = env-steps played;
- * returns GQ_EDEVICE with a message when the rollout was aborted */
+/* waits for hip_stream, then out[0] = abort code (0 = the rollout ran to its end, else GQ_CLOSED_ABORT_*), out[1] = who gave up,
+ * out[2] = env-steps played; returns GQ_EDEVICE with a message when the rollout was aborted */
 int gq_rollout_closed_status(GqBatch* b, int32_t out[4], void* hip_stream);
+/* the abort codes, status[0] of the mailbox (csrc/gq_mailbox.h is their definition), and what out[1] / status[1] holds with each */
+#define GQ_CLOSED_ABORT_STEP_DEADLINE 1   /* a step wavefront waited past the deadline for its ticket's item; the pop ticket */
+#define GQ_CLOSED_ABORT_POLICY_DEADLINE 2 /* a policy wait passed the deadline; the policy lane, or -1 - rank of a wavefront still registering */
+#define GQ_CLOSED_ABORT_POLICY_ABSENT 3   /* the built-in policy kernel did not become resident (raised by the host) */
+#define GQ_CLOSED_ABORT_XCD_NO_POLICY 4   /* an XCD got no policy wavefront; its queue */
 int gq_mailbox_get(GqBatch* b, GqMailboxView* out);
 /* A LEARNED policy in the mailbox seat of the closed-loop rollout: an MLP evaluated on the matrix cores by a resident policy kernel, the
  * form of

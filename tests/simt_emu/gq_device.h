@@ -75,6 +75,7 @@ static inline float ld_pub(const float* p) { return *p; }
 static inline void st_pub(int32_t* p, int v) { *p = v; }
 static inline void st_pub(float* p, float v) { *p = v; }
 static inline int add_pub(int32_t* p, int v) { const int o = *p; *p = o + v; return o; }
+static inline int add_sys(int32_t* p, int v) { return add_pub(p, v); }
 inline int g_emu_cas_ok = 0; /* successful compare-and-swaps (the pair exchange: reservations + claims) */
 static inline bool cas_pub(int32_t* p, int expect, int v) { if (*p != expect) return false; *p = v; g_emu_cas_ok++; return true; }
 static inline void publish_fence() {}
