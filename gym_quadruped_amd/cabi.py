@@ -146,6 +146,13 @@ class GqPolicyMlp(C.Structure):
                 ('noise_sigma', C.c_float * 12), ('action_clip', C.c_float), ('pad_', C.c_int32)]
 
 
+class GqPolicyGru(C.Structure):
+    """gq_rollout_policy_gru's / gq_policy_gru_eval's block next to a ``GqPolicyMlp`` (the loop, the cell's input row and the head): the cell's
+    width, the blob of cell and head and the hidden state; ``struct_size`` must hold ``sizeof(GqPolicyGru)``."""
+    _fields_ = [('struct_size', C.c_int32), ('hidden', C.c_int32), ('blob', C.c_void_p), ('blob_floats', C.c_int64), ('hidden_state', C.c_void_p),
+                ('hidden_seq', C.c_void_p)]
+
+
 class GqLearn(C.Structure):
     """gq_rollout_policy_learn's / gq_reward_eval's block: the reward weights in the order of the law's sum, and the rollout's output
     pointers; ``struct_size`` must hold ``sizeof(GqLearn)`` (the library refuses a stale layout)."""

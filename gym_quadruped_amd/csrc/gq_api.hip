@@ -22,6 +22,7 @@
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
+#include "gq_policy_gru.h"
 #include "gq_learn.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
@@ -45,6 +46,8 @@ extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyM
 extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
                                       const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, int feet, hipStream_t stream);
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
+extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream);
+extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
 static thread_local char g_err[512] = "";
@@ -93,6 +96,7 @@ struct Mailbox {
   Buf<int32_t, gq::PinnedMem> alive, status_host; /* the word the policy workgroups count themselves into; a copy of the status words (gq_rollout_closed_status) */
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
   gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
+  gq::Staged<gq::PolicyGruDev> gru;         /* the recurrent policy's (gq_rollout_policy_gru, gq_policy_gru_eval): the MLP block first, then the cell */
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
@@ -468,6 +472,7 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.dev.ensure(1, false));
   HIP_TRY(t.policy.create());
   HIP_TRY(t.mlp.create());
+  HIP_TRY(t.gru.create());
   HIP_TRY(t.held.ensure(12 * N, true));
   HIP_TRY(t.last.ensure(12 * N, true));
   HIP_TRY(t.learn.create());
@@ -644,6 +649,31 @@ static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char*
   return GQ_OK;
 }
 
+/* the recurrent policy: `mlp` describes the cell's input row and the HEAD (its input width is gru->hidden), `gru` the cell and the blob of
+ * both.  Fills G.cell, G.blob and G.mlp's network part (net = the head, blob = the head's layers). */
+static int gru_describe(const GqPolicyMlp* mlp, const GqPolicyGru* gru, gq::PolicyGruDev& G, const char* who) {
+  if (gru->hidden < 1 || gru->hidden > GQ_GRU_MAXH) { SET_ERR("%s: hidden = %d: 1 to %d are supported", who, gru->hidden, GQ_GRU_MAXH); return GQ_EINVAL; }
+  if (mlp->n_layers < 1 || mlp->n_layers > GQ_GRU_HEAD_MAXL) { SET_ERR("%s: the head has %d linear layers: 1 to %d are supported", who, mlp->n_layers, GQ_GRU_HEAD_MAXL); return GQ_EINVAL; }
+  const int in_dim = mlp->in_obs + (mlp->feed_last_action ? 12 : 0);
+  if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
+  if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the cell's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
+  gq::PolicyMlpDev& P = G.mlp;
+  for (int l = 0; l < mlp->n_layers; l++)
+    if (mlp->width[l] < 1 || mlp->width[l] > GQ_MLP_MAXW) { SET_ERR("%s: layer %d of the head has %d outputs: 1 to %d are supported", who, l, mlp->width[l], GQ_MLP_MAXW); return GQ_EINVAL; }
+  if (mlp->width[mlp->n_layers - 1] != 12) { SET_ERR("%s: the head has %d outputs: 12 (one per hinge) are needed", who, mlp->width[mlp->n_layers - 1]); return GQ_EINVAL; }
+  if (mlp->activation < GQ_ACT_RELU || mlp->activation > GQ_ACT_TANH) { SET_ERR("%s: activation %d: relu (1), elu (2) or tanh (3)", who, mlp->activation); return GQ_EINVAL; }
+  if (mlp->out_activation != GQ_ACT_NONE && mlp->out_activation != GQ_ACT_TANH) { SET_ERR("%s: out_activation %d: none (0) or tanh (3)", who, mlp->out_activation); return GQ_EINVAL; }
+  if (!gru->blob) { SET_ERR("%s: GqPolicyGru.blob is null", who); return GQ_EINVAL; }
+  G.cell.in_dim = in_dim; G.cell.hidden = gru->hidden;
+  P.net.n_layers = mlp->n_layers; P.net.in_dim = gru->hidden; P.net.act = mlp->activation; P.net.out_act = mlp->out_activation;
+  for (int l = 0; l < GQ_MLP_MAXL; l++) P.net.width[l] = l < mlp->n_layers ? mlp->width[l] : 0;
+  const long long want = (long long)gq::gru_blob_floats(G.cell, P.net);
+  if (gru->blob_floats != want) { SET_ERR("%s: GqPolicyGru.blob_floats is %lld, this cell and head have %lld", who, (long long)gru->blob_floats, want); return GQ_EINVAL; }
+  P.in_obs = mlp->in_obs; P.feed_last = mlp->feed_last_action ? 1 : 0; P.decimation = mlp->decimation; P.pad_ = 0; P.pad2_ = 0;
+  G.blob = gru->blob; P.blob = gru->blob + gq::gru_cell_floats(G.cell); P.shift = mlp->obs_shift; P.scale = mlp->obs_scale;
+  return GQ_OK;
+}
+
 /* ---- the reward law's block (gq_reward.h) from the C block: weights checked, columns resolved by observable in this batch's row ---- */
 static int obs_column(const GqBatch* b, int canonical) {
   for (int c = 0; c < b->host.obs_dim; c++)
@@ -732,20 +762,27 @@ static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw
   return ok ? GQ_OK : GQ_EINVAL;
 }
 
-static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+/* gru: null for the MLP (the three entry points as they were), else the recurrent policy's block (gq_rollout_policy_gru) */
+static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                           const GqFootReward* feet, void* hip_stream, const char* const who) {
   if (feet && !fresh(feet, "GqFootReward", who)) return GQ_EINVAL;
   if (!fresh(mlp, "GqPolicyMlp", who)) return GQ_EINVAL;
+  if (gru && !fresh(gru, "GqPolicyGru", who)) return GQ_EINVAL;
   if (learn && !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
-  gq::PolicyMlpDev P = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
-  if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
+  gq::PolicyGruDev G = b->mb.gru.shadow;
+  gq::PolicyMlpDev Pm = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
+  gq::PolicyMlpDev& P = gru ? G.mlp : Pm;
+  if (gru) {
+    if (const int rc = gru_describe(mlp, gru, G, who); rc != GQ_OK) return rc;
+    if (!gru->hidden_state) { SET_ERR("%s: GqPolicyGru.hidden_state (device [N][hidden], in / out) is null", who); return GQ_EINVAL; }
+  } else if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
-  if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, "MLP"); rc != GQ_OK) return rc;
+  if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, gru ? "GRU" : "MLP"); rc != GQ_OK) return rc;
   gq::LearnFeetDev LF = b->mb.learn.shadow;
   gq::LearnDev& L = LF.learn;
   bool reward_on = false;
@@ -766,7 +803,8 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   const int N = b->host.n_envs, od = b->host.obs_dim;
   Mailbox& mb = b->mb;
   gq::MailboxDev& h = mb.host;
-  policy_waves = gq::mb_policy_waves(policy_waves, 128, 1024, h.nq); /* a wavefront takes its ready envs through the network 16 at a time */
+  /* a wavefront takes its ready envs through the network 16 at a time; a recurrent one holds 48 KB of LDS: 512 of them are resident on any device the mailbox runs on */
+  policy_waves = gq::mb_policy_waves(policy_waves, 128, gru ? 512 : 1024, h.nq);
   for (int j = 0; j < 12; j++) {
     P.kp[j] = mlp->kp[j]; P.kd[j] = mlp->kd[j]; P.q_default[j] = mlp->q_default[j]; P.action_scale[j] = mlp->action_scale[j]; P.sigma[j] = mlp->noise_sigma[j];
   }
@@ -775,7 +813,13 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
   P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
   P.learn = learn ? mb.learn.dev.get() : nullptr;
-  HIP_TRY(mb.mlp.push(P, stream, true));
+  if (gru) {
+    G.hidden_state = gru->hidden_state; G.hidden_seq = gru->hidden_seq;
+    G.terminated = out.terminated; G.pending = b->p.pending;
+    HIP_TRY(mb.gru.push(G, stream, true));
+  } else {
+    HIP_TRY(mb.mlp.push(P, stream, true));
+  }
   HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
   if (learn) {
     /* the reward is evaluated when anything of it is asked for (a spec without a weighted term is a reward of zero) */
@@ -789,18 +833,26 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int p
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
+  if (gru) gq_launch_policy_gru(mb.dev.get(), mb.gru.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
+  else gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
 }
+int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, int policy_waves, int step_waves, double timeout_s, GqState st,
+                          GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                          const GqFootReward* feet, void* hip_stream) {
+  const char* const who = "gq_rollout_policy_gru";
+  if (!gru) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return rollout_policy(b, n_steps, mlp, gru, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+}
 int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
+  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
 }
 int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                             const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                             void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
+  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
                         learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
 }
 int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
@@ -808,7 +860,7 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
                                  const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_learn_feet";
   if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
 /* gq_reward_eval (feet null) and gq_reward_eval_feet */
@@ -858,6 +910,24 @@ int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, in
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(b->mb.mlp.push(P, stream, true));
   gq_launch_policy_mlp_eval(b->mb.mlp.dev.get(), rows, n_rows, impl, out, stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_policy_gru_eval(GqBatch* b, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const float* rows, const float* h_in, int n_rows, int impl, float* out, float* h_out,
+                       void* hip_stream) {
+  const char* const who = "gq_policy_gru_eval";
+  if (!fresh(mlp, "GqPolicyMlp", who) || !fresh(gru, "GqPolicyGru", who)) return GQ_EINVAL;
+  if (!b || !rows || !h_in || !out || !h_out || n_rows < 0 || (impl != 0 && impl != 1)) { SET_ERR("gq_policy_gru_eval: bad argument"); return GQ_EINVAL; }
+  DeviceGuard guard(b->model->device);
+  if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
+  gq::PolicyGruDev G = b->mb.gru.shadow;
+  if (const int rc = gru_describe(mlp, gru, G, who); rc != GQ_OK) return rc;
+  if (n_rows == 0) return GQ_OK;
+  G.hidden_state = const_cast<float*>(h_in); G.hidden_seq = h_out; /* the kernels read the first, write the second */
+  hipStream_t stream = (hipStream_t)hip_stream;
+  HIP_TRY(b->mb.gru.push(G, stream, true));
+  gq_launch_policy_gru_eval(b->mb.gru.dev.get(), rows, n_rows, impl, out, stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

@@ -14,6 +14,7 @@
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
 #include "gq_learn.h"
+#include "gq_policy_gru.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -176,18 +177,27 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * overlap in three alternated turns, profiles/learn_window_refactor.md) - the foot law's block and branches stay in the visit's way even when
  * nothing of it is on.  Against the kernels before the fold the visit needs fewer VGPRs in both modes (132 / 160 against 180 / 204); mode 2
  * has 280 SGPR spills (to VGPR lanes, no scratch) against 252: the step's reward now leaves learn_step as a value and is added to acc under
- * a second `if (earns)` in learn_visit, where it was added inside the branch that evaluated it. */
+ * a second `if (earns)` in learn_visit, where it was added inside the branch that evaluated it.
+ * RECURRENT (MODE & 4, gq_rollout_policy_gru; MODE 0 .. 2 compile to the kernels they were): the network is a GRU cell and a head
+ * (gq_policy_gru.h), Pp points at the first member of a PolicyGruDev.  The episode rule runs for every ready lane before the tile loop; the
+ * tile stage also loads each row's hidden state (device scope: the row is its env's lane's store of an earlier visit) - a row the rule
+ * zeroed in THIS visit is staged as zeros from the lane's own flag, not from memory - and h' is stored by the env's own lane between the
+ * cell and the head.  The flags come from the recurrent block: P.learn is not read in mode 4. */
 template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
-  constexpr bool LEARN = MODE != 0;
-  __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
+  constexpr bool GRU = (MODE & 4) != 0;
+  constexpr int LMODE = MODE & 3;
+  constexpr bool LEARN = LMODE != 0;
+  __shared__ __attribute__((aligned(16))) float xt[GRU ? 3 : 2][GQ_MLP_MAXW * GQ_MLP_ROWS];
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
   const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
   const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
   const int N = MB.n_envs, K = MB.n_steps, D = P.decimation;
   GQ_MB_POLICY_REGISTER() /* rank, mine, t_last (gq_mailbox.h) */
   const MlpNet net = mlp_net_load(P.net);
-  const int in_obs = P.in_obs, in_dim = net.in_dim;
+  [[maybe_unused]] GruNet cell{};
+  if constexpr (GRU) cell = gru_net_load(mptr(reinterpret_cast<const PolicyGruDev*>(Pp))->cell);
+  const int in_obs = P.in_obs, in_dim = GRU ? cell.in_dim : net.in_dim;
   const float* const shift = P.shift;
   const float* const scale = P.scale;
   const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
@@ -207,9 +217,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
       const bool ready = live && ld_pub(MB.steps_done + e) >= k; /* the observation after step k - 1 is out */
       const bool fresh = ready && k % D == 0 && (!LEARN || k < K); /* ... and the env is due for a new action */
       float a[12];
+      [[maybe_unused]] bool h_zeroed = false;
+      if constexpr (GRU) { /* the episode rule (gq_policy_gru.h), before any cell evaluation of this visit */
+        const GQ_MODEL PolicyGruDev& GP = *mptr(reinterpret_cast<const PolicyGruDev*>(Pp));
+        if (ready) h_zeroed = gru_episode_rule<LearnPub>(GP.terminated, GP.pending, GP.hidden_state, cell.hidden, e, k);
+      }
       if constexpr (LEARN) { /* the visit of the window law (gq_learn.h): step k - 1 is evaluated, the window flushed at k % D == 0 */
         const GQ_MODEL LearnFeetDev& LF = *mptr(P.learn);
-        if (LF.learn.has_reward && ready) learn_visit<MODE == 2, LearnPub>(LF, obs + (size_t)e * od, MB.act + (size_t)e * 12, P.held + (size_t)e * 12, e, k, D, N);
+        if (LF.learn.has_reward && ready) learn_visit<LMODE == 2, LearnPub>(LF, obs + (size_t)e * od, MB.act + (size_t)e * 12, P.held + (size_t)e * 12, e, k, D, N);
       }
       /* (the observation words are read AFTER the count has been seen: the ballot below waits for every lane's count) */
       for (uint64_t todo = ballot(fresh); todo != 0;) {
@@ -230,7 +245,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           float* const rec = mptr(P.learn)->learn.policy_obs;
           if (rec) rec_row = rec + ((size_t)(kr / D) * N + er) * in_dim;
         }
-        mlp_tile_stage(net, xt[0], [&](const int, const int c) {
+        const auto x_value = [&](const int, const int c) {
           if (src < 0 || c >= in_dim) return 0.0f;
           const auto word = [&](const float* const p) { /* a device-scope load, recorded with LEARN */
             const float o = ld_pub(p);
@@ -241,8 +256,33 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           };
           if (c < in_obs) return mlp_obs_in(word(row + c), shift, scale, c);
           return word(prev + (c - in_obs));
-        });
-        const float* const out = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
+        };
+        const float* out;
+        if constexpr (GRU) {
+          const GQ_MODEL PolicyGruDev& GP = *mptr(reinterpret_cast<const PolicyGruDev*>(Pp));
+          const int H = cell.hidden;
+          const bool zr = shfl_idx((int)h_zeroed, src < 0 ? 0 : src) != 0;
+          const int kr = shfl_idx(k, src < 0 ? 0 : src);
+          const float* const hrow = GP.hidden_state + (size_t)er * H;
+          float* const hrec = GP.hidden_seq ? GP.hidden_seq + ((size_t)(kr / D) * N + er) * H : nullptr; /* the state as the cell is fed it */
+          wave_barrier(); /* whoever still read the buffers has done so */
+          gru_tile_stage(mlp_kp(in_dim), &xt[0][0], x_value);
+          gru_tile_stage(mlp_np(H), &xt[1][0], [&](const int, const int c) {
+            if (src < 0 || c >= H) return 0.0f;
+            const float v = zr ? 0.0f : ld_pub(hrow + c);
+            if (hrec) hrec[c] = v;
+            return v;
+          });
+          const bool owns = fresh && ((tile >> lane) & 1);
+          const int hslot = popc64(tile & (((uint64_t)1 << lane) - 1));
+          out = gru_tile_forward(cell, net, GP.blob, P.blob, &xt[0][0], [&](const float* hn) { /* h': by the env's own lane, like acc / wstate */
+            if (owns)
+              for (int c = 0; c < H; c++) st_pub(GP.hidden_state + (size_t)e * H + c, hn[c * GQ_MLP_ROWS + hslot]);
+          });
+        } else {
+          mlp_tile_stage(net, xt[0], x_value);
+          out = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
+        }
         if (fresh && ((tile >> lane) & 1)) {
           const int slot = popc64(tile & (((uint64_t)1 << lane) - 1));
           const uint32_t gid = (uint32_t)(e + P.env_id_offset);
@@ -333,6 +373,49 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const Pol
     return c < in_obs ? mlp_obs_in(v, shift, scale, c) : v;
   });
   const float* const y = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
+  for (int w = lane; w < GQ_MLP_ROWS * 12; w += GQ_WAVE) {
+    const int r = w / 12, j = w % 12;
+    if (r0 + r < n) out[(size_t)(r0 + r) * 12 + j] = y[j * GQ_MLP_ROWS + r];
+  }
+}
+
+/* the recurrent policy alone over rows [n][in_dim] and states [n][H] (gq_policy_gru_eval): the two forms of gq_policy_gru.h side by side.
+ * G.hidden_state: h_in, G.hidden_seq: h_out (read / written plainly: nothing else runs on them) */
+__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_row_kernel(const PolicyGruDev* __restrict__ Gp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  const GQ_MODEL PolicyGruDev& GP = *mptr(Gp);
+  const MlpNet head = mlp_net_load(GP.mlp.net);
+  const GruNet cell = gru_net_load(GP.cell);
+  const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x), H = cell.hidden;
+  if (r >= n) return;
+  float x[GQ_MLP_MAXW], h[GQ_GRU_MAXH], hn[GQ_GRU_MAXH], y[GQ_MLP_ROWS];
+  for (int c = 0; c < cell.in_dim; c++) { const float v = rows[(size_t)r * cell.in_dim + c]; x[c] = c < GP.mlp.in_obs ? mlp_obs_in(v, GP.mlp.shift, GP.mlp.scale, c) : v; }
+  for (int c = 0; c < H; c++) h[c] = GP.hidden_state[(size_t)r * H + c];
+  gru_row_forward(cell, head, GP.blob, x, h, y, hn);
+  for (int j = 0; j < 12; j++) out[(size_t)r * 12 + j] = y[j];
+  for (int c = 0; c < H; c++) GP.hidden_seq[(size_t)r * H + c] = hn[c];
+}
+__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_tile_kernel(const PolicyGruDev* __restrict__ Gp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float xt[GQ_GRU_LDS_FLOATS];
+  const GQ_MODEL PolicyGruDev& GP = *mptr(Gp);
+  const MlpNet head = mlp_net_load(GP.mlp.net);
+  const GruNet cell = gru_net_load(GP.cell);
+  const int lane = (int)threadIdx.x, r0 = (int)blockIdx.x * GQ_MLP_ROWS, in_dim = cell.in_dim, in_obs = GP.mlp.in_obs, H = cell.hidden;
+  const float* const shift = GP.mlp.shift;
+  const float* const scale = GP.mlp.scale;
+  const float* const h_in = GP.hidden_state;
+  float* const h_out = GP.hidden_seq;
+  gru_tile_stage(mlp_kp(in_dim), xt, [&](const int r, const int c) {
+    if (r0 + r >= n || c >= in_dim) return 0.0f;
+    const float v = rows[(size_t)(r0 + r) * in_dim + c];
+    return c < in_obs ? mlp_obs_in(v, shift, scale, c) : v;
+  });
+  gru_tile_stage(mlp_np(H), xt + GQ_GRU_REGION, [&](const int r, const int c) { return (r0 + r >= n || c >= H) ? 0.0f : h_in[(size_t)(r0 + r) * H + c]; });
+  const float* const y = gru_tile_forward(cell, head, GP.blob, GP.mlp.blob, xt, [&](const float* hn) {
+    for (int w = lane; w < GQ_MLP_ROWS * H; w += GQ_WAVE) {
+      const int r = w / H, c = w % H;
+      if (r0 + r < n) h_out[(size_t)(r0 + r) * H + c] = hn[c * GQ_MLP_ROWS + r];
+    }
+  });
   for (int w = lane; w < GQ_MLP_ROWS * 12; w += GQ_WAVE) {
     const int r = w / 12, j = w % 12;
     if (r0 + r < n) out[(size_t)(r0 + r) * 12 + j] = y[j * GQ_MLP_ROWS + r];
@@ -609,6 +692,18 @@ extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyM
   if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<2>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
   else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<1>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
   else hipLaunchKernelGGL(gq::policy_mlp_kernel<0>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+}
+/* gq_rollout_policy_gru: the recurrent instantiations, mode as above; gru->mlp is the block the kernel's parameter points at */
+extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream) {
+  const gq::PolicyMlpDev* const seat = &gru->mlp; /* (address arithmetic on a device pointer: offset 0) */
+  if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<6>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+  else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<5>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+  else hipLaunchKernelGGL(gq::policy_mlp_kernel<4>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+}
+/* impl 0: gru_row_forward, a thread per row; 1: gru_tile_forward, a wavefront per 16 rows */
+extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
+  if (impl == 0) hipLaunchKernelGGL(gq::policy_gru_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, gru, rows, n_rows, out);
+  else hipLaunchKernelGGL(gq::policy_gru_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, gru, rows, n_rows, out);
 }
 /* feet 0: gq_reward_eval (air_in / air_out are not looked at), 1: gq_reward_eval_feet */
 extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,

@@ -2,7 +2,10 @@
 on the matrix cores, between the published observation rows and the action mailboxes of ``gq_rollout_closed``'s machinery.
 
 The law and the weight blob are defined in ``csrc/gq_policy_mlp.h``; this module packs a network into that blob (no GPU needed) and
-restates the network in float64 for tests."""
+restates the network in float64 for tests.
+
+``GruPolicy`` is the recurrent form - one GRU cell and an MLP head, the hidden state on the device (``QuadrupedEnv.policy_hidden``) - defined
+in ``csrc/gq_policy_gru.h``."""
 from __future__ import annotations
 
 import numpy as np
@@ -152,3 +155,154 @@ class MlpPolicy:
                         blob_floats=blob.numel(), obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
         m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))
         return m
+
+
+MAX_HIDDEN, MAX_HEAD_LAYERS = 128, 3
+
+
+def sig64(x):
+    return 0.5 * np.tanh(0.5 * x) + 0.5
+
+
+class GruPolicy:
+    """A recurrent policy: one GRU cell (``torch.nn.GRUCell``'s law: gates r, z, n, both bias vectors) on the input row, followed by a head -
+    an MLP of 1 to 3 linear layers from the hidden state to the 12 joint-target actions.  Limits: input row ``in_dim <= 256`` columns,
+    ``1 <= H <= 128`` hidden units, head widths ``<= 256``; fp32 weights.  The law is ``csrc/gq_policy_gru.h``::
+
+        gi = x @ w_ih + b_ih;  gh = h @ w_hh + b_hh                 (columns [0:H] r, [H:2H] z, [2H:3H] n)
+        r = sig(gi_r + gh_r);  z = sig(gi_z + gh_z);  n = tanh(gi_n + r * gh_n);  h' = n + z * (h - n);  a = head(h')
+
+    w_ih ``[in, 3H]``, w_hh ``[H, 3H]`` (``GRUCell.weight_ih`` / ``weight_hh`` are their transposes), b_ih, b_hh ``[3H]``; head_weights /
+    head_biases: one ``[in, out]`` / ``[out]`` array per head layer (the first has ``H`` inputs, the last 12 outputs); activation /
+    out_activation, obs_shift / obs_scale, feed_last_action: as for ``MlpPolicy`` (they act on the head's layers and on the cell's input row).
+
+    In ``rollout_policy`` the hidden state lives in ``env.policy_hidden`` ``[N, H]`` and follows THE EPISODE RULE: an env's row is zeroed at the
+    policy seat's visit that sees its termination (or, at the first step of a call, that it waits for its re-spawn), before any cell
+    evaluation - the state fed at policy step ``s + 1`` is zero exactly where ``dones[s]`` is set.  The fed-back last action is not reset
+    with the env (zeros at the first policy step of a call, kept across a re-spawn)."""
+
+    default_policy_waves = 128   # the sweep of profiles/gru_policy_throughput.txt: no count is best everywhere, 128 loses the least
+
+    def __init__(self, w_ih, w_hh, b_ih, b_hh, head_weights, head_biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None,
+                 feed_last_action=False):
+        f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+        self.w_ih, self.w_hh, self.b_ih, self.b_hh = f(w_ih), f(w_hh), f(b_ih).reshape(-1), f(b_hh).reshape(-1)
+        if self.w_hh.ndim != 2 or self.w_hh.shape[1] != 3 * self.w_hh.shape[0]:
+            raise ValueError(f'w_hh must be [H, 3H], got {self.w_hh.shape}')
+        H = self.hidden = int(self.w_hh.shape[0])
+        if not 1 <= H <= MAX_HIDDEN:
+            raise ValueError(f'{H} hidden units: 1 to {MAX_HIDDEN} are supported')
+        if self.w_ih.ndim != 2 or self.w_ih.shape[1] != 3 * H or self.b_ih.shape != (3 * H,) or self.b_hh.shape != (3 * H,):
+            raise ValueError(f'w_ih must be [in, {3 * H}] and b_ih, b_hh [{3 * H}], got {self.w_ih.shape}, {self.b_ih.shape}, {self.b_hh.shape}')
+        self.in_dim = int(self.w_ih.shape[0])
+        if not 1 <= self.in_dim <= MAX_WIDTH:
+            raise ValueError(f'the cell has {self.in_dim} inputs: 1 to {MAX_WIDTH} are supported')
+        self.head_weights = [f(w) for w in head_weights]
+        self.head_biases = [f(b).reshape(-1) for b in head_biases]
+        if not 1 <= len(self.head_weights) <= MAX_HEAD_LAYERS:
+            raise ValueError(f'the head has {len(self.head_weights)} linear layers: 1 to {MAX_HEAD_LAYERS} are supported')
+        if len(self.head_biases) != len(self.head_weights):
+            raise ValueError('one bias vector per weight matrix of the head')
+        k = H
+        for l, (w, b) in enumerate(zip(self.head_weights, self.head_biases)):
+            if w.ndim != 2 or b.shape != (w.shape[1],) or w.shape[0] != k:
+                raise ValueError(f'head layer {l}: weights {w.shape} (expected [in, out] with in = {k}) and bias {b.shape} do not fit')
+            if not 1 <= w.shape[1] <= MAX_WIDTH:
+                raise ValueError(f'head layer {l}: {w.shape[1]} outputs: 1 to {MAX_WIDTH} are supported')
+            k = w.shape[1]
+        if k != N_ACTIONS:
+            raise ValueError(f'the head has {k} outputs: {N_ACTIONS} (one per hinge) are needed')
+        if activation not in ('relu', 'elu', 'tanh'):
+            raise ValueError(f"activation must be 'relu', 'elu' or 'tanh', got {activation!r}")
+        if out_activation not in (None, 'none', 'tanh'):
+            raise ValueError(f"out_activation must be None or 'tanh', got {out_activation!r}")
+        self.activation, self.out_activation = activation, out_activation or 'none'
+        self.feed_last_action = bool(feed_last_action)
+        self.in_obs = self.in_dim - (N_ACTIONS if self.feed_last_action else 0)
+        if self.in_obs < 0:
+            raise ValueError(f'feed_last_action needs at least {N_ACTIONS} inputs, the cell has {self.in_dim}')
+        self.widths = [w.shape[1] for w in self.head_weights]
+        col = lambda v: None if v is None else np.array(np.broadcast_to(np.asarray(v, dtype=np.float32), (self.in_obs,)), dtype=np.float32)
+        self.obs_shift, self.obs_scale = col(obs_shift), col(obs_scale)
+        # the head as an MlpPolicy of its own: its packing, its float64 form
+        self.head = MlpPolicy(self.head_weights, self.head_biases, activation=activation, out_activation=out_activation)
+        self._device = {}
+
+    @classmethod
+    def from_torch(cls, cell, head, **kw):
+        """From a ``torch.nn.GRUCell`` or a one-layer unidirectional ``torch.nn.GRU`` (its ``weight_ih_l0`` ...) and a head
+        ``torch.nn.Sequential`` as ``MlpPolicy.from_torch`` takes it; anything else raises ``ValueError``."""
+        import torch.nn as nn
+        if isinstance(cell, nn.GRUCell):
+            names = ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')
+            has_bias = cell.bias
+        elif isinstance(cell, nn.GRU):
+            if cell.num_layers != 1 or cell.bidirectional or getattr(cell, 'proj_size', 0):
+                raise ValueError(f'a one-layer unidirectional GRU is supported, got num_layers = {cell.num_layers}, bidirectional = {cell.bidirectional}')
+            names = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0')
+            has_bias = cell.bias
+        else:
+            raise ValueError(f'from_torch takes a torch.nn.GRUCell or torch.nn.GRU, got {type(cell).__name__}')
+        H = cell.hidden_size
+        get = lambda n: getattr(cell, n).detach().cpu().numpy()
+        zeros = np.zeros(3 * H, dtype=np.float32)
+        h = MlpPolicy.from_torch(head)
+        return cls(get(names[0]).T, get(names[1]).T, get(names[2]) if has_bias else zeros, get(names[3]) if has_bias else zeros, h.weights, h.biases,
+                   activation=h.activation, out_activation=h.out_activation, **kw)
+
+    def _gates(self):
+        """the six gate layers in the blob's order: (W [K, H], b [H]) of ir, hr, iz, hz, in, hn"""
+        H = self.hidden
+        out = []
+        for g in range(3):
+            sl = slice(g * H, (g + 1) * H)
+            out += [(self.w_ih[:, sl], self.b_ih[sl]), (self.w_hh[:, sl], self.b_hh[sl])]
+        return out
+
+    def blob_floats(self):
+        return sum(_np(w.shape[1]) * (_kp(w.shape[0]) + 1) for w, _ in self._gates()) + self.head.blob_floats()
+
+    def pack(self):
+        """The padded blob (float32 numpy): the gate layers ``W_ir b_ir | W_hr b_hr | W_iz b_iz | W_hz b_hz | W_in b_in | W_hn b_hn`` in
+        ``MlpPolicy.pack``'s per-layer layout, then the head's layers; zeros in the padding."""
+        gates = self._gates()
+        cell = MlpPolicy.__new__(MlpPolicy)   # (its pack() reads the two lists alone)
+        cell.weights, cell.biases = [np.ascontiguousarray(w) for w, _ in gates], [np.ascontiguousarray(b) for _, b in gates]
+        return np.ascontiguousarray(np.concatenate([cell.pack(), self.head.pack()]))
+
+    def reference(self, x, h):
+        """float64 evaluation over rows ``x [n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns) and states ``h [n, H]``:
+        ``(a [n, 12], h' [n, H])``."""
+        x = np.array(x, dtype=np.float64).reshape(-1, self.in_dim)
+        h = np.array(h, dtype=np.float64).reshape(-1, self.hidden)
+        if self.obs_shift is not None:
+            x[:, :self.in_obs] -= self.obs_shift.astype(np.float64)
+        if self.obs_scale is not None:
+            x[:, :self.in_obs] *= self.obs_scale.astype(np.float64)
+        H = self.hidden
+        gi = x @ self.w_ih.astype(np.float64) + self.b_ih.astype(np.float64)
+        gh = h @ self.w_hh.astype(np.float64) + self.b_hh.astype(np.float64)
+        r = sig64(gi[:, :H] + gh[:, :H])
+        z = sig64(gi[:, H:2 * H] + gh[:, H:2 * H])
+        n = np.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        hn = n + z * (h - n)
+        return self.head.reference(hn), hn
+
+    # -- the two C blocks, with the blob on `device`: (GqPolicyMlp - the loop, the input row, the head -, GqPolicyGru)
+    def _struct(self, device):
+        import ctypes as C
+
+        import torch
+
+        from .cabi import GqPolicyGru, GqPolicyMlp
+        key = str(device)
+        if key not in self._device:
+            up = lambda v: None if v is None else torch.from_numpy(v).to(device)
+            self._device[key] = (up(self.pack()), up(self.obs_shift), up(self.obs_scale))
+        blob, shift, scale = self._device[key]
+        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=self.in_obs, feed_last_action=int(self.feed_last_action),
+                        activation=GQ_ACT[self.activation], out_activation=GQ_ACT[self.out_activation], decimation=1, blob=None, blob_floats=0,
+                        obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
+        m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))
+        g = GqPolicyGru(struct_size=C.sizeof(GqPolicyGru), hidden=self.hidden, blob=blob.data_ptr(), blob_floats=blob.numel(), hidden_state=None, hidden_seq=None)
+        return m, g

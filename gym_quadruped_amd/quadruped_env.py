@@ -189,6 +189,7 @@ class QuadrupedEnv(AccessorsMixin):
         self._obs_buf = torch.zeros(N, self._obs_dim, **f32)
         self._reward = torch.zeros(N, **f32)
         self._feet_air = torch.zeros(N, 4, **f32)   # the foot reward terms' state (feet_air_time)
+        self._policy_hidden = None                  # a GruPolicy's hidden state [N, H] (policy_hidden): allocated on first use
         self._terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._invalid = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -420,13 +421,23 @@ class QuadrupedEnv(AccessorsMixin):
 
     def _policy_struct(self, policy, rollout=True):
         """``policy``'s C block for this batch; rollout: after the check only this side can make - the network reads the user's own columns"""
-        from .policy import MlpPolicy
-        if not isinstance(policy, MlpPolicy):
-            raise ValueError(f'policy must be an MlpPolicy, got {type(policy).__name__}')
+        from .policy import GruPolicy, MlpPolicy
+        if not isinstance(policy, (MlpPolicy, GruPolicy)):
+            raise ValueError(f'policy must be an MlpPolicy or a GruPolicy, got {type(policy).__name__}')
         width = sum(int(v.shape[1]) for v in self._obs_views.values())
         if rollout and policy.in_obs > width:
             raise ValueError(f"the policy reads {policy.in_obs} observation columns, state_obs_names gives {width} (the accessors' extra columns are not fed to a policy)")
         return policy._struct(self.device)
+
+    def _hidden_for(self, policy):
+        """``policy_hidden`` for a ``GruPolicy``: zeros on first use, refused when it was sized for another ``H``"""
+        H = policy.hidden
+        if self._policy_hidden is None:
+            self._policy_hidden = torch.zeros(self.num_envs, H, dtype=torch.float32, device=self.device)
+        if self._policy_hidden.shape[1] != H:
+            raise ValueError(f'env.policy_hidden holds {self._policy_hidden.shape[1]} hidden units per env, the policy has {H}: assign env.policy_hidden '
+                             f'a [{self.num_envs}, {H}] tensor first')
+        return self._policy_hidden
 
     def rollout_policy(self, n_steps: int, policy, kp, kd, q_default=None, action_scale=0.25, action_clip=None, decimation: int = 4, noise_sigma=0.0,
                        record_obs: bool = False, record_actions: bool = False, policy_waves: int = 0, step_waves: int = 0, timeout_s: float = 5.0,
@@ -476,7 +487,16 @@ class QuadrupedEnv(AccessorsMixin):
         THE FOOT TERMS (``gq_rollout_policy_learn_feet``; a ``reward`` without ``feet``, or with every foot weight 0, is the call above):
         ``RewardSpec(..., feet=FootRewardSpec(...))`` continues every step's sum with air time, slip, impact and clearance
         (``csrc/gq_reward_feet.h``).  The air times are ``env.feet_air_time``: they persist across calls, advance at every step but an env's
-        re-spawn step, which zeroes them - also in the tail of a window after a fall, which earns nothing."""
+        re-spawn step, which zeroes them - also in the tail of a window after a fall, which earns nothing.
+
+        A RECURRENT POLICY (``policy``: a ``GruPolicy``, every mode above; ``gq_rollout_policy_gru``): a GRU cell on the same input row, a
+        head on its hidden state.  The hidden state is ``env.policy_hidden`` ``[N, H]``: it persists across calls and follows the episode
+        rule of ``csrc/gq_policy_gru.h`` - the policy seat zeroes an env's row at the visit that sees its termination (at the first step of
+        a call: that the env waits for its re-spawn), before any cell evaluation, so the state fed at policy step ``s + 1`` is zero exactly
+        where ``dones[s]`` is set, the mask ``h <- (1 - done) h`` of a recurrent learner.  With ``record_transitions`` the dict gains
+        'policy_hidden' ``[K // D, N, H]``: the state FED at each policy step, after the rule.  ``policy_waves=0``: the policy's default."""
+        from .policy import GruPolicy
+        recurrent = isinstance(policy, GruPolicy)
         K, D = int(n_steps), int(decimation)
         if K < 0:
             raise ValueError('n_steps must be >= 0')
@@ -485,6 +505,10 @@ class QuadrupedEnv(AccessorsMixin):
         if K % D:
             raise ValueError(f'n_steps = {K} must be a multiple of decimation = {D}: no held action crosses calls')
         m = self._policy_struct(policy)
+        if recurrent:
+            m, gr = m
+            gr.hidden_state = self._hidden_for(policy).data_ptr()
+            policy_waves = int(policy_waves) or policy.default_policy_waves
         row12 = lambda v: (C.c_float * 12)(*np.broadcast_to(np.asarray(v, dtype=np.float32), (12,)))
         m.kp, m.kd, m.action_scale, m.noise_sigma = row12(kp), row12(kd), row12(action_scale), row12(noise_sigma)
         m.q_default = row12(self._key_qpos[7:19].float().cpu().numpy() if q_default is None else np.asarray(q_default, dtype=np.float32).reshape(12))
@@ -513,10 +537,17 @@ class QuadrupedEnv(AccessorsMixin):
                 extra['policy_means'] = torch.zeros(K // D, self.num_envs, 12, **f32)
             g.rewards, g.dones = ptr(extra.get('rewards')), ptr(extra.get('dones'))
             g.policy_obs, g.policy_means = ptr(extra.get('policy_obs')), ptr(extra.get('policy_means'))
+        if recurrent and record_transitions:
+            extra['policy_hidden'] = torch.zeros(K // D, self.num_envs, policy.hidden, **f32)
+            gr.hidden_seq = extra['policy_hidden'].data_ptr()
         self._hm_fresh = False
         args = (self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
                 self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq))
-        if learning and reward is not None and reward.feet_on:
+        if recurrent:   # one entry point, the modes selected by the blocks given
+            gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
+            _lib.check(self._L.gq_rollout_policy_gru(*args[:3], C.byref(gr), *args[3:], C.byref(g) if learning else None, None if gf is None else C.byref(gf), stream),
+                       'gq_rollout_policy_gru')
+        elif learning and reward is not None and reward.feet_on:
             gf = reward.feet._struct(self._feet_air.data_ptr())
             _lib.check(self._L.gq_rollout_policy_learn_feet(*args, C.byref(g), C.byref(gf), stream), 'gq_rollout_policy_learn_feet')
         elif learning:
@@ -576,11 +607,15 @@ class QuadrupedEnv(AccessorsMixin):
         _lib.check(self._L.gq_reward_eval(self._hbatch, C.byref(g), rows.data_ptr(), ptr(u), ptr(a), ptr(ap), ptr(term), n, out.data_ptr(), stream), 'gq_reward_eval')
         return out if air is None else (out, air.clone())
 
-    def policy_eval(self, policy, rows, impl: str = 'tile'):
+    def policy_eval(self, policy, rows, impl: str = 'tile', hidden=None):
         """The network of ``policy`` alone over ``rows`` (``[n, policy.in_dim]`` float32 on the env's device; shift / scale applied to
         the first ``in_obs`` columns; no noise, no clip, no control law) -> ``[n, 12]``.  impl 'tile': the matrix-core form the rollout
         runs, a wavefront per 16 rows; 'scalar': the plain ``fmaf`` loop that defines the law, a thread per row.  Both give the same
-        bits (``gq_policy_mlp_eval``)."""
+        bits (``gq_policy_mlp_eval``).
+
+        A ``GruPolicy`` needs ``hidden`` (``[n, H]`` float32, the states the rows are evaluated from) and returns ``(actions, hidden_next)``
+        (``gq_policy_gru_eval``); ``env.policy_hidden`` is neither read nor written."""
+        from .policy import GruPolicy
         if impl not in ('tile', 'scalar'):
             raise ValueError("impl must be 'tile' or 'scalar'")
         m = self._policy_struct(policy, rollout=False)
@@ -589,6 +624,18 @@ class QuadrupedEnv(AccessorsMixin):
         rows = rows.contiguous()
         out = torch.empty(rows.shape[0], 12, dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if isinstance(policy, GruPolicy):
+            n, H = int(rows.shape[0]), policy.hidden
+            if not torch.is_tensor(hidden) or hidden.dtype != torch.float32 or hidden.device != self.device or tuple(hidden.shape) != (n, H):
+                raise ValueError(f'hidden must be a float32 tensor of shape ({n}, {H}) on {self.device}')
+            hidden = hidden.contiguous()
+            h_next = torch.empty(n, H, dtype=torch.float32, device=self.device)
+            m, gr = m
+            _lib.check(self._L.gq_policy_gru_eval(self._hbatch, C.byref(m), C.byref(gr), rows.data_ptr(), hidden.data_ptr(), n, int(impl == 'tile'), out.data_ptr(),
+                                                  h_next.data_ptr(), stream), 'gq_policy_gru_eval')
+            return out, h_next
+        if hidden is not None:
+            raise ValueError('hidden is the state of a GruPolicy: an MlpPolicy has none')
         _lib.check(self._L.gq_policy_mlp_eval(self._hbatch, C.byref(m), rows.data_ptr(), int(rows.shape[0]), int(impl == 'tile'), out.data_ptr(), stream),
                    'gq_policy_mlp_eval')
         return out
@@ -838,6 +885,8 @@ class QuadrupedEnv(AccessorsMixin):
         self._launches += 1
         self._note_step()
         self._feet_air.masked_fill_(mask.bool().unsqueeze(1), 0.0)   # a new episode starts with no air time behind it
+        if self._policy_hidden is not None:
+            self._policy_hidden.masked_fill_(mask.bool().unsqueeze(1), 0.0)   # ... and with no memory
         if mask is self._mask_all:  # the reference zeroes mjData.ctrl in reset (:334): torque_ctrl_setpoint reads zero afterwards
             self._ctrl.zero_()
             self._last_action = self._ctrl
@@ -950,6 +999,27 @@ class QuadrupedEnv(AccessorsMixin):
         self._feet_air.copy_(torch.as_tensor(value, dtype=torch.float32, device=self.device).reshape(self.num_envs, 4))
 
     @property
+    def policy_hidden(self):
+        """``[N, H]`` float32: the hidden state of the ``GruPolicy`` that ``rollout_policy`` runs, or None before the first recurrent call
+        (which allocates it as zeros for that policy's ``H``).  The rollout reads and writes it; the policy seat zeroes an env's row when it
+        sees the env's termination (the episode rule of ``csrc/gq_policy_gru.h``), ``reset`` zeroes the rows of the envs it resets.
+        Assigning a ``[N, H']`` tensor replaces it (a policy with another ``H`` is refused until then); ``state_dict`` carries it."""
+        return self._policy_hidden
+
+    @policy_hidden.setter
+    def policy_hidden(self, value):
+        if value is None:
+            self._policy_hidden = None
+            return
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if v.dim() != 2 or v.shape[0] != self.num_envs or not 1 <= v.shape[1] <= 128:
+            raise ValueError(f'policy_hidden must be [{self.num_envs}, H] with 1 <= H <= 128, got {tuple(v.shape)}')
+        if self._policy_hidden is not None and self._policy_hidden.shape == v.shape:
+            self._policy_hidden.copy_(v)
+        else:
+            self._policy_hidden = v.clone().contiguous()
+
+    @property
     def ground_friction_coeff_range(self):
         """``(low, high)`` of the ground friction the resets draw from.  Assigning a scalar or a pair applies from the next reset (the
         auto-resets inside ``step`` included); a range whose lower end is under the solver's floor is refused (``check_ground_friction``)."""
@@ -973,6 +1043,8 @@ class QuadrupedEnv(AccessorsMixin):
                 '_h9', '_ext_dist', '_step_num_prev']
         keys += ['_lift_failed', '_feet_air']
         d = {k: getattr(self, k).clone() for k in keys}
+        if self._policy_hidden is not None:
+            d['_policy_hidden'] = self._policy_hidden.clone()
         d['rng'] = self._gen.get_state()
         # sensor state the kernel reads and writes every step: the IMU bias random walks
         d['sensor_bias'] = [sn.bias_state.clone() if hasattr(sn, 'bias_state') else None for sn in self.sensors]
@@ -993,6 +1065,8 @@ class QuadrupedEnv(AccessorsMixin):
                 continue
             if k == 'rng':
                 self._gen.set_state(v)
+            elif k == '_policy_hidden':
+                self.policy_hidden = v
             elif k == 'sensor_bias':
                 for sn, b in zip(self.sensors, v):
                     if b is not None:

@@ -603,6 +603,40 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
  * with air_time off; feet->air_time is not read).  The same routine, the same bits, as inside the rollout. */
 int gq_reward_eval_feet(GqBatch* b, const GqLearn* learn, const GqFootReward* feet, const float* rows, const float* torques, const float* act,
                         const float* act_prev, const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, void* hip_stream);
+/* A RECURRENT policy in the same seat (additive: the three entry points above are what they were): one GRU cell followed by an MLP head,
+ *   x = [(obs[:, :in_obs] - obs_shift) * obs_scale, a_prev]      in_dim = in_obs + 12 feed_last_action <= 256
+ *   gi_g = layer(x; W_ig, b_ig)   gh_g = layer(h; W_hg, b_hg)     g in (r, z, n): torch.nn.GRUCell's gates and bias vectors; a layer is the fmaf chain above
+ *   r = sig(gi_r + gh_r)   z = sig(gi_z + gh_z)   n = tanh(fmaf(r, gh_n, gi_n))   h' = fmaf(z, h - n, n)   a = head(h')
+ * with sig(v) = fmaf(0.5, tanh(0.5 v), 0.5) and the MLP's tanh (csrc/gq_policy_gru.h is the definition: fp32, contraction off, that order).
+ * `mlp` describes the loop (decimation, gains, noise, clip, policy_actions), the cell's input row (in_obs, feed_last_action, shift / scale) and
+ * the HEAD: n_layers <= 3 linear layers from `hidden` inputs to width[n_layers - 1] = 12, widths <= 256, activation / out_activation as
+ * above; mlp->blob and mlp->blob_floats are not read.  1 <= hidden <= 128.
+ * blob (device floats): six layers in the per-layer layout above, W_ir b_ir | W_hr b_hr | W_iz b_iz | W_hz b_hz | W_in b_in | W_hn b_hn
+ * (W_i*: in_dim inputs, W_h*: hidden inputs, hidden outputs each), then the head's layers; blob_floats must be their sum.
+ * hidden_state: device [N][hidden] f32, in / out - the caller owns it, it persists across calls.  THE EPISODE RULE: at the policy seat's
+ * visit of env e for step k, before any cell evaluation, the env's row is zeroed if k == 0 and the env waits for its re-spawn, or if k >= 1
+ * and `terminated` after step k - 1 is set (the learning modes' closing visit k = n_steps included; in the plain mode a fall in the last
+ * step is caught by the next call's k == 0).  Hence the state fed at policy step s + 1 is zero exactly when window s contained a
+ * termination - where dones[s] is set: the mask h <- (1 - done) h of a recurrent learner.  a_prev is NOT reset with the env (as above).
+ * hidden_seq: device [n_steps / decimation][N][hidden] or NULL: the state FED at each policy step, after the rule.
+ * learn / feet: NULL, or the blocks of gq_rollout_policy_learn / _learn_feet - the same three modes, selected the same way.
+ * Refused with a message, the batch stays usable: a stale struct_size of either struct, hidden outside 1 .. 128, a head with more than 3
+ * layers or whose output is not 12, a null hidden_state, a null blob or a wrong blob_floats, and everything gq_rollout_policy refuses. */
+typedef struct GqPolicyGru {
+  int32_t struct_size;        /* sizeof(GqPolicyGru): a stale binding is refused */
+  int32_t hidden;             /* 1 .. 128 */
+  const float *blob;          /* device, see above */
+  int64_t blob_floats;
+  float *hidden_state;        /* device [N][hidden], in / out; required in the rollout (gq_policy_gru_eval does not read it) */
+  float *hidden_seq;          /* device [n_steps / decimation][N][hidden] or NULL */
+} GqPolicyGru;
+int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, int policy_waves, int step_waves, double timeout_s, GqState st,
+                          GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
+                          const GqFootReward* feet, void* hip_stream);
+/* cell and head alone over rows: device [n_rows][in_dim] and h_in: device [n_rows][hidden] -> out: device [n_rows][12], h_out: device
+ * [n_rows][hidden] (not h_in).  impl 0: the plain loops, a thread per row; 1: the matrix-core form, a wavefront per 16 rows; the same bits. */
+int gq_policy_gru_eval(GqBatch* b, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const float* rows, const float* h_in, int n_rows, int impl, float* out, float* h_out,
+                       void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

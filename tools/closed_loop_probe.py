@@ -1,6 +1,7 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
-usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R] [--learn]]
+usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R] [--learn]
+                             | --gru H [--mlp H1,H2] [--decimation D] [--policy-waves W1,..] [--runs R] [--side loop|rollout]]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
 against the loop they replace - D x (torch PD expression, env.step) - from the same state with the same per-env commands; K windows
@@ -15,6 +16,11 @@ rollout (QuadrupedEnv.rollout_policy, a new action every D steps: --decimation, 
 commit - a = torch_module(obs); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
 network; one timing of the loop, then one of the rollout per entry of --policy-waves (default 64,128,256,512), R times over (--runs,
 default 3).  Prints every run of both sides.
+
+--gru H: a recurrent policy - torch.nn.GRUCell(33, H) and a head with the hidden widths of --mlp (default 128,64; elu) - in the closed-loop
+rollout (QuadrupedEnv.rollout_policy with a GruPolicy, the hidden state in env.policy_hidden) against the loop it replaces on the same commit -
+h = cell(obs, h); a = head(h); h = h * (1 - terminated); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
+weights; timed as --mlp is.  --side loop / rollout: that side alone, one timing per entry of --policy-waves (a process per timing).
 
 --learn (with --mlp): the learning half instead.  The observation row gets the reward's observables behind the network's 33 columns, and
 three forms are timed in turn, R times over, from the same state with the same network and exploration noise: plain rollout_policy; the
@@ -48,6 +54,8 @@ MLP = _opt('--mlp', None, lambda t: [int(h) for h in t.split(',')])
 MLP_D = _opt('--decimation', 4, int)
 MLP_WAVES = _opt('--policy-waves', [64, 128, 256, 512], lambda t: [int(w) for w in t.split(',')])
 MLP_RUNS = _opt('--runs', 3, int)
+GRU = _opt('--gru', 0, int)
+SIDE = _opt('--side', None, str)
 LEARN = '--learn' in sys.argv
 if LEARN:
     sys.argv.remove('--learn')
@@ -68,6 +76,50 @@ def timed(fn, steps):
     torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return n * steps / dt / 1e6, dt / steps * 1e6
+
+if GRU:
+    from gym_quadruped_amd.policy import GruPolicy
+    D, scale, head_w = MLP_D, 0.25, MLP or [128, 64]
+    names = ('qpos_js', 'qvel_js', 'base_lin_vel:base', 'base_ang_vel:base', 'gravity_vector:base')   # 33 columns
+    env = QuadrupedEnv(robot, scene=scene, state_obs_names=names, num_envs=n, auto_reset='next_step', seed=1)
+    env.reset(random=True)
+    torch.manual_seed(0)
+    cell = torch.nn.GRUCell(33, GRU).to('cuda')
+    dims = [GRU] + head_w + [12]
+    mods = []
+    for a, b in zip(dims[:-1], dims[1:]):
+        mods += [torch.nn.Linear(a, b), torch.nn.ELU()]
+    head = torch.nn.Sequential(*mods[:-1]).to('cuda')
+    policy = GruPolicy.from_torch(cell, head)
+    q0 = env._key_qpos[7:19].float()
+    W = max(1, K // D)
+    env.rollout_policy(300 // D * D, policy, KP, KD, action_scale=scale, decimation=D)   # settle into the policy's regime
+    sd = env.state_dict(); launches = env._launches
+    row0 = env._obs_buf.clone()   # the policy's first action reads the observation row, which is no part of the checkpoint
+    def restore():
+        env.load_state_dict(sd); env._launches = launches; env._obs_buf.copy_(row0); torch.cuda.synchronize()
+    def feature(pw):
+        env.rollout_policy(W * D, policy, KP, KD, action_scale=scale, decimation=D, policy_waves=pw)
+    def loop():
+        with torch.no_grad():
+            h = env.policy_hidden.clone()
+            for w in range(W):
+                h = cell(env._obs_buf, h)
+                a = head(h)
+                env.step_pd(q0 + scale * a, KP, KD, decimation=D)
+                h = h * (1.0 - env._terminated.float()).unsqueeze(1)
+    restore(); feature(0); restore(); loop()   # warm both paths
+    tag = f'{robot} {scene} n={n} gru={GRU} head={head_w} D={D}'
+    for r in range(MLP_RUNS):
+        if SIDE in (None, 'loop'):
+            restore(); m, us = timed(loop, W * D)
+            print(f'{tag} run {r}: loop (torch GRUCell + head + step_pd)   {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+        if SIDE in (None, 'rollout'):
+            for pw in MLP_WAVES:
+                restore(); m, us = timed(lambda: feature(pw), W * D)
+                print(f'{tag} run {r}: rollout_policy, policy waves {pw:4d}       {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
+    print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
+    sys.exit(0)
 
 if MLP:
     from gym_quadruped_amd.policy import MlpPolicy
@@ -143,9 +195,10 @@ if MLP:
     restore(); feature(0); restore(); loop()   # warm both paths
     tag = f'{robot} {scene} n={n} mlp={MLP} D={D}'
     for r in range(MLP_RUNS):
-        restore(); m, us = timed(loop, W * D)
-        print(f'{tag} run {r}: loop (torch module + step_pd)          {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
-        for pw in MLP_WAVES:
+        if SIDE in (None, 'loop'):
+            restore(); m, us = timed(loop, W * D)
+            print(f'{tag} run {r}: loop (torch module + step_pd)          {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+        for pw in MLP_WAVES if SIDE in (None, 'rollout') else ():
             restore(); m, us = timed(lambda: feature(pw), W * D)
             print(f'{tag} run {r}: rollout_policy, policy waves {pw:4d}       {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
     print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
