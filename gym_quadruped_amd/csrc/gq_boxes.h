@@ -715,6 +715,21 @@ __device__ __forceinline__ SelfPrefetch self_prefetch(const GQ_MODEL GqDevModel&
   return P;
 }
 
+/* world end points of every item's proxy capsule: lane = collision item, into the table cw in the J block (12 words per item: end points p0, p1,
+ * radius, and the bounding sphere the first pass tests).  No barrier.  (A macro, expanded in the caller's scope with its `lane` and `cw`: as a
+ * function it changed the register allocation of kernels that never run the early block - the elliptic primitive-geom variant 16 -> 28 B/lane of scratch.) */
+#define GQ_SELF_END_POINTS(W, pre, nlg, lane, cw) \
+  { /* lane = item; lanes past the last item repeat item 0 (self_prefetch fetched its record for them): no exec-mask block */ \
+    const int it = lane < 4 + nlg ? lane : 0; \
+    const int b = pre.body; \
+    const V3 o = ld3(W.xpos[b]); \
+    const V3 e0 = o + matvec(W.xmat[b], v3(pre.caps[0], pre.caps[1], pre.caps[2])), e1 = o + matvec(W.xmat[b], v3(pre.caps[3], pre.caps[4], pre.caps[5])); \
+    st3(cw[it], e0); st3(cw[it] + 3, e1); \
+    cw[it][6] = pre.caps[6]; \
+    st3(cw[it] + 8, o + matvec(W.xmat[b], v3(pre.bsph[0], pre.bsph[1], pre.bsph[2]))); /* broad-phase sphere: the primitive itself where the item is one */ \
+    cw[it][11] = pre.bsph[3]; \
+  }
+
 /* a collision item as a shape of the convex routine (wave-uniform): feet and sphere / capsule geoms are their cores (the world end points of
  * the self-collision table + radius), everything else is its vertex cloud in the geom's frame */
 __device__ inline void self_item_shape(const WaveMem& W, const GQ_MODEL GqDevModel& m, const int it, const float* k, LdsF dst) {
@@ -768,6 +783,106 @@ __device__ inline void sepc_store(const WaveMem& W, float* row, V3 d) {
   row[0] = b.x; row[1] = b.y; row[2] = b.z;
 }
 
+/* ... and of a pair that yielded a contact: a row that is no unit vector.  It is the pair's PREDICTION WORD - the next step publishes the pair
+ * right after its kinematics (early_publish, gq_exchange.h "published early"); the mid phase reads it as "no direction".  A hint only: a stale
+ * or a missed one changes when the pair is computed and by whom, never what comes out. */
+#define GQ_SEPC_TOUCH 2.0f
+__device__ __forceinline__ void sepc_touch(float* row) { row[0] = GQ_SEPC_TOUCH; row[1] = 0.0f; row[2] = 0.0f; }
+
+/* Hand-over of the early publication to pass B, in words of W.force that are dead from S0 to the solver ([0] the clock, [1] GQ_LIFT_DUE) and
+ * that the floor pass does not touch: which of the first 128 pairs are out in a slot since the early block, and their slots in pair order. */
+#define GQ_XQ_EARLY_MAX 32
+#define GQ_XE_MASK(W) (reinterpret_cast<uint32_t*>(&(W).force[2]))  /* [4] bit p: pair p is out */
+#define GQ_XE_SLOT(W) (reinterpret_cast<int32_t*>(&(W).force[8]))   /* [GQ_XQ_EARLY_MAX] */
+static_assert((8 + GQ_XQ_EARLY_MAX) * sizeof(float) <= sizeof(WaveMem::force), "hand-over words of the early publication: force[2 .. 8 + GQ_XQ_EARLY_MAX)");
+
+/* first word of the env's axis-cache rows lane and 64 + lane (lane = row, not pair: no model word stands in front of the load), fetched a stage
+ * ahead of early_publish: the one thing an env without a prediction word pays for, under the velocity stage */
+struct EarlyPrefetch { float s[2]; };
+__device__ __forceinline__ EarlyPrefetch early_prefetch(const GQ_MODEL GqDevBatch& Bt, const int env) {
+  const int lane = lane_id();
+  EarlyPrefetch E;
+  const int stride = Bt.sepc_stride;
+  const float* sepc = Bt.sepc ? Bt.sepc + (size_t)env * stride : nullptr;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const int w = 3 * (h * GQ_WAVE + lane);
+    E.s[h] = (sepc && w < stride) ? sepc[w] : 0.0f;
+  }
+  return E;
+}
+
+/* the k lowest set bits of x (wave-uniform) */
+__device__ __forceinline__ uint64_t low_bits(uint64_t x, int k) {
+  uint64_t r = 0;
+  for (; k > 0 && x; k--) { r |= x & (~x + 1); x &= x - 1; }
+  return r;
+}
+
+/* Between the last smooth stage and the floor pass (flat hull scenes): the convex pairs that touched a step ago go into the exchange now -
+ * xpos / xmat are final, that is all a pair's shapes need - instead of behind the floor pass, the cull and the mid phase (gq_exchange.h).
+ * Leaves GQ_XE_MASK / GQ_XE_SLOT for append_self_contacts, which takes the pairs up as published; the end-point table it builds in the J
+ * block is scratch (the floor pass writes over it).  An env without a prediction word pays the ballots and four LDS words.
+ * `cut`: a stage cut is active (MODE 2, gq_debug_stop_stage) - the step may end between here and pass B, which alone gives slots back:
+ * nothing is published, so that every slot's life still lies between two stage markers. */
+__device__ inline void early_publish(WaveMem& W, const GQ_MODEL GqDevModel& m, const SelfPrefetch& pre, const EarlyPrefetch& E, const StepConsts& K, const int nlg,
+                                     const GQ_MODEL GqDevBatch& Bt, float* xdbg, const bool cut) {
+  const int lane = lane_id();
+  const uint64_t rows[2] = {ballot(E.s[0] == GQ_SEPC_TOUCH), ballot(E.s[1] == GQ_SEPC_TOUCH)}; /* bit = row of the axis cache */
+  if (lane < 4) GQ_XE_MASK(W)[lane] = 0u;
+  if (xdbg && lane == 0) xdbg[10] = 0.0f;
+  if ((rows[0] | rows[1]) == 0) return;
+#ifdef GQ_XQ_OFF
+  return;
+#else
+  Xq X; X.q = Bt.xq; X.slots = Bt.xq_slots;
+  /* (a stage cut; no table; a profiling cut that leaves the stage early; the reset's lift loop is due and will move xpos) */
+  if (cut || X.q == nullptr || K.self_cut != 0 || uniform(GQ_LIFT_DUE(W)) != 0) return;
+  const int xq_pre = ld_pub(X.q + xq_window(X, wave_index()) + lane);
+  int cidx[2]; /* lane = pair from here on: whose rows are those?  (rows past the first 128 are not predicted) */
+#pragma unroll
+  for (int h = 0; h < 2; h++) cidx[h] = h * GQ_WAVE + lane < K.nsp ? m.sp[h * GQ_WAVE + lane].cidx : -1;
+  float(*cw)[12] = reinterpret_cast<float(*)[12]>(&W.u.B[0][0]);
+  GQ_SELF_END_POINTS(W, pre, nlg, lane, cw)
+  wave_barrier();
+  if (!xq_is_hot(bcast(xq_pre, 63), wall_clock64())) return; /* owners publish only while envs with time on their hands are around */
+  uint64_t em[2]; /* bit = pair */
+#pragma unroll
+  for (int h = 0; h < 2; h++) em[h] = ballot(cidx[h] >= 0 && cidx[h] < 2 * GQ_WAVE && (((cidx[h] < GQ_WAVE ? rows[0] : rows[1]) >> (cidx[h] & 63)) & 1ull) != 0);
+  em[0] = low_bits(em[0], GQ_XQ_EARLY_MAX);
+  em[1] = low_bits(em[1], GQ_XQ_EARLY_MAX - popc64(em[0]));
+  int myslot[2] = {-1, -1};
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+    if ((em[h] >> lane) & 1ull) myslot[h] = xq_reserve(X, wave_index(), opaque_lane(lane) + h * GQ_WAVE);
+  uint64_t got[2];
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    got[h] = ballot(myslot[h] >= 0);
+    for (uint64_t r = got[h]; r;) {
+      const int jj = ffs64(r); r &= r - 1;
+      const int i1 = bcast(pre.it1[h], jj), i2 = bcast(pre.it2[h], jj), sj = bcast(myslot[h], jj);
+      wave_barrier();
+      self_item_shape(W, m, i1, cw[i1], GQ_CVX_SHP(W));
+      self_item_shape(W, m, i2, cw[i2], GQ_CVX_SHP(W) + GQ_CVX_SHAPE_WORDS);
+      wave_barrier();
+      xq_put(X, sj, GQ_CVX_SHP(W), m.sp[h * GQ_WAVE + jj].mix.margin);
+    }
+  }
+  publish_fence();
+  const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+    if (myslot[h] >= 0) {
+      xq_ready(X, myslot[h]); xq_mark_active(X, myslot[h]);
+      GQ_XE_SLOT(W)[(h ? popc64(got[0]) : 0) + popc64(got[h] & lt)] = myslot[h];
+    }
+  if (lane < 4) GQ_XE_MASK(W)[lane] = (uint32_t)(((lane & 2) ? got[1] : got[0]) >> (32 * (lane & 1)));
+  if (xdbg && lane == 0) { xdbg[10] = (float)(popc64(got[0]) + popc64(got[1])); xdbg[11] = (float)(wall_clock64() & 0xFFFFF); }
+  wave_barrier();
+#endif
+}
+
 /* third mid-phase test of a convex self pair, ONE lane: the two shapes along the line of their origins (the direction GJK tries first) - a
  * hull by the upper bound of its support function (cvx_hgrid), a sphere / capsule core exactly - or along `dir` (the axis cache: the direction
  * the pair was found apart along a step ago).  true: farther apart than margin + radii,
@@ -795,8 +910,11 @@ __device__ inline bool self_hulls_apart(const WaveMem& W, const GQ_MODEL GqDevMo
  * pair (aliengo perlin + 8 %), do; the flat-scene variants, whose launch on the headline workload IS the convex routine, do not (- 4 % with it).
  * CVX false (SCENE_FLAT_SELF_PRIM: the model's pair table holds no kind 4): the convex mid phase, the convex routine and everything of the pair
  * exchange - the fetches up here, publication, claim / linger loop, collect - are not compiled in; PRIM false (SCENE_FLAT_SELF_HULL, world hull
- * scenes: no kind 1 - 3): nor are the exact box routines.  gq_step_call.h model_scene picks the scene from the same table that pass B walks. */
-template <bool CONE, bool PRIM = true, bool COLD = false, bool CVX = true>
+ * scenes: no kind 1 - 3): nor are the exact box routines.  gq_step_call.h model_scene picks the scene from the same table that pass B walks.
+ * XEARLY (the flat hull scenes): early_publish ran in front of the floor pass - the pairs it named in GQ_XE_MASK are candidates whatever the cull says,
+ * skip the mid phase and enter the exchange block as published, lane = pair with its early slot; a pair that yields a contact leaves its prediction
+ * word (sepc_touch).  Without it the function is the world-box variants' of old: they neither write nor meet that word. */
+template <bool CONE, bool PRIM = true, bool COLD = false, bool CVX = true, bool XEARLY = false>
 __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevModel& m, float mu_env, WorldAppend& S, const SelfPrefetch& pre, const StepConsts& K, const int nlg, const GQ_MODEL GqDevBatch& Bt, float* xdbg = nullptr, const int env = 0) {
   constexpr int NP = PRIM ? 4 : 1; /* points per pair: only the exact pair routines return more than one */
   const int lane = lane_id();
@@ -805,6 +923,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
   int32_t* xq_tab = nullptr; int xq_slots = 0; /* the pair exchange: none without the convex block - and none in the experiment builds with -DGQ_XQ_OFF */
   float* sepc = nullptr; /* this env's rows of the separating-axis cache */
   int xq_pre = 0;
+  uint64_t xe[2] = {0ull, 0ull}; /* pairs 0 - 63, 64 - 127 that are out in a slot since early_publish (XEARLY: it ran in front of the floor pass and left GQ_XE_MASK) */
   (void)Bt; (void)env; (void)xdbg;
   if constexpr (CVX) {
 #ifndef GQ_XQ_OFF
@@ -814,22 +933,18 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
      * an env without convex work (a potential helper) last passed by - fetched here, so that the latency passes behind the end points and the cull */
     sepc = Bt.sepc ? Bt.sepc + (size_t)env * Bt.sepc_stride : nullptr;
     if (xq_tab) { Xq X0; X0.q = xq_tab; X0.slots = xq_slots; xq_pre = ld_pub(xq_tab + xq_window(X0, wave_index()) + lane); }
+    if constexpr (XEARLY) {
+      const uint32_t* e = GQ_XE_MASK(W);
+      xe[0] = (uint64_t)(uint32_t)uniform((int)e[0]) | ((uint64_t)(uint32_t)uniform((int)e[1]) << 32);
+      xe[1] = (uint64_t)(uint32_t)uniform((int)e[2]) | ((uint64_t)(uint32_t)uniform((int)e[3]) << 32);
+    }
   }
   const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   /* world end points of every item's proxy capsule, once: lane = collision item; scratch in the J block, which is free
    * until S7 (the spatial-dynamics scratch it overlays is dead since S5) */
   /* per item: end points p0, p1, radius, and the bounding sphere (centre, radius) the first pass tests */
   float(*cw)[12] = reinterpret_cast<float(*)[12]>(&W.u.B[0][0]);
-  { /* lane = item; lanes past the last item repeat item 0 (self_prefetch fetched its record for them): no exec-mask block */
-    const int it = lane < 4 + nlg ? lane : 0;
-    const int b = pre.body;
-    const V3 o = ld3(W.xpos[b]);
-    const V3 e0 = o + matvec(W.xmat[b], v3(pre.caps[0], pre.caps[1], pre.caps[2])), e1 = o + matvec(W.xmat[b], v3(pre.caps[3], pre.caps[4], pre.caps[5]));
-    st3(cw[it], e0); st3(cw[it] + 3, e1);
-    cw[it][6] = pre.caps[6];
-    st3(cw[it] + 8, o + matvec(W.xmat[b], v3(pre.bsph[0], pre.bsph[1], pre.bsph[2]))); /* broad-phase sphere: the primitive itself where the item is one */
-    cw[it][11] = pre.bsph[3];
-  }
+  GQ_SELF_END_POINTS(W, pre, nlg, lane, cw) /* (once more where the early publication built it: the floor pass used its words in between) */
   /* models with many pairs: body-pair broad phase, so that passes whose pairs all belong to far-apart bodies are skipped */
   uint64_t near[2] = {~0ull, ~0ull};
   if (nsp > 2 * GQ_WAVE) {
@@ -865,7 +980,9 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
   int ncand = 0;
 #pragma unroll 1
   for (int p0 = 0; p0 < nsp; p0 += GQ_WAVE) {
-    if constexpr (CONE) if (!((live_pass >> (p0 / GQ_WAVE)) & 1ull)) continue; /* wave-uniform: every body pair of this pass is far apart */
+    uint64_t xep = 0ull; /* published early: candidates whatever the spheres say - their slots are collected in pass B */
+    if constexpr (XEARLY) xep = p0 == 0 ? xe[0] : (p0 == GQ_WAVE ? xe[1] : 0ull);
+    if constexpr (CONE) if (!((live_pass >> (p0 / GQ_WAVE)) & 1ull) && (!XEARLY || xep == 0)) continue; /* wave-uniform: every body pair of this pass is far apart */
     const int p = p0 + lane;
     bool cand;
     { /* branch-free: lanes past the last pair test pair 0 (the prefetch's fall-back) and are masked */
@@ -878,7 +995,8 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
       const float* k2 = cw[it2] + 8;
       const V3 dm = ld3(k2) - ld3(k1);
       const float reach = k1[3] + k2[3] + K.self_margin;
-      cand = p < nsp && nr && dot(dm, dm) < reach * reach;
+      if constexpr (XEARLY) cand = p < nsp && ((nr && dot(dm, dm) < reach * reach) || ((xep >> lane) & 1ull));
+      else cand = p < nsp && nr && dot(dm, dm) < reach * reach;
     }
     const uint64_t cm = ballot(cand);
     if (cm == 0) continue;
@@ -910,6 +1028,8 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
     H.n = 0;
     int it1 = 0, it2 = 0;
     bool cvx = false;
+    bool pre_out = false; /* the pair is out in a slot since the early block: no mid phase - it enters the block below as published */
+    if constexpr (CVX && XEARLY) pre_out = cand && p < 2 * GQ_WAVE && (((p < GQ_WAVE ? xe[0] : xe[1]) >> (p & 63)) & 1ull) != 0;
     if (cand) {
       const GQ_MODEL GqDevSelfPair& Pp = m.sp[p];
       it1 = Pp.it1; it2 = Pp.it2;
@@ -917,7 +1037,8 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
       const float marg = Pp.mix.margin;
       const float* k1 = cw[it1];
       const float* k2 = cw[it2];
-      if (kind == 0) { /* capsule proxies: closest points of the two axes */
+      if (XEARLY && pre_out) {
+      } else if (kind == 0) { /* capsule proxies: closest points of the two axes */
         V3 c1, c2;
         closest_seg_seg(ld3(k1), ld3(k1 + 3), ld3(k2), ld3(k2 + 3), c1, c2);
         const V3 d = c2 - c1;
@@ -935,7 +1056,8 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
         if (cvx && sepc) { /* ... and along the direction that told them apart a step ago (two links a few centimetres apart for ever: hyqreal1's trunk and upper legs) */
           const float* c = sepc + 3 * Pp.cidx;
           const V3 dw = matvec(W.xmat[0], v3(c[0], c[1], c[2]));
-          if (dot(dw, dw) > 0.25f) cvx = !self_hulls_apart(W, m, K.vx, it1, k1, R1, it2, k2, R2, marg, true, dw);
+          const float dd = dot(dw, dw);
+          if (dd > 0.25f && (!XEARLY || dd < 2.0f)) cvx = /* (0 0 0: nothing remembered; GQ_SEPC_TOUCH: the prediction word, no direction) */ !self_hulls_apart(W, m, K.vx, it1, k1, R1, it2, k2, R2, marg, true, dw);
         }
       } } else if constexpr (PRIM) { /* a box is involved: exact routines (gq_pairs.h); the box of kind 1 / 3 is item 1, of kind 2 item 2 */
         const int ib = kind == 2 ? it2 : it1;
@@ -980,23 +1102,26 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
       if (K.self_cut == 5) cm = 0;        /* profiling aid: the mid phase without the convex routine */
       if (K.self_cut == 6) cm &= cm - 1;  /* ... and without the first pair that reaches it */
       Xq X; X.q = xq_tab; X.slots = xq_slots;
-      uint64_t local = cm, own = 0; /* pairs to run here / published */
-      int myslot = -1;              /* lane = pair: the slot it reserved */
+      const uint64_t xem = XEARLY ? ballot(pre_out) : 0ull;
+      uint64_t local = cm, own = xem; /* pairs to run here / published */
+      int myslot = -1;                /* lane = pair: the slot it reserved */
+      if (pre_out) myslot = GQ_XE_SLOT(W)[p < GQ_WAVE ? popc64(xe[0] & ((1ull << p) - 1ull)) : popc64(xe[0]) + popc64(xe[1] & ((1ull << (p - GQ_WAVE)) - 1ull))];
       /* an env without convex work of its own has 40 us to spare before the launch's entangled envs are through: it lingers here for a few
        * microseconds - if its group of the table has seen pairs lately - and takes what gets published meanwhile */
-      bool linger = X.q != nullptr && cm == 0 && c0 + GQ_WAVE >= npass && xq_is_hot(xq_act, wall_clock64());
+      bool linger = X.q != nullptr && cm == 0 && xem == 0 && c0 + GQ_WAVE >= npass && xq_is_hot(xq_act, wall_clock64());
       int t_ref = 0; bool t_set = false; /* start of the wait in progress, 100 MHz ticks (low word): an owner's deadline or the lingering */
 #define GQ_XSTAT(i, v) do { if (xdbg && lane == 0) xdbg[i] = (float)(v); } while (0)
 #define GQ_XTIME(i) GQ_XSTAT(i, wall_clock64() & 0xFFFFF)
       int x_back = 0, x_help = 0; long long x_ticks = 0, x_t0 = 0; bool x_ld = false;
-      if (cm) GQ_XSTAT(0, popc64(cm));
-      if (X.q != nullptr && cm == 0 && ncand != 0 && c0 + GQ_WAVE >= npass) xq_mark_helper(X, wave_index(), xq_hlp);
+      if (cm | xem) GQ_XSTAT(0, popc64(cm) + popc64(xem));
+      if (X.q != nullptr && cm == 0 && xem == 0 && ncand != 0 && c0 + GQ_WAVE >= npass) xq_mark_helper(X, wave_index(), xq_hlp);
       if (GQ_COLD_HINT(X.q != nullptr && (cm & (cm - 1)) != 0 && xq_is_hot(xq_hlp, wall_clock64()))) { /* two pairs or more - and envs with time on their hands around (hyqreal1 on boxes: every env has four or five pairs, publishing would be pure overhead): keep the first, publish the others - at once, helpers come by only so often */
         const uint64_t rest = cm & (cm - 1);
         if ((rest >> lane) & 1ull) myslot = xq_reserve(X, wave_index(), opaque_lane(lane)); /* (opaque: the four candidate slots' addresses depend on wavefront and lane alone, and were computed in front of pass B and kept across it in scratch memory - 7 64-bit stores there, as many reloads in front of the reservation) */
         own = ballot(myslot >= 0);
+        const uint64_t fresh = own & ~xem; /* (the pairs published early are in `own` from the start, READY long since) */
         local = cm & ~own; /* (no free slot among a pair's candidates: it stays here) */
-        for (uint64_t r = own; r;) {
+        for (uint64_t r = fresh; r;) {
           const int jj = ffs64(r); r &= r - 1;
           const int pj = bcast(p, jj), i1 = bcast(it1, jj), i2 = bcast(it2, jj), sj = bcast(myslot, jj);
           wave_barrier();
@@ -1006,8 +1131,8 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
           xq_put(X, sj, GQ_CVX_SHP(W), m.sp[pj].mix.margin);
         }
         publish_fence();
-        if (myslot >= 0) { xq_ready(X, myslot); xq_mark_active(X, myslot); }
-        GQ_XSTAT(1, popc64(own)); GQ_XTIME(2);
+        if ((fresh >> lane) & 1ull) { xq_ready(X, myslot); xq_mark_active(X, myslot); }
+        GQ_XSTAT(1, popc64(fresh)); GQ_XTIME(2);
       }
       /* (marked unlikely for the register allocator's sake: block frequencies are its spill weights, and the routine's loops otherwise outweigh
        * values that live across the whole step - they were spilled all over the kernel, 57 scratch instructions in gq_step_body.h alone) */
@@ -1057,7 +1182,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
         const bool hit = cvx_pair_wave(GQ_CVX_SHP(W), GQ_CVX_POLY_SELF(W), K.vx, K.vy, K.vz, marg);
         LdsCF out = GQ_CVX_SHP(W) + 2 * GQ_CVX_SHAPE_WORDS;
         if (j >= 0) {
-          if (hit && lane == j) { H.n = 1; H.dist[0] = out[0]; H.nrm[0] = ld3(out + 1); H.pos[0] = ld3(out + 4); }
+          if (hit && lane == j) { H.n = 1; H.dist[0] = out[0]; H.nrm[0] = ld3(out + 1); H.pos[0] = ld3(out + 4); if (XEARLY && sepc) sepc_touch(sepc + 3 * m.sp[p].cidx); }
           if (!hit && lane == j && sepc) sepc_store(W, sepc + 3 * m.sp[p].cidx, ld3(out + 1));
         } else {
           wave_barrier(); xq_done(X, slot, hit, out);
@@ -1072,6 +1197,7 @@ __device__ inline void append_self_contacts(WaveMem& W, const GQ_MODEL GqDevMode
           if (ld_pub(it + GQ_XQ_RES) != 0) {
             const float* r = reinterpret_cast<const float*>(it) + GQ_XQ_RES;
             H.n = 1; H.dist[0] = ld_pub(r + 1); H.nrm[0] = v3(ld_pub(r + 2), ld_pub(r + 3), ld_pub(r + 4)); H.pos[0] = v3(ld_pub(r + 5), ld_pub(r + 6), ld_pub(r + 7));
+            if (XEARLY && sepc) sepc_touch(sepc + 3 * m.sp[p].cidx);
           }
           else if (sepc) { const float* r = reinterpret_cast<const float*>(it) + GQ_XQ_RES; sepc_store(W, sepc + 3 * m.sp[p].cidx, v3(ld_pub(r + 2), ld_pub(r + 3), ld_pub(r + 4))); }
           st_pub(xq_state(X, myslot), XQ_FREE); /* (the loads above have returned: H is used below) */
@@ -1162,7 +1288,7 @@ __device__ __forceinline__ void stage_self_contacts(WaveMem& W, const GQ_MODEL G
   }
   if constexpr (CONE)
     for (int c = 0; c < ncon; c++) { const int d = uniform(W.con_dim[c]); S.reserve += d > 1 ? d - 1 : 0; }
-  append_self_contacts<CONE, PRIM, false, CVX>(W, m, mu_env, S, pre, K, nlg, Bt, xdbg, env);
+  append_self_contacts<CONE, PRIM, false, CVX, CVX>(W, m, mu_env, S, pre, K, nlg, Bt, xdbg, env);
   { W.ncon = S.ncon; W.nefc = S.rows; W.nself = S.nself; W.ndrop = S.ndrop; } /* (every lane: the same words) */
   wave_barrier();
 }

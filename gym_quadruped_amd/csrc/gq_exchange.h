@@ -35,6 +35,26 @@
  * launch is resident at once.  (A second visit of every wavefront at the END of its step, tried first, changed nothing once the
  * lingering was in: removed.)
  *
+ * Published early (flat hull scenes; gq_boxes.h early_publish).  The pairs that end a launch are deep tangles, and a tangle lasts: on the
+ * benchmark's state distribution 96 % of the EPA iterations of a step - and every contact of twelve iterations or more - fall on pairs that
+ * already touched a step earlier (tools/early_publish_census.py, profiles/early_publish_census.txt).  All a pair's publication needs is there as soon
+ * as xpos / xmat are final; the floor pass, the cull and the mid phase between that point and the publication above only decide WHETHER the routine
+ * must run.  So a pair that yields a contact leaves a PREDICTION WORD in its row of the axis cache (GqDevBatch::sepc: a row that is no unit
+ * vector, 2 0 0 - a pair found apart overwrites it with its direction as before, the mid phase reads it as "no direction"), and the next step,
+ * between its last smooth stage and the floor pass - lane = row of the cache, the words prefetched in one batch under the velocity stage, one
+ * ballot: six envs in ten leave here, the others look up which pairs own the rows - reserves slots for all such pairs at once, writes them, fences once and marks them READY, while the launch's helpers are just
+ * arriving at their convex block; under the rule above: only while helpers are around (not in the step of a reset, whose lift loop moves
+ * xpos afterwards; not under a stage cut, which may end the step before pass B gives the slots back).  Pair -> slot goes to pass B in dead LDS words.  There such a pair is a candidate whatever the bounding spheres say now,
+ * skips the mid phase, and its lane enters the block as if it had just published: slot in hand, bit set among the owner's published pairs.  The
+ * wait, the take-back of a pair nobody claimed, the collection, XQ_FREE and the GQ_XQ_OWNER_TICKS net are the code of any other published pair;
+ * an owner all of whose pairs went out early keeps none and waits at the usual place.  The other pairs are published as before (keep the first,
+ * publish the rest).  Slot life is unchanged - no new state, no shared word, no barrier.
+ * Why results stay bit-identical: a pair's result depends on its 41 input words alone, and those are the ones pass B would have written
+ * (same xpos / xmat, same routine for the shapes).  The cull and the mid phase are filters: for a pair they would have rejected the routine
+ * returns "no contact" (what they prove apart is farther apart than the margin) - a stale word, after a re-spawn say, costs one useless
+ * publication and nothing else.  Contacts are appended in pair order after the collection.  Hence the contact list, the rows and the state
+ * are those of a step without the early block, exchange on or off (tests/test_gpu_early_publish.py, tests/test_early_publish_emulated.py).
+ *
  * What it buys and what is left (MI355X, 4096 mini_cheetah envs, steady state): the launch 375 -> 147 us.  What remains is one chain:
  * the owner's pairs are READY after 25 - 37 us, the launch's most expensive pair takes 77 us whoever computes it, the owner's solver and
  * epilogue 25 - 30 us.  Only a faster routine shortens it further.

@@ -731,6 +731,9 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
     K.vx = vxq; K.vy = vyq; K.vz = vzq;
   }
   const GQ_MODEL float* vx_p = K.vx; const GQ_MODEL float* vy_p = K.vy; const GQ_MODEL float* vz_p = K.vz;
+  EarlyPrefetch early_pre; /* the convex self pairs' prediction words (flat hull scenes): one batch of loads, in flight during the velocity stage */
+  early_pre.s[0] = early_pre.s[1] = 0.0f;
+  if constexpr (SELF && !BOXES && CVX) early_pre = early_prefetch(Bt, env);
   /* ================================================================ S5: velocity stage (mj_comVel, mj_rne) */
   { /* lane = leg, mirror lanes */
     /* base velocity and bias acceleration, recomputed per leg lane */
@@ -794,6 +797,8 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   /* ================================================================ S6: collision with the floor (z = 0) */
   SelfPrefetch self_pre;
   if constexpr (SELF && !BOXES) self_pre = self_prefetch(m, nlg, K.nsp); /* (world-box variants fetch it behind the box loop: 18 registers less across it) */
+  /* the convex pairs that touched a step ago go into the pair exchange now: xpos / xmat are final, helpers are arriving (gq_exchange.h "published early") */
+  if constexpr (SELF && !BOXES && CVX) early_publish(W, m, self_pre, early_pre, K, nlg, Bt, (DBG && timing) ? call.debug + (size_t)env * GQ_DBG_SIZE + GQ_DBG_XQ : nullptr, MODE == 2 && call.stop_stage != 0);
   stage_collision_scan(W, m, vx_p, vy_p, vz_p, false, FRec);
   GQ_SUB(W, 1, 7); /* hull cloud scan */
   /* reset on a scene without world boxes / height field: the lift loop of QuadrupedEnv.reset (quadruped_env.py:376-388:

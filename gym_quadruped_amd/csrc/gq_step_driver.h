@@ -74,7 +74,7 @@ __device__ __forceinline__ void joint_cmd_inline(const GQ_MODEL JointCmdDev& J, 
  *     register to spare);
  *   lane = hinge (12): W.ctrl / act_seq / tau_out, exactly as joint_cmd_inline.
  * Fetched at every substep, nothing carried across step_wave (profiles/joint_cmd_kernel_resources.md).  W.force[0..1] are not
- * touched: they carry the clock and GQ_LIFT_DUE. */
+ * touched: they carry the clock and GQ_LIFT_DUE (force[2 .. 40) are written and read inside step_wave only: gq_boxes.h GQ_XE_MASK). */
 __device__ __forceinline__ void foot_cmd_inline(const GQ_MODEL FootCmdDev& F, const GQ_MODEL GqDevModel& m, const StepArgs& a, const StepCall& c, WaveMem& W,
                                                 const int env, const int kstep, const bool last, const bool apply) {
   const int lane = lane_id();

@@ -256,7 +256,9 @@ struct WaveMem {
 };
 static_assert(sizeof(WaveMem) <= 10240 || GQ_TICKSET != 0, "16 one-wave workgroups per CU need <= 10 240 B of LDS each: WaveMem is full, a new field must reuse a dead one");
 /* S0 .. S6: whether the reset's lift loop is due in this step's S6, as an int in force[1] (free until the solver, like the clock in force[0];
- * carried in a register from the prologue across the re-spawn branch it was spilled to scratch memory, and WaveMem has no byte to spare) */
+ * carried in a register from the prologue across the re-spawn branch it was spilled to scratch memory, and WaveMem has no byte to spare).
+ * force[2 .. 40), from the last smooth stage to the end of S6 in the flat hull scenes: the hand-over of the early publication of convex pairs to
+ * pass B (gq_boxes.h GQ_XE_MASK / GQ_XE_SLOT, with the static_assert on their extent).  The solver is force's first other writer. */
 #define GQ_LIFT_DUE(W) (reinterpret_cast<int32_t*>(&(W).force[1])[0])
 
 /* ------------------------------------------------------------------ small math */

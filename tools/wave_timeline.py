@@ -1,6 +1,6 @@
 """Where and when each wave of one step launch runs (debug kernel: it records a device-wide 100 MHz clock at wave start
 and end, the per-stage cycle stamps and the hardware slot).  Shows the dispatch ramp, the end-time distribution, how
-waves sharing a SIMD affect each other and which waves form the tail.   Usage: wave_timeline.py [n] [robot]"""
+waves sharing a SIMD affect each other and which waves form the tail.   Usage: wave_timeline.py [n] [robot] [noself|capsule|-] [scene] [the file this output is committed as]"""
 import sys
 from pathlib import Path
 import numpy as np, torch
@@ -48,18 +48,23 @@ rel = lambda col: ((XQ[:, col] - (T[:, 24] - 0)) % (1 << 20)) / 100.0      # us 
 own = XQ[:, 1] > 0; hlp = XQ[:, 6] > 0; lin = (XQ[:, 9] > 0)
 if own.sum():
     print(f'pair exchange: {int((XQ[:, 0] > 0).sum())} envs with convex pairs past the mid phase ({XQ[:, 0].sum():.0f} pairs, max {XQ[:, 0].max():.0f}), {own.sum()} of them published {XQ[own, 1].sum():.0f} (max {XQ[own, 1].max():.0f}), took back {XQ[own, 5].sum():.0f};')
-    print(f'  owners, us since their start: pairs READY p50 {np.median(rel(2)[own]):.1f} p99 {np.percentile(rel(2)[own], 99):.1f}; own pairs done p50 {np.median(rel(3)[own]):.1f} p99 {np.percentile(rel(3)[own], 99):.1f}; all DONE p50 {np.median(rel(4)[own]):.1f} p90 {np.percentile(rel(4)[own], 90):.1f} p99 {np.percentile(rel(4)[own], 99):.1f} max {rel(4)[own].max():.1f}')
+    late = own; own = own | (XQ[:, 10] > 0)      # (an owner may have published early only)
+    print(f'  owners, us since their start: pairs READY p50 {np.median(rel(2)[late]):.1f} p99 {np.percentile(rel(2)[late], 99):.1f}; own pairs done p50 {np.median(rel(3)[own]):.1f} p99 {np.percentile(rel(3)[own], 99):.1f}; all DONE p50 {np.median(rel(4)[own]):.1f} p90 {np.percentile(rel(4)[own], 90):.1f} p99 {np.percentile(rel(4)[own], 99):.1f} max {rel(4)[own].max():.1f}')
+erl = XQ[:, 10] > 0      # published early: between the smooth stages and the floor pass (gq_exchange.h), record words 10 (pairs) and 11 (time)
+if erl.sum():
+    print(f'  published early: {erl.sum()} envs, {XQ[erl, 10].sum():.0f} pairs (max {XQ[erl, 10].max():.0f}); early READY p50 {np.median(rel(11)[erl]):.1f} p99 {np.percentile(rel(11)[erl], 99):.1f} us since their start')
 if hlp.sum():
     per = XQ[hlp, 8] / np.maximum(XQ[hlp, 6], 1) / 100.0
     print(f'  {lin.sum()} envs lingered at the convex block (end p50 {np.median(rel(9)[lin]):.1f} p99 {np.percentile(rel(9)[lin], 99):.1f} us since start); {hlp.sum()} of them computed {XQ[hlp, 6].sum():.0f} pairs for others (max {XQ[hlp, 6].max():.0f}), first claim p50 {np.median(rel(7)[hlp]):.1f} p99 {np.percentile(rel(7)[hlp], 99):.1f} us; us per pair p50 {np.median(per):.1f} p90 {np.percentile(per, 90):.1f} max {per.max():.1f}')
 last = np.argsort(-t1)[:12]
+print(f'last 12 waves: {XQ[last, 0].sum():.0f} convex pairs past the mid phase or published early, {XQ[last, 10].sum():.0f} of them predicted and published early ({100 * XQ[last, 10].sum() / max(XQ[last, 0].sum(), 1):.0f} %)')
 print('last waves to finish (end us | start | niter nefc pending | co-resident waves on the SIMD: their niter):')
 for e in last:
     co = np.where(slot == slot[e])[0]
     print(f'  env {e:5d}: {t1[e]:6.1f} | {t0[e]:5.1f} | {nit[e]} {int(d[e]["nefc"][0]):2d} {int(pend[e])} hint {hint[e]} self {int(T[e, 31])} | ' + ' '.join(f'{nit[c]}{"r" if pend[c] else ""}h{hint[c]}@{t1[c]:.0f}' for c in co if c != e))
     # stage ends of this wave in us from its start (stage stamps are shader cycles; scaled by the wave's own wall time / cycle count)
     sc = (t1[e] - t0[e]) / max(T[e, 13], 1.0)
-    print(f'             exchange: pairs {XQ[e, 0]:.0f} published {XQ[e, 1]:.0f} READY@{rel(2)[e] if XQ[e, 1] else 0:.0f} own done@{rel(3)[e] if XQ[e, 1] else 0:.0f} all DONE@{rel(4)[e] if XQ[e, 1] else 0:.0f} back {XQ[e, 5]:.0f} | helped {XQ[e, 6]:.0f} first@{rel(7)[e] if XQ[e, 6] else 0:.0f} us spent {XQ[e, 8] / 100:.0f} linger end@{rel(9)[e] if XQ[e, 9] else 0:.0f}')
+    print(f'             exchange: pairs {XQ[e, 0]:.0f} early {XQ[e, 10]:.0f} READY@{rel(11)[e] if XQ[e, 10] else 0:.0f} published {XQ[e, 1]:.0f} READY@{rel(2)[e] if XQ[e, 1] else 0:.0f} own done@{rel(3)[e] if XQ[e, 1] + XQ[e, 10] else 0:.0f} all DONE@{rel(4)[e] if XQ[e, 1] + XQ[e, 10] else 0:.0f} back {XQ[e, 5]:.0f} | helped {XQ[e, 6]:.0f} first@{rel(7)[e] if XQ[e, 6] else 0:.0f} us spent {XQ[e, 8] / 100:.0f} linger end@{rel(9)[e] if XQ[e, 9] else 0:.0f}')
     print('             stage ends (us from wave start): ' + ' '.join(f'{nm} {T[e, k] * sc:.0f}' for nm, k in (('kin', 5), ('floor', 14), ('collide', 6), ('rows', 7), ('pre', 8), ('solve', 9), ('euler', 10), ('integ', 11), ('obs', 12), ('end', 13))))
 
 # the launch's tail as one number (bench.py roofline.tail replays it from profiles/latest_tail.json, with the kernel-source hash it was taken on):
@@ -68,7 +73,7 @@ import json, os
 import bench
 tail = {'tail': float((t1.max() - np.median(t1)) / t1.max()), 'launch_us': float(t1.max()), 'median_wave_end_us': float(np.median(t1)), 'p99_wave_end_us': float(np.percentile(t1, 99)),
         'kernel_src_sha16': bench.kernel_source_hash(), 'workload': f'{robot} {scene}, {n} envs, instrumented step kernel, launch 301 of a random-action rollout',
-        'profile': 'profiles/r06_wave_timeline.txt'}
+        'profile': sys.argv[5] if len(sys.argv) > 5 else 'profiles/early_publish_wave_timeline.txt'}
 print('tail json:', json.dumps(tail))
 if robot == 'mini_cheetah' and scene == 'flat' and selfcol is None and n == 4096:
     os.makedirs(ROOT / 'gpurun_out', exist_ok=True)
