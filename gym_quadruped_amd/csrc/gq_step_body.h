@@ -1384,14 +1384,21 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   pin(e_qpos); pin(e_qvel); pin(e_qacc); pin(e_warm); pin(e_obs); pin(e_reward); pin(e_term); pin(e_trunc); pin(e_inval); pin(e_pending);
   pin(e_dropped); pin(e_imu_bias); pin(e_contacts); pin(e_h9); pin(e_obs_seq); pin(e_hint); pin(od); pin(obs_need); pin(imu_en);
   pin(tlim0); pin(tlim1); pin(tlim2); pin(tlim3);
+  /* the epilogue's lane indices, made again from an opaque copy of the lane id.  The prologue's clamped indices (ld, lj, lq), the LDS addresses
+   * built on them, S3's table entries and the foot's leg do not survive the solver in registers: the allocator kept them in scratch memory,
+   * and S11 reloaded them one by one, each reload a memory round trip in front of its first use - twelve in the headline kernel, on a wave
+   * that is alone on its SIMD by then.  A clamp is one instruction, and the table words come with the batch of loads below. */
+  int lane_e = lane;
+  opaque(lane_e);
+  const int ld_e = lane_e < GQ_NVD ? lane_e : GQ_NVD - 1, lj_e = lane_e < GQ_NJ ? lane_e : GQ_NJ - 1, lq_e = lane_e < 4 ? lane_e : 3;
   /* the output layout (column -> canonical scalar) of this lane's columns: fetched now, used by the gather at the end */
   int omap[4], s3k[3];
 #pragma unroll
-  for (int i = 0; i < 4; i++) { const int k = lane + GQ_WAVE * i; omap[i] = k < od ? Bt.obs_map[k] : 0; }
-  int lane_s3 = lane;
-  if constexpr (!EARLY) opaque(lane_s3); /* (a fresh load through an opaque index: otherwise S3's copy of the same words is kept - in scratch memory - across the solver) */
+  for (int i = 0; i < 4; i++) { const int k = lane_e + GQ_WAVE * i; omap[i] = k < od ? Bt.obs_map[k] : 0; }
+  const int lane_s3 = lane_e; /* (a fresh load through an opaque index: otherwise S3's copy of the same words is kept - in scratch memory - across the solver) */
 #pragma unroll
   for (int p = 0; p < 3; p++) s3k[p] = (SOLVER == 1 && (obs_need & GQ_NEED_ENERGY)) ? m.s3_ent[p][lane_s3] : 0; /* the energy sums walk M's stored entries */
+  const int leg_e = (obs_need & (GQ_NEED_FEET | GQ_NEED_CONTACT)) ? m.foot_leg[lq_e] : 0; /* lane = foot (mirror lanes): its leg, for the feet block */
   /* IMU ground truth (mj_sensorAcc / mj_sensorVel of this forward pass: OLD pose and velocity, this step's qacc).
    * accelerometer = site-frame acceleration of the site point minus gravity; gyro = site-frame angular velocity */
   const bool imu_on = e_imu_bias != nullptr && imu_en;
@@ -1412,24 +1419,24 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   /* mj_checkAcc: a non-finite or absurd acceleration (|qacc| >= 1e10, MuJoCo's mjMAXVAL) means the simulation diverged.
    * MuJoCo resets the data and warns; here the env is frozen for this step (zero acceleration) and flagged terminated +
    * truncated, so that an auto-resetting batch re-spawns it and a NaN never reaches the next step */
-  const float qa_raw = W.qacc[ld], qi_raw = W.qacc_int[ld]; /* lane = dof, mirror lanes */
+  const float qa_raw = W.qacc[ld_e], qi_raw = W.qacc_int[ld_e]; /* lane = dof, mirror lanes */
   const bool diverged = ballot(!(fabsf(qa_raw) < 1e10f && fabsf(qi_raw) < 1e10f)) != 0;
   /* semi-implicit Euler (mj_Euler): velocity with the damped system, then positions with the new velocity */
   float vnew = 0.0f;
   {
     const float qa = diverged ? 0.0f : qa_raw, qi = diverged ? 0.0f : qi_raw;
-    if (diverged) { W.qacc[ld] = 0.0f; W.qacc_int[ld] = 0.0f; } /* wave-uniform, rare */
-    vnew = W.qvel[ld] + h * qi;
+    if (diverged) { W.qacc[ld_e] = 0.0f; W.qacc_int[ld_e] = 0.0f; } /* wave-uniform, rare */
+    vnew = W.qvel[ld_e] + h * qi;
     vnew = fabsf(vnew) < 1e10f ? vnew : 0.0f;
-    gptr(e_qvel)[(size_t)env * 18 + ld] = vnew;
-    gptr(e_qacc)[(size_t)env * 18 + ld] = qa;
-    gptr(e_warm)[(size_t)env * 18 + ld] = qa;
+    gptr(e_qvel)[(size_t)env * 18 + ld_e] = vnew;
+    gptr(e_qacc)[(size_t)env * 18 + ld_e] = qa;
+    gptr(e_warm)[(size_t)env * 18 + ld_e] = qa;
   }
   /* base x,y stay in f64 (uniform: every lane reads the same two words) and never enter fp32 arithmetic; they wait
    * in LDS since S0, so they do not occupy registers across the solver */
   const double bx_d = W.bxy[0], by_d = W.bxy[1];
   wave_barrier();
-  W.qvel[ld] = vnew; /* new qvel; old one is not needed any more */
+  W.qvel[ld_e] = vnew; /* new qvel; old one is not needed any more */
   wave_barrier();
   /* positions */
   const double bxn_d = bx_d + (double)h * (double)W.qvel[0], byn_d = by_d + (double)h * (double)W.qvel[1];
@@ -1453,7 +1460,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
     qn = qnormalize(qn);
   }
   /* the qpos row: lane = column (mirror lanes), ONE store - base x, y (f64), z, the quaternion, the joint angles picked by selects */
-  const int l19 = lane < 19 ? lane : 18, jq = l19 < 7 ? 0 : l19 - 7;
+  const int l19 = lane_e < 19 ? lane_e : 18, jq = l19 < 7 ? 0 : l19 - 7;
   const float qjn = W.qj[jq] + h * W.qvel[6 + jq];
   const float qcol = l19 < 3 ? znew : (l19 == 3 ? qn.w : (l19 == 4 ? qn.x : (l19 == 5 ? qn.y : (l19 == 6 ? qn.z : qjn)))); /* columns 2 .. 18 */
   {
@@ -1499,8 +1506,8 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   }
   }
   GQ_SUB(W, 2, 7); /* base observables */
-  ob[OB_QVEL + ld] = W.qvel[ld];
-  ob[OB_TAU + lj] = W.ctrl[lj]; ob[OB_QVEL_JS + lj] = W.qvel[6 + lj];
+  ob[OB_QVEL + ld_e] = W.qvel[ld_e];
+  ob[OB_TAU + lj_e] = W.ctrl[lj_e]; ob[OB_QVEL_JS + lj_e] = W.qvel[6 + lj_e];
   ob[OB_QPOS_JS + jq] = qjn;
   /* kinetic energy 1/2 v'Mv and work (M qacc).v with the OLD mass matrix, NEW velocity, qacc of this step */
   if (obs_need & GQ_NEED_ENERGY) {
@@ -1518,7 +1525,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
         const float coef = counts ? ((p < 2 && (p == 0 || lane < 108 - GQ_WAVE) && dd != sa) ? 1.0f : 0.5f) : 0.0f;
         ke_part += coef * M0[e < 143 ? e : 143] * W.qvel[dd] * W.qvel[sa];
       }
-      wk_part = (lane < GQ_NVD && !diverged) ? W.act[ld] * W.qvel[ld] : 0.0f; /* (a frozen env: qacc was zeroed) */
+      wk_part = (lane < GQ_NVD && !diverged) ? W.act[ld_e] * W.qvel[ld_e] : 0.0f; /* (a frozen env: qacc was zeroed) */
     } else if (lane < GQ_NVD) {
       const float mv = mul_m_row(W, W.qvel, lane), ma = mul_m_row(W, W.qacc, lane);
       ke_part = 0.5f * W.qvel[lane] * mv; wk_part = ma * W.qvel[lane];
@@ -1529,8 +1536,8 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   GQ_SUB(W, 2, 8); /* joint observables + energy */
   /* feet: lane k < 4 = foot k in FL FR RL RR order */
   if (obs_need & (GQ_NEED_FEET | GQ_NEED_CONTACT)) { /* wave-uniform; lane = foot, mirror lanes */
-    const int leg = FRec.leg, body = 3 + 3 * leg;
-    V3 pw = ld3(W.foot_world[lq]); /* relative to the OLD base x/y */
+    const int leg = leg_e, body = 3 + 3 * leg;
+    V3 pw = ld3(W.foot_world[lq_e]); /* relative to the OLD base x/y */
     /* spatial velocity of the calf with old cdof and new qvel (J_old * qvel_new) */
     float sv[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -1579,17 +1586,17 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
       cs = mine ? 1.0f : cs;
       cf = v3(mine ? cf.x + add.x : cf.x, mine ? cf.y + add.y : cf.y, mine ? cf.z + add.z : cf.z);
     }
-    if ((W.foot_touch >> lq) & 1) cs = 1.0f; /* contact detected but dropped by the row budget */
+    if ((W.foot_touch >> lq_e) & 1) cs = 1.0f; /* contact detected but dropped by the row budget */
     /* slot of this foot in legs_order-dependent observables is resolved by obs_map; canonical order = FL FR RL RR */
-    st3(ob + OB_FEET_POS + 3 * lq, pworld);
-    st3(ob + OB_FEET_POS_B + 3 * lq, matTvec(Rn, prel_new));
-    st3(ob + OB_FEET_VEL + 3 * lq, fv);
-    st3(ob + OB_FEET_VEL_REL + 3 * lq, fvr);
-    st3(ob + OB_FEET_VEL_B + 3 * lq, matTvec(Rn, fv));
-    st3(ob + OB_FEET_VEL_REL_B + 3 * lq, matTvec(Rn, fvr));
-    ob[OB_CONTACT_STATE + lq] = cs;
-    st3(ob + OB_CONTACT_F + 3 * lq, cf);
-    st3(ob + OB_CONTACT_F_B + 3 * lq, matTvec(Rn, cf));
+    st3(ob + OB_FEET_POS + 3 * lq_e, pworld);
+    st3(ob + OB_FEET_POS_B + 3 * lq_e, matTvec(Rn, prel_new));
+    st3(ob + OB_FEET_VEL + 3 * lq_e, fv);
+    st3(ob + OB_FEET_VEL_REL + 3 * lq_e, fvr);
+    st3(ob + OB_FEET_VEL_B + 3 * lq_e, matTvec(Rn, fv));
+    st3(ob + OB_FEET_VEL_REL_B + 3 * lq_e, matTvec(Rn, fvr));
+    ob[OB_CONTACT_STATE + lq_e] = cs;
+    st3(ob + OB_CONTACT_F + 3 * lq_e, cf);
+    st3(ob + OB_CONTACT_F_B + 3 * lq_e, matTvec(Rn, cf));
   }
   wave_barrier();
   GQ_SUB(W, 2, 9); /* feet + contact forces */
@@ -1614,7 +1621,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
       const int o = g == 0 ? OB_IMU_ACC : OB_IMU_GYRO;
       ob[o + ax] = W.warm[lane] + bias + noise; ob[o + 3 + ax] = noise; ob[o + 6 + ax] = bias;
     }
-  } else ob[OB_IMU_ACC + ld] = 0.0f;
+  } else ob[OB_IMU_ACC + ld_e] = 0.0f;
   /* termination (quadruped_env.py:283-285): non-foot contact with the ground, or base outside the terrain */
   int terminated = 0;
   {
@@ -1679,7 +1686,7 @@ __device__ __forceinline__ int step_wave(const StepArgs& a, const StepCall& call
   {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const int k = lane + GQ_WAVE * i;
+      const int k = lane_e + GQ_WAVE * i;
       if (k < od) {
         const float val = ob[omap[i]];
         if constexpr (PUB) st_pub(e_obs + (size_t)env * od + k, val);
