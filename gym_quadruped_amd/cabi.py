@@ -153,6 +153,12 @@ class GqPolicyGru(C.Structure):
                 ('hidden_seq', C.c_void_p)]
 
 
+class GqPolicyScan(C.Structure):
+    """gq_rollout_policy_scan's / gq_height_scan_eval's block: the grid of the batch's base-following height map and the scan law's
+    parameters (``csrc/gq_policy_scan.h``); ``struct_size`` must hold ``sizeof(GqPolicyScan)``."""
+    _fields_ = [('struct_size', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32), ('offset', C.c_float), ('clip', C.c_float), ('scale', C.c_float)]
+
+
 class GqLearn(C.Structure):
     """gq_rollout_policy_learn's / gq_reward_eval's block: the reward weights in the order of the law's sum, and the rollout's output
     pointers; ``struct_size`` must hold ``sizeof(GqLearn)`` (the library refuses a stale layout)."""

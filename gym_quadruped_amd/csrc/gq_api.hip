@@ -23,6 +23,7 @@
 #include "gq_foot_cmd.h"
 #include "gq_policy_mlp.h"
 #include "gq_policy_gru.h"
+#include "gq_policy_scan.h"
 #include "gq_learn.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
@@ -48,6 +49,8 @@ extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream);
 extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
+extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::PolicyScanDev* scan, const float* obs, int od, int waves, int mode, int gru, hipStream_t stream);
+extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
 static thread_local char g_err[512] = "";
@@ -97,6 +100,7 @@ struct Mailbox {
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
   gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
   gq::Staged<gq::PolicyGruDev> gru;         /* the recurrent policy's (gq_rollout_policy_gru, gq_policy_gru_eval): the MLP block first, then the cell */
+  gq::Staged<gq::PolicyScanDev> scan;       /* a policy with a height scan (gq_rollout_policy_scan): the seat's block - MLP or recurrent - first, then the scan's */
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
@@ -473,6 +477,7 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.policy.create());
   HIP_TRY(t.mlp.create());
   HIP_TRY(t.gru.create());
+  HIP_TRY(t.scan.create());
   HIP_TRY(t.held.ensure(12 * N, true));
   HIP_TRY(t.last.ensure(12 * N, true));
   HIP_TRY(t.learn.create());
@@ -630,9 +635,10 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
 }
 
 /* the shape of the network and what the law needs, checked and copied into the device block's form */
-static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who) {
+/* scan_cells: the columns of a height scan between the observation columns and the last action (0: none) */
+static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who, const int scan_cells = 0) {
   if (mlp->n_layers < 1 || mlp->n_layers > GQ_MLP_MAXL) { SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, GQ_MLP_MAXL); return GQ_EINVAL; }
-  const int in_dim = mlp->in_obs + (mlp->feed_last_action ? 12 : 0);
+  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0);
   if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
   if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the network's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
   for (int l = 0; l < mlp->n_layers; l++)
@@ -651,10 +657,10 @@ static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char*
 
 /* the recurrent policy: `mlp` describes the cell's input row and the HEAD (its input width is gru->hidden), `gru` the cell and the blob of
  * both.  Fills G.cell, G.blob and G.mlp's network part (net = the head, blob = the head's layers). */
-static int gru_describe(const GqPolicyMlp* mlp, const GqPolicyGru* gru, gq::PolicyGruDev& G, const char* who) {
+static int gru_describe(const GqPolicyMlp* mlp, const GqPolicyGru* gru, gq::PolicyGruDev& G, const char* who, const int scan_cells = 0) {
   if (gru->hidden < 1 || gru->hidden > GQ_GRU_MAXH) { SET_ERR("%s: hidden = %d: 1 to %d are supported", who, gru->hidden, GQ_GRU_MAXH); return GQ_EINVAL; }
   if (mlp->n_layers < 1 || mlp->n_layers > GQ_GRU_HEAD_MAXL) { SET_ERR("%s: the head has %d linear layers: 1 to %d are supported", who, mlp->n_layers, GQ_GRU_HEAD_MAXL); return GQ_EINVAL; }
-  const int in_dim = mlp->in_obs + (mlp->feed_last_action ? 12 : 0);
+  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0);
   if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
   if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the cell's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
   gq::PolicyMlpDev& P = G.mlp;
@@ -762,24 +768,50 @@ static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw
   return ok ? GQ_OK : GQ_EINVAL;
 }
 
-/* gru: null for the MLP (the three entry points as they were), else the recurrent policy's block (gq_rollout_policy_gru) */
-static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+/* ---- the height scan's block (gq_policy_scan.h) from the C block: the law's parameters checked; with a batch, the grid held to the batch's
+ * base-following map and the base's z column resolved in its observation row (b null: gq_height_scan_eval, the law alone) ---- */
+static int scan_describe(const GqBatch* b, const GqPolicyScan* scan, gq::PolicyScanDev& S, const char* who) {
+  if (!std::isfinite(scan->offset) || !std::isfinite(scan->clip) || !std::isfinite(scan->scale)) { SET_ERR("%s: the height scan's offset, clip and scale must be finite (got %g, %g, %g)", who, (double)scan->offset, (double)scan->clip, (double)scan->scale); return GQ_EINVAL; }
+  if (!(scan->clip > 0.0f)) { SET_ERR("%s: the height scan's clip = %g: it must be positive", who, (double)scan->clip); return GQ_EINVAL; }
+  if (scan->rows <= 0 || scan->cols <= 0 || scan->rows > 4096 || scan->cols > 4096 || scan->rows * scan->cols > 4096) { SET_ERR("%s: the height scan's grid is %d x %d", who, scan->rows, scan->cols); return GQ_EINVAL; }
+  S.law.offset = scan->offset; S.law.clip = scan->clip; S.law.scale = scan->scale;
+  S.cells = scan->rows * scan->cols; S.col_z = -1; S.pad_[0] = S.pad_[1] = S.pad_[2] = 0; S.hits = nullptr;
+  if (!b) return GQ_OK;
+  if (!b->p.heightmap || b->host.hm_rows <= 0) { SET_ERR("%s: the height scan reads the batch's base-following height map: none is set (gq_batch_set_heightmap; a flat scene has none)", who); return GQ_EINVAL; }
+  if (b->host.hm_rows != scan->rows || b->host.hm_cols != scan->cols) { SET_ERR("%s: the height scan is %d x %d, the batch's base-following height map %d x %d", who, scan->rows, scan->cols, b->host.hm_rows, b->host.hm_cols); return GQ_EINVAL; }
+  int c = obs_column(b, gq::OB_BASE_POS + 2);
+  if (c < 0) c = obs_column(b, gq::OB_QPOS + 2);
+  if (c < 0) { SET_ERR("%s: the height scan reads the base's z from base_pos (or qpos): not in this batch's observation row", who); return GQ_EINVAL; }
+  S.col_z = c; S.hits = b->p.heightmap;
+  return GQ_OK;
+}
+
+/* gru: null for the MLP (the three entry points as they were), else the recurrent policy's block (gq_rollout_policy_gru); scan: null, or the
+ * height scan's block (gq_rollout_policy_scan) */
+static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                           const GqFootReward* feet, void* hip_stream, const char* const who) {
   if (feet && !fresh(feet, "GqFootReward", who)) return GQ_EINVAL;
   if (!fresh(mlp, "GqPolicyMlp", who)) return GQ_EINVAL;
   if (gru && !fresh(gru, "GqPolicyGru", who)) return GQ_EINVAL;
+  if (scan && !fresh(scan, "GqPolicyScan", who)) return GQ_EINVAL;
   if (learn && !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
-  gq::PolicyGruDev G = b->mb.gru.shadow;
+  gq::PolicyScanDev S = b->mb.scan.shadow;
+  if (scan) {
+    if (const int rc = scan_describe(b, scan, S, who); rc != GQ_OK) return rc;
+  }
+  const int scan_cells = scan ? S.cells : 0;
+  gq::PolicyGruDev Gm = b->mb.gru.shadow;
+  gq::PolicyGruDev& G = scan ? S.seat : Gm;  /* with a scan the seat's block - MLP or recurrent - is the first member of the scan's */
   gq::PolicyMlpDev Pm = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
-  gq::PolicyMlpDev& P = gru ? G.mlp : Pm;
+  gq::PolicyMlpDev& P = gru || scan ? G.mlp : Pm;
   if (gru) {
-    if (const int rc = gru_describe(mlp, gru, G, who); rc != GQ_OK) return rc;
+    if (const int rc = gru_describe(mlp, gru, G, who, scan_cells); rc != GQ_OK) return rc;
     if (!gru->hidden_state) { SET_ERR("%s: GqPolicyGru.hidden_state (device [N][hidden], in / out) is null", who); return GQ_EINVAL; }
-  } else if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
+  } else if (const int rc = mlp_describe(mlp, P, who, scan_cells); rc != GQ_OK) return rc;
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, gru ? "GRU" : "MLP"); rc != GQ_OK) return rc;
@@ -816,6 +848,10 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   if (gru) {
     G.hidden_state = gru->hidden_state; G.hidden_seq = gru->hidden_seq;
     G.terminated = out.terminated; G.pending = b->p.pending;
+  }
+  if (scan) {
+    HIP_TRY(mb.scan.push(S, stream, true));
+  } else if (gru) {
     HIP_TRY(mb.gru.push(G, stream, true));
   } else {
     HIP_TRY(mb.mlp.push(P, stream, true));
@@ -833,7 +869,8 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  if (gru) gq_launch_policy_gru(mb.dev.get(), mb.gru.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
+  if (scan) gq_launch_policy_scan(mb.dev.get(), mb.scan.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), gru != nullptr, mb.stream.get());
+  else if (gru) gq_launch_policy_gru(mb.dev.get(), mb.gru.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   else gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
@@ -843,16 +880,23 @@ int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
                           const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_gru";
   if (!gru) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, gru, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, gru, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+}
+int gq_rollout_policy_scan(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves,
+                           double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
+                           float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
+  const char* const who = "gq_rollout_policy_scan";
+  if (!scan) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return rollout_policy(b, n_steps, mlp, gru, scan, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
 }
 int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                             const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                             void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
                         learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
 }
 int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
@@ -860,7 +904,7 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
                                  const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_learn_feet";
   if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
 /* gq_reward_eval (feet null) and gq_reward_eval_feet */
@@ -910,6 +954,19 @@ int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, in
   hipStream_t stream = (hipStream_t)hip_stream;
   HIP_TRY(b->mb.mlp.push(P, stream, true));
   gq_launch_policy_mlp_eval(b->mb.mlp.dev.get(), rows, n_rows, impl, out, stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_height_scan_eval(GqBatch* b, const GqPolicyScan* scan, const float* hits, const float* z, int n, float* out, void* hip_stream) {
+  const char* const who = "gq_height_scan_eval";
+  if (!fresh(scan, "GqPolicyScan", who)) return GQ_EINVAL;
+  if (!b || !hits || !z || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  gq::PolicyScanDev S{};
+  if (const int rc = scan_describe(nullptr, scan, S, who); rc != GQ_OK) return rc;
+  if (n == 0) return GQ_OK;
+  DeviceGuard guard(b->model->device);
+  gq_launch_height_scan_eval(&S.law, hits, z, n, S.cells, out, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

@@ -15,6 +15,7 @@
 #include "gq_policy_mlp.h"
 #include "gq_learn.h"
 #include "gq_policy_gru.h"
+#include "gq_policy_scan.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -182,10 +183,18 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * (gq_policy_gru.h), Pp points at the first member of a PolicyGruDev.  The episode rule runs for every ready lane before the tile loop; the
  * tile stage also loads each row's hidden state (device scope: the row is its env's lane's store of an earlier visit) - a row the rule
  * zeroed in THIS visit is staged as zeros from the lane's own flag, not from memory - and h' is stored by the env's own lane between the
- * cell and the head.  The flags come from the recurrent block: P.learn is not read in mode 4. */
+ * cell and the head.  The flags come from the recurrent block: P.learn is not read in mode 4.
+ * HEIGHT SCAN (MODE & 8, gq_rollout_policy_scan, with every mode above; MODE 0 .. 6 compile to the kernels they were): Pp points at the first
+ * member of a PolicyScanDev, and the input row has a middle block, columns in_obs .. in_obs + cells - 1: the scan law (gq_policy_scan.h) on
+ * word 2 of the env's hit points - the batch's base-following HeightMap, whose rays the env's stepping wavefront cast in the step whose
+ * observation row is being fed - and the z column of that row.  Both are device-scope loads.  The hit words are plain stores of the stepping
+ * wavefront, like the env's state rows: it waits for them (publish_fence, vmcnt(0)) before it raises steps_done, policy and stepping
+ * wavefront of an env share one XCD (gq_mailbox.h), so they are in that XCD's L2 when the count is seen and a load that misses the L1 reads
+ * them.  The last-action columns follow the scan; scan words are recorded in policy_obs like every other word the network is fed. */
 template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   constexpr bool GRU = (MODE & 4) != 0;
+  constexpr bool SCAN = (MODE & 8) != 0;
   constexpr int LMODE = MODE & 3;
   constexpr bool LEARN = LMODE != 0;
   __shared__ __attribute__((aligned(16))) float xt[GRU ? 3 : 2][GQ_MLP_MAXW * GQ_MLP_ROWS];
@@ -200,6 +209,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
   const int in_obs = P.in_obs, in_dim = GRU ? cell.in_dim : net.in_dim;
   const float* const shift = P.shift;
   const float* const scale = P.scale;
+  [[maybe_unused]] ScanLaw scan_law{};
+  [[maybe_unused]] int scan_cells = 0, scan_col_z = 0;
+  [[maybe_unused]] const float* scan_hits = nullptr;
+  if constexpr (SCAN) {
+    const GQ_MODEL PolicyScanDev& SD = *mptr(reinterpret_cast<const PolicyScanDev*>(Pp));
+    scan_law.offset = SD.law.offset; scan_law.clip = SD.law.clip; scan_law.scale = SD.law.scale;
+    scan_cells = SD.cells; scan_col_z = SD.col_z; scan_hits = SD.hits;
+  }
   const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int G = mine * GQ_WAVE;
   int32_t* const tail = mb_ctr(MB.q_ctr, q, MB_CTR_PUSH);
@@ -245,6 +262,12 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           float* const rec = mptr(P.learn)->learn.policy_obs;
           if (rec) rec_row = rec + ((size_t)(kr / D) * N + er) * in_dim;
         }
+        [[maybe_unused]] float z_base = 0.0f;       /* SCAN: the base's z of this lane's row, and the row's hit points */
+        [[maybe_unused]] const float* hit_row = nullptr;
+        if constexpr (SCAN) {
+          if (src >= 0) z_base = ld_pub(row + scan_col_z);
+          hit_row = scan_hits + (size_t)er * (size_t)scan_cells * 3;
+        }
         const auto x_value = [&](const int, const int c) {
           if (src < 0 || c >= in_dim) return 0.0f;
           const auto word = [&](const float* const p) { /* a device-scope load, recorded with LEARN */
@@ -255,6 +278,15 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
             return o;
           };
           if (c < in_obs) return mlp_obs_in(word(row + c), shift, scale, c);
+          if constexpr (SCAN) {
+            const int cell = c - in_obs;
+            if (cell >= scan_cells) return word(prev + (cell - scan_cells)); /* the last action, behind the scan */
+            const float s = height_scan_cell(scan_law, z_base, ld_pub(hit_row + 3 * cell + 2));
+            if constexpr (LEARN) {
+              if (rec_row) rec_row[c] = s;
+            }
+            return s;
+          }
           return word(prev + (c - in_obs));
         };
         const float* out;
@@ -446,6 +478,15 @@ __global__ void __launch_bounds__(GQ_WAVE) reward_eval_kernel(const LearnFeetDev
       for (int i = 0; i < 4; i++) air_out[(size_t)r * 4 + i] = t[i];
     }
   }
+}
+
+/* the scan law alone (gq_height_scan_eval), a thread per cell: hits [n][cells][3], z [n] -> out [n][cells]; height_scan_cell's bits, to be
+ * compared with the rollout's and the host's */
+__global__ void __launch_bounds__(GQ_WAVE) height_scan_eval_kernel(const ScanLaw law, const float* __restrict__ hits, const float* __restrict__ z, const long long total,
+                                                                   const int cells, float* __restrict__ out) {
+  const long long w = (long long)blockIdx.x * GQ_WAVE + threadIdx.x;
+  if (w >= total) return;
+  out[w] = height_scan_cell(law, z[w / cells], hits[w * 3 + 2]);
 }
 
 /* which XCDs does this device expose?  bit HW_REG_XCC_ID of *mask is set by every workgroup */
@@ -699,6 +740,18 @@ extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyG
   if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<6>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
   else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<5>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
   else hipLaunchKernelGGL(gq::policy_mlp_kernel<4>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+}
+/* gq_rollout_policy_scan: the instantiations with the height scan in the input row - mode as above, gru: the recurrent ones; scan->seat.mlp is
+ * the block the kernel's parameter points at */
+extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::PolicyScanDev* scan, const float* obs, int od, int waves, int mode, int gru, hipStream_t stream) {
+  const gq::PolicyMlpDev* const seat = &scan->seat.mlp; /* (address arithmetic on a device pointer: offset 0) */
+  const auto kernel = gru ? (mode == 2 ? gq::policy_mlp_kernel<14> : mode == 1 ? gq::policy_mlp_kernel<13> : gq::policy_mlp_kernel<12>)
+                          : (mode == 2 ? gq::policy_mlp_kernel<10> : mode == 1 ? gq::policy_mlp_kernel<9> : gq::policy_mlp_kernel<8>);
+  hipLaunchKernelGGL(kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+}
+extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream) {
+  const long long total = (long long)n * cells;
+  hipLaunchKernelGGL(gq::height_scan_eval_kernel, dim3((unsigned)((total + GQ_WAVE - 1) / GQ_WAVE)), dim3(GQ_WAVE), 0, stream, *law, hits, z, total, cells, out);
 }
 /* impl 0: gru_row_forward, a thread per row; 1: gru_tile_forward, a wavefront per 16 rows */
 extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {

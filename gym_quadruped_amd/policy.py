@@ -5,7 +5,9 @@ The law and the weight blob are defined in ``csrc/gq_policy_mlp.h``; this module
 restates the network in float64 for tests.
 
 ``GruPolicy`` is the recurrent form - one GRU cell and an MLP head, the hidden state on the device (``QuadrupedEnv.policy_hidden``) - defined
-in ``csrc/gq_policy_gru.h``."""
+in ``csrc/gq_policy_gru.h``.
+
+``HeightScan`` puts the env's base-following height map into either policy's input row (``csrc/gq_policy_scan.h``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -30,6 +32,73 @@ def elu64(x):
 _ACT64 = dict(none=lambda x: x, relu=lambda x: np.maximum(x, 0.0), elu=elu64, tanh=np.tanh)
 
 
+class HeightScan:
+    """A height scan in a policy's input row: the ``rows x cols`` cells of the env's ``HeightMap(rows, cols, ..., follow_base=True)``, in
+    the map's own cell order ``i * cols + j``, between the observation columns and the fed-back action::
+
+        x = [ obs_row[:in_obs] (shift / scale) | scan[0 : rows * cols] | last action (12, with feed_last_action) ]
+        scan_c = clamp((z_base - offset) - z_hit_c, -clip, +clip) * scale
+
+    in float32, every operation rounded (``csrc/gq_policy_scan.h``).  ``z_hit_c`` is the z of the cell's hit point (a ray that hits nothing
+    saturates at ``-clip``), ``z_base`` the base's z in the env's observation row (``base_pos`` or ``qpos`` must be observed; the column need
+    not be one the network reads).  ``obs_shift`` / ``obs_scale`` never act on scan columns: ``offset`` and ``scale`` are the scan's own."""
+
+    default_policy_waves = 256   # an MlpPolicy's rollout (profiles/height_scan_throughput.txt): 16 384 envs gain a quarter over 128, 4096 lose 1 %
+
+    def __init__(self, rows, cols, offset=0.0, clip=1.0, scale=1.0):
+        self.rows, self.cols = int(rows), int(cols)
+        if self.rows < 1 or self.cols < 1 or self.rows != rows or self.cols != cols:
+            raise ValueError(f'a height scan needs rows, cols >= 1, got {rows} x {cols}')
+        self.offset, self.clip, self.scale = float(offset), float(clip), float(scale)
+        if not all(np.isfinite(v) for v in (self.offset, self.clip, self.scale)):
+            raise ValueError(f'offset, clip and scale must be finite, got {offset}, {clip}, {scale}')
+        if not self.clip > 0.0:
+            raise ValueError(f'clip must be positive, got {clip}')
+
+    @property
+    def cells(self):
+        return self.rows * self.cols
+
+    def _struct(self):
+        import ctypes as C
+
+        from .cabi import GqPolicyScan
+        return GqPolicyScan(struct_size=C.sizeof(GqPolicyScan), rows=self.rows, cols=self.cols, offset=self.offset, clip=self.clip, scale=self.scale)
+
+
+def _scan_split(in_dim, feed_last_action, height_scan, what):
+    """in_obs of an input row of ``in_dim`` columns: what the scan and the fed-back action leave"""
+    if height_scan is not None and not isinstance(height_scan, HeightScan):
+        raise ValueError(f'height_scan must be a HeightScan, got {type(height_scan).__name__}')
+    cells = 0 if height_scan is None else height_scan.cells
+    in_obs = in_dim - cells - (N_ACTIONS if feed_last_action else 0)
+    if in_obs < 0 and not cells:
+        raise ValueError(f'feed_last_action needs at least {N_ACTIONS} inputs, {what} has {in_dim}')
+    if in_obs < 0:
+        raise ValueError(f'a height scan of {cells} cells{" and feed_last_action" if feed_last_action else ""} need at least {in_dim - in_obs} inputs, {what} has {in_dim}')
+    return in_obs
+
+
+def _device_tables(policy, device, rows_given):
+    """(blob, shift, scale, in_obs) of ``policy`` on ``device``.  rows_given (``policy_eval``: the rows are the full input rows and no scan block
+    travels with the call): a policy with a scan counts its scan columns as given columns - ``in_obs`` grows by them and the tables are
+    continued with shift 0 and scale 1, which leave every float32 as it is."""
+    import torch
+    key = str(device)
+    up = lambda v: None if v is None else torch.from_numpy(v).to(device)
+    if key not in policy._device:
+        policy._device[key] = (up(policy.pack()), up(policy.obs_shift), up(policy.obs_scale))
+    blob, shift, scale = policy._device[key]
+    cells = policy.height_scan.cells if rows_given and policy.height_scan is not None else 0
+    if not cells:
+        return blob, shift, scale, policy.in_obs
+    if key + ':rows' not in policy._device:
+        pad = lambda v, fill: None if v is None else up(np.concatenate([v, np.full(cells, fill, dtype=np.float32)]))
+        policy._device[key + ':rows'] = (pad(policy.obs_shift, 0.0), pad(policy.obs_scale, 1.0))
+    shift, scale = policy._device[key + ':rows']
+    return blob, shift, scale, policy.in_obs + cells
+
+
 class MlpPolicy:
     """An MLP with up to 4 linear layers (at most 3 hidden layers and the output layer), every width and the input width <= 256, 12 outputs
     (joint-target actions in the hinge order of ``qpos[7:]``), fp32 weights.
@@ -38,9 +107,10 @@ class MlpPolicy:
     array per layer.  activation: 'relu', 'elu' or 'tanh' between the layers; out_activation: None or 'tanh'.  obs_shift / obs_scale:
     optional per-column ``(o - shift) * scale`` on the observation columns the network reads.  feed_last_action: the env's previous
     policy action (12 values, zeros at the first policy step of a rollout call) follows the observation columns in the input row, so the
-    first layer has ``in_obs + 12`` inputs."""
+    first layer has ``in_obs + 12`` inputs.  height_scan: a ``HeightScan`` - its ``rows * cols`` columns stand between the observation columns
+    and the fed-back action, so ``in_obs = in_dim - rows * cols - 12 feed_last_action``; shift / scale keep covering the first ``in_obs``."""
 
-    def __init__(self, weights, biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None, feed_last_action=False):
+    def __init__(self, weights, biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None, feed_last_action=False, height_scan=None):
         self.weights = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         self.biases = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
         if not 1 <= len(self.weights) <= MAX_LAYERS:
@@ -63,9 +133,8 @@ class MlpPolicy:
         self.activation, self.out_activation = activation, out_activation or 'none'
         self.feed_last_action = bool(feed_last_action)
         self.in_dim = self.weights[0].shape[0]
-        self.in_obs = self.in_dim - (N_ACTIONS if self.feed_last_action else 0)
-        if self.in_obs < 0:
-            raise ValueError(f'feed_last_action needs at least {N_ACTIONS} inputs, the first layer has {self.in_dim}')
+        self.height_scan = height_scan
+        self.in_obs = _scan_split(self.in_dim, self.feed_last_action, height_scan, 'the first layer')
         self.widths = [w.shape[1] for w in self.weights]
 
         def col(v, name):
@@ -127,7 +196,8 @@ class MlpPolicy:
         return np.ascontiguousarray(np.concatenate(parts))
 
     def reference(self, x):
-        """float64 forward pass of the same network over rows ``[n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns)."""
+        """float64 forward pass of the same network over rows ``[n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns; scan
+        columns and the fed-back action are taken as given)."""
         h = np.array(x, dtype=np.float64).reshape(-1, self.in_dim)
         if self.obs_shift is not None:
             h[:, :self.in_obs] -= self.obs_shift.astype(np.float64)
@@ -139,18 +209,12 @@ class MlpPolicy:
         return h
 
     # -- the C struct's network part, with the blob on `device`
-    def _struct(self, device):
+    def _struct(self, device, rows_given=False):
         import ctypes as C
 
-        import torch
-
         from .cabi import GqPolicyMlp
-        key = str(device)
-        if key not in self._device:
-            up = lambda v: None if v is None else torch.from_numpy(v).to(device)
-            self._device[key] = (up(self.pack()), up(self.obs_shift), up(self.obs_scale))
-        blob, shift, scale = self._device[key]
-        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=self.in_obs, feed_last_action=int(self.feed_last_action),
+        blob, shift, scale, in_obs = _device_tables(self, device, rows_given)
+        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=in_obs, feed_last_action=int(self.feed_last_action),
                         activation=GQ_ACT[self.activation], out_activation=GQ_ACT[self.out_activation], decimation=1, blob=blob.data_ptr(),
                         blob_floats=blob.numel(), obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
         m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))
@@ -174,7 +238,8 @@ class GruPolicy:
 
     w_ih ``[in, 3H]``, w_hh ``[H, 3H]`` (``GRUCell.weight_ih`` / ``weight_hh`` are their transposes), b_ih, b_hh ``[3H]``; head_weights /
     head_biases: one ``[in, out]`` / ``[out]`` array per head layer (the first has ``H`` inputs, the last 12 outputs); activation /
-    out_activation, obs_shift / obs_scale, feed_last_action: as for ``MlpPolicy`` (they act on the head's layers and on the cell's input row).
+    out_activation, obs_shift / obs_scale, feed_last_action, height_scan: as for ``MlpPolicy`` (they act on the head's layers and on the cell's
+    input row).
 
     In ``rollout_policy`` the hidden state lives in ``env.policy_hidden`` ``[N, H]`` and follows THE EPISODE RULE: an env's row is zeroed at the
     policy seat's visit that sees its termination (or, at the first step of a call, that it waits for its re-spawn), before any cell
@@ -184,7 +249,7 @@ class GruPolicy:
     default_policy_waves = 128   # the sweep of profiles/gru_policy_throughput.txt: no count is best everywhere, 128 loses the least
 
     def __init__(self, w_ih, w_hh, b_ih, b_hh, head_weights, head_biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None,
-                 feed_last_action=False):
+                 feed_last_action=False, height_scan=None):
         f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
         self.w_ih, self.w_hh, self.b_ih, self.b_hh = f(w_ih), f(w_hh), f(b_ih).reshape(-1), f(b_hh).reshape(-1)
         if self.w_hh.ndim != 2 or self.w_hh.shape[1] != 3 * self.w_hh.shape[0]:
@@ -218,9 +283,8 @@ class GruPolicy:
             raise ValueError(f"out_activation must be None or 'tanh', got {out_activation!r}")
         self.activation, self.out_activation = activation, out_activation or 'none'
         self.feed_last_action = bool(feed_last_action)
-        self.in_obs = self.in_dim - (N_ACTIONS if self.feed_last_action else 0)
-        if self.in_obs < 0:
-            raise ValueError(f'feed_last_action needs at least {N_ACTIONS} inputs, the cell has {self.in_dim}')
+        self.height_scan = height_scan
+        self.in_obs = _scan_split(self.in_dim, self.feed_last_action, height_scan, 'the cell')
         self.widths = [w.shape[1] for w in self.head_weights]
         col = lambda v: None if v is None else np.array(np.broadcast_to(np.asarray(v, dtype=np.float32), (self.in_obs,)), dtype=np.float32)
         self.obs_shift, self.obs_scale = col(obs_shift), col(obs_scale)
@@ -289,18 +353,12 @@ class GruPolicy:
         return self.head.reference(hn), hn
 
     # -- the two C blocks, with the blob on `device`: (GqPolicyMlp - the loop, the input row, the head -, GqPolicyGru)
-    def _struct(self, device):
+    def _struct(self, device, rows_given=False):
         import ctypes as C
 
-        import torch
-
         from .cabi import GqPolicyGru, GqPolicyMlp
-        key = str(device)
-        if key not in self._device:
-            up = lambda v: None if v is None else torch.from_numpy(v).to(device)
-            self._device[key] = (up(self.pack()), up(self.obs_shift), up(self.obs_scale))
-        blob, shift, scale = self._device[key]
-        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=self.in_obs, feed_last_action=int(self.feed_last_action),
+        blob, shift, scale, in_obs = _device_tables(self, device, rows_given)
+        m = GqPolicyMlp(struct_size=C.sizeof(GqPolicyMlp), n_layers=len(self.widths), in_obs=in_obs, feed_last_action=int(self.feed_last_action),
                         activation=GQ_ACT[self.activation], out_activation=GQ_ACT[self.out_activation], decimation=1, blob=None, blob_floats=0,
                         obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
         m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))

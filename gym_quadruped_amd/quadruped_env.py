@@ -427,7 +427,7 @@ class QuadrupedEnv(AccessorsMixin):
         width = sum(int(v.shape[1]) for v in self._obs_views.values())
         if rollout and policy.in_obs > width:
             raise ValueError(f"the policy reads {policy.in_obs} observation columns, state_obs_names gives {width} (the accessors' extra columns are not fed to a policy)")
-        return policy._struct(self.device)
+        return policy._struct(self.device, rows_given=not rollout)   # (policy_eval: the rows are the full input rows, a scan's columns among them)
 
     def _hidden_for(self, policy):
         """``policy_hidden`` for a ``GruPolicy``: zeros on first use, refused when it was sized for another ``H``"""
@@ -494,7 +494,14 @@ class QuadrupedEnv(AccessorsMixin):
         rule of ``csrc/gq_policy_gru.h`` - the policy seat zeroes an env's row at the visit that sees its termination (at the first step of
         a call: that the env waits for its re-spawn), before any cell evaluation, so the state fed at policy step ``s + 1`` is zero exactly
         where ``dones[s]`` is set, the mask ``h <- (1 - done) h`` of a recurrent learner.  With ``record_transitions`` the dict gains
-        'policy_hidden' ``[K // D, N, H]``: the state FED at each policy step, after the rule.  ``policy_waves=0``: the policy's default."""
+        'policy_hidden' ``[K // D, N, H]``: the state FED at each policy step, after the rule.  ``policy_waves=0``: the policy's default.
+
+        A HEIGHT SCAN (a policy built with ``height_scan=HeightScan(rows, cols, ...)``, every mode above; ``gq_rollout_policy_scan``): the env
+        must hold a ``HeightMap(rows, cols, ..., follow_base=True)``; its cells, through the scan law of ``csrc/gq_policy_scan.h``, are the
+        columns between the observation columns and the fed-back action.  The stepping wavefront casts the map's rays at every step, so the
+        scan fed at a policy step is that of the state the observation row fed with it describes - across a re-spawn too.  Before the launch
+        the map is brought up to date (``update_height_map()``: nothing when the last step left it, one ray launch after a reset or a state
+        write).  'policy_obs' records the scan words as fed; ``env.height_scan`` evaluates the same law on any hits."""
         from .policy import GruPolicy
         recurrent = isinstance(policy, GruPolicy)
         K, D = int(n_steps), int(decimation)
@@ -509,6 +516,12 @@ class QuadrupedEnv(AccessorsMixin):
             m, gr = m
             gr.hidden_state = self._hidden_for(policy).data_ptr()
             policy_waves = int(policy_waves) or policy.default_policy_waves
+        scan = getattr(policy, 'height_scan', None)
+        if scan is not None:
+            sc = scan._struct()
+            self._scan_map(scan).update_height_map()   # the hits at policy step 0 belong to the state the env now holds
+            if not recurrent:   # (a GruPolicy keeps its own default)
+                policy_waves = int(policy_waves) or scan.default_policy_waves
         row12 = lambda v: (C.c_float * 12)(*np.broadcast_to(np.asarray(v, dtype=np.float32), (12,)))
         m.kp, m.kd, m.action_scale, m.noise_sigma = row12(kp), row12(kd), row12(action_scale), row12(noise_sigma)
         m.q_default = row12(self._key_qpos[7:19].float().cpu().numpy() if q_default is None else np.asarray(q_default, dtype=np.float32).reshape(12))
@@ -543,7 +556,11 @@ class QuadrupedEnv(AccessorsMixin):
         self._hm_fresh = False
         args = (self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
                 self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq))
-        if recurrent:   # one entry point, the modes selected by the blocks given
+        if scan is not None:   # one entry point: the network, the modes and the scan selected by the blocks given
+            gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
+            _lib.check(self._L.gq_rollout_policy_scan(*args[:3], C.byref(gr) if recurrent else None, C.byref(sc), *args[3:], C.byref(g) if learning else None,
+                                                      None if gf is None else C.byref(gf), stream), 'gq_rollout_policy_scan')
+        elif recurrent:   # one entry point, the modes selected by the blocks given
             gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
             _lib.check(self._L.gq_rollout_policy_gru(*args[:3], C.byref(gr), *args[3:], C.byref(g) if learning else None, None if gf is None else C.byref(gf), stream),
                        'gq_rollout_policy_gru')
@@ -554,6 +571,8 @@ class QuadrupedEnv(AccessorsMixin):
             _lib.check(self._L.gq_rollout_policy_learn(*args, C.byref(g), stream), 'gq_rollout_policy_learn')
         else:
             _lib.check(self._L.gq_rollout_policy(*args, stream), 'gq_rollout_policy')
+        if scan is not None and K > 0:   # every env's last step cast its rays: the map holds those of the state the call leaves, as after step()
+            self._hm_fresh, self._hm_version = True, self._qpos._version
         self._launches += K
         if check:
             self.closed_loop_status()
@@ -606,6 +625,48 @@ class QuadrupedEnv(AccessorsMixin):
             return out if air is None else (out, air_next)
         _lib.check(self._L.gq_reward_eval(self._hbatch, C.byref(g), rows.data_ptr(), ptr(u), ptr(a), ptr(ap), ptr(term), n, out.data_ptr(), stream), 'gq_reward_eval')
         return out if air is None else (out, air.clone())
+
+    def _scan_map(self, scan):
+        """the env's ``HeightMap(follow_base=True)`` for ``scan`` (a ``policy.HeightScan``): there, and of the scan's grid"""
+        hm = self._hm_follow() if self._hm_follow is not None else None
+        if hm is None:
+            raise ValueError('a height scan reads the env\'s base-following height map: build HeightMap(rows, cols, dist_x, dist_y, env.mjModel, env, '
+                             'follow_base=True) first (scenes with world boxes or a height field)')
+        if (hm.num_rows, hm.num_cols) != (scan.rows, scan.cols):
+            raise ValueError(f'the height scan is {scan.rows} x {scan.cols}, the env\'s base-following height map {hm.num_rows} x {hm.num_cols}')
+        return hm
+
+    def height_scan(self, spec, hits=None, z=None):
+        """The scan law of ``spec`` (a ``policy.HeightScan``) alone (``gq_height_scan_eval``; the same routine, hence the same bits, as inside
+        ``rollout_policy``): hits ``[n, rows, cols, 1, 3]`` or ``[n, rows * cols, 3]`` float32 hit points, z ``[n]`` float32, the base's z of
+        each row -> ``[n, rows * cols]`` float32.  Defaults: the env's ``HeightMap(follow_base=True)``, brought up to date, and the base's z
+        of the current observation row (``base_pos`` or ``qpos`` must be observed) - what a rollout started now feeds at its first policy
+        step.  For a critic's input, or a torch-side loop."""
+        from .policy import HeightScan
+        if not isinstance(spec, HeightScan):
+            raise ValueError(f'spec must be a HeightScan, got {type(spec).__name__}')
+        if hits is None:
+            hits = self._scan_map(spec).update_height_map()
+        if not torch.is_tensor(hits) or hits.dtype != torch.float32 or hits.device != self.device or hits.dim() < 2 or hits.shape[-1] != 3 or \
+                hits.numel() != hits.shape[0] * spec.cells * 3:
+            raise ValueError(f'hits must be a float32 tensor of shape (n, {spec.rows}, {spec.cols}, 1, 3) or (n, {spec.cells}, 3) on {self.device}')
+        n = int(hits.shape[0])
+        if z is None:
+            if n != self.num_envs:
+                raise ValueError(f'z defaults to the env\'s own rows: hits must have {self.num_envs} rows, got {n}')
+            views = {**self._extra_views, **self._obs_views}   # the library looks through the whole row: base_pos first, then qpos
+            view = views.get('base_pos', views.get('qpos'))
+            if view is None:
+                raise ValueError('the height scan reads the base\'s z from base_pos (or qpos): not in the env\'s observation row')
+            z = view[:, 2]
+        if not torch.is_tensor(z) or z.dtype != torch.float32 or z.device != self.device or tuple(z.shape) != (n,):
+            raise ValueError(f'z must be a float32 tensor of shape ({n},) on {self.device}')
+        hits, z = hits.contiguous(), z.contiguous()
+        out = torch.empty(n, spec.cells, dtype=torch.float32, device=self.device)
+        sc = spec._struct()
+        _lib.check(self._L.gq_height_scan_eval(self._hbatch, C.byref(sc), hits.data_ptr(), z.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                   'gq_height_scan_eval')
+        return out
 
     def policy_eval(self, policy, rows, impl: str = 'tile', hidden=None):
         """The network of ``policy`` alone over ``rows`` (``[n, policy.in_dim]`` float32 on the env's device; shift / scale applied to

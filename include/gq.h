@@ -637,6 +637,32 @@ int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
  * [n_rows][hidden] (not h_in).  impl 0: the plain loops, a thread per row; 1: the matrix-core form, a wavefront per 16 rows; the same bits. */
 int gq_policy_gru_eval(GqBatch* b, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const float* rows, const float* h_in, int n_rows, int impl, float* out, float* h_out,
                        void* hip_stream);
+/* A HEIGHT SCAN in the policy's input row (additive: the entry points above are what they were): the hit points of the batch's base-following
+ * HeightMap (gq_batch_set_heightmap: the stepping wavefront casts the rays at every step) become a third block of the row,
+ *   x = [(obs[:, :in_obs] - obs_shift) * obs_scale, scan[0 : rows * cols], a_prev]      in_dim = in_obs + rows * cols + 12 feed_last_action <= 256
+ *   scan_c = clamp((z_base - offset) - z_hit_c, -clip, +clip) * scale                   (csrc/gq_policy_scan.h is the definition: fp32, contraction off,
+ * two subtractions in that order, fmaxf, fminf, one multiply), c = i * cols + j in the map's own cell order; z_hit_c is word 2 of the cell's hit
+ * point (a ray that hits nothing lands 1 m above its origin: -clip); z_base is the z column of the env's observation row - base_pos, failing that
+ * qpos - which may lie beyond in_obs.  obs_shift / obs_scale cover the first in_obs columns only.  mlp->blob (gru->blob) is the network whose
+ * first layer (cell) has in_dim inputs.  The scan fed at a policy step is that of the state the observation row fed with it describes, also
+ * across a re-spawn: every pass that advances an env casts its rays.  The CALLER makes the map hold the rays of the state the batch is in before
+ * the call (gq_heightmap_strided into the registered tensor after a reset or a state write; a step leaves it current).  GqLearn.policy_obs records
+ * the scan words like every other word of the row.
+ * gru: NULL for the MLP, else the recurrent policy's block; learn / feet: NULL, or the blocks of gq_rollout_policy_learn / _learn_feet.
+ * Refused with a message, the batch stays usable: a stale struct_size, no base-following map set on the batch (a flat scene has none:
+ * gq_batch_set_heightmap refuses there), a map whose rows x cols differ from the scan's, no base_pos and no qpos in the observation row, a
+ * non-finite offset / clip / scale or clip <= 0, an in_dim beyond 256, and everything gq_rollout_policy / gq_rollout_policy_gru refuse. */
+typedef struct GqPolicyScan {
+  int32_t struct_size;        /* sizeof(GqPolicyScan): a stale binding is refused */
+  int32_t rows, cols;         /* the grid of the batch's base-following map */
+  float offset, clip, scale;  /* finite; clip > 0 */
+} GqPolicyScan;
+int gq_rollout_policy_scan(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves,
+                           double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
+                           float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream);
+/* the scan law alone: hits: device [n][rows * cols][3], z: device [n] (the base's z of each row) -> out: device [n][rows * cols].  The same
+ * routine, the same bits, as inside the rollout; no map needs to be set on the batch. */
+int gq_height_scan_eval(GqBatch* b, const GqPolicyScan* scan, const float* hits, const float* z, int n, float* out, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

@@ -1,0 +1,366 @@
+"""GPU tests of the height scan in the in-loop policy's input row (include/gq.h gq_rollout_policy_scan / gq_height_scan_eval,
+QuadrupedEnv.rollout_policy(policy with height_scan=) / height_scan, csrc/gq_policy_scan.h), aliengo on the non-flat scenes:
+
+* env.height_scan is the numpy float32 law on the map's hit points and the row's z, bit for bit, on grids of one cell, odd and even sides and
+  more cells than a wavefront has lanes;
+* the rows the network is fed are cat(observation columns, scan, previous action) rebuilt from the replayed step loop - the scan of the SAME
+  state as the observation row, at every policy step, also after a termination;
+* the recorded torques replayed through `step` leave the same state, flags, rows and the same map;
+* the recurrent and the learning modes are what they were with the scan in the row; the widest input row;
+* the map is refreshed before the launch after a state write or a reset; refusals; a policy without a scan is the call it was.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import foot_reward_ref as F
+import height_scan_ref as H
+from learn_windows import _bits, _replay_flags, _same
+from test_gpu_closed_loop import STATE, _env, _twin
+from test_gpu_foot_reward import CMD, _spec, _windows
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+OBS = F.OBS_NAMES            # qpos_js, qvel_js, base_pos, ...: 70 columns
+ZCOL = 26                    # base_pos z: beyond the 24 columns the test policies read
+IN_OBS = 24
+KP, KD, SCALE = 25.0, 0.8, 0.25
+SIGMA = 2.0                  # exploration noise large enough that robots fall inside the windows (tests/test_gpu_foot_reward.py)
+DIST = 0.1                   # cell pitch of the maps, m
+
+
+def _map(env, rows, cols):
+    from gym_quadruped_amd.sensors import HeightMap
+    return HeightMap(rows, cols, DIST, DIST, env.mjModel, env, follow_base=True)   # (the env holds a weak reference: the caller keeps the map)
+
+
+def _scan_twin(n, scene, rows, cols, warm=60, **kw):
+    kw.setdefault('state_obs_names', OBS)
+    a, b = _twin('aliengo', n, scene, warm=warm, **kw)
+    return a, b, _map(a, rows, cols), _map(b, rows, cols)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _replay(a, hm_a, b, r, K):
+    """the recorded torques through `step` on the twin: rows, `terminated` and the twin's map after every step; states, rows and the map end
+    bit-equal"""
+    maps = []
+    rows, term = [], []
+    for k in range(K):
+        a.step(r['actions'][k])
+        rows.append(a._obs_buf.clone()); term.append(a._terminated.clone()); maps.append(hm_a.sensor_data_matrix.clone())
+    torch.cuda.synchronize()
+    for f in STATE:
+        assert torch.equal(getattr(a, f), getattr(b, f)), f
+    rows = torch.stack(rows)
+    assert torch.equal(rows, r['obs_seq'])
+    return rows, torch.stack(term).bool(), maps
+
+
+def _fed_rows(env, p, r, before, hits0, rows, maps, D):
+    """cat(observation columns, scan, previous action) of every policy step from the replayed loop; checked against policy_obs"""
+    spec, xs = p.height_scan, []
+    for s in range(r['policy_obs'].shape[0]):
+        row = before if s == 0 else rows[D * s - 1]
+        hits = hits0 if s == 0 else maps[D * s - 1]
+        z = row[:, ZCOL].contiguous()
+        scan = env.height_scan(spec, hits=hits, z=z)
+        want = H.scan_of(spec, _np(hits), _np(z))
+        assert np.array_equal(_bits(_np(scan)), _bits(want)), s          # the device's law is the numpy float32 law
+        parts = [row[:, :p.in_obs], scan]
+        if p.feed_last_action:
+            parts.append(torch.zeros(row.shape[0], 12, device=DEV) if s == 0 else r['policy_actions'][s - 1])
+        x = torch.cat(parts, dim=1)
+        assert x.shape[1] == p.in_dim
+        assert _same(r['policy_obs'][s], x), (s, int((_bits(r['policy_obs'][s]) != _bits(x)).sum()))
+        xs.append(x)
+    return xs
+
+
+@pytest.mark.parametrize('scene', ['perlin', 'random_boxes'])
+@pytest.mark.parametrize('rows,cols', [(1, 1), (3, 5), (4, 4), (9, 8)])
+def test_height_scan_is_the_numpy_law_on_the_maps_hits(scene, rows, cols):
+    from gym_quadruped_amd.policy import HeightScan
+    n = 96
+    env = _env('aliengo', n, scene, seed=5, state_obs_names=OBS)
+    hm = _map(env, rows, cols)
+    env.reset(random=True)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for _ in range(25):   # bases at different heights and headings, some robots down
+        env.step(torch.randn(n, 12, generator=g, device=DEV) * 40)
+    # clip: a few centimetres - floor cells under a standing base saturate at +clip, cells on a box or a miss at -clip, and the bases that sag or
+    # fall pass through the band in between
+    spec = HeightScan(rows, cols, offset=0.3, clip=0.05, scale=4.0)
+    assert env._hm_fresh, 'the last step wrote the map: the defaults need no ray launch'
+    s = env.height_scan(spec)
+    assert s.shape == (n, rows * cols) and s.dtype == torch.float32
+    hits, z = hm.update_height_map(), env._obs_buf[:, ZCOL]
+    want = H.scan_of(spec, _np(hits), _np(z))
+    assert np.array_equal(_bits(_np(s)), _bits(want))
+    assert _same(env.height_scan(spec, hits=hits.reshape(n, rows * cols, 3), z=z.contiguous()), s), 'the explicit arguments are the defaults'
+    top = np.float32(spec.clip) * np.float32(spec.scale)
+    hi, lo, mid = int((want == top).sum()), int((want == -top).sum()), int((np.abs(want) < top).sum())
+    print(f'{scene} {rows} x {cols}: cells at +clip {hi}, at -clip {lo}, inside {mid} of {want.size}; z_hit in [{float(hits[..., 2].min()):.3f}, {float(hits[..., 2].max()):.3f}]')
+    assert hi + lo + mid == want.size
+    if scene == 'random_boxes' and rows * cols > 1:
+        assert hi > 0 and lo > 0 and mid > 0, 'both saturated signs and unsaturated cells'
+    # another law on the same hits; a scale of zero
+    other = HeightScan(rows, cols, offset=-0.1, clip=2.0, scale=-1.5)
+    assert np.array_equal(_bits(_np(env.height_scan(other))), _bits(H.scan_of(other, _np(hits), _np(z))))
+    assert not env.height_scan(HeightScan(rows, cols, scale=0.0)).any()
+
+
+def test_fed_rows_are_the_scan_of_the_state_the_observation_row_describes():
+    from gym_quadruped_amd.policy import HeightScan
+    from gym_quadruped_amd.reward import RewardSpec
+    n, K, D = 256, 24, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5)
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1, scale=5.0)
+    p = H.make_mlp(IN_OBS, spec)
+    seen = dict(done=0, done_before_last=0, pending=[])
+    for call in range(2):   # the second call starts from the map the first one's last steps left
+        before, pending = b._obs_buf.clone(), b._terminated.clone().bool()
+        hits0 = hm_a.update_height_map().clone()     # the twin is in the same state: its rays, cast apart from the rollout
+        r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True,
+                             reward=RewardSpec(alive=1.0, termination=-1.0))
+        code, _, played = b.closed_loop_status()
+        assert code == 0 and played == n * K
+        rows, term, maps = _replay(a, hm_a, b, r, K)
+        assert torch.equal(hm_b.sensor_data_matrix, hm_a.sensor_data_matrix), 'the map after the rollout is the replay\'s'
+        xs = _fed_rows(b, p, r, before, hits0, rows, maps, D)
+        for s, x in enumerate(xs):
+            assert _same(r['policy_means'][s], b.policy_eval(p, x)), s
+        win = term.view(K // D, D, n).any(dim=1)
+        assert torch.equal(r['dones'], win)
+        # (windows before the last one with a termination: the policy step after them feeds row and scan of the re-spawned env - checked above
+        # like every other step)
+        seen['done'] += int(win.sum()); seen['done_before_last'] += int(win[:-1].sum()); seen['pending'].append(int(pending.sum()))
+        assert b._hm_fresh, 'the rollout leaves the map current, as a step does'
+    print(f'windows with a termination {seen["done"]}, of them followed by a policy step {seen["done_before_last"]}, pending before the calls {seen["pending"]}')
+    assert seen['done'] > 0 and seen['done_before_last'] > 0, 'the workload must contain a termination followed by a policy step'
+    assert float(r['policy_obs'][:, :, IN_OBS:IN_OBS + 15].abs().max()) > 0
+
+
+@pytest.mark.parametrize('D,K', [(1, 8), (4, 12)])
+@pytest.mark.parametrize('n', [1, 7, 70, 131])
+def test_replay_leaves_the_same_state_rows_and_map(n, D, K):
+    from gym_quadruped_amd.policy import HeightScan
+    a, b, hm_a, hm_b = _scan_twin(n, 'random_boxes', 4, 4)
+    spec = HeightScan(4, 4, offset=0.3, clip=0.05, scale=2.0)
+    p = H.make_mlp(IN_OBS, spec, feed_last_action=(D == 4))
+    before = b._obs_buf.clone()
+    hits0 = hm_a.update_height_map().clone()
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True)
+    code, _, played = b.closed_loop_status()
+    assert code == 0 and played == n * K
+    assert set(r) == {'obs', 'obs_seq', 'actions', 'policy_actions', 'policy_obs', 'policy_means'}
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    assert torch.equal(hm_b.sensor_data_matrix, hm_a.sensor_data_matrix)
+    _fed_rows(b, p, r, before, hits0, rows, maps, D)
+    # and the batch is an ordinary batch afterwards
+    act = torch.randn(n, 12, device=DEV) * 20
+    a.step(act); b.step(act)
+    assert torch.equal(a._qpos, b._qpos) and torch.equal(a._obs_buf, b._obs_buf) and torch.equal(hm_b.sensor_data_matrix, hm_a.sensor_data_matrix)
+
+
+def test_recurrent_policy_with_a_scan_keeps_the_episode_rule():
+    from gym_quadruped_amd.policy import HeightScan
+    from gym_quadruped_amd.reward import RewardSpec
+    n, K, D = 200, 16, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5)
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1)
+    p = H.make_gru(IN_OBS, spec)
+    Hd = p.hidden
+    b.policy_hidden = torch.rand(n, Hd, generator=torch.Generator(device=DEV).manual_seed(4), device=DEV) * 2 - 1
+    before, pending, h0 = b._obs_buf.clone(), b._terminated.clone().bool(), b.policy_hidden.clone()
+    hits0 = hm_a.update_height_map().clone()
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True,
+                         reward=RewardSpec(alive=1.0, termination=-1.0))
+    code, _, played = b.closed_loop_status()
+    assert code == 0 and played == n * K
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    xs = _fed_rows(b, p, r, before, hits0, rows, maps, D)
+    zero = torch.zeros(n, Hd, device=DEV)
+    fed = torch.where(pending[:, None], zero, h0)
+    assert torch.equal(r['dones'], term.view(K // D, D, n).any(dim=1)) and bool(r['dones'][:-1].any())
+    for s, x in enumerate(xs):
+        assert _same(r['policy_hidden'][s], fed), s                    # the state the rule leaves: zero exactly where dones[s - 1]
+        act, hn = b.policy_eval(p, x, hidden=fed)
+        assert _same(r['policy_means'][s], act), s
+        fed = torch.where(r['dones'][s][:, None], zero, hn)
+    assert _same(b.policy_hidden, fed)
+
+
+def test_learning_rollout_with_foot_terms_and_a_scan_equals_the_replayed_loop():
+    from gym_quadruped_amd.policy import HeightScan
+    n, K, D = 131, 24, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5, **CMD)
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1)
+    p = H.make_mlp(IN_OBS, spec)
+    reward = _spec()
+    b.feet_air_time = torch.rand(n, 4, device=DEV) * 0.05
+    pending, air, before = b._terminated.clone().bool(), b.feet_air_time.clone(), b._obs_buf.clone()
+    hits0 = hm_a.update_height_map().clone()
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True, reward=reward)
+    code, _, played = b.closed_loop_status()
+    assert code == 0 and played == n * K
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    _fed_rows(b, p, r, before, hits0, rows, maps, D)
+    want_r, want_d, want_air, _ = _windows(b, reward, rows, term, r['actions'], r['policy_actions'], pending, D, air)
+    assert torch.equal(r['dones'], want_d) and _same(r['rewards'], want_r) and _same(b.feet_air_time, want_air)
+    assert torch.isfinite(r['rewards']).all() and bool(r['dones'].any())
+
+
+def test_the_widest_input_row():
+    from gym_quadruped_amd.policy import HeightScan
+    n, K, D = 70, 8, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 11, 17)
+    spec = HeightScan(11, 17, offset=0.3, clip=0.2, scale=2.0)
+    p = H.make_mlp(57, spec, hidden=(64,))
+    assert p.in_dim == 256 and p.in_obs == 57 and ZCOL < p.in_obs, 'here the z column is one the network reads too'
+    before = b._obs_buf.clone()
+    hits0 = hm_a.update_height_map().clone()
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, record_obs=True, record_actions=True, record_transitions=True)
+    assert b.closed_loop_status()[2] == n * K
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    xs = _fed_rows(b, p, r, before, hits0, rows, maps, D)
+    for s, x in enumerate(xs):
+        assert _same(r['policy_means'][s], b.policy_eval(p, x)), s
+
+
+@pytest.mark.parametrize('how', ['state_write', 'reset'])
+def test_the_map_is_refreshed_before_the_launch(how):
+    from gym_quadruped_amd.policy import HeightScan
+    n, K, D = 64, 4, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5, warm=10)
+    spec = HeightScan(3, 5, offset=0.3, clip=0.5)
+    p = H.make_mlp(IN_OBS, spec)
+    act = torch.randn(n, 12, device=DEV) * 20
+    a.step(act); b.step(act)                    # both maps hold the rays of this state
+    old = hm_b.update_height_map().clone()
+    assert torch.equal(old, hm_a.update_height_map())
+    if how == 'state_write':
+        for e in (a, b):
+            e.qpos[:, 0] += 0.5                 # half a metre along x, over other ground; the observation row is not recomputed
+    else:
+        a.reset(random=True); b.reset(random=True)
+    before = b._obs_buf.clone()
+    assert torch.equal(before, a._obs_buf) and torch.equal(a.qpos, b.qpos)
+    hits0 = hm_a.update_height_map().clone()    # the twin's rays for the state both envs now hold
+    assert not torch.equal(hits0[..., 2], old[..., 2])
+    if how == 'state_write':   # (a reset's own forward pass casts rays, but leaves the env's map marked stale: both ways the launch must refresh it)
+        assert torch.equal(hm_b.sensor_data_matrix, old), 'b still holds the stale map'
+    assert not b._hm_fresh or b._hm_version != b._qpos._version
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, record_obs=True, record_actions=True, record_transitions=True)
+    assert b.closed_loop_status()[2] == n * K
+    fed = r['policy_obs'][0][:, IN_OBS:IN_OBS + 15]
+    z = before[:, ZCOL].contiguous()
+    assert _same(fed, b.height_scan(spec, hits=hits0, z=z))
+    assert not _same(fed, b.height_scan(spec, hits=old, z=z)), 'the stale map would have been seen'
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    _fed_rows(b, p, r, before, hits0, rows, maps, D)
+
+
+def _raw(env, m, sc, gr=None, K=4):
+    from gym_quadruped_amd import _lib
+    stream = torch.cuda.current_stream(env.device).cuda_stream
+    _lib.check(env._L.gq_rollout_policy_scan(env._hbatch, K, C.byref(m), None if gr is None else C.byref(gr), C.byref(sc), 0, 0, 5.0, env._st, env._out, env._auto_cfg,
+                                             env._episode.data_ptr(), env._lift_failed.data_ptr(), None, None, None, None, stream), 'gq_rollout_policy_scan')
+
+
+def test_what_cannot_be_done_is_refused_and_the_batch_stays_usable():
+    from gym_quadruped_amd import _lib
+    from gym_quadruped_amd.policy import HeightScan
+    n = 64
+    a, env, hm_a, hm = _scan_twin(n, 'perlin', 3, 5, warm=5)
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1)
+    p = H.make_mlp(IN_OBS, spec)
+
+    def blocks(mk=None, sk=None):
+        m, sc = env._policy_struct(p), spec._struct()
+        m.decimation = 4
+        for k, v in (mk or {}).items():
+            setattr(m, k, v)
+        for k, v in (sk or {}).items():
+            setattr(sc, k, v)
+        return m, sc
+    for mk, sk, msg in ((None, dict(struct_size=16), 'GqPolicyScan.struct_size.*stale binding'), (None, dict(rows=5, cols=3), '5 x 3.*3 x 5'), (None, dict(cols=4), '3 x 4'),
+                        (None, dict(clip=0.0), 'clip'), (None, dict(clip=-1.0), 'clip'), (None, dict(clip=float('nan')), 'finite'), (None, dict(offset=float('inf')), 'finite'),
+                        (None, dict(scale=float('-inf')), 'finite'), (dict(in_obs=60), None, 'blob_floats'), (dict(in_obs=env._obs_dim + 1), None, 'in_obs')):
+        with pytest.raises(_lib.GqError, match=msg):
+            _raw(env, *blocks(mk, sk))
+    # an input row that does not fit: 11 x 17 cells, 60 observation columns and the last action are 259 columns
+    wide_env = _env('aliengo', 8, 'perlin', seed=2, state_obs_names=OBS)
+    wide_map = _map(wide_env, 11, 17)
+    wide_env.reset(random=True)
+    wide = HeightScan(11, 17)
+    m = wide_env._policy_struct(H.make_mlp(57, wide, hidden=(8,)))
+    m.decimation, m.in_obs = 4, 60
+    with pytest.raises(_lib.GqError, match='259 columns'):
+        _raw(wide_env, m, wide._struct())
+    # a grid other than the env's map, from the Python side
+    with pytest.raises(ValueError, match='4 x 4'):
+        env.rollout_policy(4, H.make_mlp(IN_OBS, HeightScan(4, 4)), KP, KD)
+    # no base-following map on the batch
+    bare = _env('aliengo', 8, 'perlin', seed=2, state_obs_names=OBS)
+    bare.reset(random=True)
+    with pytest.raises(ValueError, match='follow_base'):
+        bare.rollout_policy(4, p, KP, KD)
+    with pytest.raises(ValueError, match='follow_base'):
+        bare.height_scan(spec)
+    with pytest.raises(_lib.GqError, match='none is set'):
+        _raw(bare, bare._policy_struct(p), spec._struct())
+    # a flat scene has none: gq_batch_set_heightmap refuses there
+    flat = _env('aliengo', 8, 'flat', seed=2, state_obs_names=OBS)
+    flat.reset(random=True)
+    with pytest.raises(_lib.GqError, match='gq_batch_set_heightmap'):
+        _map(flat, 3, 5)
+    with pytest.raises(_lib.GqError, match='none is set'):
+        _raw(flat, flat._policy_struct(p), spec._struct())
+    # neither base_pos nor qpos in the observation row
+    blind = _env('aliengo', 8, 'perlin', seed=2)   # qpos_js, qvel_js, base_lin_vel, contact_forces
+    blind_map = _map(blind, 3, 5)
+    blind.reset(random=True)
+    with pytest.raises(_lib.GqError, match='base_pos'):
+        blind.rollout_policy(4, p, KP, KD)
+    with pytest.raises(ValueError, match='base_pos'):
+        blind.height_scan(spec)
+    # every one of these batches steps afterwards; the twin still agrees, and the scan rollout works
+    for e in (wide_env, bare, flat, blind):
+        e.step(torch.zeros(e.num_envs, 12, device=DEV))
+        assert torch.isfinite(e.qpos).all()
+    act = torch.randn(n, 12, device=DEV) * 20
+    a.step(act); env.step(act)
+    assert torch.equal(a._qpos, env._qpos) and torch.equal(a._obs_buf, env._obs_buf)
+    before, hits0 = env._obs_buf.clone(), hm_a.update_height_map().clone()
+    r = env.rollout_policy(8, p, KP, KD, record_obs=True, record_actions=True, record_transitions=True)
+    assert env.closed_loop_status()[2] == n * 8
+    rows, term, maps = _replay(a, hm_a, env, r, 8)
+    _fed_rows(env, p, r, before, hits0, rows, maps, 4)
+
+
+def test_a_policy_without_a_scan_is_the_call_it_was():
+    n, K, D = 131, 12, 4
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5)
+    p = H.make_mlp(IN_OBS, None)
+    assert p.height_scan is None and p.in_dim == IN_OBS + 12
+    before = b._obs_buf.clone()
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True)
+    assert b.closed_loop_status()[2] == n * K
+    assert set(r) == {'obs', 'obs_seq', 'actions', 'policy_actions', 'policy_obs', 'policy_means'} and not b._hm_fresh
+    rows, term = _replay_flags(a, b, r, K, STATE)    # the existing replay test's method: state, flags and rows equal the step loop's
+    for s in range(K // D):
+        row = before if s == 0 else rows[D * s - 1]
+        prev = torch.zeros(n, 12, device=DEV) if s == 0 else r['policy_actions'][s - 1]
+        x = torch.cat([row[:, :IN_OBS], prev], dim=1)
+        assert _same(r['policy_obs'][s], x) and _same(r['policy_means'][s], b.policy_eval(p, x)), s
+    # the stepping side casts the registered map's rays in a scan-less rollout as it always did
+    assert torch.equal(hm_b.sensor_data_matrix, hm_a.sensor_data_matrix)
+    r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, record_obs=True, record_actions=True)
+    assert set(r) == {'obs', 'obs_seq', 'actions', 'policy_actions'}
+    _replay_flags(a, b, r, K, STATE)
