@@ -159,6 +159,13 @@ class GqPolicyScan(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32), ('offset', C.c_float), ('clip', C.c_float), ('scale', C.c_float)]
 
 
+class GqPolicyHist(C.Structure):
+    """gq_rollout_policy_hist's block: the observation history of an MLP policy (``csrc/gq_policy_hist.h``) - ``frames`` frames of ``cols``
+    observation words (and the fed-back action), the first layer's ``in_dim``, and the caller's state: ``state`` ``[N][2][frames][F]`` floats,
+    ``ctl`` ``[N]`` int32 control words; ``struct_size`` must hold ``sizeof(GqPolicyHist)``."""
+    _fields_ = [('struct_size', C.c_int32), ('frames', C.c_int32), ('cols', C.c_int32), ('in_dim', C.c_int32), ('state', C.c_void_p), ('ctl', C.c_void_p)]
+
+
 class GqLearn(C.Structure):
     """gq_rollout_policy_learn's / gq_reward_eval's block: the reward weights in the order of the law's sum, and the rollout's output
     pointers; ``struct_size`` must hold ``sizeof(GqLearn)`` (the library refuses a stale layout)."""

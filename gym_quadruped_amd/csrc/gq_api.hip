@@ -24,6 +24,7 @@
 #include "gq_policy_mlp.h"
 #include "gq_policy_gru.h"
 #include "gq_policy_scan.h"
+#include "gq_policy_hist.h"
 #include "gq_learn.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
@@ -50,6 +51,7 @@ extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const flo
 extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream);
 extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::PolicyScanDev* scan, const float* obs, int od, int waves, int mode, int gru, hipStream_t stream);
+extern "C" void gq_launch_policy_hist(const gq::MailboxDev* mb, const gq::PolicyHistDev* hist, const float* obs, int od, int waves, int mode, int scan, hipStream_t stream);
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
@@ -101,6 +103,7 @@ struct Mailbox {
   gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
   gq::Staged<gq::PolicyGruDev> gru;         /* the recurrent policy's (gq_rollout_policy_gru, gq_policy_gru_eval): the MLP block first, then the cell */
   gq::Staged<gq::PolicyScanDev> scan;       /* a policy with a height scan (gq_rollout_policy_scan): the seat's block - MLP or recurrent - first, then the scan's */
+  gq::Staged<gq::PolicyHistDev> hist;       /* an MLP with an observation history (gq_rollout_policy_hist): the scan's block - used or not - first, then the history's */
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
@@ -478,6 +481,7 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.mlp.create());
   HIP_TRY(t.gru.create());
   HIP_TRY(t.scan.create());
+  HIP_TRY(t.hist.create());
   HIP_TRY(t.held.ensure(12 * N, true));
   HIP_TRY(t.last.ensure(12 * N, true));
   HIP_TRY(t.learn.create());
@@ -635,10 +639,11 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
 }
 
 /* the shape of the network and what the law needs, checked and copied into the device block's form */
-/* scan_cells: the columns of a height scan between the observation columns and the last action (0: none) */
-static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who, const int scan_cells = 0) {
+/* scan_cells: the columns of a height scan between the observation columns and the last action (0: none); hist_words: the columns of an
+ * observation history behind the last action (0: none) */
+static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who, const int scan_cells = 0, const int hist_words = 0) {
   if (mlp->n_layers < 1 || mlp->n_layers > GQ_MLP_MAXL) { SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, GQ_MLP_MAXL); return GQ_EINVAL; }
-  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0);
+  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0) + hist_words;
   if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
   if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the network's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
   for (int l = 0; l < mlp->n_layers; l++)
@@ -786,32 +791,59 @@ static int scan_describe(const GqBatch* b, const GqPolicyScan* scan, gq::PolicyS
   return GQ_OK;
 }
 
+/* ---- the observation history's law (gq_policy_hist.h) from the C block, for an MLP whose scan (if any) has scan_cells cells ---- */
+static int hist_describe(const GqPolicyMlp* mlp, const GqPolicyHist* hist, const int scan_cells, gq::HistLaw& H, const char* who) {
+  if (hist->frames < 1) { SET_ERR("%s: the observation history has frames = %d: at least 1 is needed", who, hist->frames); return GQ_EINVAL; }
+  if (hist->cols < 1 || hist->cols > mlp->in_obs) { SET_ERR("%s: the observation history's cols = %d: 1 to in_obs = %d", who, hist->cols, mlp->in_obs); return GQ_EINVAL; }
+  const int f12 = mlp->feed_last_action ? 12 : 0, col0 = mlp->in_obs + scan_cells + f12;
+  const long long want = (long long)col0 + (long long)hist->frames * (hist->cols + f12);
+  if (hist->in_dim != want) {
+    SET_ERR("%s: the observation history's in_dim = %d: in_obs + scan cells + 12 feed_last_action + frames * (cols + 12 feed_last_action) = %d + %d + %d + %d * %d = %lld", who,
+            hist->in_dim, mlp->in_obs, scan_cells, f12, hist->frames, hist->cols + f12, want);
+    return GQ_EINVAL;
+  }
+  if (want > GQ_MLP_MAXW) { SET_ERR("%s: the network's input has %lld columns with the observation history: 1 to %d are supported", who, want, GQ_MLP_MAXW); return GQ_EINVAL; }
+  if (!hist->state || !hist->ctl) { SET_ERR("%s: GqPolicyHist.state (device [N][2][frames][F], in / out) or .ctl (device [N]) is null", who); return GQ_EINVAL; }
+  H = gq::hist_law(hist->frames, hist->cols, f12 != 0, col0);
+  return GQ_OK;
+}
+
 /* gru: null for the MLP (the three entry points as they were), else the recurrent policy's block (gq_rollout_policy_gru); scan: null, or the
- * height scan's block (gq_rollout_policy_scan) */
-static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+ * height scan's block (gq_rollout_policy_scan); hist: null, or the observation history's (gq_rollout_policy_hist, the MLP alone) */
+static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                           const GqFootReward* feet, void* hip_stream, const char* const who) {
   if (feet && !fresh(feet, "GqFootReward", who)) return GQ_EINVAL;
   if (!fresh(mlp, "GqPolicyMlp", who)) return GQ_EINVAL;
   if (gru && !fresh(gru, "GqPolicyGru", who)) return GQ_EINVAL;
   if (scan && !fresh(scan, "GqPolicyScan", who)) return GQ_EINVAL;
+  if (hist && !fresh(hist, "GqPolicyHist", who)) return GQ_EINVAL;
   if (learn && !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
-  gq::PolicyScanDev S = b->mb.scan.shadow;
+  gq::PolicyHistDev HD = b->mb.hist.shadow;
+  gq::PolicyScanDev Sm = b->mb.scan.shadow;
+  gq::PolicyScanDev& S = hist ? HD.scan : Sm;  /* with a history the scan's block - used or not - is the first member of the history's */
   if (scan) {
     if (const int rc = scan_describe(b, scan, S, who); rc != GQ_OK) return rc;
+  } else if (hist) {
+    S.law = gq::ScanLaw{}; S.cells = 0; S.col_z = -1; S.pad_[0] = S.pad_[1] = S.pad_[2] = 0; S.hits = nullptr;
   }
   const int scan_cells = scan ? S.cells : 0;
+  if (hist) {
+    if (const int rc = hist_describe(mlp, hist, scan_cells, HD.law, who); rc != GQ_OK) return rc;
+    HD.state = hist->state; HD.ctl = hist->ctl;
+  }
+  const int hist_words = hist ? gq::hist_words(HD.law) : 0;
   gq::PolicyGruDev Gm = b->mb.gru.shadow;
-  gq::PolicyGruDev& G = scan ? S.seat : Gm;  /* with a scan the seat's block - MLP or recurrent - is the first member of the scan's */
+  gq::PolicyGruDev& G = scan || hist ? S.seat : Gm;  /* with a scan the seat's block - MLP or recurrent - is the first member of the scan's */
   gq::PolicyMlpDev Pm = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
-  gq::PolicyMlpDev& P = gru || scan ? G.mlp : Pm;
+  gq::PolicyMlpDev& P = gru || scan || hist ? G.mlp : Pm;
   if (gru) {
     if (const int rc = gru_describe(mlp, gru, G, who, scan_cells); rc != GQ_OK) return rc;
     if (!gru->hidden_state) { SET_ERR("%s: GqPolicyGru.hidden_state (device [N][hidden], in / out) is null", who); return GQ_EINVAL; }
-  } else if (const int rc = mlp_describe(mlp, P, who, scan_cells); rc != GQ_OK) return rc;
+  } else if (const int rc = mlp_describe(mlp, P, who, scan_cells, hist_words); rc != GQ_OK) return rc;
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, gru ? "GRU" : "MLP"); rc != GQ_OK) return rc;
@@ -849,7 +881,10 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
     G.hidden_state = gru->hidden_state; G.hidden_seq = gru->hidden_seq;
     G.terminated = out.terminated; G.pending = b->p.pending;
   }
-  if (scan) {
+  if (hist) {
+    G.terminated = out.terminated; G.pending = b->p.pending; /* the episode rule's flags, where the recurrent seat has them */
+    HIP_TRY(mb.hist.push(HD, stream, true));
+  } else if (scan) {
     HIP_TRY(mb.scan.push(S, stream, true));
   } else if (gru) {
     HIP_TRY(mb.gru.push(G, stream, true));
@@ -869,7 +904,8 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  if (scan) gq_launch_policy_scan(mb.dev.get(), mb.scan.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), gru != nullptr, mb.stream.get());
+  if (hist) gq_launch_policy_hist(mb.dev.get(), mb.hist.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), scan != nullptr, mb.stream.get());
+  else if (scan) gq_launch_policy_scan(mb.dev.get(), mb.scan.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), gru != nullptr, mb.stream.get());
   else if (gru) gq_launch_policy_gru(mb.dev.get(), mb.gru.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   else gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
@@ -880,23 +916,30 @@ int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
                           const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_gru";
   if (!gru) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, gru, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, gru, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy_scan(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves,
                            double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
                            float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_scan";
   if (!scan) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, gru, scan, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, gru, scan, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+}
+int gq_rollout_policy_hist(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves,
+                           double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
+                           float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
+  const char* const who = "gq_rollout_policy_hist";
+  if (!hist) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return rollout_policy(b, n_steps, mlp, nullptr, scan, hist, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
 }
 int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                             const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                             void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
                         learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
 }
 int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
@@ -904,7 +947,7 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
                                  const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_learn_feet";
   if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
 /* gq_reward_eval (feet null) and gq_reward_eval_feet */

@@ -16,6 +16,7 @@
 #include "gq_learn.h"
 #include "gq_policy_gru.h"
 #include "gq_policy_scan.h"
+#include "gq_policy_hist.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -190,11 +191,20 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * observation row is being fed - and the z column of that row.  Both are device-scope loads.  The hit words are plain stores of the stepping
  * wavefront, like the env's state rows: it waits for them (publish_fence, vmcnt(0)) before it raises steps_done, policy and stepping
  * wavefront of an env share one XCD (gq_mailbox.h), so they are in that XCD's L2 when the count is seen and a load that misses the L1 reads
- * them.  The last-action columns follow the scan; scan words are recorded in policy_obs like every other word the network is fed. */
+ * them.  The last-action columns follow the scan; scan words are recorded in policy_obs like every other word the network is fed.
+ * OBSERVATION HISTORY (MODE & 16, gq_rollout_policy_hist, the MLP's modes with or without the scan; MODE 0 .. 14 compile to the kernels they
+ * were): Pp points at the first member of a PolicyHistDev, and the frames of the env's last L policy steps follow the last action
+ * (gq_policy_hist.h: the law, the two-buffer store, the episode rule).  The rule runs for every ready lane before the tile loop and costs one
+ * control word; whoever stages a word of the current block also stores it as the newest frame of the env's OTHER buffer, whoever stages a
+ * history word moves it one slot on into that buffer - every word has one staging lane, and nobody writes the buffer being read.  History
+ * words are stores of another visit of this launch, possibly by another lane of this wavefront: device-scope loads and stores, as for the
+ * hidden state (a plain load may hit the line an earlier plain load left in the vector L1).  The control word is the env's own lane's. */
 template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   constexpr bool GRU = (MODE & 4) != 0;
   constexpr bool SCAN = (MODE & 8) != 0;
+  constexpr bool HIST = (MODE & 16) != 0;
+  static_assert(!(GRU && HIST), "the observation history is the MLP's: a recurrent policy has its hidden state");
   constexpr int LMODE = MODE & 3;
   constexpr bool LEARN = LMODE != 0;
   __shared__ __attribute__((aligned(16))) float xt[GRU ? 3 : 2][GQ_MLP_MAXW * GQ_MLP_ROWS];
@@ -217,6 +227,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
     scan_law.offset = SD.law.offset; scan_law.clip = SD.law.clip; scan_law.scale = SD.law.scale;
     scan_cells = SD.cells; scan_col_z = SD.col_z; scan_hits = SD.hits;
   }
+  [[maybe_unused]] HistLaw hist{};
+  [[maybe_unused]] float* hist_state = nullptr;
+  [[maybe_unused]] int32_t* hist_ctl = nullptr;
+  if constexpr (HIST) {
+    const GQ_MODEL PolicyHistDev& HD = *mptr(reinterpret_cast<const PolicyHistDev*>(Pp));
+    hist.frames = HD.law.frames; hist.cols = HD.law.cols; hist.width = HD.law.width; hist.col0 = HD.law.col0; hist.inv = HD.law.inv;
+    hist_state = HD.state; hist_ctl = HD.ctl;
+  }
   const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int G = mine * GQ_WAVE;
   int32_t* const tail = mb_ctr(MB.q_ctr, q, MB_CTR_PUSH);
@@ -238,6 +256,11 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
       if constexpr (GRU) { /* the episode rule (gq_policy_gru.h), before any cell evaluation of this visit */
         const GQ_MODEL PolicyGruDev& GP = *mptr(reinterpret_cast<const PolicyGruDev*>(Pp));
         if (ready) h_zeroed = gru_episode_rule<LearnPub>(GP.terminated, GP.pending, GP.hidden_state, cell.hidden, e, k);
+      }
+      [[maybe_unused]] int hist_c = 0;
+      if constexpr (HIST) { /* the episode rule of the history (gq_policy_hist.h), before anything of this visit is staged */
+        const GQ_MODEL PolicyGruDev& SP = mptr(reinterpret_cast<const PolicyHistDev*>(Pp))->scan.seat;
+        if (ready) hist_c = hist_episode_rule<LearnPub>(SP.terminated, SP.pending, hist_ctl, e, k);
       }
       if constexpr (LEARN) { /* the visit of the window law (gq_learn.h): step k - 1 is evaluated, the window flushed at k % D == 0 */
         const GQ_MODEL LearnFeetDev& LF = *mptr(P.learn);
@@ -268,6 +291,12 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           if (src >= 0) z_base = ld_pub(row + scan_col_z);
           hit_row = scan_hits + (size_t)er * (size_t)scan_cells * 3;
         }
+        [[maybe_unused]] int hc_r = 0;              /* HIST: the control word of this lane's row, and the row's store */
+        [[maybe_unused]] float* hist_row = nullptr;
+        if constexpr (HIST) {
+          hc_r = shfl_idx(hist_c, src < 0 ? 0 : src);
+          hist_row = hist_state + (size_t)er * hist_env_floats(hist);
+        }
         const auto x_value = [&](const int, const int c) {
           if (src < 0 || c >= in_dim) return 0.0f;
           const auto word = [&](const float* const p) { /* a device-scope load, recorded with LEARN */
@@ -277,6 +306,26 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
             }
             return o;
           };
+          if constexpr (HIST) {
+            if (c >= hist.col0) { /* a word of frame_1 .. frame_L: raw in the store and in the record, shift / scale by its original column */
+              int w;
+              const float o = hist_stage_frame<LearnPub>(hist, hist_row, hc_r, c - hist.col0, &w);
+              if constexpr (LEARN) {
+                if (rec_row) rec_row[c] = o;
+              }
+              return w < hist.cols ? mlp_obs_in(o, shift, scale, w) : o;
+            }
+            if (c < in_obs) {
+              const float o = word(row + c);
+              if (c < hist.cols) hist_stage_current<LearnPub>(hist, hist_row, hc_r, c, o);
+              return mlp_obs_in(o, shift, scale, c);
+            }
+            if (c >= in_obs + scan_cells) { /* the last action: the tail of the current frame */
+              const float o = word(prev + (c - in_obs - scan_cells));
+              hist_stage_current<LearnPub>(hist, hist_row, hc_r, hist.cols + (c - in_obs - scan_cells), o);
+              return o;
+            }
+          }
           if (c < in_obs) return mlp_obs_in(word(row + c), shift, scale, c);
           if constexpr (SCAN) {
             const int cell = c - in_obs;
@@ -316,6 +365,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           out = mlp_tile_forward(net, P.blob, xt[0], xt[1]);
         }
         if (fresh && ((tile >> lane) & 1)) {
+          if constexpr (HIST) hist_push<LearnPub>(hist_ctl, e, hist_c); /* the frame just staged is the newest: by the env's own lane */
           const int slot = popc64(tile & (((uint64_t)1 << lane) - 1));
           const uint32_t gid = (uint32_t)(e + P.env_id_offset);
 #pragma unroll
@@ -747,6 +797,14 @@ extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::Policy
   const gq::PolicyMlpDev* const seat = &scan->seat.mlp; /* (address arithmetic on a device pointer: offset 0) */
   const auto kernel = gru ? (mode == 2 ? gq::policy_mlp_kernel<14> : mode == 1 ? gq::policy_mlp_kernel<13> : gq::policy_mlp_kernel<12>)
                           : (mode == 2 ? gq::policy_mlp_kernel<10> : mode == 1 ? gq::policy_mlp_kernel<9> : gq::policy_mlp_kernel<8>);
+  hipLaunchKernelGGL(kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+}
+/* gq_rollout_policy_hist: the MLP's instantiations with the observation history - mode as above, scan: the ones with the height scan too;
+ * hist->scan.seat.mlp is the block the kernel's parameter points at */
+extern "C" void gq_launch_policy_hist(const gq::MailboxDev* mb, const gq::PolicyHistDev* hist, const float* obs, int od, int waves, int mode, int scan, hipStream_t stream) {
+  const gq::PolicyMlpDev* const seat = &hist->scan.seat.mlp; /* (address arithmetic on a device pointer: offset 0) */
+  const auto kernel = scan ? (mode == 2 ? gq::policy_mlp_kernel<26> : mode == 1 ? gq::policy_mlp_kernel<25> : gq::policy_mlp_kernel<24>)
+                           : (mode == 2 ? gq::policy_mlp_kernel<18> : mode == 1 ? gq::policy_mlp_kernel<17> : gq::policy_mlp_kernel<16>);
   hipLaunchKernelGGL(kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
 }
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream) {

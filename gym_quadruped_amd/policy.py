@@ -7,7 +7,10 @@ restates the network in float64 for tests.
 ``GruPolicy`` is the recurrent form - one GRU cell and an MLP head, the hidden state on the device (``QuadrupedEnv.policy_hidden``) - defined
 in ``csrc/gq_policy_gru.h``.
 
-``HeightScan`` puts the env's base-following height map into either policy's input row (``csrc/gq_policy_scan.h``)."""
+``HeightScan`` puts the env's base-following height map into either policy's input row (``csrc/gq_policy_scan.h``).
+
+``ObsHistory`` gives the MLP a memory: the frames of the last policy steps as further columns of its input row, the state on the device
+(``QuadrupedEnv.policy_history``), defined in ``csrc/gq_policy_hist.h``."""
 from __future__ import annotations
 
 import numpy as np
@@ -66,8 +69,57 @@ class HeightScan:
         return GqPolicyScan(struct_size=C.sizeof(GqPolicyScan), rows=self.rows, cols=self.cols, offset=self.offset, clip=self.clip, scale=self.scale)
 
 
-def _scan_split(in_dim, feed_last_action, height_scan, what):
-    """in_obs of an input row of ``in_dim`` columns: what the scan and the fed-back action leave"""
+class ObsHistory:
+    """A history of past policy inputs in an ``MlpPolicy``'s input row: the FRAMES of the last ``frames`` policy steps behind the fed-back
+    action, newest first::
+
+        x = [ obs_row[:in_obs] (shift / scale) | scan (if any) | last action (12, if fed) | frame_1 | ... | frame_L ]
+
+    A frame is what the network was fed as its current block at one policy step, raw: the first ``cols`` observation words (default: all
+    ``in_obs``) as loaded and, with ``feed_last_action``, the 12 fed-back action words of that step - ``F = cols + 12 feed_last_action``
+    words, ``in_dim = in_obs + cells + 12 f + frames * F <= 256``.  When a frame is fed, ``obs_shift`` / ``obs_scale`` act on its
+    observation words by their original column and not on its action words, so ``frame_i`` at policy step ``s`` carries exactly the values
+    the current block carried at step ``s - i``.  The weights behind the current block are ordinary first-layer rows.
+
+    In ``rollout_policy`` the frames live in ``env.policy_history`` ``[N, frames, F]`` and follow the GRU's episode rule
+    (``csrc/gq_policy_hist.h``): all frames of an env become zero at the policy seat's visit that sees its termination (at the first step of
+    a call: that it waits for its re-spawn), so the history fed at policy step ``s + 1`` is zero exactly where ``dones[s]`` is set.  The
+    fed-back last action itself is NOT reset with the env: zeros at the first policy step of a call, kept across a re-spawn, as without a
+    history - and a frame records it as it was fed."""
+
+    default_policy_waves = 256   # the sweep of profiles/obs_history_throughput.txt: no count is best everywhere, 256 loses the least (go2, 16 384 envs: 14 %)
+
+    def __init__(self, frames, cols=None):
+        if int(frames) != frames or int(frames) < 1:
+            raise ValueError(f'an observation history needs frames >= 1, got frames = {frames}')
+        if cols is not None and (int(cols) != cols or int(cols) < 1):
+            raise ValueError(f'an observation history needs 1 <= cols <= in_obs, got cols = {cols}')
+        self.frames, self.cols = int(frames), None if cols is None else int(cols)
+
+    def frame_words(self, in_obs, feed_last_action):
+        """F: the words of one frame for a policy of ``in_obs`` observation columns"""
+        return (in_obs if self.cols is None else self.cols) + (N_ACTIONS if feed_last_action else 0)
+
+
+def _scan_split(in_dim, feed_last_action, height_scan, what, history=None):
+    """in_obs of an input row of ``in_dim`` columns: what the scan, the fed-back action and the history leave"""
+    if history is not None:
+        if not isinstance(history, ObsHistory):
+            raise ValueError(f'history must be an ObsHistory, got {type(history).__name__}')
+        if height_scan is not None and not isinstance(height_scan, HeightScan):
+            raise ValueError(f'height_scan must be a HeightScan, got {type(height_scan).__name__}')
+        cells, f12, L = 0 if height_scan is None else height_scan.cells, N_ACTIONS if feed_last_action else 0, history.frames
+        if in_dim > MAX_WIDTH:
+            raise ValueError(f'{what} has in_dim = {in_dim} inputs with the observation history: 1 to {MAX_WIDTH} are supported')
+        if history.cols is None:   # in_dim = in_obs + cells + f12 + L (in_obs + f12)
+            in_obs, rest = divmod(in_dim - cells - (L + 1) * f12, L + 1)
+        else:
+            in_obs, rest = in_dim - cells - f12 - L * (history.cols + f12), 0
+        if rest or in_obs < 1:
+            raise ValueError(f'{what} has in_dim = {in_dim} inputs: in_obs + {cells} scan cells + {f12} + {L} frames of (cols + {f12}) words leaves no in_obs >= 1')
+        if history.cols is not None and history.cols > in_obs:
+            raise ValueError(f'the observation history has cols = {history.cols}, the policy in_obs = {in_obs}: 1 <= cols <= in_obs')
+        return in_obs
     if height_scan is not None and not isinstance(height_scan, HeightScan):
         raise ValueError(f'height_scan must be a HeightScan, got {type(height_scan).__name__}')
     cells = 0 if height_scan is None else height_scan.cells
@@ -90,13 +142,25 @@ def _device_tables(policy, device, rows_given):
         policy._device[key] = (up(policy.pack()), up(policy.obs_shift), up(policy.obs_scale))
     blob, shift, scale = policy._device[key]
     cells = policy.height_scan.cells if rows_given and policy.height_scan is not None else 0
-    if not cells:
+    hist = getattr(policy, 'history', None) if rows_given else None
+    if not cells and hist is None:
         return blob, shift, scale, policy.in_obs
+    # a history's frames are given columns too: their observation words keep the shift / scale of their original column, the fed-back action
+    # between the current block and the frames passes unchanged; with feed_last_action the row's last 12 words are the oldest frame's action
+    f12 = N_ACTIONS if policy.feed_last_action else 0
+    given = policy.in_obs + cells if hist is None else policy.in_dim - f12
     if key + ':rows' not in policy._device:
-        pad = lambda v, fill: None if v is None else up(np.concatenate([v, np.full(cells, fill, dtype=np.float32)]))
+        def pad(v, fill):
+            if v is None:
+                return None
+            same = lambda n: np.full(n, fill, dtype=np.float32)
+            parts = [v, same(cells)]
+            if hist is not None:
+                parts += [same(f12)] + [w for _ in range(hist.frames) for w in (v[:policy.hist_cols], same(f12))]
+            return up(np.concatenate(parts)[:given])
         policy._device[key + ':rows'] = (pad(policy.obs_shift, 0.0), pad(policy.obs_scale, 1.0))
     shift, scale = policy._device[key + ':rows']
-    return blob, shift, scale, policy.in_obs + cells
+    return blob, shift, scale, given
 
 
 class MlpPolicy:
@@ -108,9 +172,12 @@ class MlpPolicy:
     optional per-column ``(o - shift) * scale`` on the observation columns the network reads.  feed_last_action: the env's previous
     policy action (12 values, zeros at the first policy step of a rollout call) follows the observation columns in the input row, so the
     first layer has ``in_obs + 12`` inputs.  height_scan: a ``HeightScan`` - its ``rows * cols`` columns stand between the observation columns
-    and the fed-back action, so ``in_obs = in_dim - rows * cols - 12 feed_last_action``; shift / scale keep covering the first ``in_obs``."""
+    and the fed-back action, so ``in_obs = in_dim - rows * cols - 12 feed_last_action``; shift / scale keep covering the first ``in_obs``.
+    history: an ``ObsHistory`` - ``frames`` frames of ``F = cols + 12 feed_last_action`` words follow the fed-back action, so
+    ``in_dim = in_obs + rows * cols + 12 feed_last_action + frames * F``; ``hist_cols`` / ``hist_words`` are ``cols`` and ``F`` resolved."""
 
-    def __init__(self, weights, biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None, feed_last_action=False, height_scan=None):
+    def __init__(self, weights, biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None, feed_last_action=False, height_scan=None,
+                 history=None):
         self.weights = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
         self.biases = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for b in biases]
         if not 1 <= len(self.weights) <= MAX_LAYERS:
@@ -134,7 +201,12 @@ class MlpPolicy:
         self.feed_last_action = bool(feed_last_action)
         self.in_dim = self.weights[0].shape[0]
         self.height_scan = height_scan
-        self.in_obs = _scan_split(self.in_dim, self.feed_last_action, height_scan, 'the first layer')
+        self.history = history
+        self.in_obs = _scan_split(self.in_dim, self.feed_last_action, height_scan, 'the first layer', history)
+        self.hist_cols = self.hist_words = 0
+        if history is not None:
+            self.hist_cols = self.in_obs if history.cols is None else history.cols
+            self.hist_words = history.frame_words(self.in_obs, self.feed_last_action)
         self.widths = [w.shape[1] for w in self.weights]
 
         def col(v, name):
@@ -147,7 +219,8 @@ class MlpPolicy:
     @classmethod
     def from_torch(cls, module, **kw):
         """From a ``torch.nn.Sequential`` of ``Linear`` layers with ``ReLU``, ``ELU`` (alpha 1) or ``Tanh`` between them (one kind), optionally a
-        ``Tanh`` at the end; anything else raises ``ValueError``."""
+        ``Tanh`` at the end; anything else raises ``ValueError``.  With ``history=`` (``height_scan=``, ``feed_last_action=``) the first
+        layer's ``in_features`` must be the ``in_dim`` of ``ObsHistory``'s formula."""
         import torch.nn as nn
         if not isinstance(module, nn.Sequential):
             raise ValueError(f'from_torch takes a torch.nn.Sequential, got {type(module).__name__}')
@@ -195,14 +268,23 @@ class MlpPolicy:
             parts.append(bp)
         return np.ascontiguousarray(np.concatenate(parts))
 
+    def _obs_blocks(self):
+        """(first column, words) of every block of the input row that shift / scale act on: the current one, then each frame's"""
+        blocks = [(0, self.in_obs)]
+        if self.history is not None:
+            col0 = self.in_dim - self.history.frames * self.hist_words
+            blocks += [(col0 + i * self.hist_words, self.hist_cols) for i in range(self.history.frames)]
+        return blocks
+
     def reference(self, x):
-        """float64 forward pass of the same network over rows ``[n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns; scan
-        columns and the fed-back action are taken as given)."""
+        """float64 forward pass of the same network over rows ``[n, in_dim]`` (shift / scale applied to the first ``in_obs`` columns and to
+        the observation words of a history's frames; scan columns and the fed-back action are taken as given)."""
         h = np.array(x, dtype=np.float64).reshape(-1, self.in_dim)
-        if self.obs_shift is not None:
-            h[:, :self.in_obs] -= self.obs_shift.astype(np.float64)
-        if self.obs_scale is not None:
-            h[:, :self.in_obs] *= self.obs_scale.astype(np.float64)
+        for c0, n in self._obs_blocks():
+            if self.obs_shift is not None:
+                h[:, c0:c0 + n] -= self.obs_shift[:n].astype(np.float64)
+            if self.obs_scale is not None:
+                h[:, c0:c0 + n] *= self.obs_scale[:n].astype(np.float64)
         for l, (w, b) in enumerate(zip(self.weights, self.biases)):
             h = h @ w.astype(np.float64) + b.astype(np.float64)
             h = _ACT64[self.out_activation if l == len(self.weights) - 1 else self.activation](h)
@@ -219,6 +301,14 @@ class MlpPolicy:
                         blob_floats=blob.numel(), obs_shift=None if shift is None else shift.data_ptr(), obs_scale=None if scale is None else scale.data_ptr())
         m.width = (C.c_int32 * 4)(*(self.widths + [0] * (4 - len(self.widths))))
         return m
+
+    def _hist_struct(self, state, ctl):
+        """the history's C block around the env's store: ``state`` ``[N, 2, frames, F]`` float32, ``ctl`` ``[N]`` int32"""
+        import ctypes as C
+
+        from .cabi import GqPolicyHist
+        return GqPolicyHist(struct_size=C.sizeof(GqPolicyHist), frames=self.history.frames, cols=self.hist_cols, in_dim=self.in_dim, state=state.data_ptr(),
+                            ctl=ctl.data_ptr())
 
 
 MAX_HIDDEN, MAX_HEAD_LAYERS = 128, 3
@@ -249,7 +339,9 @@ class GruPolicy:
     default_policy_waves = 128   # the sweep of profiles/gru_policy_throughput.txt: no count is best everywhere, 128 loses the least
 
     def __init__(self, w_ih, w_hh, b_ih, b_hh, head_weights, head_biases, activation='elu', out_activation=None, obs_shift=None, obs_scale=None,
-                 feed_last_action=False, height_scan=None):
+                 feed_last_action=False, height_scan=None, history=None):
+        if history is not None:
+            raise ValueError('a GruPolicy takes no history (ObsHistory): its memory is the hidden state; give the history to an MlpPolicy')
         f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
         self.w_ih, self.w_hh, self.b_ih, self.b_hh = f(w_ih), f(w_hh), f(b_ih).reshape(-1), f(b_hh).reshape(-1)
         if self.w_hh.ndim != 2 or self.w_hh.shape[1] != 3 * self.w_hh.shape[0]:

@@ -190,6 +190,7 @@ class QuadrupedEnv(AccessorsMixin):
         self._reward = torch.zeros(N, **f32)
         self._feet_air = torch.zeros(N, 4, **f32)   # the foot reward terms' state (feet_air_time)
         self._policy_hidden = None                  # a GruPolicy's hidden state [N, H] (policy_hidden): allocated on first use
+        self._policy_hist = None                    # an ObsHistory's store (policy_history): (state [N, 2, L, F], ctl [N] int32), on first use
         self._terminated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._truncated = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._invalid = torch.zeros(N, dtype=torch.uint8, device=dev)
@@ -439,6 +440,19 @@ class QuadrupedEnv(AccessorsMixin):
                              f'a [{self.num_envs}, {H}] tensor first')
         return self._policy_hidden
 
+    def _history_for(self, policy):
+        """the store behind ``policy_history`` for an ``MlpPolicy`` with an ``ObsHistory``: empty on first use, refused when it was sized for
+        another ``(L, F)``"""
+        L, F = policy.history.frames, policy.hist_words
+        if self._policy_hist is None:
+            self._policy_hist = (torch.zeros(self.num_envs, 2, L, F, dtype=torch.float32, device=self.device),
+                                 torch.zeros(self.num_envs, dtype=torch.int32, device=self.device))
+        have = tuple(self._policy_hist[0].shape[2:])
+        if have != (L, F):
+            raise ValueError(f'env.policy_history holds {have[0]} frames of {have[1]} words per env, the policy has {L} of {F}: assign env.policy_history '
+                             f'a [{self.num_envs}, {L}, {F}] tensor first')
+        return self._policy_hist
+
     def rollout_policy(self, n_steps: int, policy, kp, kd, q_default=None, action_scale=0.25, action_clip=None, decimation: int = 4, noise_sigma=0.0,
                        record_obs: bool = False, record_actions: bool = False, policy_waves: int = 0, step_waves: int = 0, timeout_s: float = 5.0,
                        check: bool = True, reward=None, record_transitions: bool = False):
@@ -501,7 +515,18 @@ class QuadrupedEnv(AccessorsMixin):
         columns between the observation columns and the fed-back action.  The stepping wavefront casts the map's rays at every step, so the
         scan fed at a policy step is that of the state the observation row fed with it describes - across a re-spawn too.  Before the launch
         the map is brought up to date (``update_height_map()``: nothing when the last step left it, one ray launch after a reset or a state
-        write).  'policy_obs' records the scan words as fed; ``env.height_scan`` evaluates the same law on any hits."""
+        write).  'policy_obs' records the scan words as fed; ``env.height_scan`` evaluates the same law on any hits.
+
+        AN OBSERVATION HISTORY (an ``MlpPolicy`` built with ``history=ObsHistory(frames, cols)``, every mode of the MLP above, with or without
+        a scan; ``gq_rollout_policy_hist``): the frames of the env's last ``frames`` policy steps - what the network was fed as its current
+        block, raw: the first ``cols`` observation words and the fed-back action - follow the fed-back action in the input row, newest first;
+        the device-side form of ``hist = where(done, 0, hist); x = cat(row, a_prev, hist); hist = roll(hist) with the current block first``.
+        The frames are ``env.policy_history`` ``[N, frames, F]``: they persist across calls and follow the GRU's episode rule
+        (``csrc/gq_policy_hist.h``) - all frames of an env become zero at the visit that sees its termination (at the first step of a call:
+        that the env waits for its re-spawn), so the history fed at policy step ``s + 1`` is all zero exactly where ``dones[s]`` is set; in
+        the plain mode a fall in the call's last step is left to the next call's first step.  The fed-back last action itself keeps its rule
+        - zeros at the first policy step of a call, kept across a re-spawn, NOT reset with the env - and a frame holds it as it was fed.
+        'policy_obs' records the history words raw, as fed."""
         from .policy import GruPolicy
         recurrent = isinstance(policy, GruPolicy)
         K, D = int(n_steps), int(decimation)
@@ -522,6 +547,11 @@ class QuadrupedEnv(AccessorsMixin):
             self._scan_map(scan).update_height_map()   # the hits at policy step 0 belong to the state the env now holds
             if not recurrent:   # (a GruPolicy keeps its own default)
                 policy_waves = int(policy_waves) or scan.default_policy_waves
+        hist = getattr(policy, 'history', None)
+        if hist is not None:
+            hs = policy._hist_struct(*self._history_for(policy))
+            if scan is None:
+                policy_waves = int(policy_waves) or hist.default_policy_waves
         row12 = lambda v: (C.c_float * 12)(*np.broadcast_to(np.asarray(v, dtype=np.float32), (12,)))
         m.kp, m.kd, m.action_scale, m.noise_sigma = row12(kp), row12(kd), row12(action_scale), row12(noise_sigma)
         m.q_default = row12(self._key_qpos[7:19].float().cpu().numpy() if q_default is None else np.asarray(q_default, dtype=np.float32).reshape(12))
@@ -556,7 +586,11 @@ class QuadrupedEnv(AccessorsMixin):
         self._hm_fresh = False
         args = (self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
                 self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq))
-        if scan is not None:   # one entry point: the network, the modes and the scan selected by the blocks given
+        if hist is not None:   # one entry point: the modes and the scan selected by the blocks given
+            gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
+            _lib.check(self._L.gq_rollout_policy_hist(*args[:3], None if scan is None else C.byref(sc), C.byref(hs), *args[3:], C.byref(g) if learning else None,
+                                                      None if gf is None else C.byref(gf), stream), 'gq_rollout_policy_hist')
+        elif scan is not None:   # one entry point: the network, the modes and the scan selected by the blocks given
             gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
             _lib.check(self._L.gq_rollout_policy_scan(*args[:3], C.byref(gr) if recurrent else None, C.byref(sc), *args[3:], C.byref(g) if learning else None,
                                                       None if gf is None else C.byref(gf), stream), 'gq_rollout_policy_scan')
@@ -948,6 +982,8 @@ class QuadrupedEnv(AccessorsMixin):
         self._feet_air.masked_fill_(mask.bool().unsqueeze(1), 0.0)   # a new episode starts with no air time behind it
         if self._policy_hidden is not None:
             self._policy_hidden.masked_fill_(mask.bool().unsqueeze(1), 0.0)   # ... and with no memory
+        if self._policy_hist is not None:
+            self._policy_hist[1].masked_fill_(mask.bool(), 0)                 # ... of either kind: a control word without VALID is an empty history
         if mask is self._mask_all:  # the reference zeroes mjData.ctrl in reset (:334): torque_ctrl_setpoint reads zero afterwards
             self._ctrl.zero_()
             self._last_action = self._ctrl
@@ -1081,6 +1117,35 @@ class QuadrupedEnv(AccessorsMixin):
             self._policy_hidden = v.clone().contiguous()
 
     @property
+    def policy_history(self):
+        """``[N, L, F]`` float32, newest first: the frames the ``ObsHistory`` of the ``MlpPolicy`` that ``rollout_policy`` runs would be fed
+        next, or None before the first such call (which starts every env with an empty - all zero - history for that policy's ``(L, F)``).
+        A copy: the rollout keeps two buffers and a control word per env (``csrc/gq_policy_hist.h``), read here into the law's form.  The
+        policy seat empties an env's history when it sees the env's termination (the episode rule), ``reset`` empties those of the envs it
+        resets.  Assigning a ``[N, L', F']`` tensor replaces it (a policy with another ``(L, F)`` is refused until then); ``state_dict``
+        carries it."""
+        if self._policy_hist is None:
+            return None
+        state, ctl = self._policy_hist
+        cur = state[torch.arange(self.num_envs, device=self.device), (ctl & 1).long()]
+        return torch.where(((ctl >> 1) & 1).bool().view(-1, 1, 1), cur, torch.zeros_like(cur))
+
+    @policy_history.setter
+    def policy_history(self, value):
+        if value is None:
+            self._policy_hist = None
+            return
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if v.dim() != 3 or v.shape[0] != self.num_envs or v.shape[1] < 1 or v.shape[2] < 1 or v.shape[1] * v.shape[2] >= 256:
+            raise ValueError(f'policy_history must be [{self.num_envs}, L, F] with L, F >= 1 and L * F < 256, got {tuple(v.shape)}')
+        if self._policy_hist is None or self._policy_hist[0].shape[2:] != v.shape[1:]:
+            self._policy_hist = (torch.zeros(self.num_envs, 2, v.shape[1], v.shape[2], dtype=torch.float32, device=self.device),
+                                 torch.zeros(self.num_envs, dtype=torch.int32, device=self.device))
+        state, ctl = self._policy_hist
+        state[:, 0].copy_(v)
+        ctl.fill_(2)   # parity 0, VALID
+
+    @property
     def ground_friction_coeff_range(self):
         """``(low, high)`` of the ground friction the resets draw from.  Assigning a scalar or a pair applies from the next reset (the
         auto-resets inside ``step`` included); a range whose lower end is under the solver's floor is refused (``check_ground_friction``)."""
@@ -1106,6 +1171,8 @@ class QuadrupedEnv(AccessorsMixin):
         d = {k: getattr(self, k).clone() for k in keys}
         if self._policy_hidden is not None:
             d['_policy_hidden'] = self._policy_hidden.clone()
+        if self._policy_hist is not None:
+            d['_policy_history'] = self.policy_history
         d['rng'] = self._gen.get_state()
         # sensor state the kernel reads and writes every step: the IMU bias random walks
         d['sensor_bias'] = [sn.bias_state.clone() if hasattr(sn, 'bias_state') else None for sn in self.sensors]
@@ -1128,6 +1195,8 @@ class QuadrupedEnv(AccessorsMixin):
                 self._gen.set_state(v)
             elif k == '_policy_hidden':
                 self.policy_hidden = v
+            elif k == '_policy_history':
+                self.policy_history = v
             elif k == 'sensor_bias':
                 for sn, b in zip(self.sensors, v):
                     if b is not None:

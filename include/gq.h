@@ -663,6 +663,37 @@ int gq_rollout_policy_scan(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, cons
 /* the scan law alone: hits: device [n][rows * cols][3], z: device [n] (the base's z of each row) -> out: device [n][rows * cols].  The same
  * routine, the same bits, as inside the rollout; no map needs to be set on the batch. */
 int gq_height_scan_eval(GqBatch* b, const GqPolicyScan* scan, const float* hits, const float* z, int n, float* out, void* hip_stream);
+/* AN OBSERVATION HISTORY in the MLP policy's input row (additive: the entry points above are what they were): the frames of the env's last
+ * `frames` policy steps follow the fed-back action,
+ *   x = [(obs[:, :in_obs] - obs_shift) * obs_scale, scan (if any), a_prev, frame_1, ..., frame_L]      newest first
+ *   in_dim = in_obs + rows * cols (scan) + 12 feed_last_action + L F <= 256,    F = cols + 12 feed_last_action
+ * (csrc/gq_policy_hist.h is the definition).  A frame is what the network was fed as its current block at one policy step, raw: the first
+ * `cols` observation words as loaded and, with feed_last_action, the 12 fed-back action words of that step.  When a frame is staged obs_shift /
+ * obs_scale act on its observation words by their original column and not on its action words: frame_i at policy step s carries exactly the
+ * values the current block carried at step s - i.  GqLearn.policy_obs records the history words raw.  mlp->blob is the network whose first layer
+ * has in_dim inputs.
+ * THE STATE lives with the caller and persists across calls: `state`, device [N][2][frames][F] floats - two buffers of `frames` slots per env -
+ * and `ctl`, device [N] int32 control words: bit 0 the parity p of the buffer that holds what is fed next (its slot i - 1 is frame_i), bit 1
+ * VALID - clear: every frame is zero whatever the buffers hold (all-zero words are a valid empty state).  A policy step reads buffer p, writes
+ * buffer 1 - p and stores (1 - p) | VALID.  THE EPISODE RULE is the recurrent policy's, on the same flags: at the visit that sees an env's
+ * termination (at step 0 of a call: that the env waits for its re-spawn) VALID is cleared before anything of that visit is staged, so the
+ * history fed at policy step s + 1 is all zero exactly where GqLearn.dones[s] is set.  The learning modes' closing visit applies the rule; in
+ * the plain mode a fall in the call's last step is left to the next call's step 0.  The fed-back action itself keeps its rule: zeros at the
+ * first policy step of a call, kept across a re-spawn.
+ * scan: NULL, or the height scan's block; learn / feet: NULL, or the blocks of gq_rollout_policy_learn / _learn_feet.  Refused with a message,
+ * the batch stays usable: a stale struct_size, frames < 1, cols outside 1 .. in_obs, an in_dim that is not the formula's or beyond 256 (the first
+ * layer's width is taken from mlp->blob_floats), a null state or ctl, and everything gq_rollout_policy / gq_rollout_policy_scan refuse. */
+typedef struct GqPolicyHist {
+  int32_t struct_size;        /* sizeof(GqPolicyHist): a stale binding is refused */
+  int32_t frames;             /* L >= 1 */
+  int32_t cols;               /* 1 .. in_obs: the leading observation words of a frame */
+  int32_t in_dim;             /* the first layer's inputs: must equal in_obs + scan cells + 12 feed_last_action + frames * F */
+  float* state;               /* device [N][2][frames][F], in / out */
+  int32_t* ctl;               /* device [N], in / out */
+} GqPolicyHist;
+int gq_rollout_policy_hist(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves,
+                           double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
+                           float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

@@ -1,6 +1,7 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
 usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R] [--learn]
+                             [--history L[,cols]]
                              | --gru H [--mlp H1,H2] [--decimation D] [--policy-waves W1,..] [--runs R] [--side loop|rollout]]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
@@ -16,6 +17,12 @@ rollout (QuadrupedEnv.rollout_policy, a new action every D steps: --decimation, 
 commit - a = torch_module(obs); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
 network; one timing of the loop, then one of the rollout per entry of --policy-waves (default 64,128,256,512), R times over (--runs,
 default 3).  Prints every run of both sides.
+
+--history L[,cols] (with --mlp): the network also reads the last action and the frames of the last L policy steps (ObsHistory(L, cols), cols
+default 33: a 45-word frame; env.policy_history) - against the loop it replaces with the history kept in torch - hist = where(terminated, 0,
+hist); cur = cat(obs, a_prev); a = module(cat(cur, hist)); step_pd; hist = cat(cur[:, :cols] | a_prev, hist[:, :-1]) - and against the
+history-less rollout_policy of a network with the same hidden widths that reads the observation and the last action (the first entry of
+--policy-waves), all three in turn, R times over.
 
 --gru H: a recurrent policy - torch.nn.GRUCell(33, H) and a head with the hidden widths of --mlp (default 128,64; elu) - in the closed-loop
 rollout (QuadrupedEnv.rollout_policy with a GruPolicy, the hidden state in env.policy_hidden) against the loop it replaces on the same commit -
@@ -54,6 +61,7 @@ MLP = _opt('--mlp', None, lambda t: [int(h) for h in t.split(',')])
 MLP_D = _opt('--decimation', 4, int)
 MLP_WAVES = _opt('--policy-waves', [64, 128, 256, 512], lambda t: [int(w) for w in t.split(',')])
 MLP_RUNS = _opt('--runs', 3, int)
+HIST = _opt('--history', None, lambda t: [int(v) for v in t.split(',')])
 GRU = _opt('--gru', 0, int)
 SIDE = _opt('--side', None, str)
 LEARN = '--learn' in sys.argv
@@ -190,6 +198,49 @@ if MLP:
             for name, fn in forms:
                 restore(); m, us = timed(fn, W * D)
                 print(f'{tag} run {r}: {name:46s} {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
+        print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
+        sys.exit(0)
+    if HIST:
+        from gym_quadruped_amd.policy import ObsHistory
+        L, cols = HIST[0], HIST[1] if len(HIST) > 1 else 33
+        F = cols + 12
+        def net(k):
+            dims, mods = [k] + MLP + [12], []
+            for a, b in zip(dims[:-1], dims[1:]):
+                mods += [torch.nn.Linear(a, b), torch.nn.ELU()]
+            return torch.nn.Sequential(*mods[:-1]).to('cuda')
+        module, module0 = net(45 + L * F), net(45)
+        policy = MlpPolicy.from_torch(module, feed_last_action=True, history=ObsHistory(L, cols))
+        policy0 = MlpPolicy.from_torch(module0, feed_last_action=True)
+        env.rollout_policy(300 // D * D, policy, KP, KD, action_scale=scale, decimation=D)   # fill the history in the policy's regime
+        sd = env.state_dict(); launches = env._launches
+        row0 = env._obs_buf.clone()   # the policy's first action reads the observation row, which is no part of the checkpoint
+        def restore():
+            env.load_state_dict(sd); env._launches = launches; env._obs_buf.copy_(row0); torch.cuda.synchronize()
+        def with_history(pw):
+            env.rollout_policy(W * D, policy, KP, KD, action_scale=scale, decimation=D, policy_waves=pw)
+        def without():
+            env.rollout_policy(W * D, policy0, KP, KD, action_scale=scale, decimation=D, policy_waves=MLP_WAVES[0])
+        def loop():
+            with torch.no_grad():
+                hist, a_prev = env.policy_history.clone(), torch.zeros(n, 12, device='cuda')
+                for w in range(W):
+                    hist = torch.where(env._terminated.bool()[:, None, None], 0.0, hist)
+                    obs = env._obs_buf
+                    a = module(torch.cat([obs, a_prev, hist.flatten(1)], dim=1))
+                    hist = torch.cat([torch.cat([obs[:, :cols], a_prev], dim=1)[:, None], hist[:, :-1]], dim=1)
+                    env.step_pd(q0 + scale * a, KP, KD, decimation=D)
+                    a_prev = a
+        restore(); with_history(0); restore(); without(); restore(); loop()   # warm every path
+        tag = f'{robot} {scene} n={n} mlp={MLP} D={D} history L={L} cols={cols} (in_dim {policy.in_dim})'
+        for r in range(MLP_RUNS):
+            restore(); m, us = timed(loop, W * D)
+            print(f'{tag} run {r}: loop (torch module + history in torch + step_pd)  {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+            restore(); m, us = timed(without, W * D)
+            print(f'{tag} run {r}: rollout_policy WITHOUT history (in_dim 45), waves {MLP_WAVES[0]:4d} {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+            for pw in MLP_WAVES:
+                restore(); m, us = timed(lambda: with_history(pw), W * D)
+                print(f'{tag} run {r}: rollout_policy with history, policy waves {pw:4d}       {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
         print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
         sys.exit(0)
     restore(); feature(0); restore(); loop()   # warm both paths
