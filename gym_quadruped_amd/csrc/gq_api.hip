@@ -21,10 +21,7 @@
 #include "gq_step_kernel.h"
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
-#include "gq_policy_mlp.h"
-#include "gq_policy_gru.h"
-#include "gq_policy_scan.h"
-#include "gq_policy_hist.h"
+#include "gq_policy_dev.h"
 #include "gq_learn.h"
 #include "gq_step_call.h"
 #include "gq_camera_call.h"
@@ -44,14 +41,11 @@ extern "C" void gq_launch_heightmap(const GqDevModel* model, const double* cente
 
 extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream);
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream);
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream);
+extern "C" int gq_launch_policy(const gq::MailboxDev* mb, const gq::PolicyDev* dev, const float* obs, int od, int waves, int mode, hipStream_t stream);
 extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
                                       const uint8_t* terminated, const float* air_in, int n, float* out, float* air_out, int feet, hipStream_t stream);
-extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
-extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream);
-extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
-extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::PolicyScanDev* scan, const float* obs, int od, int waves, int mode, int gru, hipStream_t stream);
-extern "C" void gq_launch_policy_hist(const gq::MailboxDev* mb, const gq::PolicyHistDev* hist, const float* obs, int od, int waves, int mode, int scan, hipStream_t stream);
+extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
+extern "C" void gq_launch_policy_gru_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
@@ -100,10 +94,10 @@ struct Mailbox {
   Buf<gq::MailboxDev> dev; Buf<gq::MailboxDev, gq::PinnedMem> staging;
   Buf<int32_t, gq::PinnedMem> alive, status_host; /* the word the policy workgroups count themselves into; a copy of the status words (gq_rollout_closed_status) */
   gq::Staged<gq::PolicyPdDev> policy;       /* the built-in policy's parameters (both modes read them from device memory) */
-  gq::Staged<gq::PolicyMlpDev> mlp;         /* the MLP policy's (gq_rollout_policy, gq_policy_mlp_eval) */
-  gq::Staged<gq::PolicyGruDev> gru;         /* the recurrent policy's (gq_rollout_policy_gru, gq_policy_gru_eval): the MLP block first, then the cell */
-  gq::Staged<gq::PolicyScanDev> scan;       /* a policy with a height scan (gq_rollout_policy_scan): the seat's block - MLP or recurrent - first, then the scan's */
-  gq::Staged<gq::PolicyHistDev> hist;       /* an MLP with an observation history (gq_rollout_policy_hist): the scan's block - used or not - first, then the history's */
+  /* the in-loop policy's block (gq_policy_dev.h): every gq_rollout_policy* call and gq_policy_mlp_eval / gq_policy_gru_eval fill the parts
+   * they use and zero the others.  One ring of GQ_ARG_SLOTS slots serves all of them, where each kind of call had its own: it wraps after
+   * fewer calls, and a caller that mixes them drains its stream once more often than before (Staged::push). */
+  gq::Staged<gq::PolicyDev> net;
   Buf<float> held, last;                    /* [N][12] each: the action an env tracks until its next policy step; its previous policy action */
   gq::Staged<gq::LearnFeetDev> learn;       /* gq_rollout_policy_learn's / gq_reward_eval's block (its first member), and the foot terms' behind it */
   Buf<float> learn_acc, learn_prev;         /* [N], [N][12]: the reward window's sum, the policy action before the held one */
@@ -478,10 +472,7 @@ static int mailbox_setup(GqBatch* b) {
   HIP_TRY(t.status.ensure(8, true));
   HIP_TRY(t.dev.ensure(1, false));
   HIP_TRY(t.policy.create());
-  HIP_TRY(t.mlp.create());
-  HIP_TRY(t.gru.create());
-  HIP_TRY(t.scan.create());
-  HIP_TRY(t.hist.create());
+  HIP_TRY(t.net.create());
   HIP_TRY(t.held.ensure(12 * N, true));
   HIP_TRY(t.last.ensure(12 * N, true));
   HIP_TRY(t.learn.create());
@@ -638,50 +629,63 @@ int gq_rollout_closed(GqBatch* b, int n_steps, int mode, const GqPolicyPd* pd, i
   return mailbox_steps(b, auto_reset, step_waves, pd != nullptr, stream, who);
 }
 
-/* the shape of the network and what the law needs, checked and copied into the device block's form */
-/* scan_cells: the columns of a height scan between the observation columns and the last action (0: none); hist_words: the columns of an
- * observation history behind the last action (0: none) */
-static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who, const int scan_cells = 0, const int hist_words = 0) {
-  if (mlp->n_layers < 1 || mlp->n_layers > GQ_MLP_MAXL) { SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, GQ_MLP_MAXL); return GQ_EINVAL; }
-  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0) + hist_words;
+/* the shape of the network and what the law needs, checked and copied into the seat's part of the device block: what the MLP and the
+ * recurrent policy's head share.  head: the network is a GRU's head (at most GQ_GRU_HEAD_MAXL layers) - the messages then say "head" where
+ * they say "network", and "cell" for whatever the input row feeds.  scan_cells: the columns of a height scan between the observation columns
+ * and the last action (0: none); hist_words: the columns of an observation history behind the last action (0: none).  P.net.in_dim is the
+ * INPUT ROW's width on return. */
+static int net_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char* who, const bool head, const int scan_cells, const int hist_words) {
+  const char* const net = head ? "head" : "network";
+  const char* const fed = head ? "cell" : "network";
+  const int max_layers = head ? GQ_GRU_HEAD_MAXL : GQ_MLP_MAXL;
+  if (mlp->n_layers < 1 || mlp->n_layers > max_layers) {
+    if (head) SET_ERR("%s: the head has %d linear layers: 1 to %d are supported", who, mlp->n_layers, max_layers);
+    else SET_ERR("%s: %d linear layers: 1 to %d are supported (3 hidden layers and the output)", who, mlp->n_layers, max_layers);
+    return GQ_EINVAL;
+  }
+  const int in_dim = gq::policy_row_dim(mlp->in_obs, scan_cells, mlp->feed_last_action, hist_words);
   if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
-  if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the network's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
+  if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the %s's input has %d columns: 1 to %d are supported", who, fed, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
   for (int l = 0; l < mlp->n_layers; l++)
-    if (mlp->width[l] < 1 || mlp->width[l] > GQ_MLP_MAXW) { SET_ERR("%s: layer %d has %d outputs: 1 to %d are supported", who, l, mlp->width[l], GQ_MLP_MAXW); return GQ_EINVAL; }
-  if (mlp->width[mlp->n_layers - 1] != 12) { SET_ERR("%s: the network has %d outputs: 12 (one per hinge) are needed", who, mlp->width[mlp->n_layers - 1]); return GQ_EINVAL; }
+    if (mlp->width[l] < 1 || mlp->width[l] > GQ_MLP_MAXW) { SET_ERR("%s: layer %d%s has %d outputs: 1 to %d are supported", who, l, head ? " of the head" : "", mlp->width[l], GQ_MLP_MAXW); return GQ_EINVAL; }
+  if (mlp->width[mlp->n_layers - 1] != 12) { SET_ERR("%s: the %s has %d outputs: 12 (one per hinge) are needed", who, net, mlp->width[mlp->n_layers - 1]); return GQ_EINVAL; }
   if (mlp->activation < GQ_ACT_RELU || mlp->activation > GQ_ACT_TANH) { SET_ERR("%s: activation %d: relu (1), elu (2) or tanh (3)", who, mlp->activation); return GQ_EINVAL; }
   if (mlp->out_activation != GQ_ACT_NONE && mlp->out_activation != GQ_ACT_TANH) { SET_ERR("%s: out_activation %d: none (0) or tanh (3)", who, mlp->out_activation); return GQ_EINVAL; }
-  if (!mlp->blob) { SET_ERR("%s: blob is null", who); return GQ_EINVAL; }
   P.net.n_layers = mlp->n_layers; P.net.in_dim = in_dim; P.net.act = mlp->activation; P.net.out_act = mlp->out_activation;
   for (int l = 0; l < GQ_MLP_MAXL; l++) P.net.width[l] = l < mlp->n_layers ? mlp->width[l] : 0;
-  if (mlp->blob_floats != (int64_t)gq::mlp_blob_floats(P.net)) { SET_ERR("%s: blob_floats is %lld, this network's blob has %lld", who, (long long)mlp->blob_floats, (long long)gq::mlp_blob_floats(P.net)); return GQ_EINVAL; }
   P.in_obs = mlp->in_obs; P.feed_last = mlp->feed_last_action ? 1 : 0; P.decimation = mlp->decimation; P.pad_ = 0; P.pad2_ = 0;
-  P.blob = mlp->blob; P.shift = mlp->obs_shift; P.scale = mlp->obs_scale;
+  P.shift = mlp->obs_shift; P.scale = mlp->obs_scale;
   return GQ_OK;
 }
-
+/* what every caller starts from: a copy of the staged block's shadow (see Staged) with the feature parts at fixed zeros - a call then fills
+ * the ones it uses, and nothing of an earlier call's scan, history, cell or flags travels with it */
+static gq::PolicyDev policy_block(const Mailbox& mb) {
+  gq::PolicyDev D = mb.net.shadow;
+  D.gru = gq::GruDev{}; D.episode = gq::EpisodeDev{}; D.scan = gq::ScanDev{}; D.hist = gq::HistDev{};
+  return D;
+}
+/* the MLP policy: the block's seat part */
+static int mlp_describe(const GqPolicyMlp* mlp, gq::PolicyDev& D, const char* who, const int scan_cells = 0, const int hist_words = 0) {
+  gq::PolicyMlpDev& P = D.seat;
+  if (const int rc = net_describe(mlp, P, who, false, scan_cells, hist_words); rc != GQ_OK) return rc;
+  if (!mlp->blob) { SET_ERR("%s: blob is null", who); return GQ_EINVAL; }
+  if (mlp->blob_floats != (int64_t)gq::mlp_blob_floats(P.net)) { SET_ERR("%s: blob_floats is %lld, this network's blob has %lld", who, (long long)mlp->blob_floats, (long long)gq::mlp_blob_floats(P.net)); return GQ_EINVAL; }
+  P.blob = mlp->blob;
+  return GQ_OK;
+}
 /* the recurrent policy: `mlp` describes the cell's input row and the HEAD (its input width is gru->hidden), `gru` the cell and the blob of
- * both.  Fills G.cell, G.blob and G.mlp's network part (net = the head, blob = the head's layers). */
-static int gru_describe(const GqPolicyMlp* mlp, const GqPolicyGru* gru, gq::PolicyGruDev& G, const char* who, const int scan_cells = 0) {
+ * both.  Fills the gru part's cell and blob and the seat's network part (net = the head, blob = the head's layers). */
+static int gru_describe(const GqPolicyMlp* mlp, const GqPolicyGru* gru, gq::PolicyDev& D, const char* who, const int scan_cells = 0) {
+  gq::PolicyMlpDev& P = D.seat;
+  gq::GruDev& G = D.gru;
   if (gru->hidden < 1 || gru->hidden > GQ_GRU_MAXH) { SET_ERR("%s: hidden = %d: 1 to %d are supported", who, gru->hidden, GQ_GRU_MAXH); return GQ_EINVAL; }
-  if (mlp->n_layers < 1 || mlp->n_layers > GQ_GRU_HEAD_MAXL) { SET_ERR("%s: the head has %d linear layers: 1 to %d are supported", who, mlp->n_layers, GQ_GRU_HEAD_MAXL); return GQ_EINVAL; }
-  const int in_dim = mlp->in_obs + scan_cells + (mlp->feed_last_action ? 12 : 0);
-  if (mlp->in_obs < 0) { SET_ERR("%s: in_obs = %d", who, mlp->in_obs); return GQ_EINVAL; }
-  if (in_dim < 1 || in_dim > GQ_MLP_MAXW) { SET_ERR("%s: the cell's input has %d columns: 1 to %d are supported", who, in_dim, GQ_MLP_MAXW); return GQ_EINVAL; }
-  gq::PolicyMlpDev& P = G.mlp;
-  for (int l = 0; l < mlp->n_layers; l++)
-    if (mlp->width[l] < 1 || mlp->width[l] > GQ_MLP_MAXW) { SET_ERR("%s: layer %d of the head has %d outputs: 1 to %d are supported", who, l, mlp->width[l], GQ_MLP_MAXW); return GQ_EINVAL; }
-  if (mlp->width[mlp->n_layers - 1] != 12) { SET_ERR("%s: the head has %d outputs: 12 (one per hinge) are needed", who, mlp->width[mlp->n_layers - 1]); return GQ_EINVAL; }
-  if (mlp->activation < GQ_ACT_RELU || mlp->activation > GQ_ACT_TANH) { SET_ERR("%s: activation %d: relu (1), elu (2) or tanh (3)", who, mlp->activation); return GQ_EINVAL; }
-  if (mlp->out_activation != GQ_ACT_NONE && mlp->out_activation != GQ_ACT_TANH) { SET_ERR("%s: out_activation %d: none (0) or tanh (3)", who, mlp->out_activation); return GQ_EINVAL; }
+  if (const int rc = net_describe(mlp, P, who, true, scan_cells, 0); rc != GQ_OK) return rc;
   if (!gru->blob) { SET_ERR("%s: GqPolicyGru.blob is null", who); return GQ_EINVAL; }
-  G.cell.in_dim = in_dim; G.cell.hidden = gru->hidden;
-  P.net.n_layers = mlp->n_layers; P.net.in_dim = gru->hidden; P.net.act = mlp->activation; P.net.out_act = mlp->out_activation;
-  for (int l = 0; l < GQ_MLP_MAXL; l++) P.net.width[l] = l < mlp->n_layers ? mlp->width[l] : 0;
+  G.cell.in_dim = P.net.in_dim; G.cell.hidden = gru->hidden; /* the row feeds the cell, the cell the head */
+  P.net.in_dim = gru->hidden;
   const long long want = (long long)gq::gru_blob_floats(G.cell, P.net);
   if (gru->blob_floats != want) { SET_ERR("%s: GqPolicyGru.blob_floats is %lld, this cell and head have %lld", who, (long long)gru->blob_floats, want); return GQ_EINVAL; }
-  P.in_obs = mlp->in_obs; P.feed_last = mlp->feed_last_action ? 1 : 0; P.decimation = mlp->decimation; P.pad_ = 0; P.pad2_ = 0;
-  G.blob = gru->blob; P.blob = gru->blob + gq::gru_cell_floats(G.cell); P.shift = mlp->obs_shift; P.scale = mlp->obs_scale;
+  G.blob = gru->blob; P.blob = gru->blob + gq::gru_cell_floats(G.cell);
   return GQ_OK;
 }
 
@@ -775,7 +779,7 @@ static int foot_describe(const GqBatch* b, const GqFootReward* feet, gq::FootLaw
 
 /* ---- the height scan's block (gq_policy_scan.h) from the C block: the law's parameters checked; with a batch, the grid held to the batch's
  * base-following map and the base's z column resolved in its observation row (b null: gq_height_scan_eval, the law alone) ---- */
-static int scan_describe(const GqBatch* b, const GqPolicyScan* scan, gq::PolicyScanDev& S, const char* who) {
+static int scan_describe(const GqBatch* b, const GqPolicyScan* scan, gq::ScanDev& S, const char* who) {
   if (!std::isfinite(scan->offset) || !std::isfinite(scan->clip) || !std::isfinite(scan->scale)) { SET_ERR("%s: the height scan's offset, clip and scale must be finite (got %g, %g, %g)", who, (double)scan->offset, (double)scan->clip, (double)scan->scale); return GQ_EINVAL; }
   if (!(scan->clip > 0.0f)) { SET_ERR("%s: the height scan's clip = %g: it must be positive", who, (double)scan->clip); return GQ_EINVAL; }
   if (scan->rows <= 0 || scan->cols <= 0 || scan->rows > 4096 || scan->cols > 4096 || scan->rows * scan->cols > 4096) { SET_ERR("%s: the height scan's grid is %d x %d", who, scan->rows, scan->cols); return GQ_EINVAL; }
@@ -822,28 +826,22 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
   if (mlp->in_obs > b->host.obs_dim) { SET_ERR("%s: in_obs = %d, the observation row has %d columns", who, mlp->in_obs, b->host.obs_dim); return GQ_EINVAL; }
-  gq::PolicyHistDev HD = b->mb.hist.shadow;
-  gq::PolicyScanDev Sm = b->mb.scan.shadow;
-  gq::PolicyScanDev& S = hist ? HD.scan : Sm;  /* with a history the scan's block - used or not - is the first member of the history's */
+  gq::PolicyDev PD = policy_block(b->mb);
+  gq::PolicyMlpDev& P = PD.seat;
   if (scan) {
-    if (const int rc = scan_describe(b, scan, S, who); rc != GQ_OK) return rc;
-  } else if (hist) {
-    S.law = gq::ScanLaw{}; S.cells = 0; S.col_z = -1; S.pad_[0] = S.pad_[1] = S.pad_[2] = 0; S.hits = nullptr;
+    if (const int rc = scan_describe(b, scan, PD.scan, who); rc != GQ_OK) return rc;
   }
-  const int scan_cells = scan ? S.cells : 0;
+  const int scan_cells = PD.scan.cells;
   if (hist) {
-    if (const int rc = hist_describe(mlp, hist, scan_cells, HD.law, who); rc != GQ_OK) return rc;
-    HD.state = hist->state; HD.ctl = hist->ctl;
+    if (const int rc = hist_describe(mlp, hist, scan_cells, PD.hist.law, who); rc != GQ_OK) return rc;
+    PD.hist.state = hist->state; PD.hist.ctl = hist->ctl;
   }
-  const int hist_words = hist ? gq::hist_words(HD.law) : 0;
-  gq::PolicyGruDev Gm = b->mb.gru.shadow;
-  gq::PolicyGruDev& G = scan || hist ? S.seat : Gm;  /* with a scan the seat's block - MLP or recurrent - is the first member of the scan's */
-  gq::PolicyMlpDev Pm = b->mb.mlp.shadow; /* a copy of the shadow, then the fields: see Staged */
-  gq::PolicyMlpDev& P = gru || scan || hist ? G.mlp : Pm;
+  const int hist_words = hist ? gq::hist_words(PD.hist.law) : 0;
   if (gru) {
-    if (const int rc = gru_describe(mlp, gru, G, who, scan_cells); rc != GQ_OK) return rc;
+    if (const int rc = gru_describe(mlp, gru, PD, who, scan_cells); rc != GQ_OK) return rc;
     if (!gru->hidden_state) { SET_ERR("%s: GqPolicyGru.hidden_state (device [N][hidden], in / out) is null", who); return GQ_EINVAL; }
-  } else if (const int rc = mlp_describe(mlp, P, who, scan_cells, hist_words); rc != GQ_OK) return rc;
+    PD.gru.hidden_state = gru->hidden_state; PD.gru.hidden_seq = gru->hidden_seq;
+  } else if (const int rc = mlp_describe(mlp, PD, who, scan_cells, hist_words); rc != GQ_OK) return rc;
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, gru ? "GRU" : "MLP"); rc != GQ_OK) return rc;
@@ -877,20 +875,8 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   P.step0 = mlp->noise_step0; P.env_id_offset = auto_reset ? auto_reset->env_id_offset : 0;
   P.issued = h.issued; P.held = mb.held.get(); P.last = mb.last.get(); P.policy_actions = mlp->policy_actions;
   P.learn = learn ? mb.learn.dev.get() : nullptr;
-  if (gru) {
-    G.hidden_state = gru->hidden_state; G.hidden_seq = gru->hidden_seq;
-    G.terminated = out.terminated; G.pending = b->p.pending;
-  }
-  if (hist) {
-    G.terminated = out.terminated; G.pending = b->p.pending; /* the episode rule's flags, where the recurrent seat has them */
-    HIP_TRY(mb.hist.push(HD, stream, true));
-  } else if (scan) {
-    HIP_TRY(mb.scan.push(S, stream, true));
-  } else if (gru) {
-    HIP_TRY(mb.gru.push(G, stream, true));
-  } else {
-    HIP_TRY(mb.mlp.push(P, stream, true));
-  }
+  if (gru || hist) { PD.episode.terminated = out.terminated; PD.episode.pending = b->p.pending; } /* both episode rules read them */
+  HIP_TRY(mb.net.push(PD, stream, true));
   HIP_TRY(hipMemsetAsync(mb.last.get(), 0, sizeof(float) * 12 * (size_t)N, stream)); /* the first policy step of a call sees zeros */
   if (learn) {
     /* the reward is evaluated when anything of it is asked for (a spec without a weighted term is a reward of zero) */
@@ -904,10 +890,10 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  if (hist) gq_launch_policy_hist(mb.dev.get(), mb.hist.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), scan != nullptr, mb.stream.get());
-  else if (scan) gq_launch_policy_scan(mb.dev.get(), mb.scan.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), gru != nullptr, mb.stream.get());
-  else if (gru) gq_launch_policy_gru(mb.dev.get(), mb.gru.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
-  else gq_launch_policy_mlp(mb.dev.get(), mb.mlp.dev.get(), out.obs, od, policy_waves, feet_on ? 2 : (learn ? 1 : 0), mb.stream.get());
+  const int mode = (feet_on ? 2 : (learn ? 1 : 0)) | (gru ? 4 : 0) | (scan ? 8 : 0) | (hist ? 16 : 0); /* policy_mlp_kernel's MODE */
+  if (!gq_launch_policy(mb.dev.get(), mb.net.dev.get(), out.obs, od, policy_waves, mode, mb.stream.get())) {
+    SET_ERR("%s: no policy kernel for this combination of recurrent policy, height scan and observation history (mode %d)", who, mode); return GQ_EINVAL;
+  }
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
 }
@@ -991,12 +977,12 @@ int gq_policy_mlp_eval(GqBatch* b, const GqPolicyMlp* mlp, const float* rows, in
   if (!b || !rows || !out || n_rows < 0 || (impl != 0 && impl != 1)) { SET_ERR("gq_policy_mlp_eval: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
-  gq::PolicyMlpDev P = b->mb.mlp.shadow;
-  if (const int rc = mlp_describe(mlp, P, who); rc != GQ_OK) return rc;
+  gq::PolicyDev PD = policy_block(b->mb);
+  if (const int rc = mlp_describe(mlp, PD, who); rc != GQ_OK) return rc;
   if (n_rows == 0) return GQ_OK;
   hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(b->mb.mlp.push(P, stream, true));
-  gq_launch_policy_mlp_eval(b->mb.mlp.dev.get(), rows, n_rows, impl, out, stream);
+  HIP_TRY(b->mb.net.push(PD, stream, true));
+  gq_launch_policy_mlp_eval(b->mb.net.dev.get(), rows, n_rows, impl, out, stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }
@@ -1005,7 +991,7 @@ int gq_height_scan_eval(GqBatch* b, const GqPolicyScan* scan, const float* hits,
   const char* const who = "gq_height_scan_eval";
   if (!fresh(scan, "GqPolicyScan", who)) return GQ_EINVAL;
   if (!b || !hits || !z || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  gq::PolicyScanDev S{};
+  gq::ScanDev S{};
   if (const int rc = scan_describe(nullptr, scan, S, who); rc != GQ_OK) return rc;
   if (n == 0) return GQ_OK;
   DeviceGuard guard(b->model->device);
@@ -1021,13 +1007,13 @@ int gq_policy_gru_eval(GqBatch* b, const GqPolicyMlp* mlp, const GqPolicyGru* gr
   if (!b || !rows || !h_in || !out || !h_out || n_rows < 0 || (impl != 0 && impl != 1)) { SET_ERR("gq_policy_gru_eval: bad argument"); return GQ_EINVAL; }
   DeviceGuard guard(b->model->device);
   if (const int rc = mailbox_setup(b); rc != GQ_OK) return rc;
-  gq::PolicyGruDev G = b->mb.gru.shadow;
-  if (const int rc = gru_describe(mlp, gru, G, who); rc != GQ_OK) return rc;
+  gq::PolicyDev PD = policy_block(b->mb);
+  if (const int rc = gru_describe(mlp, gru, PD, who); rc != GQ_OK) return rc;
   if (n_rows == 0) return GQ_OK;
-  G.hidden_state = const_cast<float*>(h_in); G.hidden_seq = h_out; /* the kernels read the first, write the second */
+  PD.gru.hidden_state = const_cast<float*>(h_in); PD.gru.hidden_seq = h_out; /* the kernels read the first, write the second */
   hipStream_t stream = (hipStream_t)hip_stream;
-  HIP_TRY(b->mb.gru.push(G, stream, true));
-  gq_launch_policy_gru_eval(b->mb.gru.dev.get(), rows, n_rows, impl, out, stream);
+  HIP_TRY(b->mb.net.push(PD, stream, true));
+  gq_launch_policy_gru_eval(b->mb.net.dev.get(), rows, n_rows, impl, out, stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

@@ -12,11 +12,8 @@
 #include <gq_device.h>
 #include "gq_step_body.h"
 #include "gq_foot_cmd.h"
-#include "gq_policy_mlp.h"
 #include "gq_learn.h"
-#include "gq_policy_gru.h"
-#include "gq_policy_scan.h"
-#include "gq_policy_hist.h"
+#include "gq_policy_dev.h"
 #include "gq_camera.h"
 
 /* Parallel build (csrc/Makefile): this file is compiled once per part (-DGQ_PART=k; the variants are 60 large, fully inlined kernels - one
@@ -181,26 +178,28 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * has 280 SGPR spills (to VGPR lanes, no scratch) against 252: the step's reward now leaves learn_step as a value and is added to acc under
  * a second `if (earns)` in learn_visit, where it was added inside the branch that evaluated it.
  * RECURRENT (MODE & 4, gq_rollout_policy_gru; MODE 0 .. 2 compile to the kernels they were): the network is a GRU cell and a head
- * (gq_policy_gru.h), Pp points at the first member of a PolicyGruDev.  The episode rule runs for every ready lane before the tile loop; the
+ * (gq_policy_gru.h), the block's gru part.  The episode rule runs for every ready lane before the tile loop; the
  * tile stage also loads each row's hidden state (device scope: the row is its env's lane's store of an earlier visit) - a row the rule
  * zeroed in THIS visit is staged as zeros from the lane's own flag, not from memory - and h' is stored by the env's own lane between the
- * cell and the head.  The flags come from the recurrent block: P.learn is not read in mode 4.
- * HEIGHT SCAN (MODE & 8, gq_rollout_policy_scan, with every mode above; MODE 0 .. 6 compile to the kernels they were): Pp points at the first
- * member of a PolicyScanDev, and the input row has a middle block, columns in_obs .. in_obs + cells - 1: the scan law (gq_policy_scan.h) on
+ * cell and the head.  The flags come from the block's episode part: P.learn is not read in mode 4.
+ * THE INPUT ROW of every mode is policy_row_value (gq_policy_dev.h, its one definition), called once per staged word with device-scope
+ * memory access; the wave-level work around it - which lane's env is which row of the tile, that row's sources - is done here.
+ * HEIGHT SCAN (MODE & 8, gq_rollout_policy_scan, with every mode above; MODE 0 .. 6 compile to the kernels they were): the input row has a
+ * middle block, the scan law (gq_policy_scan.h) on
  * word 2 of the env's hit points - the batch's base-following HeightMap, whose rays the env's stepping wavefront cast in the step whose
  * observation row is being fed - and the z column of that row.  Both are device-scope loads.  The hit words are plain stores of the stepping
  * wavefront, like the env's state rows: it waits for them (publish_fence, vmcnt(0)) before it raises steps_done, policy and stepping
  * wavefront of an env share one XCD (gq_mailbox.h), so they are in that XCD's L2 when the count is seen and a load that misses the L1 reads
  * them.  The last-action columns follow the scan; scan words are recorded in policy_obs like every other word the network is fed.
  * OBSERVATION HISTORY (MODE & 16, gq_rollout_policy_hist, the MLP's modes with or without the scan; MODE 0 .. 14 compile to the kernels they
- * were): Pp points at the first member of a PolicyHistDev, and the frames of the env's last L policy steps follow the last action
- * (gq_policy_hist.h: the law, the two-buffer store, the episode rule).  The rule runs for every ready lane before the tile loop and costs one
+ * were): the frames of the env's last L policy steps follow the last action (gq_policy_hist.h: the law, the two-buffer store, the episode
+ * rule).  The rule runs for every ready lane before the tile loop and costs one
  * control word; whoever stages a word of the current block also stores it as the newest frame of the env's OTHER buffer, whoever stages a
  * history word moves it one slot on into that buffer - every word has one staging lane, and nobody writes the buffer being read.  History
  * words are stores of another visit of this launch, possibly by another lane of this wavefront: device-scope loads and stores, as for the
  * hidden state (a plain load may hit the line an earlier plain load left in the vector L1).  The control word is the env's own lane's. */
 template <int MODE>
-__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   constexpr bool GRU = (MODE & 4) != 0;
   constexpr bool SCAN = (MODE & 8) != 0;
   constexpr bool HIST = (MODE & 16) != 0;
@@ -209,31 +208,30 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
   constexpr bool LEARN = LMODE != 0;
   __shared__ __attribute__((aligned(16))) float xt[GRU ? 3 : 2][GQ_MLP_MAXW * GQ_MLP_ROWS];
   const GQ_MODEL MailboxDev& MB = *mptr(MBp);
-  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+  const GQ_MODEL PolicyDev& PD = *mptr(Pp);
+  const GQ_MODEL PolicyMlpDev& P = PD.seat;
   const int lane = (int)threadIdx.x, nq = MB.nq, q = MB.xcc_queue[xcc_id()], qmask = MB.qcap - 1, qshift = __builtin_ctz(MB.qcap);
   const int N = MB.n_envs, K = MB.n_steps, D = P.decimation;
   GQ_MB_POLICY_REGISTER() /* rank, mine, t_last (gq_mailbox.h) */
   const MlpNet net = mlp_net_load(P.net);
   [[maybe_unused]] GruNet cell{};
-  if constexpr (GRU) cell = gru_net_load(mptr(reinterpret_cast<const PolicyGruDev*>(Pp))->cell);
-  const int in_obs = P.in_obs, in_dim = GRU ? cell.in_dim : net.in_dim;
-  const float* const shift = P.shift;
-  const float* const scale = P.scale;
-  [[maybe_unused]] ScanLaw scan_law{};
-  [[maybe_unused]] int scan_cells = 0, scan_col_z = 0;
+  if constexpr (GRU) cell = gru_net_load(PD.gru.cell);
+  const int in_dim = GRU ? cell.in_dim : net.in_dim;
+  RowLaw row_law{}; /* the input row (gq_policy_dev.h) */
+  row_law.in_obs = P.in_obs; row_law.in_dim = in_dim; row_law.shift = P.shift; row_law.scale = P.scale;
+  [[maybe_unused]] int scan_col_z = 0;
   [[maybe_unused]] const float* scan_hits = nullptr;
   if constexpr (SCAN) {
-    const GQ_MODEL PolicyScanDev& SD = *mptr(reinterpret_cast<const PolicyScanDev*>(Pp));
-    scan_law.offset = SD.law.offset; scan_law.clip = SD.law.clip; scan_law.scale = SD.law.scale;
-    scan_cells = SD.cells; scan_col_z = SD.col_z; scan_hits = SD.hits;
+    row_law.scan.offset = PD.scan.law.offset; row_law.scan.clip = PD.scan.law.clip; row_law.scan.scale = PD.scan.law.scale;
+    row_law.cells = PD.scan.cells; scan_col_z = PD.scan.col_z; scan_hits = PD.scan.hits;
   }
-  [[maybe_unused]] HistLaw hist{};
+  const HistLaw& hist = row_law.hist;
   [[maybe_unused]] float* hist_state = nullptr;
   [[maybe_unused]] int32_t* hist_ctl = nullptr;
   if constexpr (HIST) {
-    const GQ_MODEL PolicyHistDev& HD = *mptr(reinterpret_cast<const PolicyHistDev*>(Pp));
-    hist.frames = HD.law.frames; hist.cols = HD.law.cols; hist.width = HD.law.width; hist.col0 = HD.law.col0; hist.inv = HD.law.inv;
-    hist_state = HD.state; hist_ctl = HD.ctl;
+    const GQ_MODEL HistLaw& HL = PD.hist.law;
+    row_law.hist.frames = HL.frames; row_law.hist.cols = HL.cols; row_law.hist.width = HL.width; row_law.hist.col0 = HL.col0; row_law.hist.inv = HL.inv;
+    hist_state = PD.hist.state; hist_ctl = PD.hist.ctl;
   }
   const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int G = mine * GQ_WAVE;
@@ -254,13 +252,11 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
       float a[12];
       [[maybe_unused]] bool h_zeroed = false;
       if constexpr (GRU) { /* the episode rule (gq_policy_gru.h), before any cell evaluation of this visit */
-        const GQ_MODEL PolicyGruDev& GP = *mptr(reinterpret_cast<const PolicyGruDev*>(Pp));
-        if (ready) h_zeroed = gru_episode_rule<LearnPub>(GP.terminated, GP.pending, GP.hidden_state, cell.hidden, e, k);
+        if (ready) h_zeroed = gru_episode_rule<LearnPub>(PD.episode.terminated, PD.episode.pending, PD.gru.hidden_state, cell.hidden, e, k);
       }
       [[maybe_unused]] int hist_c = 0;
       if constexpr (HIST) { /* the episode rule of the history (gq_policy_hist.h), before anything of this visit is staged */
-        const GQ_MODEL PolicyGruDev& SP = mptr(reinterpret_cast<const PolicyHistDev*>(Pp))->scan.seat;
-        if (ready) hist_c = hist_episode_rule<LearnPub>(SP.terminated, SP.pending, hist_ctl, e, k);
+        if (ready) hist_c = hist_episode_rule<LearnPub>(PD.episode.terminated, PD.episode.pending, hist_ctl, e, k);
       }
       if constexpr (LEARN) { /* the visit of the window law (gq_learn.h): step k - 1 is evaluated, the window flushed at k % D == 0 */
         const GQ_MODEL LearnFeetDev& LF = *mptr(P.learn);
@@ -277,75 +273,30 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
         }
         todo &= ~tile;
         const int er = shfl_idx(e, src < 0 ? 0 : src);
-        const float* const row = obs + (size_t)er * od;
-        const float* const prev = P.last + (size_t)er * 12;
-        [[maybe_unused]] float* rec_row = nullptr; /* LEARN: the row as the network is fed it, before shift / scale */
-        if constexpr (LEARN) {
+        RowSrc rs{}; /* the sources of this lane's row */
+        rs.obs = obs + (size_t)er * od;
+        rs.last = P.last + (size_t)er * 12;
+        if constexpr (LEARN) { /* the row as the network is fed it, before shift / scale */
           const int kr = shfl_idx(k, src < 0 ? 0 : src);
           float* const rec = mptr(P.learn)->learn.policy_obs;
-          if (rec) rec_row = rec + ((size_t)(kr / D) * N + er) * in_dim;
+          if (rec) rs.rec = rec + ((size_t)(kr / D) * N + er) * in_dim;
         }
-        [[maybe_unused]] float z_base = 0.0f;       /* SCAN: the base's z of this lane's row, and the row's hit points */
-        [[maybe_unused]] const float* hit_row = nullptr;
         if constexpr (SCAN) {
-          if (src >= 0) z_base = ld_pub(row + scan_col_z);
-          hit_row = scan_hits + (size_t)er * (size_t)scan_cells * 3;
+          if (src >= 0) rs.z_base = ld_pub(rs.obs + scan_col_z);
+          rs.hits = scan_hits + (size_t)er * (size_t)row_law.cells * 3;
         }
-        [[maybe_unused]] int hc_r = 0;              /* HIST: the control word of this lane's row, and the row's store */
-        [[maybe_unused]] float* hist_row = nullptr;
         if constexpr (HIST) {
-          hc_r = shfl_idx(hist_c, src < 0 ? 0 : src);
-          hist_row = hist_state + (size_t)er * hist_env_floats(hist);
+          rs.hist_ctl = shfl_idx(hist_c, src < 0 ? 0 : src);
+          rs.hist = hist_state + (size_t)er * hist_env_floats(hist);
         }
-        const auto x_value = [&](const int, const int c) {
-          if (src < 0 || c >= in_dim) return 0.0f;
-          const auto word = [&](const float* const p) { /* a device-scope load, recorded with LEARN */
-            const float o = ld_pub(p);
-            if constexpr (LEARN) {
-              if (rec_row) rec_row[c] = o;
-            }
-            return o;
-          };
-          if constexpr (HIST) {
-            if (c >= hist.col0) { /* a word of frame_1 .. frame_L: raw in the store and in the record, shift / scale by its original column */
-              int w;
-              const float o = hist_stage_frame<LearnPub>(hist, hist_row, hc_r, c - hist.col0, &w);
-              if constexpr (LEARN) {
-                if (rec_row) rec_row[c] = o;
-              }
-              return w < hist.cols ? mlp_obs_in(o, shift, scale, w) : o;
-            }
-            if (c < in_obs) {
-              const float o = word(row + c);
-              if (c < hist.cols) hist_stage_current<LearnPub>(hist, hist_row, hc_r, c, o);
-              return mlp_obs_in(o, shift, scale, c);
-            }
-            if (c >= in_obs + scan_cells) { /* the last action: the tail of the current frame */
-              const float o = word(prev + (c - in_obs - scan_cells));
-              hist_stage_current<LearnPub>(hist, hist_row, hc_r, hist.cols + (c - in_obs - scan_cells), o);
-              return o;
-            }
-          }
-          if (c < in_obs) return mlp_obs_in(word(row + c), shift, scale, c);
-          if constexpr (SCAN) {
-            const int cell = c - in_obs;
-            if (cell >= scan_cells) return word(prev + (cell - scan_cells)); /* the last action, behind the scan */
-            const float s = height_scan_cell(scan_law, z_base, ld_pub(hit_row + 3 * cell + 2));
-            if constexpr (LEARN) {
-              if (rec_row) rec_row[c] = s;
-            }
-            return s;
-          }
-          return word(prev + (c - in_obs));
-        };
+        const auto x_value = [&](const int, const int c) { return src < 0 ? 0.0f : policy_row_value<SCAN, HIST, LearnPub>(row_law, rs, c); };
         const float* out;
         if constexpr (GRU) {
-          const GQ_MODEL PolicyGruDev& GP = *mptr(reinterpret_cast<const PolicyGruDev*>(Pp));
           const int H = cell.hidden;
           const bool zr = shfl_idx((int)h_zeroed, src < 0 ? 0 : src) != 0;
           const int kr = shfl_idx(k, src < 0 ? 0 : src);
-          const float* const hrow = GP.hidden_state + (size_t)er * H;
-          float* const hrec = GP.hidden_seq ? GP.hidden_seq + ((size_t)(kr / D) * N + er) * H : nullptr; /* the state as the cell is fed it */
+          const float* const hrow = PD.gru.hidden_state + (size_t)er * H;
+          float* const hrec = PD.gru.hidden_seq ? PD.gru.hidden_seq + ((size_t)(kr / D) * N + er) * H : nullptr; /* the state as the cell is fed it */
           wave_barrier(); /* whoever still read the buffers has done so */
           gru_tile_stage(mlp_kp(in_dim), &xt[0][0], x_value);
           gru_tile_stage(mlp_np(H), &xt[1][0], [&](const int, const int c) {
@@ -356,9 +307,9 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           });
           const bool owns = fresh && ((tile >> lane) & 1);
           const int hslot = popc64(tile & (((uint64_t)1 << lane) - 1));
-          out = gru_tile_forward(cell, net, GP.blob, P.blob, &xt[0][0], [&](const float* hn) { /* h': by the env's own lane, like acc / wstate */
+          out = gru_tile_forward(cell, net, PD.gru.blob, P.blob, &xt[0][0], [&](const float* hn) { /* h': by the env's own lane, like acc / wstate */
             if (owns)
-              for (int c = 0; c < H; c++) st_pub(GP.hidden_state + (size_t)e * H + c, hn[c * GQ_MLP_ROWS + hslot]);
+              for (int c = 0; c < H; c++) st_pub(PD.gru.hidden_state + (size_t)e * H + c, hn[c * GQ_MLP_ROWS + hslot]);
           });
         } else {
           mlp_tile_stage(net, xt[0], x_value);
@@ -432,8 +383,8 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
 
 /* the network alone over rows [n][in_dim] (gq_policy_mlp_eval): the two forms of the law side by side, so that their bits can be compared.
  * shift / scale act on the first in_obs columns, as in the rollout. */
-__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_row_kernel(const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
-  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_row_kernel(const PolicyDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  const GQ_MODEL PolicyMlpDev& P = mptr(Pp)->seat;
   const MlpNet net = mlp_net_load(P.net);
   const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x);
   if (r >= n) return;
@@ -442,9 +393,9 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_row_kernel(const Poli
   mlp_row_forward(net, P.blob, x, y);
   for (int j = 0; j < 12; j++) out[(size_t)r * 12 + j] = y[j];
 }
-__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const PolicyMlpDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+__global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const PolicyDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float xt[2][GQ_MLP_MAXW * GQ_MLP_ROWS];
-  const GQ_MODEL PolicyMlpDev& P = *mptr(Pp);
+  const GQ_MODEL PolicyMlpDev& P = mptr(Pp)->seat;
   const MlpNet net = mlp_net_load(P.net);
   const int lane = (int)threadIdx.x, r0 = (int)blockIdx.x * GQ_MLP_ROWS, in_dim = net.in_dim, in_obs = P.in_obs;
   const float* const shift = P.shift;
@@ -462,28 +413,30 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_eval_tile_kernel(const Pol
 }
 
 /* the recurrent policy alone over rows [n][in_dim] and states [n][H] (gq_policy_gru_eval): the two forms of gq_policy_gru.h side by side.
- * G.hidden_state: h_in, G.hidden_seq: h_out (read / written plainly: nothing else runs on them) */
-__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_row_kernel(const PolicyGruDev* __restrict__ Gp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
-  const GQ_MODEL PolicyGruDev& GP = *mptr(Gp);
-  const MlpNet head = mlp_net_load(GP.mlp.net);
+ * gru.hidden_state: h_in, gru.hidden_seq: h_out (read / written plainly: nothing else runs on them) */
+__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_row_kernel(const PolicyDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+  const GQ_MODEL PolicyMlpDev& P = mptr(Pp)->seat;
+  const GQ_MODEL GruDev& GP = mptr(Pp)->gru;
+  const MlpNet head = mlp_net_load(P.net);
   const GruNet cell = gru_net_load(GP.cell);
   const int r = (int)(blockIdx.x * GQ_WAVE + threadIdx.x), H = cell.hidden;
   if (r >= n) return;
   float x[GQ_MLP_MAXW], h[GQ_GRU_MAXH], hn[GQ_GRU_MAXH], y[GQ_MLP_ROWS];
-  for (int c = 0; c < cell.in_dim; c++) { const float v = rows[(size_t)r * cell.in_dim + c]; x[c] = c < GP.mlp.in_obs ? mlp_obs_in(v, GP.mlp.shift, GP.mlp.scale, c) : v; }
+  for (int c = 0; c < cell.in_dim; c++) { const float v = rows[(size_t)r * cell.in_dim + c]; x[c] = c < P.in_obs ? mlp_obs_in(v, P.shift, P.scale, c) : v; }
   for (int c = 0; c < H; c++) h[c] = GP.hidden_state[(size_t)r * H + c];
   gru_row_forward(cell, head, GP.blob, x, h, y, hn);
   for (int j = 0; j < 12; j++) out[(size_t)r * 12 + j] = y[j];
   for (int c = 0; c < H; c++) GP.hidden_seq[(size_t)r * H + c] = hn[c];
 }
-__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_tile_kernel(const PolicyGruDev* __restrict__ Gp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
+__global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_tile_kernel(const PolicyDev* __restrict__ Pp, const float* __restrict__ rows, const int n, float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float xt[GQ_GRU_LDS_FLOATS];
-  const GQ_MODEL PolicyGruDev& GP = *mptr(Gp);
-  const MlpNet head = mlp_net_load(GP.mlp.net);
+  const GQ_MODEL PolicyMlpDev& P = mptr(Pp)->seat;
+  const GQ_MODEL GruDev& GP = mptr(Pp)->gru;
+  const MlpNet head = mlp_net_load(P.net);
   const GruNet cell = gru_net_load(GP.cell);
-  const int lane = (int)threadIdx.x, r0 = (int)blockIdx.x * GQ_MLP_ROWS, in_dim = cell.in_dim, in_obs = GP.mlp.in_obs, H = cell.hidden;
-  const float* const shift = GP.mlp.shift;
-  const float* const scale = GP.mlp.scale;
+  const int lane = (int)threadIdx.x, r0 = (int)blockIdx.x * GQ_MLP_ROWS, in_dim = cell.in_dim, in_obs = P.in_obs, H = cell.hidden;
+  const float* const shift = P.shift;
+  const float* const scale = P.scale;
   const float* const h_in = GP.hidden_state;
   float* const h_out = GP.hidden_seq;
   gru_tile_stage(mlp_kp(in_dim), xt, [&](const int r, const int c) {
@@ -492,7 +445,7 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_gru_eval_tile_kernel(const Pol
     return c < in_obs ? mlp_obs_in(v, shift, scale, c) : v;
   });
   gru_tile_stage(mlp_np(H), xt + GQ_GRU_REGION, [&](const int r, const int c) { return (r0 + r >= n || c >= H) ? 0.0f : h_in[(size_t)(r0 + r) * H + c]; });
-  const float* const y = gru_tile_forward(cell, head, GP.blob, GP.mlp.blob, xt, [&](const float* hn) {
+  const float* const y = gru_tile_forward(cell, head, GP.blob, P.blob, xt, [&](const float* hn) {
     for (int w = lane; w < GQ_MLP_ROWS * H; w += GQ_WAVE) {
       const int r = w / H, c = w % H;
       if (r0 + r < n) h_out[(size_t)(r0 + r) * H + c] = hn[c * GQ_MLP_ROWS + r];
@@ -778,43 +731,30 @@ extern "C" void gq_launch_xcc_probe(int32_t* mask, hipStream_t stream) {
 extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPdDev* pd, const float* obs, int od, int waves, hipStream_t stream) {
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
-/* mode 0: gq_rollout_policy, 1: the learning half, 2: the learning half with the foot terms */
-extern "C" void gq_launch_policy_mlp(const gq::MailboxDev* mb, const gq::PolicyMlpDev* mlp, const float* obs, int od, int waves, int mode, hipStream_t stream) {
-  if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<2>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
-  else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<1>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
-  else hipLaunchKernelGGL(gq::policy_mlp_kernel<0>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, mlp, obs, od);
+/* THE TABLE of policy_mlp_kernel's instantiations, MODE = learn mode (0: gq_rollout_policy, 1: the learning half, 2: with the foot terms)
+ * | 4 recurrent | 8 height scan | 16 observation history (the MLP's alone): listed here and nowhere else - the array below instantiates
+ * them, the loop dispatches to them.  Returns whether `mode` is in the table (nothing was launched otherwise). */
+using PolicyModes = std::integer_sequence<int, 0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, 16, 17, 18, 24, 25, 26>;
+template <int... M>
+static bool launch_policy_mode(std::integer_sequence<int, M...>, const int mode, const gq::MailboxDev* mb, const gq::PolicyDev* dev, const float* obs, int od, int waves, hipStream_t stream) {
+  using Kernel = void (*)(const gq::MailboxDev*, const gq::PolicyDev*, const float*, int);
+  static constexpr int modes[] = {M...};
+  static constexpr Kernel kernels[] = {&gq::policy_mlp_kernel<M>...};
+  for (size_t i = 0; i < sizeof...(M); i++)
+    if (modes[i] == mode) { hipLaunchKernelGGL(kernels[i], dim3(waves), dim3(GQ_WAVE), 0, stream, mb, dev, obs, od); return true; }
+  return false;
 }
-/* gq_rollout_policy_gru: the recurrent instantiations, mode as above; gru->mlp is the block the kernel's parameter points at */
-extern "C" void gq_launch_policy_gru(const gq::MailboxDev* mb, const gq::PolicyGruDev* gru, const float* obs, int od, int waves, int mode, hipStream_t stream) {
-  const gq::PolicyMlpDev* const seat = &gru->mlp; /* (address arithmetic on a device pointer: offset 0) */
-  if (mode == 2) hipLaunchKernelGGL(gq::policy_mlp_kernel<6>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
-  else if (mode == 1) hipLaunchKernelGGL(gq::policy_mlp_kernel<5>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
-  else hipLaunchKernelGGL(gq::policy_mlp_kernel<4>, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
-}
-/* gq_rollout_policy_scan: the instantiations with the height scan in the input row - mode as above, gru: the recurrent ones; scan->seat.mlp is
- * the block the kernel's parameter points at */
-extern "C" void gq_launch_policy_scan(const gq::MailboxDev* mb, const gq::PolicyScanDev* scan, const float* obs, int od, int waves, int mode, int gru, hipStream_t stream) {
-  const gq::PolicyMlpDev* const seat = &scan->seat.mlp; /* (address arithmetic on a device pointer: offset 0) */
-  const auto kernel = gru ? (mode == 2 ? gq::policy_mlp_kernel<14> : mode == 1 ? gq::policy_mlp_kernel<13> : gq::policy_mlp_kernel<12>)
-                          : (mode == 2 ? gq::policy_mlp_kernel<10> : mode == 1 ? gq::policy_mlp_kernel<9> : gq::policy_mlp_kernel<8>);
-  hipLaunchKernelGGL(kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
-}
-/* gq_rollout_policy_hist: the MLP's instantiations with the observation history - mode as above, scan: the ones with the height scan too;
- * hist->scan.seat.mlp is the block the kernel's parameter points at */
-extern "C" void gq_launch_policy_hist(const gq::MailboxDev* mb, const gq::PolicyHistDev* hist, const float* obs, int od, int waves, int mode, int scan, hipStream_t stream) {
-  const gq::PolicyMlpDev* const seat = &hist->scan.seat.mlp; /* (address arithmetic on a device pointer: offset 0) */
-  const auto kernel = scan ? (mode == 2 ? gq::policy_mlp_kernel<26> : mode == 1 ? gq::policy_mlp_kernel<25> : gq::policy_mlp_kernel<24>)
-                           : (mode == 2 ? gq::policy_mlp_kernel<18> : mode == 1 ? gq::policy_mlp_kernel<17> : gq::policy_mlp_kernel<16>);
-  hipLaunchKernelGGL(kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, seat, obs, od);
+extern "C" int gq_launch_policy(const gq::MailboxDev* mb, const gq::PolicyDev* dev, const float* obs, int od, int waves, int mode, hipStream_t stream) {
+  return launch_policy_mode(PolicyModes{}, mode, mb, dev, obs, od, waves, stream) ? 1 : 0;
 }
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream) {
   const long long total = (long long)n * cells;
   hipLaunchKernelGGL(gq::height_scan_eval_kernel, dim3((unsigned)((total + GQ_WAVE - 1) / GQ_WAVE)), dim3(GQ_WAVE), 0, stream, *law, hits, z, total, cells, out);
 }
 /* impl 0: gru_row_forward, a thread per row; 1: gru_tile_forward, a wavefront per 16 rows */
-extern "C" void gq_launch_policy_gru_eval(const gq::PolicyGruDev* gru, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
-  if (impl == 0) hipLaunchKernelGGL(gq::policy_gru_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, gru, rows, n_rows, out);
-  else hipLaunchKernelGGL(gq::policy_gru_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, gru, rows, n_rows, out);
+extern "C" void gq_launch_policy_gru_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
+  if (impl == 0) hipLaunchKernelGGL(gq::policy_gru_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, dev, rows, n_rows, out);
+  else hipLaunchKernelGGL(gq::policy_gru_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, dev, rows, n_rows, out);
 }
 /* feet 0: gq_reward_eval (air_in / air_out are not looked at), 1: gq_reward_eval_feet */
 extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float* rows, int od, const float* torques, const float* act, const float* act_prev,
@@ -823,9 +763,9 @@ extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float
   hipLaunchKernelGGL(kernel, dim3((n + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, learn, rows, od, torques, act, act_prev, terminated, air_in, n, out, air_out);
 }
 /* impl 0: mlp_row_forward, a thread per row; 1: mlp_tile_forward, a wavefront per 16 rows */
-extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyMlpDev* mlp, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
-  if (impl == 0) hipLaunchKernelGGL(gq::policy_mlp_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
-  else hipLaunchKernelGGL(gq::policy_mlp_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, mlp, rows, n_rows, out);
+extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {
+  if (impl == 0) hipLaunchKernelGGL(gq::policy_mlp_eval_row_kernel, dim3((n_rows + GQ_WAVE - 1) / GQ_WAVE), dim3(GQ_WAVE), 0, stream, dev, rows, n_rows, out);
+  else hipLaunchKernelGGL(gq::policy_mlp_eval_tile_kernel, dim3((n_rows + GQ_MLP_ROWS - 1) / GQ_MLP_ROWS), dim3(GQ_WAVE), 0, stream, dev, rows, n_rows, out);
 }
 extern "C" void gq_launch_jac(const GqDevModel* model, const double* qpos, int body, const double* point, float* jacp, float* jacr, int n_envs, hipStream_t stream) {
   hipLaunchKernelGGL(gq::jac_kernel, dim3(n_envs), dim3(GQ_WAVE), 0, stream, model, qpos, body, point, jacp, jacr);

@@ -21,7 +21,7 @@
 
 namespace gq {
 
-/* what a call of gq_rollout_policy_learn adds to PolicyMlpDev (device pointers) */
+/* what a call of gq_rollout_policy_learn adds to the policy's block (PolicyDev::seat.learn points at it; device pointers) */
 struct LearnDev {
   RewardLaw law;
   int32_t has_reward, pad_;

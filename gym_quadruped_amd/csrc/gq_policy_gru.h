@@ -1,7 +1,7 @@
 /*
  * gq_policy_gru.h - the RECURRENT policy of the closed-loop rollout (gq_rollout_policy_gru, gq_policy_gru_eval): one GRU cell followed by an
- * MLP head, the law in two forms that give the same bits, the weight blob both read, THE EPISODE RULE of the hidden state and the device
- * block of a call.  Plain C++ for host and device like gq_policy_mlp.h, on which everything here is built: a gate's pre-activation IS a layer
+ * MLP head, the law in two forms that give the same bits, the weight blob both read and THE EPISODE RULE of the hidden state (the device
+ * block of a call: gq_policy_dev.h).  Plain C++ for host and device like gq_policy_mlp.h, on which everything here is built: a gate's pre-activation IS a layer
  * of that header (y_o = the k-ascending fmaf chain from the bias, Kp | 4, Np | 16, what v_mfma_f32_16x16x4_f32 computes), the transcendental
  * arithmetic is its bit-defined mlp_tanh and nothing else.  Contraction off; the ORDER of the operations below is the definition.
  *
@@ -204,17 +204,4 @@ __host__ __device__ inline bool gru_episode_rule(const uint8_t* terminated, cons
     for (int c = 0; c < H; c++) Mem::st(hidden_state + (size_t)e * H + c, 0.0f);
   return reset;
 }
-
-/* what a call of gq_rollout_policy_gru hands to the recurrent instantiations of policy_mlp_kernel: the seat's block FIRST (the kernel's
- * parameter points at it) - its net is the HEAD (in_dim = hidden), its blob the head's layers, in_obs / feed_last / shift / scale describe
- * the cell's input row - then the cell.  The flags are carried here: the plain mode has no learn block. */
-struct PolicyGruDev {
-  PolicyMlpDev mlp;
-  GruNet cell;
-  const float* blob;            /* the six gate layers */
-  float* hidden_state;          /* [N][H] in / out (gq_policy_gru_eval: h_in [n][H]) */
-  float* hidden_seq;            /* [n_steps / decimation][N][H] the state FED at each policy step, after the rule, or NULL (eval: h_out [n][H]) */
-  const uint8_t* terminated;    /* [N] the batch's flag, as LearnDev's */
-  const uint8_t* pending;       /* [N] or NULL */
-};
 }  // namespace gq

@@ -1,12 +1,13 @@
 /*
  * gq_policy_hist.h - the OBSERVATION HISTORY of the closed-loop rollout's MLP policy (gq_rollout_policy_hist): the frames of the last L
- * policy steps as further columns of the input row, the per-env store that holds them across steps, windows and calls, THE EPISODE RULE of
- * that store and the device block of a call.  Plain C++: compiles with the product's gq_device.h and with the host shim (tests/simt_emu).
+ * policy steps as further columns of the input row, the per-env store that holds them across steps, windows and calls and THE EPISODE RULE of
+ * that store (the device block of a call: gq_policy_dev.h).  Plain C++: compiles with the product's gq_device.h and with the host shim
+ * (tests/simt_emu).
  *
  * THE LAW.  A FRAME is what the network was fed as its current block at one policy step, raw: the first `cols` observation words as loaded
- * (before shift / scale), then - with feed_last_action - the 12 fed-back action words of that step; F = cols + 12 f words.  The input row:
- *   x = [ obs_row[:in_obs] (shift / scale) | scan (if any) | last action (12, if fed) | frame_1 | ... | frame_L ]
- * frame_i is the frame of the policy step i steps back, newest first; in_dim = in_obs + cells + 12 f + L F <= 256.  When a frame is staged,
+ * (before shift / scale), then - with feed_last_action - the 12 fed-back action words of that step; F = cols + 12 f words.  The frames are
+ * the last columns of the input row, frame_1 .. frame_L from column col0 on (gq_policy_dev.h holds the row's one definition); frame_i is the
+ * frame of the policy step i steps back, newest first.  When a frame is staged,
  * shift / scale act on its observation words by their original column c < cols and not on its action words, so frame_i at step s carries
  * exactly the values the current block carried at step s - i.  policy_obs records the history words raw, as every other word.
  *
@@ -30,7 +31,7 @@
 #include <gq_device.h> /* angle brackets: the include path decides (csrc/ for the product, tests/simt_emu/ for the host programs) */
 #include <cstddef>
 #include <cstdint>
-#include "gq_policy_scan.h"
+#include "gq_learn.h" /* LearnPlain / LearnPub: the memory access of the store and its episode rule */
 
 namespace gq {
 
@@ -89,14 +90,4 @@ template <class Mem>
 __host__ __device__ inline void hist_push(int32_t* ctl, const int e, const int c) {
   Mem::st(ctl + e, ((c & HIST_PARITY) ^ 1) | HIST_VALID);
 }
-
-/* what a call of gq_rollout_policy_hist hands to the HIST instantiations of policy_mlp_kernel (MODE & 16): the scan's block FIRST - the
- * kernel's parameter points at scan.seat.mlp, as before; scan.cells is 0 and the rest of it unread without a scan - then the history's.
- * The flags travel in scan.seat.terminated / .pending, the fields the recurrent seat reads them from. */
-struct PolicyHistDev {
-  PolicyScanDev scan;
-  HistLaw law;
-  float* state;                 /* [N][2][L][F] the store */
-  int32_t* ctl;                 /* [N] the control words */
-};
 }  // namespace gq

@@ -1,6 +1,6 @@
 /*
  * gq_policy_mlp.h - the MLP policy of the closed-loop rollout (gq_rollout_policy, gq_policy_mlp_eval): the law of the network in two
- * forms that give the same bits, the weight blob both read, and the device block that carries a call's parameters to policy_mlp_kernel.
+ * forms that give the same bits, the weight blob both read, and the seat's part of the device block of a call (gq_policy_dev.h).
  * Compiles with the product's gq_device.h and with the host emulator's shim (tests/simt_emu): mlp_row_forward and everything it
  * uses is plain C++, only mlp_tile_forward needs the matrix cores.
  *
@@ -295,7 +295,7 @@ __device__ __forceinline__ void mlp_tile_stage(const MlpNet& net, float* xt0, F 
 }
 #endif /* __HIPCC__ */
 
-/* what a call of gq_rollout_policy hands to policy_mlp_kernel (device pointers), next to the MailboxDev it shares with the step side */
+/* the seat's part of a call's device block (PolicyDev, gq_policy_dev.h): the network, the leading columns of the input row, the loop */
 struct LearnFeetDev;
 struct PolicyMlpDev {
   MlpNet net;

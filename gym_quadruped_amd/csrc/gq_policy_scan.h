@@ -1,22 +1,20 @@
 /*
  * gq_policy_scan.h - the HEIGHT SCAN of the closed-loop rollout's policy (gq_rollout_policy_scan, gq_height_scan_eval): the law that turns
  * the hit points of the batch's base-following HeightMap (gq_batch_set_heightmap: [N][rows * cols][3], cast by the stepping wavefront at
- * every step) into columns of the policy's input row, and the device block that carries a call's parameters to the SCAN instantiations of
- * policy_mlp_kernel.  Plain C++: compiles with the product's gq_device.h and with the host shim (tests/simt_emu).
+ * every step) into columns of the policy's input row.  Where those columns stand in the row, and the device block of a call:
+ * gq_policy_dev.h.  Plain C++: compiles with the product's gq_device.h and with the host shim (tests/simt_emu).
  *
  * THE LAW, for cell c in the HeightMap's own cell order i * cols + j:
  *   s_c = clamp((z_base - offset) - z_hit_c, -clip, +clip) * scale
  * fp32, contraction off, one rounding per operation: two subtractions in the order written, fmaxf, fminf, one multiply.  z_hit_c is word 2
  * of the cell's hit point as the step kernel wrote it (a ray that hits nothing lands at pz + 1 above the ray's origin and saturates at
  * -clip); z_base is the z column of the env's observation row (base_pos, or failing that qpos).  No shift / scale table acts on a scan
- * column.  The input row of a policy with a scan:
- *   x = [ obs_row[:in_obs] (shift / scale) | scan[0 : rows * cols] | last action (12, with feed_last_action) ]
+ * column.
  */
 #pragma once
 #include <gq_device.h> /* angle brackets: the include path decides (csrc/ for the product, tests/simt_emu/ for the host programs) */
 #include <cmath>
 #include <cstdint>
-#include "gq_policy_gru.h"
 
 namespace gq {
 
@@ -32,15 +30,4 @@ __host__ __device__ inline float height_scan_cell(const ScanLaw& S, const float 
   const float c = fminf(lo, S.clip);
   return c * S.scale;
 }
-
-/* what a call of gq_rollout_policy_scan hands to the SCAN instantiations of policy_mlp_kernel (MODE & 8): the seat's block FIRST - the
- * kernel's parameter points at seat.mlp, as with PolicyGruDev; an MLP call fills seat.mlp alone - then the scan's */
-struct PolicyScanDev {
-  PolicyGruDev seat;
-  ScanLaw law;
-  int32_t cells;                /* rows * cols of the batch's base-following map */
-  int32_t col_z;                /* column of the base's z in the observation row (may lie beyond in_obs) */
-  int32_t pad_[3];
-  const float* hits;            /* [N][cells][3], the map's tensor */
-};
 }  // namespace gq

@@ -193,6 +193,46 @@ def test_with_a_scan_the_row_is_obs_scan_action_frames():
     assert _same(b.policy_history, after) and float(r['policy_obs'][:, :, 24:39].abs().max()) > 0
 
 
+@pytest.mark.parametrize('mode', ['plain', 'feet'])
+def test_with_a_scan_the_plain_and_the_foot_term_kernels_equal_the_replayed_loop(mode):
+    """policy_mlp_kernel<24> (scan and history, no learning half) and <26> (scan, history, foot terms), which no test above launches: one full
+    tile of 16 rows and a tile of one row, two policy steps"""
+    from gym_quadruped_amd.policy import HeightScan
+    from test_gpu_policy_scan import ZCOL, _replay, _scan_twin
+    n, D, L, feet = 17, 2, 2, mode == 'feet'
+    K, S = 2 * D, 2
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5, **(CMD if feet else {}))
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1, scale=5.0)
+    p = _policy(L, 13, scan=spec, widths=(20, 12, 12))
+    b.policy_history = torch.rand(n, L, p.hist_words, generator=torch.Generator(device=DEV).manual_seed(9), device=DEV) - 0.5
+    if feet:
+        b.feet_air_time = torch.rand(n, 4, device=DEV) * 0.05
+    before, pending, h0, air = b._obs_buf.clone(), b._terminated.clone().bool(), b.policy_history.clone(), b.feet_air_time.clone()
+    hits0 = hm_a.update_height_map().clone()     # the twin is in the same state: its rays, cast apart from the rollout
+    if feet:
+        reward = _spec()
+        r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True, reward=reward)
+    else:
+        r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, record_obs=True, record_actions=True)
+        assert set(r) == {'obs', 'obs_seq', 'actions', 'policy_actions'}
+    code, _, played = b.closed_loop_status()
+    assert code == 0 and played == n * K
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    scans = []
+    for s in range(S):
+        row, hits = (before, hits0) if s == 0 else (rows[D * s - 1], maps[D * s - 1])
+        scans.append(_t(HS.scan_of(spec, _np(hits), _np(row[:, ZCOL]))))
+    xs, fed, after = _rebuild(p, before, rows, r['policy_actions'], h0, pending, term, D, feet, scans=scans)
+    for s, x in enumerate(xs):
+        if feet:
+            assert _same(r['policy_obs'][s], x), s
+        assert _same(r['policy_means' if feet else 'policy_actions'][s], b.policy_eval(p, x)), s
+    assert _same(b.policy_history, after)
+    if feet:
+        want_r, want_d, want_air, _ = _windows(b, reward, rows, term, r['actions'], r['policy_actions'], pending, D, air)
+        assert torch.equal(r['dones'], want_d) and _same(r['rewards'], want_r) and _same(b.feet_air_time, want_air)
+
+
 @pytest.mark.parametrize('D', [1, 4])
 @pytest.mark.parametrize('n,step_waves', [(1, 0), (7, 0), (120, 0), (128, 0), (136, 0), (9, 2048)])
 def test_edge_sizes_and_single_policy_steps(n, step_waves, D):

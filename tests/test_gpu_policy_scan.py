@@ -216,6 +216,56 @@ def test_learning_rollout_with_foot_terms_and_a_scan_equals_the_replayed_loop():
     assert torch.isfinite(r['rewards']).all() and bool(r['dones'].any())
 
 
+@pytest.mark.parametrize('kind,mode', [('mlp', 'plain'), ('gru', 'plain'), ('gru', 'feet')])
+def test_the_scan_kernels_no_test_above_launches_equal_the_replayed_loop(kind, mode):
+    """policy_mlp_kernel<8> (MLP, scan, no learning half), <12> (recurrent, the same) and <14> (recurrent, scan, foot terms): one full tile
+    of 16 rows and a tile of one row, two policy steps"""
+    from gym_quadruped_amd.policy import HeightScan
+    n, D, gru, feet = 17, 2, kind == 'gru', mode == 'feet'
+    K, S = 2 * D, 2
+    a, b, hm_a, hm_b = _scan_twin(n, 'perlin', 3, 5, **(CMD if feet else {}))
+    spec = HeightScan(3, 5, offset=0.3, clip=0.1)
+    p = H.make_gru(IN_OBS, spec, hidden=20, head=(12,)) if gru else H.make_mlp(IN_OBS, spec, hidden=(20, 12))
+    if gru:
+        b.policy_hidden = torch.rand(n, 20, generator=torch.Generator(device=DEV).manual_seed(4), device=DEV) * 2 - 1
+    if feet:
+        b.feet_air_time = torch.rand(n, 4, device=DEV) * 0.05
+    pending, air, before = b._terminated.clone().bool(), b.feet_air_time.clone(), b._obs_buf.clone()
+    h0 = b.policy_hidden.clone() if gru else None
+    hits0 = hm_a.update_height_map().clone()
+    if feet:
+        reward = _spec()
+        r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, noise_sigma=SIGMA, record_obs=True, record_actions=True, record_transitions=True, reward=reward)
+    else:
+        r = b.rollout_policy(K, p, KP, KD, action_scale=SCALE, decimation=D, record_obs=True, record_actions=True)
+        assert set(r) == {'obs', 'obs_seq', 'actions', 'policy_actions'}
+    code, _, played = b.closed_loop_status()
+    assert code == 0 and played == n * K
+    rows, term, maps = _replay(a, hm_a, b, r, K)
+    win = term.view(S, D, n).any(dim=1)
+    zero = torch.zeros(n, 20, device=DEV)
+    fed = torch.where(pending[:, None], zero, h0) if gru else None
+    for s in range(S):
+        row, hits = (before, hits0) if s == 0 else (rows[D * s - 1], maps[D * s - 1])
+        scan = torch.from_numpy(H.scan_of(spec, _np(hits), _np(row[:, ZCOL]))).to(DEV)
+        prev = torch.zeros(n, 12, device=DEV) if s == 0 else r['policy_actions'][s - 1]
+        x = torch.cat([row[:, :IN_OBS], scan, prev], dim=1)
+        if feet:
+            assert _same(r['policy_obs'][s], x), s
+        act = b.policy_eval(p, x, hidden=fed) if gru else b.policy_eval(p, x)
+        if gru:
+            act, hn = act
+            # the rule: the learning modes' closing visit sees a fall in step K - 1, the plain mode leaves it to the next call's k == 0
+            fell = win[s] if feet or s < S - 1 else term[D * s:K - 1].any(dim=0)
+            fed = torch.where(fell[:, None], zero, hn)
+        assert _same(r['policy_means' if feet else 'policy_actions'][s], act), s
+    if gru:
+        assert _same(b.policy_hidden, fed)
+    if feet:
+        want_r, want_d, want_air, _ = _windows(b, reward, rows, term, r['actions'], r['policy_actions'], pending, D, air)
+        assert torch.equal(r['dones'], want_d) and _same(r['rewards'], want_r) and _same(b.feet_air_time, want_air)
+
+
 def test_the_widest_input_row():
     from gym_quadruped_amd.policy import HeightScan
     n, K, D = 70, 8, 4

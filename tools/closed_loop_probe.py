@@ -1,7 +1,7 @@
 """Throughput of the closed-loop persistent rollout (gq_rollout_closed) with a PD policy in the loop, next to the step loop and the
 open-loop persistent rollout fed with the SAME actions (a standing robot is a different workload from a randomly actuated one).
 usage: closed_loop_probe.py [robot] [n_envs] [K] [scene] [--joint-cmd D | --foot-cmd D | --mlp H1,H2,H3 [--decimation D] [--policy-waves W1,W2,..] [--runs R] [--learn]
-                             [--history L[,cols]]
+                             [--history L[,cols] [--scan R,C --side rollout]]
                              | --gru H [--mlp H1,H2] [--decimation D] [--policy-waves W1,..] [--runs R] [--side loop|rollout]]
 
 --joint-cmd D: joint-impedance actions held over a window of D physics steps instead (QuadrupedEnv.step_pd, one launch per window)
@@ -22,7 +22,8 @@ default 3).  Prints every run of both sides.
 default 33: a 45-word frame; env.policy_history) - against the loop it replaces with the history kept in torch - hist = where(terminated, 0,
 hist); cur = cat(obs, a_prev); a = module(cat(cur, hist)); step_pd; hist = cat(cur[:, :cols] | a_prev, hist[:, :-1]) - and against the
 history-less rollout_policy of a network with the same hidden widths that reads the observation and the last action (the first entry of
---policy-waves), all three in turn, R times over.
+--policy-waves), all three in turn, R times over.  --side rollout: the rollout with the history alone.  --scan R,C (with --side rollout, on
+a scene with terrain such as perlin): the row also holds the R x C height scan of a base-following HeightMap (HeightScan(R, C), 0.1 m cells).
 
 --gru H: a recurrent policy - torch.nn.GRUCell(33, H) and a head with the hidden widths of --mlp (default 128,64; elu) - in the closed-loop
 rollout (QuadrupedEnv.rollout_policy with a GruPolicy, the hidden state in env.policy_hidden) against the loop it replaces on the same commit -
@@ -62,6 +63,7 @@ MLP_D = _opt('--decimation', 4, int)
 MLP_WAVES = _opt('--policy-waves', [64, 128, 256, 512], lambda t: [int(w) for w in t.split(',')])
 MLP_RUNS = _opt('--runs', 3, int)
 HIST = _opt('--history', None, lambda t: [int(v) for v in t.split(',')])
+SCAN = _opt('--scan', None, lambda t: [int(v) for v in t.split(',')])
 GRU = _opt('--gru', 0, int)
 SIDE = _opt('--side', None, str)
 LEARN = '--learn' in sys.argv
@@ -135,6 +137,8 @@ if MLP:
     names = ('qpos_js', 'qvel_js', 'base_lin_vel:base', 'base_ang_vel:base', 'gravity_vector:base')   # 33 columns
     if LEARN:
         names += ('base_pos', 'base_lin_vel_err:base', 'base_ang_vel_err:base')
+    if SCAN:
+        names += ('base_pos',)   # the scan reads the base's z
     env = QuadrupedEnv(robot, scene=scene, state_obs_names=names, num_envs=n, auto_reset='next_step', seed=1)
     env.reset(random=True)
     torch.manual_seed(0)
@@ -201,16 +205,22 @@ if MLP:
         print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
         sys.exit(0)
     if HIST:
-        from gym_quadruped_amd.policy import ObsHistory
+        from gym_quadruped_amd.policy import HeightScan, ObsHistory
         L, cols = HIST[0], HIST[1] if len(HIST) > 1 else 33
         F = cols + 12
+        spec, cells = None, 0
+        if SCAN:
+            from gym_quadruped_amd.sensors import HeightMap
+            assert SIDE == 'rollout', '--scan times the rollout alone: give --side rollout'
+            hm = HeightMap(SCAN[0], SCAN[1], 0.1, 0.1, env.mjModel, env, follow_base=True)   # (the env holds a weak reference)
+            spec, cells = HeightScan(SCAN[0], SCAN[1], offset=0.3, clip=0.5), SCAN[0] * SCAN[1]
         def net(k):
             dims, mods = [k] + MLP + [12], []
             for a, b in zip(dims[:-1], dims[1:]):
                 mods += [torch.nn.Linear(a, b), torch.nn.ELU()]
             return torch.nn.Sequential(*mods[:-1]).to('cuda')
-        module, module0 = net(45 + L * F), net(45)
-        policy = MlpPolicy.from_torch(module, feed_last_action=True, history=ObsHistory(L, cols))
+        module, module0 = net(45 + cells + L * F), net(45)
+        policy = MlpPolicy.from_torch(module, feed_last_action=True, height_scan=spec, history=ObsHistory(L, cols))
         policy0 = MlpPolicy.from_torch(module0, feed_last_action=True)
         env.rollout_policy(300 // D * D, policy, KP, KD, action_scale=scale, decimation=D)   # fill the history in the policy's regime
         sd = env.state_dict(); launches = env._launches
@@ -231,13 +241,16 @@ if MLP:
                     hist = torch.cat([torch.cat([obs[:, :cols], a_prev], dim=1)[:, None], hist[:, :-1]], dim=1)
                     env.step_pd(q0 + scale * a, KP, KD, decimation=D)
                     a_prev = a
-        restore(); with_history(0); restore(); without(); restore(); loop()   # warm every path
-        tag = f'{robot} {scene} n={n} mlp={MLP} D={D} history L={L} cols={cols} (in_dim {policy.in_dim})'
+        restore(); with_history(0)   # warm every path
+        if SIDE != 'rollout':
+            restore(); without(); restore(); loop()
+        tag = f'{robot} {scene} n={n} mlp={MLP} D={D} history L={L} cols={cols}' + (f' scan {SCAN[0]}x{SCAN[1]}' if SCAN else '') + f' (in_dim {policy.in_dim})'
         for r in range(MLP_RUNS):
-            restore(); m, us = timed(loop, W * D)
-            print(f'{tag} run {r}: loop (torch module + history in torch + step_pd)  {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
-            restore(); m, us = timed(without, W * D)
-            print(f'{tag} run {r}: rollout_policy WITHOUT history (in_dim 45), waves {MLP_WAVES[0]:4d} {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+            if SIDE != 'rollout':
+                restore(); m, us = timed(loop, W * D)
+                print(f'{tag} run {r}: loop (torch module + history in torch + step_pd)  {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
+                restore(); m, us = timed(without, W * D)
+                print(f'{tag} run {r}: rollout_policy WITHOUT history (in_dim 45), waves {MLP_WAVES[0]:4d} {m:7.2f} M env-steps/s  {us:6.1f} us/step', flush=True)
             for pw in MLP_WAVES:
                 restore(); m, us = timed(lambda: with_history(pw), W * D)
                 print(f'{tag} run {r}: rollout_policy with history, policy waves {pw:4d}       {m:7.2f} M env-steps/s  {us:6.1f} us/step  status {env.closed_loop_status()}', flush=True)
