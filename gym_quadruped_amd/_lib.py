@@ -6,7 +6,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-from .cabi import GQ_ABI_VERSION, GqCamLayers, GqCamShade, GqFootCmd, GqFootReward, GqImuCfg, GqJointCmd, GqLearn, GqMailboxView, GqModelDesc, GqObsOut, GqPolicyGru, GqPolicyHist, GqPolicyMlp, GqPolicyPd, GqPolicyScan, GqResampleCfg, GqResetCfg, GqState
+from .cabi import GQ_ABI_VERSION, GqCamLayers, GqCamShade, GqFootCmd, GqFootReward, GqImuCfg, GqJointCmd, GqLearn, GqMailboxView, GqModelDesc, GqObsOut, GqPolicyGru, GqPolicyHist, GqPolicyMlp, GqPolicyNoise, GqPolicyPd, GqPolicyScan, GqResampleCfg, GqResetCfg, GqState
 
 _LIB = None
 
@@ -56,6 +56,8 @@ ABI = {
     'gq_rollout_policy_scan': (_i, _POLICY[:3] + [_P(GqPolicyGru), _P(GqPolicyScan)] + _POLICY[3:-1] + [_P(GqLearn), _P(GqFootReward), _v]),
     'gq_rollout_policy_hist': (_i, _POLICY[:3] + [_P(GqPolicyScan), _P(GqPolicyHist)] + _POLICY[3:-1] + [_P(GqLearn), _P(GqFootReward), _v]),
     'gq_height_scan_eval': (_i, [_v, _P(GqPolicyScan), _v, _v, _i, _v, _v]),
+    'gq_rollout_policy_noise': (_i, _POLICY[:3] + [_P(GqPolicyGru), _P(GqPolicyScan), _P(GqPolicyHist), _P(GqPolicyNoise)] + _POLICY[3:-1] + [_P(GqLearn), _P(GqFootReward), _v]),
+    'gq_obs_noise_eval': (_i, [_v, _P(GqPolicyNoise), _i, _i, _i, C.c_uint64, _v, _v, _v, _i, _v, _v]),
     'gq_step_joint_cmd': (_i, [_v, _P(GqJointCmd), _i] + _LAUNCH + _SEQ),
     'gq_step_foot_cmd': (_i, [_v, _P(GqFootCmd), _i] + _LAUNCH + _SEQ),
     'gq_batch_bind': (_i, [_v] + _LAUNCH + [_v]),

@@ -166,6 +166,17 @@ class GqPolicyHist(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('frames', C.c_int32), ('cols', C.c_int32), ('in_dim', C.c_int32), ('state', C.c_void_p), ('ctl', C.c_void_p)]
 
 
+GQ_OBS_NOISE = dict(uniform=0, normal=1)   # GQ_OBS_NOISE_*
+
+
+class GqPolicyNoise(C.Structure):
+    """gq_rollout_policy_noise's / gq_obs_noise_eval's block: the sensor noise on the policy's input row (``csrc/gq_policy_noise.h``) - the kind,
+    ``amp`` a device table of ``n_amp = in_obs`` float32 amplitudes, one amplitude for the scan columns, and the record of the true rows
+    ``[K // D][N][in_dim]``; ``struct_size`` must hold ``sizeof(GqPolicyNoise)``."""
+    _fields_ = [('struct_size', C.c_int32), ('kind', C.c_int32), ('n_amp', C.c_int32), ('scan_amp', C.c_float), ('amp', C.c_void_p),
+                ('policy_obs_clean', C.c_void_p)]
+
+
 class GqLearn(C.Structure):
     """gq_rollout_policy_learn's / gq_reward_eval's block: the reward weights in the order of the law's sum, and the rollout's output
     pointers; ``struct_size`` must hold ``sizeof(GqLearn)`` (the library refuses a stale layout)."""

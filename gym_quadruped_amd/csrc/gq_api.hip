@@ -47,6 +47,8 @@ extern "C" void gq_launch_reward_eval(const gq::LearnFeetDev* learn, const float
 extern "C" void gq_launch_policy_mlp_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" void gq_launch_policy_gru_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream);
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream);
+extern "C" void gq_launch_obs_noise_eval(const gq::NoiseLaw* law, int in_obs, int cells, int in_dim, const float* rows, const int32_t* steps, const int32_t* env_ids, int n,
+                                         float* out, hipStream_t stream);
 extern "C" int gq_launch_mailbox_step(const gq::FusedArgs* dev_args, const gq::StepCall* c, const gq::MailboxDev* mb, int waves, int solver, int cone, gq::Scene scene, hipStream_t stream);
 
 static thread_local char g_err[512] = "";
@@ -661,7 +663,7 @@ static int net_describe(const GqPolicyMlp* mlp, gq::PolicyMlpDev& P, const char*
  * the ones it uses, and nothing of an earlier call's scan, history, cell or flags travels with it */
 static gq::PolicyDev policy_block(const Mailbox& mb) {
   gq::PolicyDev D = mb.net.shadow;
-  D.gru = gq::GruDev{}; D.episode = gq::EpisodeDev{}; D.scan = gq::ScanDev{}; D.hist = gq::HistDev{};
+  D.gru = gq::GruDev{}; D.episode = gq::EpisodeDev{}; D.scan = gq::ScanDev{}; D.hist = gq::HistDev{}; D.noise = gq::NoiseDev{};
   return D;
 }
 /* the MLP policy: the block's seat part */
@@ -812,9 +814,22 @@ static int hist_describe(const GqPolicyMlp* mlp, const GqPolicyHist* hist, const
   return GQ_OK;
 }
 
+/* ---- the sensor noise's law (gq_policy_noise.h) from the C block, for an input row with in_obs observation columns and scan_cells scan columns.
+ * The amplitudes are a device table: their values are the caller's ---- */
+static int noise_describe(const GqPolicyNoise* noise, const int in_obs, const int scan_cells, gq::NoiseLaw& Z, const char* who) {
+  if (noise->kind != GQ_OBS_NOISE_UNIFORM && noise->kind != GQ_OBS_NOISE_NORMAL) { SET_ERR("%s: the sensor noise's kind is %d: uniform (0) or normal (1)", who, noise->kind); return GQ_EINVAL; }
+  if (noise->n_amp != in_obs) { SET_ERR("%s: the sensor noise has n_amp = %d amplitudes, the policy in_obs = %d observation columns", who, noise->n_amp, in_obs); return GQ_EINVAL; }
+  if (in_obs > 0 && !noise->amp) { SET_ERR("%s: GqPolicyNoise.amp (device [n_amp]) is null", who); return GQ_EINVAL; }
+  if (!(noise->scan_amp >= 0.0f) || !std::isfinite(noise->scan_amp)) { SET_ERR("%s: the sensor noise's scan_amp = %g: it must be finite and >= 0", who, (double)noise->scan_amp); return GQ_EINVAL; }
+  if (noise->scan_amp != 0.0f && scan_cells == 0) { SET_ERR("%s: the sensor noise's scan_amp = %g, and the policy has no height scan", who, (double)noise->scan_amp); return GQ_EINVAL; }
+  Z.amp = noise->amp; Z.kind = noise->kind == GQ_OBS_NOISE_NORMAL ? gq::OBS_NOISE_NORMAL : gq::OBS_NOISE_UNIFORM; Z.scan_amp = noise->scan_amp;
+  return GQ_OK;
+}
+
 /* gru: null for the MLP (the three entry points as they were), else the recurrent policy's block (gq_rollout_policy_gru); scan: null, or the
- * height scan's block (gq_rollout_policy_scan); hist: null, or the observation history's (gq_rollout_policy_hist, the MLP alone) */
-static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
+ * height scan's block (gq_rollout_policy_scan); hist: null, or the observation history's (gq_rollout_policy_hist, the MLP alone); noise: null,
+ * or the sensor noise's (gq_rollout_policy_noise) */
+static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, const GqPolicyHist* hist, const GqPolicyNoise* noise, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                           const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                           const GqFootReward* feet, void* hip_stream, const char* const who) {
   if (feet && !fresh(feet, "GqFootReward", who)) return GQ_EINVAL;
@@ -822,6 +837,8 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   if (gru && !fresh(gru, "GqPolicyGru", who)) return GQ_EINVAL;
   if (scan && !fresh(scan, "GqPolicyScan", who)) return GQ_EINVAL;
   if (hist && !fresh(hist, "GqPolicyHist", who)) return GQ_EINVAL;
+  if (noise && !fresh(noise, "GqPolicyNoise", who)) return GQ_EINVAL;
+  if (gru && hist) { SET_ERR("%s: the observation history is the MLP's: a recurrent policy has its hidden state", who); return GQ_EINVAL; }
   if (learn && !fresh(learn, "GqLearn", who)) return GQ_EINVAL;
   if (feet && !learn) { SET_ERR("%s: the foot terms continue the learn block's sum: learn is null", who); return GQ_EINVAL; }
   if (!b || n_steps < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
@@ -842,6 +859,12 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
     if (!gru->hidden_state) { SET_ERR("%s: GqPolicyGru.hidden_state (device [N][hidden], in / out) is null", who); return GQ_EINVAL; }
     PD.gru.hidden_state = gru->hidden_state; PD.gru.hidden_seq = gru->hidden_seq;
   } else if (const int rc = mlp_describe(mlp, PD, who, scan_cells, hist_words); rc != GQ_OK) return rc;
+  if (noise) { /* (its seed, step0 and env id offset are the seat's, filled below) */
+    gq::NoiseLaw Z{};
+    if (const int rc = noise_describe(noise, mlp->in_obs, scan_cells, Z, who); rc != GQ_OK) return rc;
+    if (noise->policy_obs_clean && !(learn && learn->policy_obs)) { SET_ERR("%s: GqPolicyNoise.policy_obs_clean is recorded next to GqLearn.policy_obs: there is none", who); return GQ_EINVAL; }
+    PD.noise.amp = Z.amp; PD.noise.kind = Z.kind; PD.noise.scan_amp = Z.scan_amp; PD.noise.rec_clean = noise->policy_obs_clean;
+  }
   if (mlp->decimation < 1) { SET_ERR("%s: decimation must be >= 1 (got %d)", who, mlp->decimation); return GQ_EINVAL; }
   if (n_steps % mlp->decimation != 0) { SET_ERR("%s: n_steps = %d is no multiple of decimation = %d (no held action crosses calls)", who, n_steps, mlp->decimation); return GQ_EINVAL; }
   if (const int rc = joint_columns(b, P.col_q, P.col_qd, who, gru ? "GRU" : "MLP"); rc != GQ_OK) return rc;
@@ -890,9 +913,9 @@ static int rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
   }
   if (const int rc = mailbox_start(b, n_steps, step_waves, timeout_s, obs_seq, act_seq, stream); rc != GQ_OK) return rc;
   if (const int rc = policy_fork(mb, stream); rc != GQ_OK) return rc;
-  const int mode = (feet_on ? 2 : (learn ? 1 : 0)) | (gru ? 4 : 0) | (scan ? 8 : 0) | (hist ? 16 : 0); /* policy_mlp_kernel's MODE */
+  const int mode = (feet_on ? 2 : (learn ? 1 : 0)) | (gru ? 4 : 0) | (scan ? 8 : 0) | (hist ? 16 : 0) | (noise ? 32 : 0); /* policy_mlp_kernel's MODE */
   if (!gq_launch_policy(mb.dev.get(), mb.net.dev.get(), out.obs, od, policy_waves, mode, mb.stream.get())) {
-    SET_ERR("%s: no policy kernel for this combination of recurrent policy, height scan and observation history (mode %d)", who, mode); return GQ_EINVAL;
+    SET_ERR("%s: no policy kernel for this combination of recurrent policy, height scan, observation history and sensor noise (mode %d)", who, mode); return GQ_EINVAL;
   }
   if (const int rc = policy_resident(mb, policy_waves, stream, who); rc != GQ_OK) return rc;
   return mailbox_steps(b, auto_reset, step_waves, true, stream, who);
@@ -902,30 +925,37 @@ int gq_rollout_policy_gru(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const
                           const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_gru";
   if (!gru) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, gru, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, gru, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy_scan(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, int policy_waves, int step_waves,
                            double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
                            float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_scan";
   if (!scan) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, gru, scan, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, gru, scan, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy_hist(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves,
                            double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
                            float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_hist";
   if (!hist) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, nullptr, scan, hist, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, nullptr, scan, hist, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+}
+int gq_rollout_policy_noise(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, const GqPolicyHist* hist,
+                            const GqPolicyNoise* noise, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                            int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream) {
+  const char* const who = "gq_rollout_policy_noise";
+  if (!noise) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  return rollout_policy(b, n_steps, mlp, gru, scan, hist, noise, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 int gq_rollout_policy(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                       const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, nullptr, nullptr, hip_stream, "gq_rollout_policy");
 }
 int gq_rollout_policy_learn(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
                             const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn,
                             void* hip_stream) {
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, nullptr, hip_stream,
                         learn ? "gq_rollout_policy_learn" : "gq_rollout_policy");
 }
 int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out,
@@ -933,7 +963,7 @@ int gq_rollout_policy_learn_feet(GqBatch* b, int n_steps, const GqPolicyMlp* mlp
                                  const GqFootReward* feet, void* hip_stream) {
   const char* const who = "gq_rollout_policy_learn_feet";
   if (!feet) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
-  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
+  return rollout_policy(b, n_steps, mlp, nullptr, nullptr, nullptr, nullptr, policy_waves, step_waves, timeout_s, st, out, auto_reset, episode, lift_failed, obs_seq, act_seq, learn, feet, hip_stream, who);
 }
 
 /* gq_reward_eval (feet null) and gq_reward_eval_feet */
@@ -996,6 +1026,24 @@ int gq_height_scan_eval(GqBatch* b, const GqPolicyScan* scan, const float* hits,
   if (n == 0) return GQ_OK;
   DeviceGuard guard(b->model->device);
   gq_launch_height_scan_eval(&S.law, hits, z, n, S.cells, out, (hipStream_t)hip_stream);
+  HIP_TRY(hipGetLastError());
+  return GQ_OK;
+}
+
+int gq_obs_noise_eval(GqBatch* b, const GqPolicyNoise* noise, int in_obs, int scan_cells, int in_dim, uint64_t noise_seed, const float* rows, const int32_t* steps,
+                      const int32_t* env_ids, int n, float* out, void* hip_stream) {
+  const char* const who = "gq_obs_noise_eval";
+  if (!fresh(noise, "GqPolicyNoise", who)) return GQ_EINVAL;
+  if (!b || !rows || !steps || !env_ids || !out || n < 0) { SET_ERR("%s: bad argument", who); return GQ_EINVAL; }
+  if (in_obs < 0 || scan_cells < 0 || in_dim < 1 || in_dim > GQ_MLP_MAXW || in_obs + scan_cells > in_dim) {
+    SET_ERR("%s: an input row of in_dim = %d columns (1 to %d) with in_obs = %d and %d scan cells", who, in_dim, GQ_MLP_MAXW, in_obs, scan_cells); return GQ_EINVAL;
+  }
+  gq::NoiseLaw Z{};
+  if (const int rc = noise_describe(noise, in_obs, scan_cells, Z, who); rc != GQ_OK) return rc;
+  Z.seed_lo = (uint32_t)(noise_seed & 0xffffffffu); Z.seed_hi = (uint32_t)(noise_seed >> 32);
+  if (n == 0) return GQ_OK;
+  DeviceGuard guard(b->model->device);
+  gq_launch_obs_noise_eval(&Z, in_obs, scan_cells, in_dim, rows, steps, env_ids, n, out, (hipStream_t)hip_stream);
   HIP_TRY(hipGetLastError());
   return GQ_OK;
 }

@@ -197,12 +197,18 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_pd_kernel(const MailboxDev* __
  * control word; whoever stages a word of the current block also stores it as the newest frame of the env's OTHER buffer, whoever stages a
  * history word moves it one slot on into that buffer - every word has one staging lane, and nobody writes the buffer being read.  History
  * words are stores of another visit of this launch, possibly by another lane of this wavefront: device-scope loads and stores, as for the
- * hidden state (a plain load may hit the line an earlier plain load left in the vector L1).  The control word is the env's own lane's. */
+ * hidden state (a plain load may hit the line an earlier plain load left in the vector L1).  The control word is the env's own lane's.
+ * SENSOR NOISE (MODE & 32, gq_rollout_policy_noise, with every mode above; MODE 0 .. 26 compile to the kernels they were): the observation and
+ * scan words the network is fed carry the noise of gq_policy_noise.h, a Philox block per noised word keyed by (column, step0 + k, global env
+ * id) under the action noise's seed.  The amplitude table is immutable during the launch: an ordinary load per observation column, nothing
+ * of device scope.  Only policy_row_value sees the noise: the torque law below, learn_visit and both episode rules read the true row, so the
+ * state after the call is the step loop's with the recorded torques.  The true words go to the block's rec_clean, where one is given. */
 template <int MODE>
 __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* __restrict__ MBp, const PolicyDev* __restrict__ Pp, const float* __restrict__ obs, const int od) {
   constexpr bool GRU = (MODE & 4) != 0;
   constexpr bool SCAN = (MODE & 8) != 0;
   constexpr bool HIST = (MODE & 16) != 0;
+  constexpr bool NOISE = (MODE & 32) != 0;
   static_assert(!(GRU && HIST), "the observation history is the MLP's: a recurrent policy has its hidden state");
   constexpr int LMODE = MODE & 3;
   constexpr bool LEARN = LMODE != 0;
@@ -232,6 +238,14 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
     const GQ_MODEL HistLaw& HL = PD.hist.law;
     row_law.hist.frames = HL.frames; row_law.hist.cols = HL.cols; row_law.hist.width = HL.width; row_law.hist.col0 = HL.col0; row_law.hist.inv = HL.inv;
     hist_state = PD.hist.state; hist_ctl = PD.hist.ctl;
+  }
+  [[maybe_unused]] RowNoise row_noise{}; /* the law's part is the call's, the key each row's */
+  [[maybe_unused]] float* noise_clean = nullptr;
+  if constexpr (NOISE) {
+    const GQ_MODEL NoiseDev& ND = PD.noise;
+    row_noise.law.amp = ND.amp; row_noise.law.kind = ND.kind; row_noise.law.scan_amp = ND.scan_amp;
+    row_noise.law.seed_lo = P.seed_lo; row_noise.law.seed_hi = P.seed_hi;
+    noise_clean = ND.rec_clean;
   }
   const int nmine = mb_queue_envs(N, q, nq);         /* envs of this queue: e = q + nq * i */
   const int G = mine * GQ_WAVE;
@@ -289,7 +303,19 @@ __global__ void __launch_bounds__(GQ_WAVE) policy_mlp_kernel(const MailboxDev* _
           rs.hist_ctl = shfl_idx(hist_c, src < 0 ? 0 : src);
           rs.hist = hist_state + (size_t)er * hist_env_floats(hist);
         }
-        const auto x_value = [&](const int, const int c) { return src < 0 ? 0.0f : policy_row_value<SCAN, HIST, LearnPub>(row_law, rs, c); };
+        [[maybe_unused]] RowNoise rz = row_noise;
+        if constexpr (NOISE) { /* the row's key: the counter of the action noise drawn at this policy step, and the env's global id */
+          const int kr = shfl_idx(k, src < 0 ? 0 : src);
+          rz.step = (uint32_t)(P.step0 + kr); rz.gid = (uint32_t)(er + P.env_id_offset);
+          if constexpr (LEARN) { /* the true rows, laid out as policy_obs is: one distance serves every row */
+            float* const rec0 = mptr(P.learn)->learn.policy_obs;
+            if (noise_clean && rec0) rz.clean_delta = noise_clean - rec0;
+          }
+        }
+        const auto x_value = [&](const int, const int c) {
+          if constexpr (NOISE) return src < 0 ? 0.0f : policy_row_value<SCAN, HIST, LearnPub, true>(row_law, rs, c, rz);
+          else return src < 0 ? 0.0f : policy_row_value<SCAN, HIST, LearnPub>(row_law, rs, c);
+        };
         const float* out;
         if constexpr (GRU) {
           const int H = cell.hidden;
@@ -490,6 +516,18 @@ __global__ void __launch_bounds__(GQ_WAVE) height_scan_eval_kernel(const ScanLaw
   const long long w = (long long)blockIdx.x * GQ_WAVE + threadIdx.x;
   if (w >= total) return;
   out[w] = height_scan_cell(law, z[w / cells], hits[w * 3 + 2]);
+}
+
+/* the sensor noise's law alone (gq_obs_noise_eval), a thread per word: rows [n][in_dim] raw input rows, steps / env_ids [n] each row's
+ * key -> out [n][in_dim]; obs_noise_add's bits, to be compared with the rollout's and the host's */
+__global__ void __launch_bounds__(GQ_WAVE) obs_noise_eval_kernel(const NoiseLaw law, const int in_obs, const int cells, const int in_dim, const float* __restrict__ rows,
+                                                                 const int32_t* __restrict__ steps, const int32_t* __restrict__ env_ids, const long long total,
+                                                                 float* __restrict__ out) {
+  const long long w = (long long)blockIdx.x * GQ_WAVE + threadIdx.x;
+  if (w >= total) return;
+  const long long r = w / in_dim;
+  const int c = (int)(w - r * in_dim);
+  out[w] = obs_noise_add(law, obs_noise_amp(law, in_obs, cells, c), c, (uint32_t)steps[r], (uint32_t)env_ids[r], rows[w]);
 }
 
 /* which XCDs does this device expose?  bit HW_REG_XCC_ID of *mask is set by every workgroup */
@@ -732,9 +770,10 @@ extern "C" void gq_launch_policy_pd(const gq::MailboxDev* mb, const gq::PolicyPd
   hipLaunchKernelGGL(gq::policy_pd_kernel, dim3(waves), dim3(GQ_WAVE), 0, stream, mb, pd, obs, od);
 }
 /* THE TABLE of policy_mlp_kernel's instantiations, MODE = learn mode (0: gq_rollout_policy, 1: the learning half, 2: with the foot terms)
- * | 4 recurrent | 8 height scan | 16 observation history (the MLP's alone): listed here and nowhere else - the array below instantiates
+ * | 4 recurrent | 8 height scan | 16 observation history (the MLP's alone) | 32 sensor noise: listed here and nowhere else - the array below instantiates
  * them, the loop dispatches to them.  Returns whether `mode` is in the table (nothing was launched otherwise). */
-using PolicyModes = std::integer_sequence<int, 0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, 16, 17, 18, 24, 25, 26>;
+using PolicyModes = std::integer_sequence<int, 0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14, 16, 17, 18, 24, 25, 26,
+                                          32, 33, 34, 36, 37, 38, 40, 41, 42, 44, 45, 46, 48, 49, 50, 56, 57, 58>; /* | 32: each with the sensor noise */
 template <int... M>
 static bool launch_policy_mode(std::integer_sequence<int, M...>, const int mode, const gq::MailboxDev* mb, const gq::PolicyDev* dev, const float* obs, int od, int waves, hipStream_t stream) {
   using Kernel = void (*)(const gq::MailboxDev*, const gq::PolicyDev*, const float*, int);
@@ -750,6 +789,12 @@ extern "C" int gq_launch_policy(const gq::MailboxDev* mb, const gq::PolicyDev* d
 extern "C" void gq_launch_height_scan_eval(const gq::ScanLaw* law, const float* hits, const float* z, int n, int cells, float* out, hipStream_t stream) {
   const long long total = (long long)n * cells;
   hipLaunchKernelGGL(gq::height_scan_eval_kernel, dim3((unsigned)((total + GQ_WAVE - 1) / GQ_WAVE)), dim3(GQ_WAVE), 0, stream, *law, hits, z, total, cells, out);
+}
+extern "C" void gq_launch_obs_noise_eval(const gq::NoiseLaw* law, int in_obs, int cells, int in_dim, const float* rows, const int32_t* steps, const int32_t* env_ids, int n,
+                                         float* out, hipStream_t stream) {
+  const long long total = (long long)n * in_dim;
+  hipLaunchKernelGGL(gq::obs_noise_eval_kernel, dim3((unsigned)((total + GQ_WAVE - 1) / GQ_WAVE)), dim3(GQ_WAVE), 0, stream, *law, in_obs, cells, in_dim, rows, steps, env_ids,
+                     total, out);
 }
 /* impl 0: gru_row_forward, a thread per row; 1: gru_tile_forward, a wavefront per 16 rows */
 extern "C" void gq_launch_policy_gru_eval(const gq::PolicyDev* dev, const float* rows, int n_rows, int impl, float* out, hipStream_t stream) {

@@ -23,12 +23,18 @@
  *
  * "Recorded" is the learning modes' policy_obs row, where there is one.  Every column is staged exactly once per fresh visit, in any order:
  * a column's value and side effects depend on no other column of the visit (the store is read in one buffer and written in the other).
+ *
+ * SENSOR NOISE (NOISE, gq_policy_noise.h: the law): the observation and scan columns with a positive amplitude are FED with noise on the raw
+ * word, before shift / scale.  The noisy word is what is recorded, what becomes the word of the history's current frame and what goes on to
+ * shift / scale; the true word of every column goes to the second record (RowNoise::clean_delta).  z_base stays the true z.  Last-action and frame words
+ * are never noised (a frame word was noised when it was the current block's), so both records hold the same word there.
  */
 #pragma once
 #include "gq_policy_mlp.h"
 #include "gq_policy_gru.h"
 #include "gq_policy_scan.h"
 #include "gq_policy_hist.h"
+#include "gq_policy_noise.h"
 
 namespace gq {
 
@@ -54,16 +60,33 @@ struct RowSrc {
   int hist_ctl;
   float* rec;          /* [in_dim] where the row is recorded, or NULL */
 };
+/* NOISE: the call's law and one row's key and second record */
+struct RowNoise {
+  NoiseLaw law;
+  uint32_t step, gid;  /* the row's Philox key: the absolute step counter step0 + k, the global env id */
+  ptrdiff_t clean_delta; /* the second record relative to RowSrc::rec, in words: the TRUE word of column c goes to rec[c + clean_delta]; 0: none.
+                          * The two records are arrays of one shape, so the distance is the call's, not the row's: no second pointer per lane */
+};
 /* column c of the row (head comment): the value fed; records the raw word and stages the history's store on the way.  Mem: LearnPlain on
- * the host, LearnPub in the rollout (every word is another wavefront's store of this launch, or one of an earlier visit). */
-template <bool SCAN, bool HIST, class Mem>
-__host__ __device__ __forceinline__ float policy_row_value(const RowLaw& L, const RowSrc& S, const int c) {
+ * the host, LearnPub in the rollout (every word is another wavefront's store of this launch, or one of an earlier visit).  NOISE false: Z is
+ * not looked at, and the routine is what it was without the parameter. */
+template <bool SCAN, bool HIST, class Mem, bool NOISE = false>
+__host__ __device__ __forceinline__ float policy_row_value(const RowLaw& L, const RowSrc& S, const int c, const RowNoise& Z = RowNoise{}) {
   if (c >= L.in_dim) return 0.0f;
   const int in_obs = L.in_obs, cells = SCAN ? L.cells : 0;
   const auto word = [&](const float* const p) { /* a raw word, recorded as loaded */
     const float o = Mem::ld(p);
     if (S.rec) S.rec[c] = o;
+    if constexpr (NOISE) {
+      if (S.rec && Z.clean_delta) S.rec[c + Z.clean_delta] = o;
+    }
     return o;
+  };
+  [[maybe_unused]] const auto noisy = [&](const float v, const float a) { /* NOISE: the word as fed, both records */
+    const float vn = obs_noise_add(Z.law, a, c, Z.step, Z.gid, v);
+    if (S.rec) S.rec[c] = vn;
+    if (S.rec && Z.clean_delta) S.rec[c + Z.clean_delta] = v;
+    return vn;
   };
   if constexpr (HIST) {
     const HistLaw& H = L.hist;
@@ -71,10 +94,15 @@ __host__ __device__ __forceinline__ float policy_row_value(const RowLaw& L, cons
       int w;
       const float o = hist_stage_frame<Mem>(H, S.hist, S.hist_ctl, c - H.col0, &w);
       if (S.rec) S.rec[c] = o;
+      if constexpr (NOISE) {
+        if (S.rec && Z.clean_delta) S.rec[c + Z.clean_delta] = o;
+      }
       return w < H.cols ? mlp_obs_in(o, L.shift, L.scale, w) : o;
     }
     if (c < in_obs) {
-      const float o = word(S.obs + c);
+      float o;
+      if constexpr (NOISE) o = noisy(Mem::ld(S.obs + c), Z.law.amp[c]);
+      else o = word(S.obs + c);
       if (c < H.cols) hist_stage_current<Mem>(H, S.hist, S.hist_ctl, c, o);
       return mlp_obs_in(o, L.shift, L.scale, c);
     }
@@ -84,7 +112,11 @@ __host__ __device__ __forceinline__ float policy_row_value(const RowLaw& L, cons
       return o;
     }
   } else {
-    if (c < in_obs) return mlp_obs_in(word(S.obs + c), L.shift, L.scale, c);
+    if constexpr (NOISE) {
+      if (c < in_obs) return mlp_obs_in(noisy(Mem::ld(S.obs + c), Z.law.amp[c]), L.shift, L.scale, c);
+    } else {
+      if (c < in_obs) return mlp_obs_in(word(S.obs + c), L.shift, L.scale, c);
+    }
   }
   if constexpr (SCAN) { /* (with HIST only the scan's own columns come this far) */
     const int cell = c - in_obs;
@@ -92,6 +124,7 @@ __host__ __device__ __forceinline__ float policy_row_value(const RowLaw& L, cons
       if (cell >= cells) return word(S.last + (cell - cells)); /* the last action, behind the scan */
     }
     const float s = height_scan_cell(L.scan, S.z_base, Mem::ld(S.hits + 3 * cell + 2));
+    if constexpr (NOISE) return noisy(s, Z.law.scan_amp);
     if (S.rec) S.rec[c] = s;
     return s;
   }
@@ -128,16 +161,25 @@ struct HistDev {
   float* state;                 /* [N][2][L][F] the store */
   int32_t* ctl;                 /* [N] the control words */
 };
+/* MODE & 32, the sensor noise (gq_policy_noise.h): its seed, step0 and env id offset are the seat's, the action noise's.  The table is
+ * immutable during the launch: ordinary loads */
+struct NoiseDev {
+  const float* amp;             /* [seat.in_obs] */
+  int32_t kind;                 /* OBS_NOISE_* */
+  float scan_amp;
+  float* rec_clean;             /* [n_steps / decimation][N][in_dim] the row with the true words, or NULL (only next to the learn block's policy_obs) */
+};
 struct PolicyDev {
   PolicyMlpDev seat;
   GruDev gru;
   EpisodeDev episode;
   ScanDev scan;
   HistDev hist;
+  NoiseDev noise;               /* appended: the parts before it stay where the existing kernels were built to find them */
 };
 /* the layout is pinned: these are the size and the offsets the kernels were built and profiled with when the parts were nested structs
  * (the block's address is all a kernel has) - a part that moves changes the addressing of every instantiation */
-static_assert(sizeof(PolicyDev) == 608, "PolicyDev");
+static_assert(sizeof(PolicyDev) == 632, "PolicyDev");
 static_assert(offsetof(PolicyDev, gru.cell) == 472 && offsetof(PolicyDev, episode.terminated) == 504 && offsetof(PolicyDev, scan.law) == 520 && offsetof(PolicyDev, scan.hits) == 552 &&
-              offsetof(PolicyDev, hist.law) == 560 && offsetof(PolicyDev, hist.ctl) == 600, "PolicyDev");
+              offsetof(PolicyDev, hist.law) == 560 && offsetof(PolicyDev, hist.ctl) == 600 && offsetof(PolicyDev, noise.amp) == 608, "PolicyDev");
 }  // namespace gq

@@ -10,7 +10,9 @@ in ``csrc/gq_policy_gru.h``.
 ``HeightScan`` puts the env's base-following height map into either policy's input row (``csrc/gq_policy_scan.h``).
 
 ``ObsHistory`` gives the MLP a memory: the frames of the last policy steps as further columns of its input row, the state on the device
-(``QuadrupedEnv.policy_history``), defined in ``csrc/gq_policy_hist.h``."""
+(``QuadrupedEnv.policy_history``), defined in ``csrc/gq_policy_hist.h``.
+
+``ObsNoise`` puts counter-based sensor noise on the observation and scan columns either policy is fed (``csrc/gq_policy_noise.h``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -99,6 +101,92 @@ class ObsHistory:
     def frame_words(self, in_obs, feed_last_action):
         """F: the words of one frame for a policy of ``in_obs`` observation columns"""
         return (in_obs if self.cols is None else self.cols) + (N_ACTIONS if feed_last_action else 0)
+
+
+class ObsNoise:
+    """Sensor noise on what an in-loop policy observes (``rollout_policy(..., obs_noise=)``; ``csrc/gq_policy_noise.h`` is the law), in RAW
+    observation units, before ``obs_shift`` / ``obs_scale``::
+
+        o~_c = o_c + amp[c] * n      observation column c < in_obs with amp[c] > 0
+        s~_c = s_c + scan_amp * n    scan column (the scan word after clamp and scale, from the true z), with scan_amp > 0
+
+    in float32, the product and the sum each rounded.  ``kind='uniform'``: ``n = 2 u - 1`` in ``[-1, 1)``; ``'normal'``: a standard normal, the
+    action noise's Box-Muller.  The draw is counter-based - a Philox block per word keyed by the env's seed, the input-row column, the step
+    counter of the policy step and the global env id - so a seed gives one rollout and two shards draw different noise.  A column with
+    amplitude 0 draws nothing and keeps its bits.  The fed-back action and a history's frames are never noised: a frame holds the noisy word
+    its current block was fed.  Only the network's input is noised - the joint-impedance law, the reward and the episode rules read the true
+    row.
+
+    amp: a scalar or ``[policy.in_obs]`` non-negative finite values (``from_names`` fills it by observation name); scan_amp: one
+    non-negative amplitude for every column of the policy's ``HeightScan`` (refused when non-zero and the policy has none)."""
+
+    KINDS = ('uniform', 'normal')
+
+    def __init__(self, amp, kind='uniform', scan_amp=0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be 'uniform' or 'normal', got {kind!r}")
+        self.kind = kind
+        self.amp = np.array(amp, dtype=np.float32)
+        if self.amp.ndim > 1:
+            raise ValueError(f'amp must be a scalar or a vector of one amplitude per observation column, got shape {self.amp.shape}')
+        if not np.all(np.isfinite(self.amp)) or np.any(self.amp < 0):
+            raise ValueError('amp must be finite and >= 0 (non-negative amplitudes in raw observation units)')
+        self.scan_amp = float(np.float32(scan_amp))
+        if not np.isfinite(self.scan_amp) or self.scan_amp < 0:
+            raise ValueError(f'scan_amp must be finite and >= 0, got {scan_amp}')
+        self._device = {}   # (device, in_obs) -> the amplitude table
+
+    @classmethod
+    def from_names(cls, env, amps, kind='uniform', scan_amp=0.0):
+        """``amps``: ``{observation name: a scalar or one value per column of that observation}`` in the column layout of ``env``'s
+        ``state_obs_names``; every other column gets 0.  A name the env does not observe raises."""
+        from .cabi import OBS_DIMS, OBS_NAMES
+        names = list(env.state_obs_names)
+        unknown = [n for n in amps if n not in names]
+        if unknown:
+            raise ValueError(f'{unknown} not in the env\'s state_obs_names {names}: only an observed column can be noised')
+        parts = []
+        for n in names:
+            w = OBS_DIMS[OBS_NAMES.index(n)]
+            parts.append(np.broadcast_to(np.asarray(amps.get(n, 0.0), dtype=np.float32), (w,)))
+        noise = cls(np.concatenate(parts), kind=kind, scan_amp=scan_amp)
+        noise._whole_row = True
+        return noise
+
+    _whole_row = False   # from_names: amp covers the env's whole row, of which a policy may read the leading columns only
+
+    def table(self, policy):
+        """the ``[policy.in_obs]`` float32 amplitudes for ``policy``.  A vector must have ``in_obs`` values; ``from_names``' amplitudes cover
+        the env's whole row and are cut to the columns the policy reads - a noised column behind them raises."""
+        n = int(policy.in_obs)
+        if self.amp.ndim == 0:
+            return np.full(n, self.amp, dtype=np.float32)
+        if self._whole_row and self.amp.shape[0] >= n:
+            if self.amp[n:].any():
+                raise ValueError(f'an observation with noise lies behind the in_obs = {n} columns the policy reads')
+        elif self.amp.shape[0] != n:
+            raise ValueError(f'amp has {self.amp.shape[0]} values, the policy reads in_obs = {n} observation columns')
+        return np.ascontiguousarray(self.amp[:n])
+
+    def _check(self, policy):
+        if self.scan_amp != 0.0 and getattr(policy, 'height_scan', None) is None:
+            raise ValueError(f'scan_amp = {self.scan_amp} and the policy has no height scan')
+        return self.table(policy)
+
+    def _struct(self, policy, device, clean=None):
+        """the C block for ``policy`` with the table on ``device``; clean: the tensor of the true rows, or None"""
+        import ctypes as C
+
+        import torch
+
+        from .cabi import GQ_OBS_NOISE, GqPolicyNoise
+        tab = self._check(policy)
+        key = (str(device), tab.shape[0])
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(tab.copy()).to(device)
+        t = self._device[key]
+        return GqPolicyNoise(struct_size=C.sizeof(GqPolicyNoise), kind=GQ_OBS_NOISE[self.kind], n_amp=tab.shape[0], scan_amp=self.scan_amp,
+                             amp=t.data_ptr(), policy_obs_clean=None if clean is None else clean.data_ptr())
 
 
 def _scan_split(in_dim, feed_last_action, height_scan, what, history=None):

@@ -455,7 +455,7 @@ class QuadrupedEnv(AccessorsMixin):
 
     def rollout_policy(self, n_steps: int, policy, kp, kd, q_default=None, action_scale=0.25, action_clip=None, decimation: int = 4, noise_sigma=0.0,
                        record_obs: bool = False, record_actions: bool = False, policy_waves: int = 0, step_waves: int = 0, timeout_s: float = 5.0,
-                       check: bool = True, reward=None, record_transitions: bool = False):
+                       check: bool = True, reward=None, record_transitions: bool = False, obs_noise=None):
         """``n_steps`` steps of every env with an MLP policy IN the loop and no launch boundary (``gq_rollout_policy``): the device-side
         form of ::
 
@@ -526,7 +526,17 @@ class QuadrupedEnv(AccessorsMixin):
         that the env waits for its re-spawn), so the history fed at policy step ``s + 1`` is all zero exactly where ``dones[s]`` is set; in
         the plain mode a fall in the call's last step is left to the next call's first step.  The fed-back last action itself keeps its rule
         - zeros at the first policy step of a call, kept across a re-spawn, NOT reset with the env - and a frame holds it as it was fed.
-        'policy_obs' records the history words raw, as fed."""
+        'policy_obs' records the history words raw, as fed.
+
+        SENSOR NOISE (``obs_noise=ObsNoise(amp, kind, scan_amp)``, every mode above; ``gq_rollout_policy_noise``; with ``None`` the call, the
+        entry point and the dict's keys are the ones above): the observation and scan columns the network is FED carry counter-based noise
+        in raw units, before shift / scale (``csrc/gq_policy_noise.h``), keyed by the env's seed, the column, the step counter and the
+        global env id.  The fed-back action and a history's frames are never noised - a frame, and ``env.policy_history``, hold the noisy
+        word the current block was fed.  Only the network's input is noised: the joint-impedance law, the reward, the foot terms and the
+        episode rules read the true row, so state, flags and observations afterwards still equal the step loop's with the recorded
+        torques.  With ``record_transitions`` 'policy_obs' is the row AS FED, noisy - what an actor's old log-probability needs - and the
+        dict gains 'policy_obs_clean' ``[K // D, N, policy.in_dim]``, the same row with the true words in the noised columns - what an
+        asymmetric critic needs.  ``obs_noise_eval`` evaluates the same law on given rows."""
         from .policy import GruPolicy
         recurrent = isinstance(policy, GruPolicy)
         K, D = int(n_steps), int(decimation)
@@ -583,10 +593,22 @@ class QuadrupedEnv(AccessorsMixin):
         if recurrent and record_transitions:
             extra['policy_hidden'] = torch.zeros(K // D, self.num_envs, policy.hidden, **f32)
             gr.hidden_seq = extra['policy_hidden'].data_ptr()
+        if obs_noise is not None:
+            from .policy import ObsNoise
+            if not isinstance(obs_noise, ObsNoise):
+                raise ValueError(f'obs_noise must be an ObsNoise, got {type(obs_noise).__name__}')
+            if record_transitions:
+                extra['policy_obs_clean'] = torch.zeros(K // D, self.num_envs, policy.in_dim, **f32)
+            nz = obs_noise._struct(policy, self.device, extra.get('policy_obs_clean'))
         self._hm_fresh = False
         args = (self._hbatch, K, C.byref(m), int(policy_waves), int(step_waves), float(timeout_s), self._st, self._out, self._auto_cfg, self._episode.data_ptr(),
                 self._lift_failed.data_ptr(), ptr(obs_seq), ptr(act_seq))
-        if hist is not None:   # one entry point: the modes and the scan selected by the blocks given
+        if obs_noise is not None:   # one entry point: the network, the modes, the scan and the history selected by the blocks given
+            gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
+            _lib.check(self._L.gq_rollout_policy_noise(*args[:3], C.byref(gr) if recurrent else None, None if scan is None else C.byref(sc),
+                                                       None if hist is None else C.byref(hs), C.byref(nz), *args[3:], C.byref(g) if learning else None,
+                                                       None if gf is None else C.byref(gf), stream), 'gq_rollout_policy_noise')
+        elif hist is not None:   # one entry point: the modes and the scan selected by the blocks given
             gf = reward.feet._struct(self._feet_air.data_ptr()) if learning and reward is not None and reward.feet_on else None
             _lib.check(self._L.gq_rollout_policy_hist(*args[:3], None if scan is None else C.byref(sc), C.byref(hs), *args[3:], C.byref(g) if learning else None,
                                                       None if gf is None else C.byref(gf), stream), 'gq_rollout_policy_hist')
@@ -700,6 +722,33 @@ class QuadrupedEnv(AccessorsMixin):
         sc = spec._struct()
         _lib.check(self._L.gq_height_scan_eval(self._hbatch, C.byref(sc), hits.data_ptr(), z.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
                    'gq_height_scan_eval')
+        return out
+
+    def obs_noise_eval(self, policy, obs_noise, rows, steps, env_ids):
+        """The sensor noise's law alone (``gq_obs_noise_eval``; the same routine, hence the same bits, as inside
+        ``rollout_policy(obs_noise=)``): rows ``[n, policy.in_dim]`` float32 raw input rows in 'policy_obs' layout, steps ``[n]`` int - each
+        row's absolute step counter, the env's launch counter at the call plus the step ``k`` of the policy step - env_ids ``[n]`` int,
+        global env ids -> the rows with the noise added where the law adds it, under this env's seed.  For a torch-side loop, or to rebuild
+        'policy_obs' from 'policy_obs_clean'."""
+        from .policy import GruPolicy, MlpPolicy, ObsNoise
+        if not isinstance(policy, (MlpPolicy, GruPolicy)):
+            raise ValueError(f'policy must be an MlpPolicy or a GruPolicy, got {type(policy).__name__}')
+        if not isinstance(obs_noise, ObsNoise):
+            raise ValueError(f'obs_noise must be an ObsNoise, got {type(obs_noise).__name__}')
+        if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.device != self.device or rows.dim() != 2 or rows.shape[1] != policy.in_dim:
+            raise ValueError(f'rows must be a float32 tensor of shape (n, {policy.in_dim}) on {self.device}')
+        n = int(rows.shape[0])
+        key = lambda v, name: torch.as_tensor(v, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        steps, env_ids = key(steps, 'steps'), key(env_ids, 'env_ids')
+        if steps.numel() != n or env_ids.numel() != n:
+            raise ValueError(f'steps and env_ids must have one entry per row ({n}), got {steps.numel()} and {env_ids.numel()}')
+        rows = rows.contiguous()
+        out = torch.empty_like(rows)
+        nz = obs_noise._struct(policy, self.device)
+        scan = getattr(policy, 'height_scan', None)
+        _lib.check(self._L.gq_obs_noise_eval(self._hbatch, C.byref(nz), int(policy.in_obs), 0 if scan is None else scan.cells, int(policy.in_dim),
+                                             int(self._seed or 0) & (2 ** 64 - 1), rows.data_ptr(), steps.data_ptr(), env_ids.data_ptr(), n, out.data_ptr(),
+                                             torch.cuda.current_stream(self.device).cuda_stream), 'gq_obs_noise_eval')
         return out
 
     def policy_eval(self, policy, rows, impl: str = 'tile', hidden=None):

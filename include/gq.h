@@ -694,6 +694,41 @@ typedef struct GqPolicyHist {
 int gq_rollout_policy_hist(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyScan* scan, const GqPolicyHist* hist, int policy_waves, int step_waves,
                            double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset, int32_t* episode, uint8_t* lift_failed, float* obs_seq,
                            float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream);
+/* SENSOR NOISE on the policy's input row (additive: the entry points above are what they were): the observation and scan columns the network
+ * is FED carry counter-based noise, in raw units, before obs_shift / obs_scale (csrc/gq_policy_noise.h is the definition: fp32, contraction
+ * off, every operation rounded once):
+ *   observation column c < in_obs, amp[c] > 0:      o~ = o + amp[c] * n                 scan column, scan_amp > 0:   s~ = s + scan_amp * n
+ *   uniform: n = 2 u - 1, u = (x0 >> 8) 2^-24, in [-1, 1)      normal: n = the action noise's Box - Muller on (x0, x1)
+ *   x_w: word w of the Philox4x32-10 block (c, noise_step0 + k, env + env_id_offset, 0x0b5e), key = mlp->noise_seed - c the column of the INPUT
+ *   ROW, k the step of the call at which the policy step is taken.
+ * s is the scan word after clamp and scale, from the TRUE z of the row.  The fed-back action and the history's frames are never noised; a frame
+ * stores the current block's word AS FED, noisy, and no second draw is made on it.  An amplitude of 0 draws nothing and leaves the word
+ * untouched bit for bit.  Only the network's input is noised: the joint-impedance law, the reward, the foot terms and both episode rules read
+ * the true row, so state, flags and observations after the call are those of the step loop with the recorded torques.
+ * GqLearn.policy_obs records the row AS FED (noisy); policy_obs_clean, the same row with the true words in the noised columns.
+ * gru / scan / hist / learn / feet: NULL, or the blocks of the entry points above - every combination they accept, selected the same way.
+ * Refused with a message, the batch stays usable: a stale struct_size, a kind that is neither, a null amp, n_amp != mlp->in_obs, a scan_amp
+ * that is negative or not finite, or not 0 without a scan block, a policy_obs_clean without GqLearn.policy_obs, and everything the entry points above refuse.  The library does not read
+ * the device table: its values are the caller's to keep >= 0 and finite (a negative or NaN amplitude draws nothing). */
+#define GQ_OBS_NOISE_UNIFORM 0
+#define GQ_OBS_NOISE_NORMAL 1
+typedef struct GqPolicyNoise {
+  int32_t struct_size;        /* sizeof(GqPolicyNoise): a stale binding is refused */
+  int32_t kind;               /* GQ_OBS_NOISE_* */
+  int32_t n_amp;              /* must equal mlp->in_obs */
+  float scan_amp;             /* >= 0: one amplitude for every scan column; 0 without a scan */
+  const float *amp;           /* device [n_amp] f32 amplitudes >= 0, raw observation units; not written during the call */
+  float *policy_obs_clean;    /* device [n_steps / decimation][N][in_dim] f32 or NULL; needs GqLearn.policy_obs, whose shape it has */
+} GqPolicyNoise;
+int gq_rollout_policy_noise(GqBatch* b, int n_steps, const GqPolicyMlp* mlp, const GqPolicyGru* gru, const GqPolicyScan* scan, const GqPolicyHist* hist,
+                            const GqPolicyNoise* noise, int policy_waves, int step_waves, double timeout_s, GqState st, GqObsOut out, const GqResetCfg* auto_reset,
+                            int32_t* episode, uint8_t* lift_failed, float* obs_seq, float* act_seq, const GqLearn* learn, const GqFootReward* feet, void* hip_stream);
+/* the noise law alone, a thread per word: rows: device [n][in_dim] raw input rows (in_obs observation columns, then scan_cells scan columns,
+ * then whatever the row holds behind them), steps / env_ids: device [n] int32, each row's absolute step counter (noise_step0 + k) and global
+ * env id -> out: device [n][in_dim], the rows with the noise added where the law adds it.  The same routine, the same bits, as inside the
+ * rollout.  noise->policy_obs_clean is not read. */
+int gq_obs_noise_eval(GqBatch* b, const GqPolicyNoise* noise, int in_obs, int scan_cells, int in_dim, uint64_t noise_seed, const float* rows, const int32_t* steps,
+                      const int32_t* env_ids, int n, float* out, void* hip_stream);
 /* JOINT-IMPEDANCE action held over a decimation window, one launch: what a robot's low-level interface takes - per joint
  * q_des, qd_des, tau_ff, kp, kd - applied for `decimation` physics steps, the form of
  *   for k in range(decimation): tau = kp * (q_des - qpos[:, 7:]) + kd * (qd_des - qvel[:, 6:]) + tau_ff; env.step(tau)

@@ -16,7 +16,9 @@ accessors=True env - D x (feet_jacobians, feet_pos, einsums for tau_leg = J_leg^
 rollout (QuadrupedEnv.rollout_policy, a new action every D steps: --decimation, default 4) against the loop it replaces on the same
 commit - a = torch_module(obs); env.step_pd(q0 + scale * a, kp, kd, decimation=D) - from the same state with the same
 network; one timing of the loop, then one of the rollout per entry of --policy-waves (default 64,128,256,512), R times over (--runs,
-default 3).  Prints every run of both sides.
+default 3).  Prints every run of both sides.  --obs-noise none|uniform|normal (with --mlp; use --side rollout: the torch loop stays clean): the
+rollout with sensor noise on all 33 columns the network reads (ObsNoise.from_names: joint angles 0.01, joint velocities 1.5, base linear
+velocity 0.1, angular velocity 0.2, gravity vector 0.05); none is the call without the switch.
 
 --history L[,cols] (with --mlp): the network also reads the last action and the frames of the last L policy steps (ObsHistory(L, cols), cols
 default 33: a 45-word frame; env.policy_history) - against the loop it replaces with the history kept in torch - hist = where(terminated, 0,
@@ -66,6 +68,7 @@ HIST = _opt('--history', None, lambda t: [int(v) for v in t.split(',')])
 SCAN = _opt('--scan', None, lambda t: [int(v) for v in t.split(',')])
 GRU = _opt('--gru', 0, int)
 SIDE = _opt('--side', None, str)
+OBS_NOISE = _opt('--obs-noise', None, str)   # none | uniform | normal: sensor noise on the --mlp rollout's input row
 LEARN = '--learn' in sys.argv
 if LEARN:
     sys.argv.remove('--learn')
@@ -154,8 +157,13 @@ if MLP:
     sd = env.state_dict(); launches = env._launches
     def restore():
         env.load_state_dict(sd); env._launches = launches; torch.cuda.synchronize()
+    nkw = {}
+    if OBS_NOISE not in (None, 'none'):   # a sim-to-real recipe's amplitudes on every column the network reads (33), raw units
+        from gym_quadruped_amd.policy import ObsNoise
+        nkw = dict(obs_noise=ObsNoise.from_names(env, {'qpos_js': 0.01, 'qvel_js': 1.5, 'base_lin_vel:base': 0.1, 'base_ang_vel:base': 0.2, 'gravity_vector:base': 0.05},
+                                                 kind=OBS_NOISE))
     def feature(pw):
-        env.rollout_policy(W * D, policy, KP, KD, action_scale=scale, decimation=D, policy_waves=pw)
+        env.rollout_policy(W * D, policy, KP, KD, action_scale=scale, decimation=D, policy_waves=pw, **nkw)
     def loop():
         with torch.no_grad():
             for w in range(W):
@@ -257,7 +265,7 @@ if MLP:
         print(f'{tag}: episodes max {int(env._episode.max())}', flush=True)
         sys.exit(0)
     restore(); feature(0); restore(); loop()   # warm both paths
-    tag = f'{robot} {scene} n={n} mlp={MLP} D={D}'
+    tag = f'{robot} {scene} n={n} mlp={MLP} D={D}' + (f' obs-noise={OBS_NOISE}' if OBS_NOISE else '')
     for r in range(MLP_RUNS):
         if SIDE in (None, 'loop'):
             restore(); m, us = timed(loop, W * D)
